@@ -2,7 +2,11 @@
 """bench.py — scored trajectories/s of the DWA rollout + social-force scoring
 path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload target]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload target] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line; `--dump-outputs DIR` also writes what the last timed
+step returned (dump_outputs).  `--full` adds everything else, outside the timed region: the oracle check of the headline
+launch (`verify`), the secondary measurements under `extra` (each with its own `verify`) and the CPU baseline.
 
 One "step" = one BLOCKING scoring call through the C ABI, as SURVEY.md §8d defines the
 metric (the reference's grid loop is one blocking loop, src/sfw_planner.cpp:345-417):
@@ -22,8 +26,8 @@ devices than ranks over RCCL, exits 2 and prints no line.
 N > 1 (one process per GPU under torch.distributed.run): the ranks share an N-times taller
 grid (weak scaling; rows are the outer, sharded axis, ref :345) — contiguous blocks of linvel
 rows of equal planned work, about one workload-sized block each — and one all-reduce(min) of the
-[N,4] f64 key table per step picks the global best.  Every N also reports BASELINE.json config 5 (4096 x 4096, 100
-pedestrians) sharded over the N ranks under extra.cfg5_strong (strong scaling).
+[N,4] f64 key table per step picks the global best.  With --full every N also reports BASELINE.json config 5 (4096 x 4096,
+100 pedestrians) sharded over the N ranks under extra.cfg5_strong (strong scaling).
 
 Rank 0 prints ONE JSON line.
 """
@@ -59,10 +63,15 @@ def parse_args():
                     help="BASELINE.json config: target (default), cfg1..cfg5, cfg2_o64, ref5x9")
     ap.add_argument("--precision", default="f64", choices=["f64", "f32", "f64_strict"],
                     help="f64 (default, the parity mode), f32 (forces in float), f64_strict (f64 with the longer polynomials)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the secondary workloads under `extra`")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: the oracle check (verify), the secondary measurements "
+                         "under `extra` and the CPU baseline.  Off: set up, warm up, time the steps, print the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step handed its caller as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the secondary workloads under `extra`")
     ap.add_argument("--extras", default="cfg5_strong,target_strong,inproc_multi,upload,resident,cfg2,cfg2_o64,cfg2_o240,target_o720,cfg3,cfg4,cfg4_spec,f32",
-                    help="comma-separated secondary measurements to run (all by default)")
+                    help="with --full: comma-separated secondary measurements to run (all by default)")
     ap.add_argument("--extra-steps", type=int, default=20, help="timed steps of each secondary workload")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="collective backend for N > 1 (gloo: CPU tensors; lets several ranks share one GPU in tests)")
@@ -75,7 +84,7 @@ def parse_args():
     ap.add_argument("--grid", default=None, help="override the sample grid, e.g. 512x512 (experiments only)")
     ap.add_argument("--verify", action="store_true", help=argparse.SUPPRESS)  # the default since round 4 (kept for old command lines)
     ap.add_argument("--no-verify", action="store_true",
-                    help="skip the oracle check of the headline launch (outside the timed region; on by default)")
+                    help="with --full: skip the oracle check of the headline launch (outside the timed region)")
     ap.add_argument("--verify-budget", type=float, default=75.0,
                     help="seconds of all-core oracle time the verify leg may take: the WHOLE grid when it fits (the target "
                          "grid: ~30 s on the 256-thread GPU box), else a sub-grid spread over the whole grid")
@@ -390,13 +399,13 @@ def run_config(workload_name, precision, steps, warmup, ctx, scaling="weak", res
     exchange = multi_gpu.KeyExchange(dist, rank, world, device=ctx["coll_device"]) if dist is not None else None
 
     def one_step():
-        _, best, key = job.step(resident)
+        costs, best, key = job.step(resident)
         if dist is not None:  # single all-reduce(min): every rank fills its own row, +inf elsewhere
             t0 = time.perf_counter()
             wr, wk, _ = exchange(key)
             state["xchg"].append(time.perf_counter() - t0)
             state["win"] = (wr, wk)
-        return best, key
+        return costs, best, key
 
     for _ in range(warmup):
         one_step()
@@ -416,7 +425,7 @@ def run_config(workload_name, precision, steps, warmup, ctx, scaling="weak", res
     t0 = time.perf_counter()
     tp = t0
     for _ in range(steps):
-        best, key = one_step()
+        costs, best, key = one_step()
         # HIP events recorded on the handle's own stream around each kernel group: read on every fourth step (reading them is
         # host time inside the timed region, in front of the next stage)
         if len(wall) % 4 == 0:
@@ -471,7 +480,9 @@ def run_config(workload_name, precision, steps, warmup, ctx, scaling="weak", res
         "k2_ms": float(np.mean(k2_ms)),
         "k3_ms": float(np.mean(k3_ms)),
         "launch_ms": float(np.mean(all_ms)),
+        "costs": costs,  # the last timed step's cost vector (None with resident): valid until the job's next step
         "best": best,
+        "key": key,
         "global_key": win_key,
         "winner_rank": win_rank,
         "per_rank": per_rank,
@@ -713,6 +724,34 @@ def extra_entry(name, precision, steps, warmup, ctx, verify_budget=0.0):
     }
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, res, rank, world):
+    """--dump-outputs: what the timed path handed its caller in its last timed step, as float64 .npy files — `costs` (the
+    8*T-byte cost vector, -1 rejected, -2 never scored), `best` ([index, cost, vx, vtheta, n_valid]) and `best_key` (the
+    [4] selection key the ranks exchange).  A cost vector over the size limit is written as a fixed sample instead
+    (`costs_sample`, at the sorted positions `costs_sample_index` drawn with seed 0).  N > 1: every rank writes its own
+    files, suffixed _rank<r>, and the limit is shared."""
+    os.makedirs(out_dir, exist_ok=True)
+    b = res["best"]
+    arrays = {"best": np.array([b["index"], b["cost"], b["vx"], b["vtheta"], b["n_valid"]], dtype=np.float64),
+              "best_key": np.asarray(res["key"], dtype=np.float64)}
+    if res["costs"] is not None:
+        costs = np.asarray(res["costs"], dtype=np.float64)
+        budget = DUMP_LIMIT_BYTES // world - 4096
+        if costs.nbytes <= budget:
+            arrays["costs"] = np.array(costs)
+        else:
+            n = budget // 16  # a cost and its position per sampled sample
+            idx = np.sort(np.random.default_rng(0).choice(costs.size, size=n, replace=False))
+            arrays["costs_sample"] = costs[idx]
+            arrays["costs_sample_index"] = idx.astype(np.float64)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + sfx + ".npy"), a)
+
+
 def main():
     args = parse_args()
     global GRID_OVERRIDE
@@ -725,6 +764,8 @@ def main():
             res = {"error": repr(e)}
         print(json.dumps(res), flush=True)
         return
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be >= 1")
     ensure_ranks(args)  # --gpus N means N ranks: re-launches itself under torch.distributed.run, or refuses a mismatch
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -758,6 +799,8 @@ def main():
            "coll_device": f"cuda:{local_rank}" if args.backend == "nccl" else "cpu"}
 
     res = run_config(args.workload, args.precision, args.steps, args.warmup, ctx, resident=args.resident)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, res, rank, world)
     job = res["job"]
     value = res["n_scored_total"] * args.steps / res["elapsed"]
     w = job.workload
@@ -806,7 +849,7 @@ def main():
                                  "winner_rank": res["winner_rank"]}
         out["per_rank"] = res["per_rank"]
         out["collective"] = collective_info(dist, args.backend, ctx)
-        if not args.no_verify:
+        if args.full and not args.no_verify:
             if rank == 0:  # rank 0's own row block against the oracle + the globally selected sample, outside the timed region
                 costs, vbest, _ = job.step()
                 out["verify"] = verify_against_oracle(job, costs, vbest, min(args.verify_budget, 45.0), global_key=res["global_key"])
@@ -814,7 +857,7 @@ def main():
                 del costs
             host_wait(dist, rank, "sfw_verify_done")
     extra = {}
-    wanted = set() if (args.no_extra or args.resident) else set(args.extras.split(","))
+    wanted = set() if (not args.full or args.no_extra or args.resident) else set(args.extras.split(","))
     if "cfg5_strong" in wanted:
         # BASELINE.json config 5 sharded over the N ranks (strong scaling); N = 1: the whole
         # 16.8 M-sample grid on one GPU, in table chunks.  One probe step sizes the run: >= 5 timed steps when a step
@@ -863,7 +906,7 @@ def main():
         # the others wait on the HOST (a key of the rendezvous store): a collective would park a spinning RCCL kernel on
         # every device rank 0 is about to use
         host_wait(dist, rank, "sfw_inproc_multi_done")
-    if rank == 0 and world == 1 and not args.resident:
+    if args.full and rank == 0 and world == 1 and not args.resident:
         job = GridJob(args.workload, args.precision, 0, 1, local_rank)
         if not args.no_verify:
             # the oracle on the headline grid itself, outside the timed region (the metric says "cmd_vel match")

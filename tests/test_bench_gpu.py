@@ -7,6 +7,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -28,7 +29,7 @@ def _port():
 
 
 def test_single_gpu_line():
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--extras",
+    r = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--full", "--extras",
                         "upload,resident,cfg2,cfg2_o64,cfg2_o240,inproc_multi", "--extra-steps", "3"], cwd=ROOT,
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -80,10 +81,32 @@ def test_single_gpu_line():
     assert d["value"] / cb["value"] > 100  # sanity: the GPU path is not the CPU path
 
 
+def test_plain_line_and_dumped_outputs(tmp_path):
+    """Without --full the line is the headline alone (no oracle check, no `extra`, no CPU baseline); --dump-outputs writes
+    what the last timed step returned, and a second run with the same arguments writes the same arrays."""
+    runs = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "4", "--warmup", "1", "--dump-outputs", str(d)],
+                           cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        runs.append((_last_json(r.stdout), {p.stem: np.load(p) for p in d.glob("*.npy")}))
+    (line, out), (_, out2) = runs
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line, k
+    assert line["steps"] == 4 and line["ms_per_step"] > 0 and abs(line["value"] * line["ms_per_step"] * 1e-3 - 65536) < 1e-3
+    assert "verify" not in line and "extra" not in line and "cpu_baseline" not in line
+    assert sorted(out) == ["best", "best_key", "costs"] and all(a.dtype == np.float64 for a in out.values())
+    costs, best = out["costs"], out["best"]
+    assert costs.shape == (65536,) and costs[int(best[0])] == best[1] == line["cmd_vel"]["cost"]
+    assert int(best[0]) == line["cmd_vel"]["index"] and int(best[4]) == line["cmd_vel"]["n_valid"] == int(np.sum(costs >= 0))
+    assert all(np.array_equal(out[k], out2[k]) for k in out)
+
+
 def test_two_ranks_on_one_gpu_over_gloo():
     # the driver's single-process command shape: NO torchrun around it — `--gpus 2` itself launches the two ranks
     # (bench.ensure_ranks; tests/test_bench_launch.py covers the launch alone on CPU)
-    cmd = [sys.executable, "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--full",
            "--backend", "gloo", "--no-cpu-baseline", "--extras", "inproc_multi,target_strong", "--inproc-workload", "cfg2",
            "--extra-steps", "3"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
@@ -130,7 +153,7 @@ def test_a_stuck_one_process_leg_costs_its_entry_not_the_line():
     a limit no child can meet, the entries carry an error and the headline line is still printed."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_port()), "bench.py", "--gpus", "2", "--steps", "1", "--warmup", "0", "--backend", "gloo",
-           "--no-cpu-baseline", "--no-verify", "--extras", "inproc_multi", "--inproc-workload", "cfg2", "--inproc-timeout", "0.01"]
+           "--full", "--no-cpu-baseline", "--no-verify", "--extras", "inproc_multi", "--inproc-workload", "cfg2", "--inproc-timeout", "0.01"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _last_json(r.stdout)

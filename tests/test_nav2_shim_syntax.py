@@ -25,8 +25,10 @@ def test_shim_type_checks_against_the_foxy_controller_interface():
 
 
 @pytest.mark.parametrize("old,new,expect", [
-    # signature drift against the base class is caught by `override`
-    ("void setPlan(const nav_msgs::msg::Path &path) override;", "void setPlan(nav_msgs::msg::Path &path) override;", "override"),
+    # signature drift against the base class is caught by `override` (an explicit id: a C++ `::` in a test id reads as a
+    # pytest node separator)
+    pytest.param("void setPlan(const nav_msgs::msg::Path &path) override;", "void setPlan(nav_msgs::msg::Path &path) override;",
+                 "override", id="setPlan-const-dropped-override"),
     # a pure virtual left open is caught by the plugin-export assertion
     ("  void cleanup() override;\n", "", "cleanup"),
     # a host-library name that does not exist is caught

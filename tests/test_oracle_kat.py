@@ -10,6 +10,7 @@ The lightsfm / Costmap2D boundaries stay "parity unpinned" (DESIGN.md).
 """
 import ctypes as C
 import math
+import os
 
 import numpy as np
 import pytest
@@ -39,17 +40,46 @@ def test_line_iterator_appendix_b(oracle_mod, ends):
     assert len(got) == max(abs(ends[2] - ends[0]), abs(ends[3] - ends[1])) + 1
 
 
-def test_line_iterator_matches_real_reference_header(oracle_mod):
-    """oracle Bresenham == reference LineIterator (compiled from /root/reference)
-    on 2000 random segments + all Appendix B vectors."""
-    if oracle_mod.ref_lib() is None:
-        pytest.skip("oracle/_ref not built (needs /root/reference at build time)")
+REF_LINES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference", "line_iterator.npz")
+
+
+def line_iterator_cases():
+    """All Appendix B vectors + 2000 random segments: the set the reference's LineIterator is recorded on."""
     rng = np.random.default_rng(7)
-    cases = list(APPENDIX_B) + [tuple(int(v) for v in rng.integers(-40, 200, size=4)) for _ in range(2000)]
-    for ends in cases:
-        assert np.array_equal(oracle_mod.line_cells(*ends), oracle_mod.line_cells(*ends, use_ref=True)), ends
+    return list(APPENDIX_B) + [tuple(int(v) for v in rng.integers(-40, 200, size=4)) for _ in range(2000)]
+
+
+def _recorded_reference_cells():
+    """tests/golden/reference/line_iterator.npz (made by make_line_iterator.py there): [(ends, cells)] per segment."""
+    z = np.load(REF_LINES)
+    codes = z["steps"].astype(np.int64)
+    steps = np.stack([codes // 3 - 1, codes % 3 - 1], axis=1)
+    out, k = [], 0
+    for ends, n, first in zip(z["ends"], z["lengths"], z["first"]):
+        cells = np.vstack([first[None, :], first[None, :] + np.cumsum(steps[k:k + n - 1], axis=0)])
+        out.append((tuple(int(v) for v in ends), cells))
+        k += n - 1
+    assert k == len(codes)
+    return out
+
+
+def test_line_iterator_matches_real_reference_header(oracle_mod):
+    """oracle Bresenham == reference LineIterator on 2000 random segments + all Appendix B vectors: as recorded from the
+    reference header (tests/golden/reference/line_iterator.npz), and, where oracle/_ref is built, as compiled from it."""
+    cases = line_iterator_cases()
+    recorded = _recorded_reference_cells()
+    assert [e for e, _ in recorded] == cases
+    live = oracle_mod.ref_lib() is not None
+    for ends, ref_cells in recorded:
+        mine = oracle_mod.line_cells(*ends)
+        assert np.array_equal(mine, ref_cells), ends
+        if live:
+            assert np.array_equal(mine, oracle_mod.line_cells(*ends, use_ref=True)), ends
+    ref = dict(recorded)
     for ends, cells in APPENDIX_B.items():
-        assert [tuple(c) for c in oracle_mod.line_cells(*ends, use_ref=True)] == cells
+        assert [tuple(c) for c in ref[ends]] == cells
+        if live:
+            assert [tuple(c) for c in oracle_mod.line_cells(*ends, use_ref=True)] == cells
 
 
 def test_trajectory_container_real_reference(oracle_mod):

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Markdown table of one default `python bench.py` line (headline + every entry of `extra`): what DESIGN.md §8 and BASELINE.md §4
+"""Markdown table of one `python bench.py --full` line (headline + every entry of `extra`): what DESIGN.md §8 and BASELINE.md §4
 quote.  usage: bench_table.py <bench.json>"""
 import json
 import sys

@@ -1,12 +1,13 @@
 #!/bin/bash
 # Collect the rocprofv3 evidence for one workload on the GPU box:
-#   tools/profile.sh <tag> [workload]     -> gpurun_out/<tag>_{kernel_stats.csv,bench.json,pmc_summary.txt,traffic.txt}
+#   [OUT=<dir>] tools/profile.sh <tag> [workload]   -> <dir>/<tag>_{kernel_stats.csv,bench.json,pmc_summary.txt,traffic.txt}
+#   (default dir build/evidence)
 # Kernel trace + stats in one run; every PMC group in its own run with --kernel-trace only.
 set -u
 TAG=$1
 WL=${2:-cfg2}
 REPO=$(pwd)
-OUT=$REPO/gpurun_out
+OUT=$(mkdir -p "${OUT:-build/evidence}" && cd "${OUT:-build/evidence}" && pwd)
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 BENCH="python $REPO/bench.py --workload $WL --no-cpu-baseline --no-extra --no-verify"

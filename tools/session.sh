@@ -10,7 +10,7 @@
 #   cycle [cycles]               control-cycle latency (build/cycle_latency, 0 / 60 / 240 points, marker capture) + its device
 #                                timeline, the one-launch kernel against SFW_CYCLE_FUSED=0      -> <TAG>_latency.txt, <TAG>_cycle_timeline.txt
 #   hostgap <workload>           host share of a blocking step (tools/host_gap_probe.py, SFW_DEBUG_STAGE)
-#   evidence                     the round's evidence set, ONCE, on the final commit: suite, default bench line, rocprofv3 stats
+#   evidence                     the round's evidence set, ONCE, on the final commit: suite, `bench.py --full` line, rocprofv3 stats
 #                                + PMC passes (tools/gpu_profile_round.sh), cycle, timelines, the two parity sweeps, the
 #                                control-cycle K2 grid
 TAG=${TAG:-r06}
@@ -45,7 +45,7 @@ hostgap)
   SFW_DEBUG_STAGE=1 python tools/host_gap_probe.py ${1:-cfg2} ${2:-60} 2>&1 | grep -v "^\[sfw\] stage" | tail -3
   SFW_DEBUG_STAGE=1 python tools/host_gap_probe.py ${1:-cfg2} 12 2>&1 | grep "stage:" | tail -2 ;;
 evidence)
-  bash tools/gpu_profile_round.sh $TAG
+  OUT=$OUT bash tools/gpu_profile_round.sh $TAG
   TAG=$TAG bash tools/session.sh cycle
   TAG=$TAG bash tools/session.sh timeline cfg2 > /dev/null; TAG=$TAG bash tools/session.sh timeline target > /dev/null
   python tools/sweep_parity.py 100 3000 > $OUT/${TAG}_sweep_a.txt 2>&1; tail -1 $OUT/${TAG}_sweep_a.txt
