@@ -434,6 +434,47 @@ int sfw_multi_last_us(sfw_multi_handle m, int32_t which, double *us_out);
 int sfw_multi_grid_points(sfw_multi_handle m, int64_t index, double *points_xyth, int32_t points_cap,
                           int32_t *n_points);
 
+/* ---- many planners in one launch ------------------------------------------
+ * A fleet server scoring the local planners of many robots, or a harness stepping many scenes: B ordinary handles on one
+ * device that share ONE stream (the batch's), scored together.  Every member is a full sfw_handle: set its parameters,
+ * costmap, footprint and agents, stage its own grid (grids, step counts and precisions may differ), turn on points capture,
+ * or score it alone, as for any handle; only destroying it is refused (SFW_ERR_STATE: the batch owns it).
+ * sfw_batch_launch enqueues every member's staged grid: the members whose launch would be the one-kernel control cycle
+ * (sfw_plan_info.one_launch) go through ONE launch of a batched cycle kernel per kernel variant (precision x groups x
+ * laser points: a homogeneous fleet is one launch), the others through their usual kernels behind it on the same stream.
+ * Every member's results (costs, sentinels, selection, captured Trajectory points, contact steps) are bit-identical to
+ * its own launch, and after sfw_batch_fetch sfw_grid_costs_view / sfw_grid_fetch / sfw_grid_points(_batch) of a member
+ * behave as after that member's own launch.  Member timing (sfw_set_timing) is not recorded in a batch launch. */
+#define SFW_BATCH_MAX 256
+typedef struct sfw_batch_s *sfw_batch;
+/* 1 <= B <= SFW_BATCH_MAX; SFW_ERR_NO_DEVICE without a GPU, as sfw_create. */
+int sfw_batch_create(const sfw_params *params, int device, int32_t B, sfw_batch *out);
+int sfw_batch_destroy(sfw_batch b);
+const char *sfw_batch_last_error(sfw_batch b);
+int32_t sfw_batch_size(sfw_batch b);
+/* Member i (owned by b; NULL when out of range). */
+sfw_handle sfw_batch_member(sfw_batch b, int32_t i);
+/* Every member must have a staged grid (a grid staged and consumed by a single-sample score counts as none): otherwise
+ * SFW_ERR_STATE, nothing is enqueued, and the last error names the member.  No host sync. */
+int sfw_batch_launch(sfw_batch b);
+/* One wait for the whole batch; best_out (nullable) receives B selections in member order. */
+int sfw_batch_fetch(sfw_batch b, sfw_best *best_out);
+/* Stage member i with rs[i] and args[i] on the common grid (linvels x angvels), launch, fetch.  A failing stage launches
+ * nothing. */
+int sfw_batch_score_grid(sfw_batch b, const sfw_robot_state *rs, const double *linvels, int32_t nv,
+                         const double *angvels, int32_t nw, const sfw_goal_args *args, sfw_best *best_out);
+/* What the last launch did: members that went through a batched launch, members on their own path, batched launches,
+ * blocks over all batched launches and the largest dynamic LDS of a block among them (bytes). */
+typedef struct sfw_batch_desc {
+  int32_t members, one_launch_members, own_path_members, batch_launches;
+  int64_t batch_blocks;
+  int32_t lds_bytes;
+} sfw_batch_desc;
+int sfw_batch_describe(sfw_batch b, sfw_batch_desc *out);
+/* Host wall-clock of the last calls, microseconds: which = 0 staging of the last batch score (that call only), 1 the
+ * enqueue of the last launch, 2 the wait and fetch of the last fetch. */
+int sfw_batch_last_us(sfw_batch b, int32_t which, double *us_out);
+
 #ifdef __cplusplus
 }
 #endif

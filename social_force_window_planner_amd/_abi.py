@@ -190,8 +190,26 @@ EXPORTED_SYMBOLS = (
     "sfw_multi_rank_rows",
     "sfw_multi_last_us",
     "sfw_multi_grid_points",
+    "sfw_batch_create",
+    "sfw_batch_destroy",
+    "sfw_batch_last_error",
+    "sfw_batch_size",
+    "sfw_batch_member",
+    "sfw_batch_launch",
+    "sfw_batch_fetch",
+    "sfw_batch_score_grid",
+    "sfw_batch_describe",
+    "sfw_batch_last_us",
 )
 SFW_MULTI_RCCL, SFW_MULTI_HOST_REDUCE = 0, 1
+SFW_BATCH_MAX = 256
+
+
+class SfwBatchDesc(C.Structure):
+    """sfw_batch_desc (include/sfw_hip.h): what the last sfw_batch_launch did."""
+
+    _fields_ = [("members", C.c_int32), ("one_launch_members", C.c_int32), ("own_path_members", C.c_int32),
+                ("batch_launches", C.c_int32), ("batch_blocks", C.c_int64), ("lds_bytes", C.c_int32)]
 
 
 class CtrlParams(C.Structure):

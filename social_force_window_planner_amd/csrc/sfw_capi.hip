@@ -231,6 +231,9 @@ struct sfw_planner_s {
   pinned_buf pin_map, pin_world, pin_out, pin_cls;
   pinned_buf pin_one;     // sfw_score_one's outputs where the one-launch kernel writes them (cost | n_points | coll_step | points)
   pinned_buf pin_mirror;  // costs + selection record as the selection kernels of the last launch leave them (device writes)
+  // a member of a sfw_batch: the batch's streams are borrowed (sfw_destroy refuses the handle; the batch destroys it)
+  bool owns_streams = true;
+  bool batch_member = false;
 };
 
 namespace {
@@ -1251,7 +1254,20 @@ int flush_arena(sfw_handle h) {
   return SFW_OK;
 }
 
-int launch_common(sfw_handle h) {
+// What a launch of the staged grid settled before it enqueues its kernels (launch_prepare), for the two ways on: the one-kernel
+// control cycle (cycle_launch_of -> the cycle kernel, alone or in a batch -> cycle_commit) or the kernels one by one
+// (launch_kernels).
+struct launch_prep {
+  int64_t T = 0, chunk = 0;
+  int S = 0;
+  bool prefix = false, poses_done = false, single = false, timing = false;
+  char *cap_pts = nullptr, *cap_n = nullptr, *cap_coll = nullptr;
+  double *costs_host = nullptr;
+  sfw_sel *sel_host = nullptr;
+};
+
+// timing: record the per-kernel events of this launch (h->timing; a batch launch never does)
+int launch_prepare(sfw_handle h, bool timing, launch_prep &lp) {
   if (!h) return SFW_ERR_INVALID_ARG;
   if (!h->staged) return fail(h, SFW_ERR_STATE, "grid_launch before grid_stage");
   SFW_HIP(h, hipSetDevice(h->device));
@@ -1288,10 +1304,9 @@ int launch_common(sfw_handle h) {
   // the shared-prefix plan was laid out for the staged step count and for chunks of whole rows
   const bool prefix = !h->prefix_steps.empty() && h->prefix_S == S && h->prefix_chunk <= chunk;
   if (prefix) chunk = h->prefix_chunk;
-  const bool timing = h->timing;
   // the stage enqueued K1a of this (single-chunk) grid already — unless sfw_set_timing(1) arrived since: the events of a
   // timed launch bracket its own kernels, so the pose rollout runs again behind a freshly recorded ev[0]
-  const bool poses_done = h->early_poses && chunk >= T && (!h->timing || h->early_poses_timed);
+  const bool poses_done = h->early_poses && chunk >= T && (!timing || h->early_poses_timed);
   h->early_poses = false;                                 // ... once: a second launch of the same stage rolls out again
   if (timing) {
     SFW_HIP(h, h->clock.reserve(4));
@@ -1349,41 +1364,67 @@ int launch_common(sfw_handle h) {
     sel_host = reinterpret_cast<sfw_sel *>(h->pin_mirror.p + cost_bytes);
     h->mirrored = true;
   }
-  if (single && !prefix && !poses_done) {
-    // A control cycle's grid: K1 + K2 + K3 in ONE launch (sfw_cycle_kernel) when the launch qualifies
-    sfw_launch L;
-    fill_launch(h, L, 0, T, chunk);
-    if (h->captured) {
-      L.points = reinterpret_cast<double *>(cap_pts);
-      L.n_points = reinterpret_cast<int32_t *>(cap_n);
-      L.coll_step = reinterpret_cast<int32_t *>(cap_coll);
-      L.force_alive = 1;  // (as below)
-    }
-    L.clock_probe = timing ? h->clock.p : nullptr;
-    L.costs_host = costs_host;
-    L.sel_host = sel_host;
-    if (sfw_cycle_applies(L)) {
-      if (timing) SFW_HIP(h, hipEventRecord(h->ev[1], h->stream));  // (no K1 of its own: K1 time 0, the launch is "K2")
-      if (h->arena_pending) {  // the kernel's blocks fetch the arena from pinned memory themselves: no copy at all this cycle
-        L.arena_host = h->pin_world.p + h->arena_from;
-        L.arena_dev = h->world.p + h->arena_from;
-        L.arena_bytes = static_cast<uint32_t>(h->arena_bytes);
-      }
-      SFW_HIP(h, h->params.precision == SFW_PRECISION_F64_STRICT ? sfw_launch_cycle_strict(L, h->stream) : sfw_launch_cycle(L, h->stream));
-      if (h->arena_pending) {
-        h->arena_pending = false;
-        SFW_HIP(h, h->pin_world.mark(h->stream));
-      }
-      if (timing) {
-        SFW_HIP(h, hipEventRecord(h->ev[2], h->stream));
-        SFW_HIP(h, hipEventRecord(h->ev[3], h->stream));
-      }
-      h->launched = true;
-      h->launched_timed = timing;
-      h->launched_cycle = true;
-      return SFW_OK;
-    }
+  lp.T = T;
+  lp.chunk = chunk;
+  lp.S = S;
+  lp.prefix = prefix;
+  lp.poses_done = poses_done;
+  lp.single = single;
+  lp.timing = timing;
+  lp.cap_pts = cap_pts;
+  lp.cap_n = cap_n;
+  lp.cap_coll = cap_coll;
+  lp.costs_host = costs_host;
+  lp.sel_host = sel_host;
+  return SFW_OK;
+}
+
+// A control cycle's grid: K1 + K2 + K3 in ONE launch (sfw_cycle_kernel) when the launch qualifies.  Step 1: the launch record
+// (false: it does not qualify; nothing has changed).
+bool cycle_launch_of(sfw_handle h, const launch_prep &lp, sfw_launch &L) {
+  if (!(lp.single && !lp.prefix && !lp.poses_done)) return false;
+  fill_launch(h, L, 0, lp.T, lp.chunk);
+  if (h->captured) {
+    L.points = reinterpret_cast<double *>(lp.cap_pts);
+    L.n_points = reinterpret_cast<int32_t *>(lp.cap_n);
+    L.coll_step = reinterpret_cast<int32_t *>(lp.cap_coll);
+    L.force_alive = 1;  // (as in launch_kernels)
   }
+  L.clock_probe = lp.timing ? h->clock.p : nullptr;
+  L.costs_host = lp.costs_host;
+  L.sel_host = lp.sel_host;
+  if (!sfw_cycle_applies(L)) return false;
+  if (h->arena_pending) {  // the kernel's blocks fetch the arena from pinned memory themselves: no copy at all this cycle
+    L.arena_host = h->pin_world.p + h->arena_from;
+    L.arena_dev = h->world.p + h->arena_from;
+    L.arena_bytes = static_cast<uint32_t>(h->arena_bytes);
+  }
+  return true;
+}
+// Step 2, once the kernel that carries L is enqueued: the handle's state after its launch
+int cycle_commit(sfw_handle h, bool timing) {
+  if (h->arena_pending) {
+    h->arena_pending = false;
+    SFW_HIP(h, h->pin_world.mark(h->stream));
+  }
+  if (timing) {
+    SFW_HIP(h, hipEventRecord(h->ev[2], h->stream));
+    SFW_HIP(h, hipEventRecord(h->ev[3], h->stream));
+  }
+  h->launched = true;
+  h->launched_timed = timing;
+  h->launched_cycle = true;
+  return SFW_OK;
+}
+
+// Everything else: K1, K2 and the selection as kernels of their own (chunks, shared-prefix levels)
+int launch_kernels(sfw_handle h, const launch_prep &lp) {
+  const int64_t T = lp.T, chunk = lp.chunk;
+  const int S = lp.S;
+  const bool prefix = lp.prefix, poses_done = lp.poses_done, single = lp.single, timing = lp.timing;
+  char *const cap_pts = lp.cap_pts, *const cap_n = lp.cap_n, *const cap_coll = lp.cap_coll;
+  double *const costs_host = lp.costs_host;
+  sfw_sel *const sel_host = lp.sel_host;
   h->launched_cycle = false;
   if (int e = flush_arena(h)) return e;
   int c = 0;
@@ -1469,6 +1510,22 @@ int launch_common(sfw_handle h) {
   return SFW_OK;
 }
 
+hipError_t launch_cycle_of(const sfw_launch &L, hipStream_t stream) {
+  return L.p.precision == SFW_PRECISION_F64_STRICT ? sfw_launch_cycle_strict(L, stream) : sfw_launch_cycle(L, stream);
+}
+
+int launch_common(sfw_handle h) {
+  launch_prep lp;
+  if (int e = launch_prepare(h, h ? h->timing : false, lp)) return e;
+  sfw_launch L;
+  if (cycle_launch_of(h, lp, L)) {
+    if (lp.timing) SFW_HIP(h, hipEventRecord(h->ev[1], h->stream));  // (no K1 of its own: K1 time 0, the launch is "K2")
+    SFW_HIP(h, launch_cycle_of(L, h->stream));
+    return cycle_commit(h, lp.timing);
+  }
+  return launch_kernels(h, lp);
+}
+
 void sel_to_best(sfw_handle h, const sfw_sel &s, sfw_best *best, sfw_best_key *key) {
   const bool found = std::isfinite(s.cost);
   if (best) {
@@ -1530,7 +1587,12 @@ void sfw_params_default(sfw_params *p) {
 
 int sfw_abi_version(void) { return SFW_ABI_VERSION; }
 
-int sfw_create(const sfw_params *params, int device, sfw_handle *out) {
+}  // extern "C"
+
+namespace {
+int destroy_handle(sfw_handle h);
+// A handle on its own streams (sfw_create), or on a batch's (stream / side non-null: borrowed, not destroyed with it)
+int create_handle(const sfw_params *params, int device, hipStream_t stream, hipStream_t side, sfw_handle *out) {
   if (!out) return SFW_ERR_INVALID_ARG;
   *out = nullptr;
   if (int e = check_params(nullptr, params)) return e;
@@ -1591,8 +1653,14 @@ int sfw_create(const sfw_params *params, int device, sfw_handle *out) {
       if (v >= 1 && v <= 64) h->n_xcd = static_cast<int>(v);
     }
   }
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking);
+  if (stream) {
+    h->owns_streams = false;
+    h->stream = stream;
+    h->side = side;
+  } else {
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking);
+  }
   if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_poses, hipEventDisableTiming);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_side, hipEventDisableTiming);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&h->split.fork, hipEventDisableTiming);
@@ -1602,15 +1670,14 @@ int sfw_create(const sfw_params *params, int device, sfw_handle *out) {
   if (e == hipSuccess) e = h->cycle_counter.reserve(1);
   if (e == hipSuccess) e = hipMemsetAsync(h->cycle_counter.p, 0, sizeof(unsigned), h->stream);
   if (e != hipSuccess) {
-    sfw_destroy(h);
+    destroy_handle(h);
     return SFW_ERR_HIP;
   }
   *out = h;
   return SFW_OK;
 }
 
-int sfw_destroy(sfw_handle h) {
-  if (!h) return SFW_OK;
+int destroy_handle(sfw_handle h) {
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   if (h->side) (void)hipStreamSynchronize(h->side);
@@ -1655,10 +1722,25 @@ int sfw_destroy(sfw_handle h) {
   if (h->ev_side) (void)hipEventDestroy(h->ev_side);
   if (h->split.fork) (void)hipEventDestroy(h->split.fork);
   if (h->split.join) (void)hipEventDestroy(h->split.join);
-  if (h->side) (void)hipStreamDestroy(h->side);
-  if (h->stream) (void)hipStreamDestroy(h->stream);
+  if (h->owns_streams) {
+    if (h->side) (void)hipStreamDestroy(h->side);
+    if (h->stream) (void)hipStreamDestroy(h->stream);
+  }
   delete h;
   return SFW_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int sfw_create(const sfw_params *params, int device, sfw_handle *out) {
+  return create_handle(params, device, nullptr, nullptr, out);
+}
+
+int sfw_destroy(sfw_handle h) {
+  if (!h) return SFW_OK;
+  if (h->batch_member) return fail(h, SFW_ERR_STATE, "destroy: the handle is a member of a batch (sfw_batch_destroy destroys it)");
+  return destroy_handle(h);
 }
 
 int sfw_set_params(sfw_handle h, const sfw_params *params) {
@@ -2727,6 +2809,246 @@ int sfw_multi_grid_points(sfw_multi_handle m, int64_t index, double *points_xyth
   const int64_t local = index - static_cast<int64_t>(m->row0[static_cast<size_t>(r)]) * m->nw;
   if (int e = sfw_grid_points(m->h[static_cast<size_t>(r)], local, points_xyth, points_cap, n_points))
     return mrank_fail(m, r, e, "sfw_grid_points");
+  return SFW_OK;
+}
+
+}  // extern "C"
+
+// ===========================================================================
+// many handles' control cycles in one launch (sfw_batch_*)
+// ===========================================================================
+struct sfw_batch_s {
+  int device = 0;
+  hipStream_t stream = nullptr, side = nullptr;  // shared by every member
+  std::vector<sfw_handle> h;
+  std::string err;
+  // the member table of a launch (sfw_device.h sfw_batch_rec): built in pinned memory, ONE H2D copy per launch
+  pinned_buf pin_table;
+  dev_buf<char> table;
+  sfw_batch_desc desc{};
+  double us[3] = {0.0, 0.0, 0.0};
+  bool launched = false;
+};
+
+namespace {
+int bfail(sfw_batch b, int code, const std::string &msg) {
+  if (b) b->err = msg;
+  return code;
+}
+int bmember_fail(sfw_batch b, int32_t i, int code, const char *what) {
+  return bfail(b, code, std::string(what) + " (member " + std::to_string(i) + "): " + b->h[static_cast<size_t>(i)]->err);
+}
+double us_since(std::chrono::steady_clock::time_point t0) {
+  return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+}
+
+int batch_launch(sfw_batch b) {
+  const int32_t B = static_cast<int32_t>(b->h.size());
+  // every member staged, or nothing is enqueued
+  for (int32_t i = 0; i < B; ++i)
+    if (!b->h[static_cast<size_t>(i)]->staged)
+      return bfail(b, SFW_ERR_STATE, "batch_launch: member " + std::to_string(i) + " has no staged grid (sfw_grid_stage; sfw_score_one consumes it)");
+  if (hipSetDevice(b->device) != hipSuccess) return bfail(b, SFW_ERR_HIP, "batch_launch: hipSetDevice failed");
+  std::vector<launch_prep> lp(static_cast<size_t>(B));
+  std::vector<sfw_launch> L(static_cast<size_t>(B));
+  std::vector<int> variant(static_cast<size_t>(B), -1);  // -1: the member's own path
+  int32_t n_cycle = 0;
+  for (int32_t i = 0; i < B; ++i) {
+    const size_t m = static_cast<size_t>(i);
+    if (int e = launch_prepare(b->h[m], false, lp[m])) return bmember_fail(b, i, e, "batch_launch");
+    if (cycle_launch_of(b->h[m], lp[m], L[m])) {
+      variant[m] = sfw_cycle_batch_variant(L[m]);
+      ++n_cycle;
+    }
+  }
+  sfw_batch_desc d{};
+  d.members = B;
+  d.one_launch_members = n_cycle;
+  d.own_path_members = B - n_cycle;
+  if (n_cycle > 0) {
+    // table: per variant (= per launch) first[n + 1], then the records of all launches, in variant order
+    constexpr int kVariants = 9;
+    int32_t count[kVariants] = {};
+    for (int v : variant)
+      if (v >= 0) ++count[v];
+    size_t head = 0;
+    size_t first_at[kVariants] = {};
+    for (int v = 0; v < kVariants; ++v)
+      if (count[v] > 0) {
+        first_at[v] = head;
+        head += sizeof(uint32_t) * (static_cast<size_t>(count[v]) + 1);
+      }
+    head = (head + 15) & ~size_t(15);
+    const size_t bytes = head + sizeof(sfw_batch_rec) * static_cast<size_t>(n_cycle);
+    if (b->pin_table.reserve(bytes) != hipSuccess || b->table.reserve(bytes) != hipSuccess)
+      return bfail(b, SFW_ERR_HIP, "batch_launch: member table allocation failed");
+    char *const pt = b->pin_table.p;
+    size_t rec_at[kVariants] = {};
+    for (int v = 0, r = 0; v < kVariants; ++v)
+      if (count[v] > 0) {
+        rec_at[v] = head + sizeof(sfw_batch_rec) * static_cast<size_t>(r);
+        r += count[v];
+      }
+    int32_t filled[kVariants] = {};
+    uint32_t blocks[kVariants] = {};
+    size_t lds[kVariants] = {};
+    for (int32_t i = 0; i < B; ++i) {
+      const int v = variant[static_cast<size_t>(i)];
+      if (v < 0) continue;
+      sfw_batch_rec *const rec = reinterpret_cast<sfw_batch_rec *>(pt + rec_at[v]) + filled[v];
+      sfw_cycle_batch_record(L[static_cast<size_t>(i)], rec);
+      reinterpret_cast<uint32_t *>(pt + first_at[v])[filled[v]] = blocks[v];
+      blocks[v] += static_cast<uint32_t>(rec->L.chunk_count);
+      lds[v] = std::max(lds[v], static_cast<size_t>(rec->lds_bytes));
+      ++filled[v];
+    }
+    for (int v = 0; v < kVariants; ++v)
+      if (count[v] > 0) reinterpret_cast<uint32_t *>(pt + first_at[v])[count[v]] = blocks[v];
+    if (hipMemcpyAsync(b->table.p, pt, bytes, hipMemcpyHostToDevice, b->stream) != hipSuccess || b->pin_table.mark(b->stream) != hipSuccess)
+      return bfail(b, SFW_ERR_HIP, "batch_launch: member table copy failed");
+    for (int v = 0; v < kVariants; ++v) {
+      if (count[v] == 0) continue;
+      const uint32_t *const d_first = reinterpret_cast<const uint32_t *>(b->table.p + first_at[v]);
+      const sfw_batch_rec *const d_recs = reinterpret_cast<const sfw_batch_rec *>(b->table.p + rec_at[v]);
+      const hipError_t e = v / 3 == 2 ? sfw_launch_cycle_batch_strict(v, d_first, d_recs, count[v], blocks[v], lds[v], b->stream)
+                                      : sfw_launch_cycle_batch(v, d_first, d_recs, count[v], blocks[v], lds[v], b->stream);
+      if (e != hipSuccess) return bfail(b, SFW_ERR_HIP, std::string("batch_launch: sfw_batch_cycle_kernel: ") + hipGetErrorString(e));
+      ++d.batch_launches;
+      d.batch_blocks += blocks[v];
+      d.lds_bytes = std::max(d.lds_bytes, static_cast<int32_t>(lds[v]));
+    }
+    for (int32_t i = 0; i < B; ++i)
+      if (variant[static_cast<size_t>(i)] >= 0 && cycle_commit(b->h[static_cast<size_t>(i)], false) != SFW_OK)
+        return bmember_fail(b, i, SFW_ERR_HIP, "batch_launch");
+  }
+  // the others on their usual path, behind the batch launches on the same stream
+  for (int32_t i = 0; i < B; ++i)
+    if (variant[static_cast<size_t>(i)] < 0)
+      if (int e = launch_kernels(b->h[static_cast<size_t>(i)], lp[static_cast<size_t>(i)])) return bmember_fail(b, i, e, "batch_launch");
+  b->desc = d;
+  b->launched = true;
+  return SFW_OK;
+}
+
+int batch_fetch(sfw_batch b, sfw_best *best_out) {
+  const int32_t B = static_cast<int32_t>(b->h.size());
+  for (int32_t i = 0; i < B; ++i)
+    if (!b->h[static_cast<size_t>(i)]->launched)
+      return bfail(b, SFW_ERR_STATE, "batch_fetch: member " + std::to_string(i) + " has not been launched");
+  if (hipSetDevice(b->device) != hipSuccess) return bfail(b, SFW_ERR_HIP, "batch_fetch: hipSetDevice failed");
+  // one wait for the whole batch (one stream)
+  if (const hipError_t e = wait_stream(b->h[0]); e != hipSuccess) return bfail(b, SFW_ERR_HIP, std::string("batch_fetch: ") + hipGetErrorString(e));
+  for (int32_t i = 0; i < B; ++i) {
+    sfw_handle h = b->h[static_cast<size_t>(i)];
+    stream_is_idle(h);
+    sfw_best *const best = best_out ? best_out + i : nullptr;
+    if (h->mirrored) {  // (as sfw_grid_fetch: the selection kernels left vector and record in the pinned mirror)
+      h->fetched = true;
+      sfw_sel s;
+      std::memcpy(&s, h->pin_mirror.p + sizeof(double) * static_cast<size_t>(h->nv) * h->nw, sizeof(s));
+      sel_to_best(h, s, best, nullptr);
+    } else if (int e = sfw_grid_fetch(h, nullptr, best, nullptr)) {  // (a grid too large for the mirror: its own copy)
+      return bmember_fail(b, i, e, "batch_fetch");
+    }
+  }
+  return SFW_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int sfw_batch_create(const sfw_params *params, int device, int32_t B, sfw_batch *out) {
+  if (!out) return SFW_ERR_INVALID_ARG;
+  *out = nullptr;
+  if (B < 1 || B > SFW_BATCH_MAX) return SFW_ERR_INVALID_ARG;
+  if (int e = check_params(nullptr, params)) return e;
+  int count = 0;
+  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return SFW_ERR_NO_DEVICE;
+  if (device < 0 || device >= count) return SFW_ERR_INVALID_ARG;
+  sfw_batch b = new (std::nothrow) sfw_batch_s();
+  if (!b) return SFW_ERR_HIP;
+  b->device = device;
+  hipError_t e = hipSetDevice(device);
+  if (e == hipSuccess) e = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking);
+  if (e == hipSuccess) e = hipStreamCreateWithFlags(&b->side, hipStreamNonBlocking);
+  int rc = e == hipSuccess ? SFW_OK : SFW_ERR_HIP;
+  for (int32_t i = 0; i < B && rc == SFW_OK; ++i) {
+    sfw_handle h = nullptr;
+    rc = create_handle(params, device, b->stream, b->side, &h);
+    if (rc == SFW_OK) {
+      h->batch_member = true;
+      b->h.push_back(h);
+    }
+  }
+  if (rc != SFW_OK) {
+    sfw_batch_destroy(b);
+    return rc;
+  }
+  *out = b;
+  return SFW_OK;
+}
+
+int sfw_batch_destroy(sfw_batch b) {
+  if (!b) return SFW_OK;
+  (void)hipSetDevice(b->device);
+  if (b->stream) (void)hipStreamSynchronize(b->stream);
+  for (sfw_handle h : b->h) (void)destroy_handle(h);
+  b->pin_table.release();
+  b->table.release();
+  if (b->side) (void)hipStreamDestroy(b->side);
+  if (b->stream) (void)hipStreamDestroy(b->stream);
+  delete b;
+  return SFW_OK;
+}
+
+const char *sfw_batch_last_error(sfw_batch b) { return b ? b->err.c_str() : "null batch"; }
+
+int32_t sfw_batch_size(sfw_batch b) { return b ? static_cast<int32_t>(b->h.size()) : 0; }
+
+sfw_handle sfw_batch_member(sfw_batch b, int32_t i) {
+  return (b && i >= 0 && i < static_cast<int32_t>(b->h.size())) ? b->h[static_cast<size_t>(i)] : nullptr;
+}
+
+int sfw_batch_launch(sfw_batch b) {
+  if (!b) return SFW_ERR_INVALID_ARG;
+  const auto t0 = std::chrono::steady_clock::now();
+  const int rc = batch_launch(b);
+  b->us[1] = us_since(t0);
+  return rc;
+}
+
+int sfw_batch_fetch(sfw_batch b, sfw_best *best_out) {
+  if (!b) return SFW_ERR_INVALID_ARG;
+  const auto t0 = std::chrono::steady_clock::now();
+  const int rc = batch_fetch(b, best_out);
+  b->us[2] = us_since(t0);
+  return rc;
+}
+
+int sfw_batch_score_grid(sfw_batch b, const sfw_robot_state *rs, const double *linvels, int32_t nv, const double *angvels,
+                         int32_t nw, const sfw_goal_args *args, sfw_best *best_out) {
+  if (!b) return SFW_ERR_INVALID_ARG;
+  if (!rs || !args) return bfail(b, SFW_ERR_INVALID_ARG, "batch_score_grid: null robot states or goal arguments");
+  const auto t0 = std::chrono::steady_clock::now();
+  for (size_t i = 0; i < b->h.size(); ++i)
+    if (int e = sfw_grid_stage(b->h[i], rs + i, linvels, nv, angvels, nw, args + i, 0))
+      return bmember_fail(b, static_cast<int32_t>(i), e, "batch_score_grid: stage");
+  b->us[0] = us_since(t0);
+  if (int e = sfw_batch_launch(b)) return e;
+  return sfw_batch_fetch(b, best_out);
+}
+
+int sfw_batch_describe(sfw_batch b, sfw_batch_desc *out) {
+  if (!b || !out) return SFW_ERR_INVALID_ARG;
+  if (!b->launched) return bfail(b, SFW_ERR_STATE, "batch_describe before batch_launch");
+  *out = b->desc;
+  return SFW_OK;
+}
+
+int sfw_batch_last_us(sfw_batch b, int32_t which, double *us_out) {
+  if (!b || !us_out) return SFW_ERR_INVALID_ARG;
+  if (which < 0 || which > 2) return bfail(b, SFW_ERR_INVALID_ARG, "batch_last_us: which must be 0..2");
+  *us_out = b->us[which];
   return SFW_OK;
 }
 

@@ -233,7 +233,26 @@ hipError_t sfw_launch_social(const sfw_launch &L, hipStream_t stream, const sfw_
 // qualifies (L.cycle_counter / sel_out / index_base set; costs_host / sel_host optional)
 bool sfw_cycle_applies(const sfw_launch &L);
 hipError_t sfw_launch_cycle(const sfw_launch &L, hipStream_t stream);
+// Many handles' control cycles in ONE launch (sfw_batch_*, sfw_kernels.hip sfw_batch_cycle_kernel).  The device table is
+// first[B + 1] (uint32: member m owns blocks [first[m], first[m + 1]), one per sample) followed, at sfw_batch_recs_offset(B),
+// by B records; the host fills it in pinned memory and copies it in one piece.  Members of one launch share the kernel
+// instantiation: sfw_cycle_batch_variant (precision, groups, laser points) is the grouping key.
+struct sfw_batch_rec {
+  sfw_launch L;      // the member's launch as sfw_launch_cycle would launch it (sfw_cycle_batch_record)
+  int32_t k2_bytes;  // its block's LDS layout: K2 wave's area | k1s_lds | cycle_result
+  int32_t lds_bytes;
+};
+inline size_t sfw_batch_recs_offset(int B) { return (sizeof(uint32_t) * (static_cast<size_t>(B) + 1) + 15) & ~size_t(15); }
+int sfw_cycle_batch_variant(const sfw_launch &L);
+// rec <- L as the member of a batch (sfw_cycle_applies(L) must hold)
+void sfw_cycle_batch_record(const sfw_launch &L, sfw_batch_rec *rec);
+// one launch over `blocks` = first[B] blocks of `lds` dynamic LDS bytes each (the largest member's); every member of the
+// table has the variant `variant`
+hipError_t sfw_launch_cycle_batch(int variant, const uint32_t *d_first, const sfw_batch_rec *d_recs, int B, unsigned blocks,
+                                  size_t lds, hipStream_t stream);
 #ifndef SFW_STRICT_BUILD
+hipError_t sfw_launch_cycle_batch_strict(int variant, const uint32_t *d_first, const sfw_batch_rec *d_recs, int B,
+                                         unsigned blocks, size_t lds, hipStream_t stream);
 // the same launcher over the K2 kernels compiled with the longer polynomials (sfw_kernels_strict.hip): SFW_PRECISION_F64_STRICT
 // samples of a launch over T samples that the register form hands to flat-form waves (0: none)
 int64_t sfw_social_flat_items(int A, int O, int NG, int64_t T, int form, int cus);

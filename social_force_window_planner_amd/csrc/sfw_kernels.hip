@@ -732,6 +732,18 @@ __device__ __forceinline__ late_launch late_args() {
   asm volatile("" : "+s"(p));
   return static_cast<late_launch>(p);  // sfw_launch is the first kernel argument: offset 0 of the segment
 }
+// ... or, in a batched launch (sfw_batch_cycle_kernel: the kernel arguments hold no sfw_launch), the block's member record in
+// the batch table, made opaque the same way: still an s_load at the point of use
+template <bool BATCH> __device__ __forceinline__ late_launch late_args_of(late_launch rec) {
+  if constexpr (!BATCH) {
+    (void)rec;
+    return late_args();
+  } else {
+    const __attribute__((address_space(4))) void *p = rec;
+    asm volatile("" : "+s"(p));
+    return static_cast<late_launch>(p);
+  }
+}
 
 // Measurement aid (sfw_set_timing): the middle wave of a K2 launch (wave 0 is the never-scored (0,0) sample) records the shader-clock counter (s_memtime) and the
 // constant-rate counter (s_memrealtime) when it starts and when it ends; the host turns the two differences into the
@@ -2071,9 +2083,12 @@ __device__ __forceinline__ int cycle_wait_ready(const cycle_result *res, int nee
   return r;
 }
 #define K2_SYNC() do { if constexpr (CYCLE) wave_sync(); else __syncthreads(); } while (0)
-template <typename R, bool GROUPS, int CAP, bool OBS, bool CYCLE>
+// BATCH (CYCLE only): the wave of a batched cycle launch; `Lb` is its member's record (L, read late), no clock probe
+template <typename R, bool GROUPS, int CAP, bool OBS, bool CYCLE, bool BATCH = false>
 __device__ __forceinline__ void social_flat_wave(const sfw_launch &L, char *const smem, const k1s_lds *const k1, cycle_result *const res,
-                                                 const unsigned bid, const unsigned nblk, const int64_t item_base) {
+                                                 const unsigned bid, const unsigned nblk, const int64_t item_base,
+                                                 const late_launch Lb = nullptr) {
+  static_assert(CYCLE || !BATCH, "a batched wave is a cycle kernel's wave");
   const int lane = threadIdx.x;
   const int A = L.A, O = L.O;
   const int NG = GROUPS ? L.NG : 0;
@@ -2106,7 +2121,7 @@ __device__ __forceinline__ void social_flat_wave(const sfw_launch &L, char *cons
       return;
     }
   }
-  clock_probe(0);
+  if constexpr (!BATCH) clock_probe(0);
   // wave-uniform, but formed from table loads: made scalar explicitly (as a VGPR pair it is held — in scratch, once the
   // laser-point pass needs the registers — across the whole rollout for the two lanes that fetch the robot records)
   const int64_t rsample_v = CYCLE ? 0 : robot_sample_of_item(L, first_local);
@@ -2129,7 +2144,7 @@ __device__ __forceinline__ void social_flat_wave(const sfw_launch &L, char *cons
       s.fjx[sl] = s.fjy[sl] = 0.0;
     }
   } else {
-    const agent_consts c0 = load_agent_consts(late_args(), F32);
+    const agent_consts c0 = load_agent_consts(late_args_of<BATCH>(Lb), F32);
     for (int sl = lane; sl < A; sl += WAVE) {
       const double px = L.agent_pos[2 * sl], py = L.agent_pos[2 * sl + 1];
       const double vx = L.agent_vel[2 * sl], vy = L.agent_vel[2 * sl + 1];
@@ -2160,7 +2175,7 @@ __device__ __forceinline__ void social_flat_wave(const sfw_launch &L, char *cons
     }
   }
   if (OBS && O > 0) {
-    const agent_consts c0 = load_agent_consts(late_args(), F32);
+    const agent_consts c0 = load_agent_consts(late_args_of<BATCH>(Lb), F32);
     for (int sl = lane; sl < A; sl += WAVE) s.oscale[sl] = obstacle_scale<R>(k0, c0, L.agent_c[sl].radius);
   }
   for (int sl = A + lane; sl < cap; sl += WAVE) {  // the dummy slots: finite state, accumulators nobody reads
@@ -2186,7 +2201,7 @@ __device__ __forceinline__ void social_flat_wave(const sfw_launch &L, char *cons
     K2_SYNC();
   };
   if constexpr (GROUPS) {
-    if (!L.resume) add_group_forces(k0, load_agent_consts(late_args(), F32));  // a class record's force already has them
+    if (!L.resume) add_group_forces(k0, load_agent_consts(late_args_of<BATCH>(Lb), F32));  // a class record's force already has them
   }
 
   const int P = A * (A - 1) / 2;  // unordered pairs
@@ -2339,7 +2354,7 @@ __device__ __forceinline__ void social_flat_wave(const sfw_launch &L, char *cons
     if (lane < A) { s.fcx[lane] += abl_fx; s.fcy[lane] += abl_fy; abl_ix = s.px[lane] + 1e-3; abl_iy = s.py[lane]; abl_fx = abl_fy = 0.0; }
 #endif
     // ---- per-agent pass: its parameters are read here, not held across the pair loop -----------
-    const late_launch La = late_args();
+    const late_launch La = late_args_of<BATCH>(Lb);
     const agent_consts c = load_agent_consts(La, F32);
     const sfw_agent_const *const agent_c = La->agent_c;
     // the cycle kernel's hand-over, behind the pair pass (which needs the pre-step state only): the wave that rolls the robot
@@ -2543,7 +2558,7 @@ __device__ __forceinline__ void social_flat_wave(const sfw_launch &L, char *cons
     if constexpr (GROUPS) add_group_forces(k, c);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // a prefetched robot record may still be in flight
-  const late_launch Le = late_args();
+  const late_launch Le = late_args_of<BATCH>(Lb);
   if (Le->phase == SFW_PHASE_PREFIX) {  // leave the class record
     sfw_cls_agent *rec = Le->out_state + first_local * A;
     for (int sl = lane; sl < A; sl += WAVE) {
@@ -2555,7 +2570,7 @@ __device__ __forceinline__ void social_flat_wave(const sfw_launch &L, char *cons
       rec[sl] = c;
     }
     if (lane == 0) Le->out_dead[first_local] = s.dead[0];
-    clock_probe(1);
+    if constexpr (!BATCH) clock_probe(1);
     return;
   }
   double sw_acc = 0.0;
@@ -2570,7 +2585,7 @@ __device__ __forceinline__ void social_flat_wave(const sfw_launch &L, char *cons
   } else {
     finish_wave(s, lane, 1, 1, first_local, sw_acc);
   }
-  clock_probe(1);
+  if constexpr (!BATCH) clock_probe(1);
 }
 #undef K2_SYNC
 template <typename R, bool GROUPS, int CAP, bool OBS>
@@ -2738,8 +2753,12 @@ __global__ void __launch_bounds__(64) sfw_key_table_kernel(const sfw_sel *sel, d
 constexpr int CYCLE_BLOCK = 4 * WAVE;
 constexpr int CYCLE_MAX_SAMPLES = 1024;
 constexpr int CYCLE_HEAD = 8;  // robot steps handed to the pedestrians' wave ahead of the rest
-template <typename R, bool GROUPS, bool OBS>
-__global__ void __launch_bounds__(CYCLE_BLOCK) sfw_cycle_kernel(const sfw_launch L, const int k2_bytes) {
+// The block of one sample: the body of sfw_cycle_kernel (L = the kernel arguments; sample blockIdx.x of gridDim.x, read where
+// they are used as before — bid / nblk are unused) and of sfw_batch_cycle_kernel (L = the block's member record `Lb` in the batch
+// table; member-local sample `bid` of `nblk`).
+template <typename R, bool GROUPS, bool OBS, bool BATCH>
+__device__ __forceinline__ void cycle_block(const sfw_launch &L, const late_launch Lb, const int k2_bytes, const unsigned bid,
+                                            const unsigned nblk) {
   extern __shared__ __attribute__((aligned(16))) char smem[];  // K2 wave's area (from LDS address 0) | k1s_lds | cycle_result
   const int tid = threadIdx.x, wave = tid / WAVE, lane = tid % WAVE;
   const int S = L.S;
@@ -2759,12 +2778,12 @@ __global__ void __launch_bounds__(CYCLE_BLOCK) sfw_cycle_kernel(const sfw_launch
   // (the hand-over word starts at 0: written by thread 0, and a block barrier before anybody polls or publishes)
   if (tid == 0) res->ready = res->fdone = 0;
   __syncthreads();
-  const k1s_sample q = k1s_sample_of(L, blockIdx.x);
+  const k1s_sample q = k1s_sample_of(L, BATCH ? bid : blockIdx.x);
   // pedestrians to integrate?  (no agents at all, or a robot alone without a laser point: social work identically 0)
   const bool social = q.scored && L.A > 0 && !(L.A == 1 && L.O == 0 && L.NG == 0);
   if (wave == 0 && social) {
     sfwm::fp_mode_for_omod();
-    social_flat_wave<R, GROUPS, 64, OBS, true>(L, smem, &a, res, blockIdx.x, gridDim.x, 0);
+    social_flat_wave<R, GROUPS, 64, OBS, true, BATCH>(L, smem, &a, res, BATCH ? bid : blockIdx.x, BATCH ? nblk : gridDim.x, 0, Lb);
   } else {
     if (wave == 1) {
       // the first CYCLE_HEAD steps first, published to the pedestrians' wave (res->ready) as soon as they stand; then the rest
@@ -2835,7 +2854,7 @@ __global__ void __launch_bounds__(CYCLE_BLOCK) sfw_cycle_kernel(const sfw_launch
   unsigned prev = 0;
   if (lane == 0) prev = atomicAdd(L.cycle_counter, 1u);
   prev = __shfl(prev, 0, WAVE);
-  if (prev != gridDim.x - 1) return;
+  if (prev != (BATCH ? nblk : gridDim.x) - 1) return;
   __threadfence();
   sfw_sel best = sel_empty();
   for (int64_t i = lane; i < L.chunk_count; i += WAVE) {
@@ -2850,6 +2869,32 @@ __global__ void __launch_bounds__(CYCLE_BLOCK) sfw_cycle_kernel(const sfw_launch
     if (L.sel_host) *L.sel_host = best;
     *L.cycle_counter = 0u;  // for the next launch (stream order)
   }
+}
+template <typename R, bool GROUPS, bool OBS>
+__global__ void __launch_bounds__(CYCLE_BLOCK) sfw_cycle_kernel(const sfw_launch L, const int k2_bytes) {
+  cycle_block<R, GROUPS, OBS, false>(L, nullptr, k2_bytes, 0u, 0u);
+}
+// Many handles' control cycles in one launch (sfw_batch_*): a 1-D grid over the samples of all members, member m's T_m blocks
+// from first[m] on.  A block finds its member by a binary search over first[] (scalar loads, uniform) and runs the block of
+// its member-local sample with the member's record as L: same statements as sfw_cycle_kernel, so the costs, the selection
+// and the captured points are bit-identical to the member's own launch.  The dynamic LDS is the largest member's; a block lays
+// its own member's areas out from its own k2_bytes.  Each member keeps its own cycle_counter: the last of ITS blocks selects.
+template <typename R, bool GROUPS, bool OBS>
+__global__ void __launch_bounds__(CYCLE_BLOCK) sfw_batch_cycle_kernel(const uint32_t *const first, const sfw_batch_rec *const recs,
+                                                                     const int B) {
+  typedef const __attribute__((address_space(4))) uint32_t *first_ptr;
+  typedef const __attribute__((address_space(4))) sfw_batch_rec *rec_ptr;
+  const first_ptr f = (first_ptr)first;
+  const unsigned b = blockIdx.x;
+  int lo = 0, hi = B;  // first[lo] <= b < first[hi]
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (f[mid] <= b) lo = mid;
+    else hi = mid;
+  }
+  const rec_ptr r = (rec_ptr)recs + lo;
+  const late_launch Lb = (late_launch)&r->L;
+  cycle_block<R, GROUPS, OBS, true>(*(const sfw_launch *)Lb, Lb, r->k2_bytes, b - f[lo], f[lo + 1] - f[lo]);
 }
 
 }  // namespace
@@ -3293,4 +3338,42 @@ hipError_t sfw_launch_cycle(const sfw_launch &L, hipStream_t stream) {
   if (L.p.precision == SFW_PRECISION_F32) return launch_cycle_typed<float>(L, stream);
 #endif
   return launch_cycle_typed<double>(L, stream);
+}
+// ---- many handles' control cycles in one launch (sfw_batch_*) --------------------------------------------------------
+// The key members of one batched launch share: precision (the build and the force type) x the kernel variant the single
+// launcher picks (groups / laser points / neither)
+int sfw_cycle_batch_variant(const sfw_launch &L) {
+  const int v = L.NG > 0 ? 2 : L.O > 0 ? 1 : 0;
+  const int prec = L.p.precision == SFW_PRECISION_F64_STRICT ? 2 : L.p.precision == SFW_PRECISION_F32 ? 1 : 0;
+  return 3 * prec + v;
+}
+void sfw_cycle_batch_record(const sfw_launch &L, sfw_batch_rec *rec) {
+  // what launch_cycle_typed would launch: the same obs_lds decision, the same layout
+  rec->L = L;
+  const bool social = L.A > 0 && !(L.A == 1 && L.O == 0 && L.NG == 0);
+  const wave_plan fl{1, 0, true};
+  rec->L.k.obs_lds = (social && obs_in_lds(fl, L.A, L.O, L.NG, L.n_grp_mem, L.chunk_count, L.n_cu > 0 ? L.n_cu : SFW_DEFAULT_CUS)) ? 1 : 0;
+  rec->L.clock_probe = nullptr;  // (no clock probe in a batch)
+  const size_t k2 = cycle_k2_bytes(rec->L, rec->L.k.obs_lds != 0);
+  size_t k1_bytes = 0;
+  (void)k1s_lds(nullptr, L.S, &k1_bytes);
+  rec->k2_bytes = static_cast<int32_t>(k2);
+  rec->lds_bytes = static_cast<int32_t>(k2 + k1_bytes + ((sizeof(cycle_result) + 15) & ~size_t(15)));
+}
+template <typename R>
+static hipError_t launch_cycle_batch_typed(int v, const uint32_t *d_first, const sfw_batch_rec *d_recs, int B, unsigned blocks,
+                                           size_t lds, hipStream_t stream) {
+  const dim3 grid(blocks), block(CYCLE_BLOCK);
+  if (v == 2) hipLaunchKernelGGL((sfw_batch_cycle_kernel<R, true, true>), grid, block, lds, stream, d_first, d_recs, B);
+  else if (v == 1) hipLaunchKernelGGL((sfw_batch_cycle_kernel<R, false, true>), grid, block, lds, stream, d_first, d_recs, B);
+  else hipLaunchKernelGGL((sfw_batch_cycle_kernel<R, false, false>), grid, block, lds, stream, d_first, d_recs, B);
+  return hipGetLastError();
+}
+hipError_t sfw_launch_cycle_batch(int variant, const uint32_t *d_first, const sfw_batch_rec *d_recs, int B, unsigned blocks,
+                                  size_t lds, hipStream_t stream) {
+  if (B < 1 || blocks < 1 || variant < 0 || variant >= 9) return hipErrorInvalidValue;
+#ifndef SFW_STRICT_BUILD
+  if (variant / 3 == 1) return launch_cycle_batch_typed<float>(variant % 3, d_first, d_recs, B, blocks, lds, stream);
+#endif
+  return launch_cycle_batch_typed<double>(variant % 3, d_first, d_recs, B, blocks, lds, stream);
 }

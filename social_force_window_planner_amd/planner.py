@@ -17,6 +17,7 @@ from ._abi import (
     SFW_ERR_NO_DEVICE,
     SFW_OK,
     SfwAgent,
+    SfwBatchDesc,
     SfwBest,
     SfwBestKey,
     SfwGoalArgs,
@@ -116,6 +117,19 @@ def lib():
         L.sfw_plan_shared_prefix.argtypes = [vp, C.c_int32, vp, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double,
                                              C.c_double, C.c_int32, C.c_int32, vp, vp, C.c_int32, C.POINTER(C.c_int32)]
         L.sfw_multi_grid_points.argtypes = [vp, C.c_int64, vp, C.c_int32, C.POINTER(C.c_int32)]
+        L.sfw_batch_create.argtypes = [C.POINTER(SfwParams), C.c_int, C.c_int32, C.POINTER(vp)]
+        L.sfw_batch_destroy.argtypes = [vp]
+        L.sfw_batch_last_error.argtypes = [vp]
+        L.sfw_batch_last_error.restype = C.c_char_p
+        L.sfw_batch_size.argtypes = [vp]
+        L.sfw_batch_size.restype = C.c_int32
+        L.sfw_batch_member.argtypes = [vp, C.c_int32]
+        L.sfw_batch_member.restype = vp
+        L.sfw_batch_launch.argtypes = [vp]
+        L.sfw_batch_fetch.argtypes = [vp, vp]
+        L.sfw_batch_score_grid.argtypes = [vp, vp, vp, C.c_int32, vp, C.c_int32, vp, vp]
+        L.sfw_batch_describe.argtypes = [vp, C.POINTER(SfwBatchDesc)]
+        L.sfw_batch_last_us.argtypes = [vp, C.c_int32, C.POINTER(C.c_double)]
         _lib = L
     return _lib
 
@@ -143,7 +157,20 @@ class HipScorer:
             raise SfwError(rc, "sfw_create")
         self._grid = None
 
+    @classmethod
+    def _member_view(cls, handle, params, owner):
+        """A non-owning view of a handle another object owns (BatchScorer.member): every call but destruction."""
+        v = cls.__new__(cls)
+        v.params = params
+        v._h = C.c_void_p(handle)
+        v._grid = None
+        v._owner = owner  # (keeps the owner, and so the handle, alive as long as the view)
+        return v
+
     def close(self):
+        if getattr(self, "_owner", None) is not None:
+            self._h = C.c_void_p()
+            return
         if getattr(self, "_h", None):
             lib().sfw_destroy(self._h)
             self._h = C.c_void_p()
@@ -486,3 +513,85 @@ class MultiScorer:
         self._check(lib().sfw_multi_grid_points(self._m, index, pts.ctypes.data, points_cap, C.byref(n)),
                     "sfw_multi_grid_points")
         return pts[: min(n.value, points_cap)].copy()
+
+
+class BatchScorer:
+    """B planners on one MI355X whose control cycles are scored together (sfw_batch_*): one launch of the batched cycle
+    kernel per kernel variant for the members that qualify, the others on their usual path on the same stream.  Each
+    member's results are bit-identical to scoring it alone."""
+
+    def __init__(self, params: SfwParams | None = None, device: int = 0, B: int = 1):
+        self.params = params if params is not None else default_params()
+        self._b = C.c_void_p()
+        rc = lib().sfw_batch_create(C.byref(self.params), device, B, C.byref(self._b))
+        if rc == SFW_ERR_NO_DEVICE:
+            raise SfwError(rc, "sfw_batch_create", "no HIP device visible; this library has no CPU fallback")
+        if rc != SFW_OK:
+            raise SfwError(rc, "sfw_batch_create")
+        self.B = B
+        self._members = [HipScorer._member_view(lib().sfw_batch_member(self._b, i), self.params, self) for i in range(B)]
+
+    def close(self):
+        if getattr(self, "_b", None):
+            for m in self._members:
+                m.close()
+            lib().sfw_batch_destroy(self._b)
+            self._b = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc, what):
+        if rc != SFW_OK:
+            raise SfwError(rc, what, (lib().sfw_batch_last_error(self._b) or b"").decode())
+
+    def member(self, i):
+        """Member i as a HipScorer that does not own its handle (world state, staging, single-member scoring, points)."""
+        return self._members[i]
+
+    def stage(self, i, robot_state, linvels, angvels, goal_args):
+        self._members[i].stage(robot_state, linvels, angvels, goal_args)
+
+    def launch(self):
+        self._check(lib().sfw_batch_launch(self._b), "sfw_batch_launch")
+
+    def fetch(self):
+        """One wait for the batch: the B selections (dicts), member order."""
+        best = (SfwBest * self.B)()
+        self._check(lib().sfw_batch_fetch(self._b, best), "sfw_batch_fetch")
+        return [b.as_dict() for b in best]
+
+    def _costs(self, i):
+        m = self._members[i]
+        v = m.costs_view()
+        return v.copy() if v is not None else m.fetch()[0]
+
+    def score_grid(self, robot_states, linvels, angvels, goal_args_list):
+        """sfw_batch_score_grid: member i scores the grid from robot_states[i] with goal_args_list[i].  A list of
+        (costs, best), member order."""
+        lin, ang = _f64(linvels), _f64(angvels)
+        rs = (SfwRobotState * self.B)(*[SfwRobotState(*r) for r in robot_states])
+        ga = (SfwGoalArgs * self.B)(*[SfwGoalArgs(*g) for g in goal_args_list])
+        best = (SfwBest * self.B)()
+        self._check(lib().sfw_batch_score_grid(self._b, rs, lin.ctypes.data, len(lin), ang.ctypes.data, len(ang), ga, best),
+                    "sfw_batch_score_grid")
+        for m in self._members:
+            m._grid = (len(lin), len(ang))
+        return [(self._costs(i), best[i].as_dict()) for i in range(self.B)]
+
+    def describe(self):
+        d = SfwBatchDesc()
+        self._check(lib().sfw_batch_describe(self._b, C.byref(d)), "sfw_batch_describe")
+        return {n: getattr(d, n) for n, _ in SfwBatchDesc._fields_}
+
+    def last_us(self):
+        """Host wall-clock of the last calls: stage (score_grid only), enqueue, wait + fetch (microseconds)."""
+        out = {}
+        for which, name in enumerate(("stage", "enqueue", "wait_fetch")):
+            v = C.c_double()
+            self._check(lib().sfw_batch_last_us(self._b, which, C.byref(v)), "sfw_batch_last_us")
+            out[name] = v.value
+        return out
