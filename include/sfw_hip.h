@@ -376,6 +376,44 @@ int sfw_set_points_capture(sfw_handle h, int32_t enabled);
  * to record their own events. */
 void *sfw_stream(sfw_handle h);
 
+/* ---- per-term costs and re-scoring under other weights --------------------
+ * A sample's cost is the sum of five weighted terms (src/sfw_planner.cpp:643-667; the reference's debug line prints them,
+ * :668-674), and the weights are the only part of sfw_params that enters after the rollout: validity (off-map poses,
+ * illegal footprints, pedestrian contact) never depends on them.  With capture on, a scoring launch keeps the five
+ * unweighted terms of every sample, and any weight vector can be applied to them again without another rollout — the
+ * per-critic breakdown of a nav2 controller, or "what would the planner pick under these weights?". */
+#define SFW_TERM_VEL 0      /* vel_diff = |max_vel_x - vx| / max_vel_x (:654)                                */
+#define SFW_TERM_DISTANCE 1 /* d = squared distance from the final pose to the way-point (:643-646)        */
+#define SFW_TERM_ANGLE 2    /* ang_diff = |normalizeAngle(atan2 - theta)| / pi (:647-652)                  */
+#define SFW_TERM_COSTMAP 3  /* costmap_cost = mean footprint cost / 255 over the steps (:575, :656)        */
+#define SFW_TERM_SOCIAL 4   /* social_work of the pedestrian simulation (:613-629); 0.0 without agents    */
+#define SFW_N_TERMS 5
+#define SFW_RESCORE_MAX_K 1024
+/* One weight vector = the five weights of sfw_params in term order. */
+typedef struct sfw_weights {
+  double vel, distance, angle, costmap, social; /* vel_weight, distance_weight, angle_weight, costmap_weight, social_weight */
+} sfw_weights;
+/* Term capture, off by default; takes effect at the next sfw_grid_launch / sfw_score_grid (also in a sfw_batch_launch:
+ * batch members carry the capture buffer in their record of the batched cycle kernel — no member changes path for it).
+ * Every grid launch then also writes the five terms of every sample into a device buffer of the handle, SoA [5][nv*nw],
+ * from the same statements that form the cost: 40 bytes per sample (2.6 MB at 256 x 256 samples, 671 MB at 4096 x 4096),
+ * allocated by the first stage or launch that captures, grown with the grid, freed when capture is turned off (after a wait
+ * for the handle's stream) or the handle is destroyed.  A sample whose cost is a sentinel (SFW_COST_INVALID, SFW_COST_SKIPPED) has
+ * that sentinel in all five terms.  Costs, sentinels, selection and captured points do not depend on it. */
+int sfw_set_terms_capture(sfw_handle h, int32_t enabled);
+/* K weight vectors (1 <= K <= SFW_RESCORE_MAX_K, all finite: else SFW_ERR_INVALID_ARG) over the terms of the handle's last
+ * launch: best_out (K records) receives for every k what sfw_score_grid would return with those five weights in sfw_params —
+ * field for field, incl. n_valid (a negative weight can make a cost negative, hence unselectable, as in the reference), the
+ * cost == 10000.0 rule, the tie-breaks and index_base; costs_out (nullable) K x nv*nw doubles, weight-major, sample order,
+ * bit-identical to that call's cost vector.  One kernel over samples x weight tiles plus a K-way reduction on the handle's
+ * stream, ordered behind the launch; blocking.  Read-only for the launch: its cost vector (sfw_grid_costs_view,
+ * sfw_grid_fetch), selection and captured points stay as they were.  SFW_ERR_STATE when the last launch did not capture
+ * terms, or a stage or sfw_score_one came in since. */
+int sfw_grid_rescore(sfw_handle h, const sfw_weights *w, int32_t K, sfw_best *best_out, double *costs_out);
+/* count x 5 doubles, sample-major (terms_out[i * 5 + k] = term k of sample first + i), of the last launch; valid under the
+ * same conditions as sfw_grid_rescore.  One device-to-host copy per term. */
+int sfw_grid_terms(sfw_handle h, int64_t first, int64_t count, double *terms_out);
+
 /* ---- one process, several devices ---------------------------------------
  * The reference plugin is ONE process (sfw_plugin.xml:1-9; computeVelocityCommands,
  * src/sfw_planner_node.cpp:220-331), so a host that wants the (v,w) grid on several

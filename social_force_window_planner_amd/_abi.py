@@ -200,7 +200,23 @@ EXPORTED_SYMBOLS = (
     "sfw_batch_score_grid",
     "sfw_batch_describe",
     "sfw_batch_last_us",
+    "sfw_set_terms_capture",
+    "sfw_grid_rescore",
+    "sfw_grid_terms",
 )
+# per-term costs (sfw_set_terms_capture / sfw_grid_rescore / sfw_grid_terms)
+SFW_TERM_VEL, SFW_TERM_DISTANCE, SFW_TERM_ANGLE, SFW_TERM_COSTMAP, SFW_TERM_SOCIAL = 0, 1, 2, 3, 4
+SFW_N_TERMS = 5
+SFW_RESCORE_MAX_K = 1024
+
+
+class SfwWeights(C.Structure):
+    """sfw_weights (include/sfw_hip.h): the five weights of sfw_params in term order."""
+
+    _fields_ = [("vel", C.c_double), ("distance", C.c_double), ("angle", C.c_double), ("costmap", C.c_double),
+                ("social", C.c_double)]
+
+
 SFW_MULTI_RCCL, SFW_MULTI_HOST_REDUCE = 0, 1
 SFW_BATCH_MAX = 256
 

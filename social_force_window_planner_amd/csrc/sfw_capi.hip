@@ -231,6 +231,16 @@ struct sfw_planner_s {
   pinned_buf pin_map, pin_world, pin_out, pin_cls;
   pinned_buf pin_one;     // sfw_score_one's outputs where the one-launch kernel writes them (cost | n_points | coll_step | points)
   pinned_buf pin_mirror;  // costs + selection record as the selection kernels of the last launch leave them (device writes)
+  // sfw_set_terms_capture: every grid launch also leaves the five cost terms of every sample in `terms` (SoA [5][T]);
+  // sfw_grid_rescore / sfw_grid_terms read them while terms_launched holds (the last launch captured; a stage or
+  // sfw_score_one since clears `launched`)
+  bool capture_terms = false, terms_launched = false;
+  bool early_poses_terms = false;  // the pose rollout the stage enqueued (early_poses) wrote the pedestrian-free terms too
+  dev_buf<double> terms;
+  dev_buf<sfw_weights> rescore_w;  // sfw_grid_rescore: the weight vectors on the device, its partial records, its cost vectors
+  dev_buf<sfw_sel> rescore_partials;
+  dev_buf<double> rescore_costs;
+  pinned_buf pin_rescore;          // K records (written by the kernels) | K weight vectors (copied from)
   // a member of a sfw_batch: the batch's streams are borrowed (sfw_destroy refuses the handle; the batch destroys it)
   bool owns_streams = true;
   bool batch_member = false;
@@ -1003,6 +1013,12 @@ int plan_tables_device(sfw_handle h, int64_t chunk, bool may_start_poses) {
       }
       if (h->timing) SFW_HIP(h, hipEventRecord(h->ev[0], h->stream));
       h->early_poses_timed = h->timing;
+      h->early_poses_terms = h->capture_terms;
+      if (h->capture_terms) {
+        SFW_HIP(h, h->terms.reserve(static_cast<size_t>(SFW_N_TERMS) * static_cast<size_t>(T)));
+        L.terms = h->terms.p;
+        L.terms_T = T;
+      }
       if (h->arena_pending) {  // no copy was enqueued: this kernel fetches the arena, and reads its sample vectors at their host addresses
         L.arena_host = h->pin_world.p + h->arena_from;
         L.arena_dev = h->world.p + h->arena_from;
@@ -1264,6 +1280,7 @@ struct launch_prep {
   char *cap_pts = nullptr, *cap_n = nullptr, *cap_coll = nullptr;
   double *costs_host = nullptr;
   sfw_sel *sel_host = nullptr;
+  double *terms = nullptr;  // sfw_set_terms_capture: the terms buffer, else null
 };
 
 // timing: record the per-kernel events of this launch (h->timing; a batch launch never does)
@@ -1306,7 +1323,8 @@ int launch_prepare(sfw_handle h, bool timing, launch_prep &lp) {
   if (prefix) chunk = h->prefix_chunk;
   // the stage enqueued K1a of this (single-chunk) grid already — unless sfw_set_timing(1) arrived since: the events of a
   // timed launch bracket its own kernels, so the pose rollout runs again behind a freshly recorded ev[0]
-  const bool poses_done = h->early_poses && chunk >= T && (!timing || h->early_poses_timed);
+  const bool poses_done = h->early_poses && chunk >= T && (!timing || h->early_poses_timed) &&
+                          (!h->capture_terms || h->early_poses_terms);  // (capture turned on since the stage: roll out again)
   h->early_poses = false;                                 // ... once: a second launch of the same stage rolls out again
   if (timing) {
     SFW_HIP(h, h->clock.reserve(4));
@@ -1376,6 +1394,12 @@ int launch_prepare(sfw_handle h, bool timing, launch_prep &lp) {
   lp.cap_coll = cap_coll;
   lp.costs_host = costs_host;
   lp.sel_host = sel_host;
+  h->terms_launched = false;
+  if (h->capture_terms) {
+    SFW_HIP(h, h->terms.reserve(static_cast<size_t>(SFW_N_TERMS) * static_cast<size_t>(T)));
+    lp.terms = h->terms.p;
+    h->terms_launched = true;
+  }
   return SFW_OK;
 }
 
@@ -1393,6 +1417,8 @@ bool cycle_launch_of(sfw_handle h, const launch_prep &lp, sfw_launch &L) {
   L.clock_probe = lp.timing ? h->clock.p : nullptr;
   L.costs_host = lp.costs_host;
   L.sel_host = lp.sel_host;
+  L.terms = lp.terms;
+  L.terms_T = lp.T;
   if (!sfw_cycle_applies(L)) return false;
   if (h->arena_pending) {  // the kernel's blocks fetch the arena from pinned memory themselves: no copy at all this cycle
     L.arena_host = h->pin_world.p + h->arena_from;
@@ -1441,6 +1467,8 @@ int launch_kernels(sfw_handle h, const launch_prep &lp) {
       L.force_alive = 1;
     }
     L.clock_probe = timing ? h->clock.p : nullptr;  // every K2 dispatch writes it; the last one (the launch over the samples) stays
+    L.terms = lp.terms;
+    L.terms_T = T;
     if (!single && timing) SFW_HIP(h, hipEventRecord(h->chunk_ev[3 * c], h->stream));
     if (prefix) {
       // K1a -> { K2 prefix phase on the main stream  ||  K1b + K1c on the side stream } -> K2 suffix phase.
@@ -1695,6 +1723,11 @@ int destroy_handle(sfw_handle h) {
   h->clock.release();
   h->cycle_counter.release();
   h->pin_cap.release();
+  h->terms.release();
+  h->rescore_w.release();
+  h->rescore_partials.release();
+  h->rescore_costs.release();
+  h->pin_rescore.release();
   h->points.release();
   h->n_points.release();
   h->one_out.release();
@@ -2151,6 +2184,88 @@ int sfw_last_launch_ms(sfw_handle h, int32_t which, float *ms_out) {
 int sfw_set_points_capture(sfw_handle h, int32_t enabled) {
   if (!h) return SFW_ERR_INVALID_ARG;
   h->capture_points = enabled != 0;
+  return SFW_OK;
+}
+
+int sfw_set_terms_capture(sfw_handle h, int32_t enabled) {
+  if (!h) return SFW_ERR_INVALID_ARG;
+  h->capture_terms = enabled != 0;
+  if (!h->capture_terms) {
+    h->terms_launched = false;
+    h->early_poses_terms = false;
+    if (h->terms.p) {
+      SFW_HIP(h, hipSetDevice(h->device));
+      SFW_HIP(h, hipStreamSynchronize(h->stream));  // (a launch in flight may still be writing there)
+      h->terms.release();
+    }
+  }
+  return SFW_OK;
+}
+
+int sfw_grid_rescore(sfw_handle h, const sfw_weights *w, int32_t K, sfw_best *best_out, double *costs_out) {
+  if (!h) return SFW_ERR_INVALID_ARG;
+  if (!w || !best_out) return fail(h, SFW_ERR_INVALID_ARG, "grid_rescore: weights or best_out is NULL");
+  if (K < 1 || K > SFW_RESCORE_MAX_K) return fail(h, SFW_ERR_INVALID_ARG, "grid_rescore: K out of [1, SFW_RESCORE_MAX_K]");
+  if (!all_finite(reinterpret_cast<const double *>(w), static_cast<size_t>(K) * SFW_N_TERMS))
+    return fail(h, SFW_ERR_INVALID_ARG, "grid_rescore: non-finite weight");
+  if (!h->launched || !h->terms_launched)
+    return fail(h, SFW_ERR_STATE, "grid_rescore: the last launch did not capture terms (sfw_set_terms_capture), or a stage or "
+                                  "sfw_score_one came in since");
+  SFW_HIP(h, hipSetDevice(h->device));
+  const int64_t T = static_cast<int64_t>(h->nv) * h->nw;
+  const size_t sel_bytes = (sizeof(sfw_sel) * static_cast<size_t>(K) + 15) & ~size_t(15);
+  const size_t w_bytes = sizeof(sfw_weights) * static_cast<size_t>(K);
+  // (growing the pinned area frees the old one: nothing in the stream may still be writing there)
+  if (sel_bytes + w_bytes > h->pin_rescore.cap) SFW_HIP(h, hipStreamSynchronize(h->stream));
+  SFW_HIP(h, h->pin_rescore.reserve(sel_bytes + w_bytes));
+  sfw_sel *const sel_host = reinterpret_cast<sfw_sel *>(h->pin_rescore.p);
+  std::memcpy(h->pin_rescore.p + sel_bytes, w, w_bytes);
+  SFW_HIP(h, h->rescore_w.reserve(static_cast<size_t>(K)));
+  SFW_HIP(h, hipMemcpyAsync(h->rescore_w.p, h->pin_rescore.p + sel_bytes, w_bytes, hipMemcpyHostToDevice, h->stream));
+  // weight vectors per launch: all K, or — with costs_out — as many as 256 MB of device cost vectors hold (each launch's are
+  // copied out behind it)
+  int32_t k_step = K;
+  if (costs_out) {
+    const int64_t fit = std::max<int64_t>(1, (int64_t(256) << 20) / (static_cast<int64_t>(sizeof(double)) * T));
+    k_step = static_cast<int32_t>(std::min<int64_t>(K, fit));
+    SFW_HIP(h, h->rescore_costs.reserve(static_cast<size_t>(k_step) * static_cast<size_t>(T)));
+  }
+  for (int32_t k0 = 0; k0 < K; k0 += k_step) {
+    const int32_t n = std::min(k_step, K - k0);
+    const int64_t blocks = sfw_rescore_blocks(T, n);
+    SFW_HIP(h, h->rescore_partials.reserve(static_cast<size_t>(blocks) * static_cast<size_t>(n)));
+    SFW_HIP(h, sfw_launch_rescore(h->terms.p, T, h->rescore_w.p + k0, n, h->d_linvels, h->d_angvels, h->nw, h->index_base,
+                                  h->rescore_partials.p, costs_out ? h->rescore_costs.p : nullptr, sel_host + k0, h->stream));
+    if (costs_out)
+      SFW_HIP(h, hipMemcpyAsync(costs_out + static_cast<int64_t>(k0) * T, h->rescore_costs.p,
+                                sizeof(double) * static_cast<size_t>(n) * static_cast<size_t>(T), hipMemcpyDeviceToHost, h->stream));
+  }
+  SFW_HIP(h, h->pin_rescore.mark(h->stream));
+  SFW_HIP(h, wait_stream(h));
+  h->pin_rescore.pending = false;
+  stream_is_idle(h);
+  for (int32_t k = 0; k < K; ++k) sel_to_best(h, sel_host[k], best_out + k, nullptr);
+  return SFW_OK;
+}
+
+int sfw_grid_terms(sfw_handle h, int64_t first, int64_t count, double *terms_out) {
+  if (!h) return SFW_ERR_INVALID_ARG;
+  if (!h->launched || !h->terms_launched)
+    return fail(h, SFW_ERR_STATE, "grid_terms: the last launch did not capture terms (sfw_set_terms_capture), or a stage or "
+                                  "sfw_score_one came in since");
+  const int64_t T = static_cast<int64_t>(h->nv) * h->nw;
+  if (count < 0 || first < 0 || first > T || count > T - first) return fail(h, SFW_ERR_INVALID_ARG, "grid_terms: range out of the grid");
+  if (count > 0 && !terms_out) return fail(h, SFW_ERR_INVALID_ARG, "grid_terms: terms_out is NULL");
+  if (count == 0) return SFW_OK;
+  SFW_HIP(h, hipSetDevice(h->device));
+  std::vector<double> soa(static_cast<size_t>(SFW_N_TERMS) * static_cast<size_t>(count));
+  for (int k = 0; k < SFW_N_TERMS; ++k)
+    SFW_HIP(h, hipMemcpyAsync(soa.data() + static_cast<size_t>(k) * count, h->terms.p + k * T + first, sizeof(double) * count,
+                              hipMemcpyDeviceToHost, h->stream));
+  SFW_HIP(h, hipStreamSynchronize(h->stream));
+  stream_is_idle(h);
+  for (int64_t i = 0; i < count; ++i)
+    for (int k = 0; k < SFW_N_TERMS; ++k) terms_out[i * SFW_N_TERMS + k] = soa[static_cast<size_t>(k * count + i)];
   return SFW_OK;
 }
 

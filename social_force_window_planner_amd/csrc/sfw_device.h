@@ -102,6 +102,23 @@ struct sfw_cls_agent {
 };
 enum { SFW_PHASE_WHOLE = 0, SFW_PHASE_PREFIX = 1, SFW_PHASE_SUFFIX = 2 };
 
+// The cost's linear combination (ref :663-667), shared by every kernel that forms a cost and by the re-score kernel
+// (sfw_grid_rescore), so that a re-scored cost is bit-identical to a scored one.  The rounding is pinned here rather than
+// left to -ffp-contract: the rollout kernels form the base terms and add the costmap term without contraction (K1 is
+// compiled under fp contract(off)), and the social term is added by ONE fused multiply-add, fma(w_s, social, base), as
+// every K2 epilogue has been compiled since round 1.
+__device__ __forceinline__ double sfw_cost_base(double w_vel, double vel, double w_dist, double d, double w_ang, double ang) {
+#pragma clang fp contract(off)
+  return w_vel * vel + w_dist * d + w_ang * ang;
+}
+__device__ __forceinline__ double sfw_cost_add_costmap(double base, double w_costmap, double cm) {
+#pragma clang fp contract(off)
+  return base + w_costmap * cm;
+}
+__device__ __forceinline__ double sfw_cost_add_social(double base, double w_social, double social) {
+  return __builtin_fma(w_social, social, base);
+}
+
 // Selection record (see sfw_best / sfw_best_key in the public header).
 struct sfw_sel {
   double cost;       // +inf when nothing selectable
@@ -210,7 +227,27 @@ struct sfw_launch {
   const char *arena_host;
   char *arena_dev;
   uint32_t arena_bytes;
+  // sfw_set_terms_capture, nullable: the five cost terms of every sample (SFW_TERM_*), SoA [SFW_N_TERMS][terms_T] by GLOBAL
+  // sample index, written where base_cost / costs are (sfw_put_term*); a sentinel cost puts its sentinel into all five
+  double *terms;
+  int64_t terms_T;
 };
+
+// Writers of the captured cost terms (no-ops when terms is null): term k of sample t, the three pedestrian-free terms, or one
+// sentinel in all five
+__device__ __forceinline__ void sfw_put_term(double *terms, int64_t T, int64_t t, int k, double v) {
+  if (terms) terms[k * T + t] = v;
+}
+__device__ __forceinline__ void sfw_put_terms3(double *terms, int64_t T, int64_t t, double vel, double d, double ang) {
+  if (!terms) return;
+  terms[SFW_TERM_VEL * T + t] = vel;
+  terms[SFW_TERM_DISTANCE * T + t] = d;
+  terms[SFW_TERM_ANGLE * T + t] = ang;
+}
+__device__ __forceinline__ void sfw_put_terms_sentinel(double *terms, int64_t T, int64_t t, double sentinel) {
+  if (!terms) return;
+  for (int k = 0; k < SFW_N_TERMS; ++k) terms[k * T + t] = sentinel;
+}
 
 
 // Fills L.k from L.p and L.O (host).
@@ -269,6 +306,12 @@ hipError_t sfw_launch_argmin(const double *costs, const double *linvels, const d
                              int32_t nw, int64_t T, int64_t index_base, sfw_sel *partials,
                              sfw_sel *out, hipStream_t stream, double *costs_host = nullptr,
                              sfw_sel *sel_host = nullptr);
+// sfw_grid_rescore: K weight vectors (device copy `w`) over the captured terms (SoA [5][T]) -> K records at sel_host (pinned).
+// partials: K x sfw_rescore_blocks(T, K) records; costs (nullable): K x T doubles, weight-major.
+int64_t sfw_rescore_blocks(int64_t T, int K);
+hipError_t sfw_launch_rescore(const double *terms, int64_t T, const sfw_weights *w, int K, const double *linvels,
+                              const double *angvels, int32_t nw, int64_t index_base, sfw_sel *partials, double *costs,
+                              sfw_sel *sel_host, hipStream_t stream);
 // Row r of the [R,5] multi-device exchange table from a selection record (+inf in every other row).
 hipError_t sfw_launch_key_table(const sfw_sel *sel, double *table, int r, int R, hipStream_t stream);
 // Pair table of the flat social kernel for A agents: sfw_pair_table_entries(A) uint16 entries.

@@ -187,6 +187,7 @@ __device__ __forceinline__ bool rollout_sample(const sfw_launch &L, int64_t loca
   if (!scored) {
     L.status[t] = SFW_ST_SKIPPED;
     L.costs[t] = SFW_COST_SKIPPED;
+    sfw_put_terms_sentinel(L.terms, L.terms_T, t, SFW_COST_SKIPPED);
   } else {
     L.status[t] = SFW_ST_VALID;  // the costmap scan downgrades it if a step is illegal
   }
@@ -223,7 +224,8 @@ __device__ __forceinline__ bool rollout_sample(const sfw_launch &L, int64_t loca
   ang = normalize_angle_f(static_cast<float>(ang), static_cast<float>(-M_PI), static_cast<float>(M_PI));
   ang = fabs(ang) / M_PI;
   const double vel = fabs(L.p.max_vel_x - vx_i) / L.p.max_vel_x;
-  L.base_cost[t] = L.p.vel_weight * vel + L.p.distance_weight * d + L.p.angle_weight * ang;
+  L.base_cost[t] = sfw_cost_base(L.p.vel_weight, vel, L.p.distance_weight, d, L.p.angle_weight, ang);
+  if (scored) sfw_put_terms3(L.terms, L.terms_T, t, vel, d, ang);
   return scored;
 }
 
@@ -244,14 +246,19 @@ __device__ __forceinline__ bool scan_finish(const sfw_launch &L, int64_t t, int6
   if (n_ok < S) {
     L.status[t] = SFW_ST_INVALID;
     L.costs[t] = SFW_COST_INVALID;
+    sfw_put_terms_sentinel(L.terms, L.terms_T, t, SFW_COST_INVALID);
     return false;
   }
   cm = cm / S;
-  const double base = (base_in ? *base_in : L.base_cost[t]) + L.p.costmap_weight * cm;
+  sfw_put_term(L.terms, L.terms_T, t, SFW_TERM_COSTMAP, cm);
+  const double base = sfw_cost_add_costmap(base_in ? *base_in : L.base_cost[t], L.p.costmap_weight, cm);
   L.base_cost[t] = base;
   if (base_out) *base_out = base;
   // No agent vector at all: social work is identically 0 and K2 is not launched.
-  if (L.A == 0) L.costs[t] = base + L.p.social_weight * 0.0;
+  if (L.A == 0) {
+    L.costs[t] = sfw_cost_add_social(base, L.p.social_weight, 0.0);
+    sfw_put_term(L.terms, L.terms_T, t, SFW_TERM_SOCIAL, 0.0);
+  }
   return true;
 }
 
@@ -314,6 +321,7 @@ __global__ void __launch_bounds__(64) sfw_rollout_team_kernel(const sfw_launch L
     if (!scored) {
       L.status[t] = SFW_ST_SKIPPED;
       L.costs[t] = SFW_COST_SKIPPED;
+      sfw_put_terms_sentinel(L.terms, L.terms_T, t, SFW_COST_SKIPPED);
     } else {
       L.status[t] = SFW_ST_VALID;  // the costmap scan downgrades it if a step is illegal
     }
@@ -385,7 +393,8 @@ __global__ void __launch_bounds__(64) sfw_rollout_team_kernel(const sfw_launch L
     ang = normalize_angle_f(static_cast<float>(ang), static_cast<float>(-M_PI), static_cast<float>(M_PI));
     ang = fabs(ang) / M_PI;
     const double vel = fabs(L.p.max_vel_x - r_end[g][3]) / L.p.max_vel_x;
-    L.base_cost[t] = L.p.vel_weight * vel + L.p.distance_weight * d + L.p.angle_weight * ang;
+    L.base_cost[t] = sfw_cost_base(L.p.vel_weight, vel, L.p.distance_weight, d, L.p.angle_weight, ang);
+    if (scored) sfw_put_terms3(L.terms, L.terms_T, t, vel, d, ang);
   }
 }
 
@@ -511,6 +520,7 @@ __device__ __forceinline__ void k1s_head(const sfw_launch &L, const k1s_sample &
   if (!q.scored) {
     L.status[q.t] = SFW_ST_SKIPPED;
     L.costs[q.t] = SFW_COST_SKIPPED;
+    sfw_put_terms_sentinel(L.terms, L.terms_T, q.t, SFW_COST_SKIPPED);
   } else {
     L.status[q.t] = SFW_ST_VALID;  // the costmap scan downgrades it if a step is illegal
   }
@@ -593,17 +603,20 @@ __device__ __forceinline__ void k1s_records(const sfw_launch &L, const k1s_lds &
   }
 }
 // ... and the pedestrian-free cost terms (one thread): ref :643-666 without the costmap and social terms (left-to-right sum order kept)
-__device__ __forceinline__ double k1s_base_cost_value(const sfw_launch &L, const k1s_lds &a, int S) {
+// (of a scored sample q, the terms go to the capture buffer too — from the thread that forms them: a never-scored sample's
+// SFW_COST_SKIPPED, written there by k1s_head, stays)
+__device__ __forceinline__ double k1s_base_cost_value(const sfw_launch &L, const k1s_lds &a, const k1s_sample &q, int S) {
   const double dx = L.ga.wpx - a.xs[S], dy = L.ga.wpy - a.ys[S];
   const double d = dx * dx + dy * dy;
   double ang = atan2(dy, dx) - *a.th_end;
   ang = normalize_angle_f(static_cast<float>(ang), static_cast<float>(-M_PI), static_cast<float>(M_PI));
   ang = fabs(ang) / M_PI;
   const double vel = fabs(L.p.max_vel_x - a.vxs[S - 1]) / L.p.max_vel_x;
-  return L.p.vel_weight * vel + L.p.distance_weight * d + L.p.angle_weight * ang;
+  if (q.scored) sfw_put_terms3(L.terms, L.terms_T, q.t, vel, d, ang);
+  return sfw_cost_base(L.p.vel_weight, vel, L.p.distance_weight, d, L.p.angle_weight, ang);
 }
 __device__ __forceinline__ void k1s_base_cost(const sfw_launch &L, const k1s_lds &a, const k1s_sample &q, int S) {
-  L.base_cost[q.t] = k1s_base_cost_value(L, a, S);
+  L.base_cost[q.t] = k1s_base_cost_value(L, a, q, S);
 }
 // (5) footprint: the pose centre must be on the map (ref :545, src/costmap_model.cpp:36-37); K < 3: centre cell
 // only; else every (pose, edge) is a task of its own and a pose's code is the maximum over its tasks
@@ -1547,17 +1560,23 @@ __device__ __forceinline__ void finish_wave(const lds_layout &s, int lane, int G
   double *const costs = La->costs;
   const double *const base_cost = La->base_cost;
   int32_t *const status = La->status, *const coll_step = La->coll_step;
+  double *const terms = La->terms;
+  const int64_t terms_T = La->terms_T;
   const int64_t t0 = La->chunk_begin + first_local;
   auto put = [&](int g, double v) {
     const int64_t t = t0 + g;
     const int d = s.dead[g];
     if (d == 0) {
-      if (status[t] == SFW_ST_VALID) costs[t] = base_cost[t] + social_weight * v;  // not VALID: force_alive run of a costmap-rejected sample
+      if (status[t] == SFW_ST_VALID) {  // not VALID: force_alive run of a costmap-rejected sample
+        costs[t] = sfw_cost_add_social(base_cost[t], social_weight, v);
+        sfw_put_term(terms, terms_T, t, SFW_TERM_SOCIAL, v);
+      }
     }
     else if (d >= 2) {
       costs[t] = SFW_COST_INVALID;
       status[t] = SFW_ST_INVALID;
       if (coll_step) coll_step[t] = d - 2;
+      sfw_put_terms_sentinel(terms, terms_T, t, SFW_COST_INVALID);
     }
   };
   if (G == 1) {
@@ -2714,6 +2733,62 @@ sfw_argmin_stage2(const sfw_sel *partials, int n, sfw_sel *out, sfw_sel *sel_hos
   }
 }
 
+// Re-score (sfw_grid_rescore): the captured terms of a launch (sfw_launch.terms, SoA [5][T]) under K other weight vectors.
+// A 2-D grid: blocks.x tile the samples, blocks.y tile the weight vectors by RESCORE_KT.  A thread loads its sample's five
+// terms once (five coalesced 8-byte loads) and evaluates the tile's weight vectors, which are wave-uniform (s_load from
+// the weight table), keeping one running selection per vector; the block then reduces each of them (block_reduce) into
+// partials[k][blockIdx.x].  The costs are the statements of the scoring kernels (sfw_cost_*), so bit-identical to a fresh
+// launch with those weights; a sentinel sample's terms all hold its sentinel, which is its cost under every weight vector
+// (the distance term of a scored sample is a sum of squares, never negative).
+constexpr int RESCORE_KT = 8;
+__global__ void __launch_bounds__(ARGMIN_BLOCK)
+sfw_rescore_stage1(const double *terms, int64_t T, const sfw_weights *w, int K, const double *linvels, const double *angvels,
+                   int nw, int64_t index_base, sfw_sel *partials, double *costs, sfw_sel *sel_host) {
+  typedef const __attribute__((address_space(4))) sfw_weights *weights_ptr;
+  const weights_ptr ws = (weights_ptr)w;
+  const int k0 = static_cast<int>(blockIdx.y) * RESCORE_KT;
+  sfw_sel best[RESCORE_KT];
+#pragma unroll
+  for (int j = 0; j < RESCORE_KT; ++j) best[j] = sel_empty();
+  for (int64_t t = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; t < T;
+       t += static_cast<int64_t>(gridDim.x) * blockDim.x) {
+    const double vel = terms[SFW_TERM_VEL * T + t], d = terms[SFW_TERM_DISTANCE * T + t];
+    const double ang = terms[SFW_TERM_ANGLE * T + t], cm = terms[SFW_TERM_COSTMAP * T + t];
+    const double sw = terms[SFW_TERM_SOCIAL * T + t];
+    const bool sentinel = d < 0.0;
+    double c[RESCORE_KT];
+#pragma unroll
+    for (int j = 0; j < RESCORE_KT; ++j) {
+      const int k = min(k0 + j, K - 1);  // (a partial last tile repeats its last vector; nothing of it is stored)
+      const double base = sfw_cost_add_costmap(sfw_cost_base(ws[k].vel, vel, ws[k].distance, d, ws[k].angle, ang), ws[k].costmap, cm);
+      c[j] = sentinel ? d : sfw_cost_add_social(base, ws[k].social, sw);
+      sel_consider(best[j], c[j], linvels, angvels, nw, t, index_base);
+    }
+    if (costs) {  // (weight-major)
+#pragma unroll
+      for (int j = 0; j < RESCORE_KT; ++j)
+        if (k0 + j < K) costs[static_cast<int64_t>(k0 + j) * T + t] = c[j];
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < RESCORE_KT; ++j) {
+    const sfw_sel b = block_reduce(best[j]);
+    if (threadIdx.x == 0 && k0 + j < K) {
+      partials[static_cast<int64_t>(k0 + j) * gridDim.x + blockIdx.x] = b;
+      if (sel_host) sel_host[k0 + j] = b;  // (one block of samples: the partial is the result)
+    }
+    __syncthreads();  // (block_reduce's LDS slots are rewritten by the next vector's reduction)
+  }
+}
+// One block per weight vector: its n partials -> the record (pinned host memory)
+__global__ void __launch_bounds__(ARGMIN_BLOCK) sfw_rescore_stage2(const sfw_sel *partials, int n, sfw_sel *sel_host) {
+  const sfw_sel *const p = partials + static_cast<int64_t>(blockIdx.x) * n;
+  sfw_sel best = sel_empty();
+  for (int i = threadIdx.x; i < n; i += blockDim.x) best = sel_merge(best, p[i]);
+  best = block_reduce(best);
+  if (threadIdx.x == 0) sel_host[blockIdx.x] = best;
+}
+
 // Multi-device exchange record (sfw_multi_*): row `r` of an [R,5] table = this rank's selection key
 // (cost, -linvel, |angvel|, -index) and its count of valid samples; every other row +inf, so that an
 // element-wise all-reduce(min) over the ranks assembles the table of all local keys.
@@ -2805,7 +2880,7 @@ __device__ __forceinline__ void cycle_block(const sfw_launch &L, const late_laun
     }
     const int ftid = social ? tid - WAVE : tid, fn = social ? CYCLE_BLOCK - WAVE : CYCLE_BLOCK;
     k1s_records<false>(L, a, q, S, ftid, fn);
-    if (ftid == fn - 1) res->base0 = k1s_base_cost_value(L, a, S);
+    if (ftid == fn - 1) res->base0 = k1s_base_cost_value(L, a, q, S);
     if (q.scored) {
       k1s_footprint(L, a, S, ftid, fn);
       // the LAST of these waves to finish scans the codes in step order (K1c) — beside the pedestrian rollout, not behind it
@@ -2837,11 +2912,14 @@ __device__ __forceinline__ void cycle_block(const sfw_launch &L, const late_laun
       const int d = social ? res->dead : 0;
       if (legal && L.A > 0) {  // (no agent vector at all: scan_finish has written the cost)
         if (d == 0) {
-          L.costs[t] = base + L.p.social_weight * (social ? res->social_work : 0.0);  // finish_wave / sfw_no_social_kernel
+          const double sw = social ? res->social_work : 0.0;
+          L.costs[t] = sfw_cost_add_social(base, L.p.social_weight, sw);  // finish_wave / sfw_no_social_kernel
+          sfw_put_term(L.terms, L.terms_T, t, SFW_TERM_SOCIAL, sw);
         } else {
           L.costs[t] = SFW_COST_INVALID;
           L.status[t] = SFW_ST_INVALID;
           if (L.coll_step) L.coll_step[t] = d - 2;
+          sfw_put_terms_sentinel(L.terms, L.terms_T, t, SFW_COST_INVALID);
         }
       } else if (!legal && L.force_alive && d >= 2 && L.coll_step) {
         L.coll_step[t] = d - 2;  // point dumps: the contact in front of the illegal pose (finish_wave, force_alive)
@@ -3247,7 +3325,10 @@ __global__ void __launch_bounds__(256) sfw_no_social_kernel(const sfw_launch L) 
   const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
   if (i >= L.chunk_count) return;
   const int64_t t = L.chunk_begin + i;
-  if (L.status[t] == SFW_ST_VALID) L.costs[t] = L.base_cost[t] + L.p.social_weight * 0.0;
+  if (L.status[t] == SFW_ST_VALID) {
+    L.costs[t] = sfw_cost_add_social(L.base_cost[t], L.p.social_weight, 0.0);
+    sfw_put_term(L.terms, L.terms_T, t, SFW_TERM_SOCIAL, 0.0);
+  }
 }
 }  // namespace
 
@@ -3288,6 +3369,26 @@ hipError_t sfw_launch_argmin(const double *costs, const double *linvels, const d
   hipLaunchKernelGGL(sfw_argmin_stage1, dim3(blocks), dim3(ARGMIN_BLOCK), 0, stream, costs, linvels,
                      angvels, nw, T, index_base, partials, costs_host, static_cast<sfw_sel *>(nullptr));
   hipLaunchKernelGGL(sfw_argmin_stage2, dim3(1), dim3(ARGMIN_BLOCK), 0, stream, partials, blocks, out, sel_host);
+  return hipGetLastError();
+}
+
+int64_t sfw_rescore_blocks(int64_t T, int K) {
+  if (T <= 16 * ARGMIN_BLOCK) return 1;  // one block per weight tile, no second stage (a control cycle's grid)
+  int64_t blocks = (T + ARGMIN_BLOCK - 1) / ARGMIN_BLOCK;
+  const int64_t cap = std::max<int64_t>(8, (int64_t(1) << 20) / std::max(K, 1));  // partials: at most ~1M records (40 MB)
+  return std::min<int64_t>(blocks, std::min<int64_t>(cap, 2048));
+}
+hipError_t sfw_launch_rescore(const double *terms, int64_t T, const sfw_weights *w, int K, const double *linvels,
+                              const double *angvels, int32_t nw, int64_t index_base, sfw_sel *partials, double *costs,
+                              sfw_sel *sel_host, hipStream_t stream) {
+  if (K < 1 || T < 1) return hipErrorInvalidValue;
+  const int64_t blocks = sfw_rescore_blocks(T, K);
+  const dim3 grid(static_cast<unsigned>(blocks), static_cast<unsigned>((K + RESCORE_KT - 1) / RESCORE_KT));
+  hipLaunchKernelGGL(sfw_rescore_stage1, grid, dim3(ARGMIN_BLOCK), 0, stream, terms, T, w, K, linvels, angvels, nw, index_base,
+                     partials, costs, blocks == 1 ? sel_host : static_cast<sfw_sel *>(nullptr));
+  if (blocks > 1)
+    hipLaunchKernelGGL(sfw_rescore_stage2, dim3(static_cast<unsigned>(K)), dim3(ARGMIN_BLOCK), 0, stream, partials,
+                       static_cast<int>(blocks), sel_host);
   return hipGetLastError();
 }
 

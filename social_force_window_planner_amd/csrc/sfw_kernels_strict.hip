@@ -28,4 +28,6 @@
 #define sfw_launch_key_table sfw_strict_unused_launch_key_table
 #define sfw_argmin_partials sfw_strict_unused_argmin_partials
 #define sfw_launch_argmin sfw_strict_unused_launch_argmin
+#define sfw_rescore_blocks sfw_strict_unused_rescore_blocks
+#define sfw_launch_rescore sfw_strict_unused_launch_rescore
 #include "sfw_kernels.hip"

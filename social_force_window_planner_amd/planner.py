@@ -24,6 +24,8 @@ from ._abi import (
     SfwParams,
     SfwRobotState,
     SfwPlanInfo,
+    SfwWeights,
+    SFW_N_TERMS,
     default_params,
 )
 
@@ -130,6 +132,9 @@ def lib():
         L.sfw_batch_score_grid.argtypes = [vp, vp, vp, C.c_int32, vp, C.c_int32, vp, vp]
         L.sfw_batch_describe.argtypes = [vp, C.POINTER(SfwBatchDesc)]
         L.sfw_batch_last_us.argtypes = [vp, C.c_int32, C.POINTER(C.c_double)]
+        L.sfw_set_terms_capture.argtypes = [vp, C.c_int32]
+        L.sfw_grid_rescore.argtypes = [vp, C.POINTER(SfwWeights), C.c_int32, C.POINTER(SfwBest), vp]
+        L.sfw_grid_terms.argtypes = [vp, C.c_int64, C.c_int64, vp]
         _lib = L
     return _lib
 
@@ -325,6 +330,34 @@ class HipScorer:
         self._check(lib().sfw_grid_points(self._h, index, pts.ctypes.data, points_cap, C.byref(n)),
                     "sfw_grid_points")
         return pts[: min(n.value, points_cap)].copy()
+
+    # -- per-term costs ------------------------------------------------------
+    def set_terms_capture(self, enabled=True):
+        """Every grid launch also keeps the five unweighted cost terms of every sample (40 B per sample on the device)."""
+        self._check(lib().sfw_set_terms_capture(self._h, 1 if enabled else 0), "sfw_set_terms_capture")
+
+    def cost_terms(self, first=0, count=None):
+        """The captured terms of the last launch: float64 (count, 5), columns SFW_TERM_VEL .. SFW_TERM_SOCIAL."""
+        if count is None:  # (no grid since sfw_score_one: the library answers SFW_ERR_STATE)
+            nv, nw = self._grid if self._grid is not None else (0, 0)
+            count = max(nv * nw - first, 0)
+        out = np.empty((count, SFW_N_TERMS), dtype=np.float64)
+        self._check(lib().sfw_grid_terms(self._h, first, count, out.ctypes.data), "sfw_grid_terms")
+        return out
+
+    def rescore(self, weights, want_costs=False):
+        """The last launch's grid under K weight vectors ((K, 5) array-like: vel, distance, angle, costmap, social) without
+        another rollout: (K best dicts as score_grid returns them, (K, nv * nw) costs or None)."""
+        w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).reshape(-1, SFW_N_TERMS))
+        K = w.shape[0]
+        best = (SfwBest * max(K, 1))()
+        costs = None
+        if want_costs and self._grid is not None:
+            nv, nw = self._grid
+            costs = np.empty((K, nv * nw), dtype=np.float64)
+        self._check(lib().sfw_grid_rescore(self._h, C.cast(w.ctypes.data, C.POINTER(SfwWeights)), K, best,
+                                           costs.ctypes.data if costs is not None else None), "sfw_grid_rescore")
+        return [best[k].as_dict() for k in range(K)], costs
 
 
 def plan_row_blocks(linvels, angvels, robot_state, goal_args, sim_time, num_steps, n_agents, n_ranks):
