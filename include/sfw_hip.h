@@ -513,6 +513,61 @@ int sfw_batch_describe(sfw_batch b, sfw_batch_desc *out);
  * enqueue of the last launch, 2 the wait and fetch of the last fetch. */
 int sfw_batch_last_us(sfw_batch b, int32_t which, double *us_out);
 
+/* ---- one grid under several crowd hypotheses ------------------------------
+ * The reference gives every person the goal position + naive_goal_time * velocity (src/sensor_interface.cpp:491-502): one
+ * guess of where the crowd is heading.  An ensemble scores one robot's grid under M hypotheses of the crowd and picks the
+ * command that is best on average over them, or best in the worst of them.  All hypotheses share the parameters, costmap,
+ * footprint, robot state, goal arguments and (v, w) grid; each has its own agents (agents[0] = the robot in every one; the
+ * number of people may differ) and laser points.  Member m scores the grid exactly as a standalone handle would, with terms
+ * captured (sfw_set_terms_capture); then, for sample t, with tau_m[k][t] member m's terms and w the ensemble's weights:
+ *   - the (0,0) sample is SFW_COST_SKIPPED in every member: ensemble cost SFW_COST_SKIPPED, rejected[t] = 0;
+ *   - rejected[t] = members whose cost is SFW_COST_INVALID; rejected[t] > 0: ensemble cost SFW_COST_INVALID (contact in any
+ *     hypothesis rejects the command).  Costmap rejection does not depend on the agents: rejected[t] == M covers it, and
+ *     0 < rejected[t] < M always means pedestrian contact in some crowds (a chance constraint reads `rejected`);
+ *   - otherwise the social work W_m is aggregated: SFW_ENSEMBLE_MEAN: acc = 0.0; acc = acc + p[m] * W_m for m = 0..M-1 in
+ *     that order, each product and sum rounded on its own (p: caller-given, finite, >= 0, need not sum to 1; NULL: 1.0 / M
+ *     each); SFW_ENSEMBLE_MAX: the largest W_m (worst case).  The cost is the scoring kernels' own combination of member 0's
+ *     pedestrian-free terms (velocity, distance, angle, costmap: the same in every member that accepts the sample) and the
+ *     aggregate, so M = 1 with p = {1} reproduces the member's cost bit for bit.
+ * Selection is the reference's rule (the 10000.0 cap, the tie-breaks) over the ensemble cost vector, index_base 0; n_valid
+ * counts ensemble-valid samples. */
+#define SFW_ENSEMBLE_MAX_M 64
+#define SFW_ENSEMBLE_MEAN 0
+#define SFW_ENSEMBLE_MAX 1
+typedef struct sfw_ensemble_s *sfw_ensemble;
+/* 1 <= M <= SFW_ENSEMBLE_MAX_M (else SFW_ERR_INVALID_ARG, before any device call); SFW_ERR_NO_DEVICE without a GPU. */
+int sfw_ensemble_create(const sfw_params *params, int device, int32_t M, sfw_ensemble *out);
+int sfw_ensemble_destroy(sfw_ensemble e);
+const char *sfw_ensemble_last_error(sfw_ensemble e);
+int32_t sfw_ensemble_size(sfw_ensemble e);
+/* Member m (owned by e; NULL when out of range): its costs (sfw_grid_costs_view), terms (sfw_grid_terms) and Trajectory
+ * points after a score, as a batch member's.  sfw_destroy of it is refused (SFW_ERR_STATE). */
+sfw_handle sfw_ensemble_member(sfw_ensemble e, int32_t m);
+/* Replicated to every member.  Parameters changed through a member handle make the next score SFW_ERR_STATE (a memcmp). */
+int sfw_ensemble_set_params(sfw_ensemble e, const sfw_params *params);
+int sfw_ensemble_set_costmap(sfw_ensemble e, const uint8_t *cells, uint32_t size_x, uint32_t size_y,
+                             double origin_x, double origin_y, double resolution);
+int sfw_ensemble_set_footprint(sfw_ensemble e, const double *xy, int32_t K);
+/* Hypothesis m: a full sfw_set_agents input. */
+int sfw_ensemble_set_hypothesis(sfw_ensemble e, int32_t m, const sfw_agent *agents, int32_t A,
+                                const double *obstacles_xy, int32_t O);
+/* Stage every member on the grid, ONE batch launch (sfw_batch_*: members that qualify for the one-launch cycle share a
+ * batched cycle kernel, the others take their usual kernels on the same stream), the aggregation kernel behind it, one wait.
+ * costs_out (nv * nw doubles), rejected_out (nv * nw int32) and best_out are nullable.  SFW_ERR_INVALID_ARG for an unknown
+ * mode or a non-finite or negative probability (checked before any device call); SFW_ERR_STATE when a hypothesis was never
+ * set or a member's sfw_params differ from the ensemble's. */
+int sfw_ensemble_score_grid(sfw_ensemble e, const sfw_robot_state *rs, const double *linvels, int32_t nv,
+                            const double *angvels, int32_t nw, const sfw_goal_args *args, int32_t mode,
+                            const double *probs, double *costs_out, int32_t *rejected_out, sfw_best *best_out);
+/* Re-aggregate the last score under another mode / probabilities, no rollout: one kernel over the members' captured terms.
+ * Same argument checks; SFW_ERR_STATE when nothing was scored, or when a member was staged, launched or used for
+ * sfw_score_one since (the rule of sfw_grid_rescore). */
+int sfw_ensemble_aggregate(sfw_ensemble e, int32_t mode, const double *probs, double *costs_out,
+                           int32_t *rejected_out, sfw_best *best_out);
+/* Host wall-clock of the last calls, microseconds: which = 0 staging of the members (score_grid only), 1 the enqueue of the
+ * launch and the aggregation, 2 the wait and the copies out. */
+int sfw_ensemble_last_us(sfw_ensemble e, int32_t which, double *us_out);
+
 #ifdef __cplusplus
 }
 #endif

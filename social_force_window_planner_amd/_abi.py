@@ -203,6 +203,18 @@ EXPORTED_SYMBOLS = (
     "sfw_set_terms_capture",
     "sfw_grid_rescore",
     "sfw_grid_terms",
+    "sfw_ensemble_create",
+    "sfw_ensemble_destroy",
+    "sfw_ensemble_last_error",
+    "sfw_ensemble_size",
+    "sfw_ensemble_member",
+    "sfw_ensemble_set_params",
+    "sfw_ensemble_set_costmap",
+    "sfw_ensemble_set_footprint",
+    "sfw_ensemble_set_hypothesis",
+    "sfw_ensemble_score_grid",
+    "sfw_ensemble_aggregate",
+    "sfw_ensemble_last_us",
 )
 # per-term costs (sfw_set_terms_capture / sfw_grid_rescore / sfw_grid_terms)
 SFW_TERM_VEL, SFW_TERM_DISTANCE, SFW_TERM_ANGLE, SFW_TERM_COSTMAP, SFW_TERM_SOCIAL = 0, 1, 2, 3, 4
@@ -216,6 +228,10 @@ class SfwWeights(C.Structure):
     _fields_ = [("vel", C.c_double), ("distance", C.c_double), ("angle", C.c_double), ("costmap", C.c_double),
                 ("social", C.c_double)]
 
+
+# one grid under several crowd hypotheses (sfw_ensemble_*)
+SFW_ENSEMBLE_MAX_M = 64
+SFW_ENSEMBLE_MEAN, SFW_ENSEMBLE_MAX = 0, 1
 
 SFW_MULTI_RCCL, SFW_MULTI_HOST_REDUCE = 0, 1
 SFW_BATCH_MAX = 256

@@ -244,6 +244,7 @@ struct sfw_planner_s {
   // a member of a sfw_batch: the batch's streams are borrowed (sfw_destroy refuses the handle; the batch destroys it)
   bool owns_streams = true;
   bool batch_member = false;
+  uint64_t launch_seq = 0;  // grid launches so far (an sfw_ensemble tells its own launch from a member's later one)
 };
 
 namespace {
@@ -1438,6 +1439,7 @@ int cycle_commit(sfw_handle h, bool timing) {
     SFW_HIP(h, hipEventRecord(h->ev[3], h->stream));
   }
   h->launched = true;
+  ++h->launch_seq;
   h->launched_timed = timing;
   h->launched_cycle = true;
   return SFW_OK;
@@ -1534,6 +1536,7 @@ int launch_kernels(sfw_handle h, const launch_prep &lp) {
                                h->partials.p, h->d_sel, h->stream, costs_host, sel_host));
   if (timing) SFW_HIP(h, hipEventRecord(h->ev[3], h->stream));
   h->launched = true;
+  ++h->launch_seq;
   h->launched_timed = timing;
   return SFW_OK;
 }
@@ -3164,6 +3167,258 @@ int sfw_batch_last_us(sfw_batch b, int32_t which, double *us_out) {
   if (!b || !us_out) return SFW_ERR_INVALID_ARG;
   if (which < 0 || which > 2) return bfail(b, SFW_ERR_INVALID_ARG, "batch_last_us: which must be 0..2");
   *us_out = b->us[which];
+  return SFW_OK;
+}
+
+}  // extern "C"
+
+// ===========================================================================
+// one grid under several crowd hypotheses (sfw_ensemble_*)
+// ===========================================================================
+struct sfw_ensemble_s {
+  int device = 0;
+  sfw_params params;
+  sfw_batch b = nullptr;       // the M members (terms capture on), one stream
+  std::vector<char> hyp_set;   // sfw_ensemble_set_hypothesis(m) has been called
+  std::string err;
+  // pinned: the record | costs (T doubles) | rejected (T int32), written by the aggregation kernels; a grid whose cost vector
+  // exceeds the members' mirror size (SFW_MIRROR_MAX_MB) leaves costs | rejected in d_out instead (copied out after the wait)
+  pinned_buf pin_out;
+  pinned_buf pin_tab;          // M term-buffer pointers | M probabilities: ONE H2D per aggregation, guarded by its event
+  dev_buf<char> tab, d_out;
+  dev_buf<sfw_sel> partials;
+  bool scored = false;         // a score_grid completed; seq: every member's launch_seq at its end
+  bool mirrored = false;       // the last aggregation wrote costs | rejected to pin_out
+  std::vector<uint64_t> seq;
+  int64_t T = 0;
+  double us[3] = {0.0, 0.0, 0.0};
+};
+
+namespace {
+constexpr size_t kEnsRecBytes = (sizeof(sfw_sel) + 15) & ~size_t(15);
+
+int efail(sfw_ensemble e, int code, const std::string &msg) {
+  if (e) e->err = msg;
+  return code;
+}
+int emember_fail(sfw_ensemble e, int32_t m, int code, const char *what) {
+  return efail(e, code, std::string(what) + " (member " + std::to_string(m) + "): " + e->b->h[static_cast<size_t>(m)]->err);
+}
+// mode and probabilities: no device call
+int ensemble_check_mode(sfw_ensemble e, int32_t mode, const double *probs, const char *what) {
+  if (mode != SFW_ENSEMBLE_MEAN && mode != SFW_ENSEMBLE_MAX)
+    return efail(e, SFW_ERR_INVALID_ARG, std::string(what) + ": mode must be SFW_ENSEMBLE_MEAN or SFW_ENSEMBLE_MAX");
+  if (probs)
+    for (size_t m = 0; m < e->hyp_set.size(); ++m)
+      if (!std::isfinite(probs[m]) || !(probs[m] >= 0.0))
+        return efail(e, SFW_ERR_INVALID_ARG, std::string(what) + ": probability " + std::to_string(m) + " is not finite and >= 0");
+  return SFW_OK;
+}
+
+// The aggregation behind the members' launch on the batch's stream: member table upload, stage 1 (+ stage 2), and for a grid
+// too large for the mirror nothing more (ensemble_finish copies it out after the wait).
+int ensemble_enqueue(sfw_ensemble e, int32_t mode, const double *probs) {
+  const int32_t M = static_cast<int32_t>(e->b->h.size());
+  sfw_handle h0 = e->b->h[0];
+  const int64_t T = static_cast<int64_t>(h0->nv) * h0->nw;
+  const size_t cost_bytes = sizeof(double) * static_cast<size_t>(T);
+  const size_t rej_bytes = (sizeof(int32_t) * static_cast<size_t>(T) + 15) & ~size_t(15);
+  e->T = T;
+  e->mirrored = cost_bytes <= h0->mirror_max_bytes;  // (the handle's rule: pinned up to SFW_MIRROR_MAX_MB of costs)
+  if (e->pin_out.reserve(kEnsRecBytes + (e->mirrored ? cost_bytes + rej_bytes : 0)) != hipSuccess ||
+      (!e->mirrored && e->d_out.reserve(cost_bytes + rej_bytes) != hipSuccess) ||
+      e->partials.reserve(static_cast<size_t>(sfw_argmin_partials(T))) != hipSuccess)
+    return efail(e, SFW_ERR_HIP, "ensemble: output allocation failed");
+  const size_t tab_bytes = 2 * sizeof(double) * static_cast<size_t>(M);
+  if (e->pin_tab.reserve(tab_bytes) != hipSuccess || e->tab.reserve(tab_bytes) != hipSuccess)
+    return efail(e, SFW_ERR_HIP, "ensemble: member table allocation failed");
+  const double **ptrs = reinterpret_cast<const double **>(e->pin_tab.p);
+  double *const p = reinterpret_cast<double *>(e->pin_tab.p + sizeof(double) * static_cast<size_t>(M));
+  for (int32_t m = 0; m < M; ++m) {
+    ptrs[m] = e->b->h[static_cast<size_t>(m)]->terms.p;
+    p[m] = probs ? probs[m] : 1.0 / M;
+  }
+  if (hipMemcpyAsync(e->tab.p, e->pin_tab.p, tab_bytes, hipMemcpyHostToDevice, e->b->stream) != hipSuccess ||
+      e->pin_tab.mark(e->b->stream) != hipSuccess)
+    return efail(e, SFW_ERR_HIP, "ensemble: member table copy failed");
+  const sfw_weights w{e->params.vel_weight, e->params.distance_weight, e->params.angle_weight, e->params.costmap_weight,
+                      e->params.social_weight};
+  char *const out = e->mirrored ? e->pin_out.p + kEnsRecBytes : e->d_out.p;
+  const hipError_t he = sfw_launch_ensemble(reinterpret_cast<const double *const *>(e->tab.p),
+                                            reinterpret_cast<const double *>(e->tab.p + sizeof(double) * static_cast<size_t>(M)), M, T,
+                                            mode, w, h0->d_linvels, h0->d_angvels, h0->nw, reinterpret_cast<double *>(out),
+                                            reinterpret_cast<int32_t *>(out + cost_bytes), e->partials.p,
+                                            reinterpret_cast<sfw_sel *>(e->pin_out.p), e->b->stream);
+  if (he != hipSuccess) return efail(e, SFW_ERR_HIP, std::string("ensemble: sfw_ensemble_stage1/2: ") + hipGetErrorString(he));
+  return SFW_OK;
+}
+
+// After the wait: the outputs to the caller
+int ensemble_finish(sfw_ensemble e, double *costs_out, int32_t *rejected_out, sfw_best *best_out) {
+  e->pin_tab.pending = false;
+  const size_t cost_bytes = sizeof(double) * static_cast<size_t>(e->T), rej_bytes = sizeof(int32_t) * static_cast<size_t>(e->T);
+  if (e->mirrored) {
+    if (costs_out) std::memcpy(costs_out, e->pin_out.p + kEnsRecBytes, cost_bytes);
+    if (rejected_out) std::memcpy(rejected_out, e->pin_out.p + kEnsRecBytes + cost_bytes, rej_bytes);
+  } else {
+    if (costs_out && hipMemcpy(costs_out, e->d_out.p, cost_bytes, hipMemcpyDeviceToHost) != hipSuccess)
+      return efail(e, SFW_ERR_HIP, "ensemble: cost copy failed");
+    if (rejected_out && hipMemcpy(rejected_out, e->d_out.p + cost_bytes, rej_bytes, hipMemcpyDeviceToHost) != hipSuccess)
+      return efail(e, SFW_ERR_HIP, "ensemble: rejected copy failed");
+  }
+  sfw_sel s;
+  std::memcpy(&s, e->pin_out.p, sizeof(s));
+  sel_to_best(e->b->h[0], s, best_out, nullptr);
+  return SFW_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int sfw_ensemble_create(const sfw_params *params, int device, int32_t M, sfw_ensemble *out) {
+  if (!out) return SFW_ERR_INVALID_ARG;
+  *out = nullptr;
+  if (M < 1 || M > SFW_ENSEMBLE_MAX_M) return SFW_ERR_INVALID_ARG;
+  if (int rc = check_params(nullptr, params)) return rc;
+  sfw_batch b = nullptr;
+  if (int rc = sfw_batch_create(params, device, M, &b)) return rc;
+  sfw_ensemble e = new (std::nothrow) sfw_ensemble_s();
+  if (!e) {
+    sfw_batch_destroy(b);
+    return SFW_ERR_HIP;
+  }
+  e->device = device;
+  e->params = *params;
+  e->b = b;
+  e->hyp_set.assign(static_cast<size_t>(M), 0);
+  e->seq.assign(static_cast<size_t>(M), 0);
+  for (sfw_handle h : b->h) h->capture_terms = true;
+  *out = e;
+  return SFW_OK;
+}
+
+int sfw_ensemble_destroy(sfw_ensemble e) {
+  if (!e) return SFW_OK;
+  (void)hipSetDevice(e->device);
+  sfw_batch_destroy(e->b);  // (waits for the stream)
+  e->pin_out.release();
+  e->pin_tab.release();
+  e->tab.release();
+  e->d_out.release();
+  e->partials.release();
+  delete e;
+  return SFW_OK;
+}
+
+const char *sfw_ensemble_last_error(sfw_ensemble e) { return e ? e->err.c_str() : "null ensemble"; }
+
+int32_t sfw_ensemble_size(sfw_ensemble e) { return e ? static_cast<int32_t>(e->b->h.size()) : 0; }
+
+sfw_handle sfw_ensemble_member(sfw_ensemble e, int32_t m) { return e ? sfw_batch_member(e->b, m) : nullptr; }
+
+int sfw_ensemble_set_params(sfw_ensemble e, const sfw_params *params) {
+  if (!e) return SFW_ERR_INVALID_ARG;
+  if (int rc = check_params(nullptr, params)) return efail(e, rc, "ensemble_set_params: invalid parameters");
+  for (size_t m = 0; m < e->b->h.size(); ++m)
+    if (int rc = sfw_set_params(e->b->h[m], params)) return emember_fail(e, static_cast<int32_t>(m), rc, "ensemble_set_params");
+  e->params = *params;
+  return SFW_OK;
+}
+
+int sfw_ensemble_set_costmap(sfw_ensemble e, const uint8_t *cells, uint32_t size_x, uint32_t size_y, double origin_x,
+                             double origin_y, double resolution) {
+  if (!e) return SFW_ERR_INVALID_ARG;
+  for (size_t m = 0; m < e->b->h.size(); ++m)
+    if (int rc = sfw_set_costmap(e->b->h[m], cells, size_x, size_y, origin_x, origin_y, resolution))
+      return emember_fail(e, static_cast<int32_t>(m), rc, "ensemble_set_costmap");
+  return SFW_OK;
+}
+
+int sfw_ensemble_set_footprint(sfw_ensemble e, const double *xy, int32_t K) {
+  if (!e) return SFW_ERR_INVALID_ARG;
+  for (size_t m = 0; m < e->b->h.size(); ++m)
+    if (int rc = sfw_set_footprint(e->b->h[m], xy, K)) return emember_fail(e, static_cast<int32_t>(m), rc, "ensemble_set_footprint");
+  return SFW_OK;
+}
+
+int sfw_ensemble_set_hypothesis(sfw_ensemble e, int32_t m, const sfw_agent *agents, int32_t A, const double *obstacles_xy,
+                                int32_t O) {
+  if (!e) return SFW_ERR_INVALID_ARG;
+  if (m < 0 || m >= static_cast<int32_t>(e->b->h.size())) return efail(e, SFW_ERR_INVALID_ARG, "ensemble_set_hypothesis: m out of range");
+  if (int rc = sfw_set_agents(e->b->h[static_cast<size_t>(m)], agents, A, obstacles_xy, O))
+    return emember_fail(e, m, rc, "ensemble_set_hypothesis");
+  e->hyp_set[static_cast<size_t>(m)] = 1;
+  return SFW_OK;
+}
+
+int sfw_ensemble_score_grid(sfw_ensemble e, const sfw_robot_state *rs, const double *linvels, int32_t nv, const double *angvels,
+                            int32_t nw, const sfw_goal_args *args, int32_t mode, const double *probs, double *costs_out,
+                            int32_t *rejected_out, sfw_best *best_out) {
+  if (!e) return SFW_ERR_INVALID_ARG;
+  if (int rc = ensemble_check_mode(e, mode, probs, "ensemble_score_grid")) return rc;
+  if (!rs || !args || !linvels || !angvels || nv <= 0 || nw <= 0)
+    return efail(e, SFW_ERR_INVALID_ARG, "ensemble_score_grid: null robot state, goal arguments or sample vectors");
+  const int32_t M = static_cast<int32_t>(e->b->h.size());
+  for (int32_t m = 0; m < M; ++m) {
+    const sfw_handle h = e->b->h[static_cast<size_t>(m)];
+    if (!e->hyp_set[static_cast<size_t>(m)])
+      return efail(e, SFW_ERR_STATE, "ensemble_score_grid: hypothesis " + std::to_string(m) + " was never set");
+    if (std::memcmp(&h->params, &e->params, sizeof(sfw_params)) != 0)
+      return efail(e, SFW_ERR_STATE, "ensemble_score_grid: member " + std::to_string(m) + "'s sfw_params differ from the ensemble's");
+    if (!h->capture_terms)
+      return efail(e, SFW_ERR_STATE, "ensemble_score_grid: member " + std::to_string(m) + "'s terms capture was turned off");
+  }
+  e->scored = false;
+  if (hipSetDevice(e->device) != hipSuccess) return efail(e, SFW_ERR_HIP, "ensemble_score_grid: hipSetDevice failed");
+  auto t0 = std::chrono::steady_clock::now();
+  for (int32_t m = 0; m < M; ++m)
+    if (int rc = sfw_grid_stage(e->b->h[static_cast<size_t>(m)], rs, linvels, nv, angvels, nw, args, 0))
+      return emember_fail(e, m, rc, "ensemble_score_grid: stage");
+  e->us[0] = us_since(t0);
+  t0 = std::chrono::steady_clock::now();
+  if (int rc = batch_launch(e->b)) return efail(e, rc, "ensemble_score_grid: " + e->b->err);
+  for (int32_t m = 0; m < M; ++m)
+    if (!e->b->h[static_cast<size_t>(m)]->terms_launched)
+      return efail(e, SFW_ERR_STATE, "ensemble_score_grid: member " + std::to_string(m) + " did not capture terms");
+  if (int rc = ensemble_enqueue(e, mode, probs)) return rc;
+  e->us[1] = us_since(t0);
+  t0 = std::chrono::steady_clock::now();
+  if (int rc = batch_fetch(e->b, nullptr)) return efail(e, rc, "ensemble_score_grid: " + e->b->err);  // (one wait, all members)
+  if (int rc = ensemble_finish(e, costs_out, rejected_out, best_out)) return rc;
+  e->us[2] = us_since(t0);
+  for (int32_t m = 0; m < M; ++m) e->seq[static_cast<size_t>(m)] = e->b->h[static_cast<size_t>(m)]->launch_seq;
+  e->scored = true;
+  return SFW_OK;
+}
+
+int sfw_ensemble_aggregate(sfw_ensemble e, int32_t mode, const double *probs, double *costs_out, int32_t *rejected_out,
+                           sfw_best *best_out) {
+  if (!e) return SFW_ERR_INVALID_ARG;
+  if (int rc = ensemble_check_mode(e, mode, probs, "ensemble_aggregate")) return rc;
+  if (!e->scored) return efail(e, SFW_ERR_STATE, "ensemble_aggregate: nothing scored (sfw_ensemble_score_grid)");
+  for (size_t m = 0; m < e->b->h.size(); ++m) {
+    const sfw_handle h = e->b->h[m];
+    if (!h->launched || !h->terms_launched || h->launch_seq != e->seq[m])
+      return efail(e, SFW_ERR_STATE, "ensemble_aggregate: member " + std::to_string(m) +
+                                         " was staged, launched or used for sfw_score_one since the last score");
+  }
+  if (hipSetDevice(e->device) != hipSuccess) return efail(e, SFW_ERR_HIP, "ensemble_aggregate: hipSetDevice failed");
+  auto t0 = std::chrono::steady_clock::now();
+  if (int rc = ensemble_enqueue(e, mode, probs)) return rc;
+  e->us[1] = us_since(t0);
+  t0 = std::chrono::steady_clock::now();
+  if (const hipError_t he = wait_stream(e->b->h[0]); he != hipSuccess)
+    return efail(e, SFW_ERR_HIP, std::string("ensemble_aggregate: ") + hipGetErrorString(he));
+  for (sfw_handle h : e->b->h) stream_is_idle(h);
+  if (int rc = ensemble_finish(e, costs_out, rejected_out, best_out)) return rc;
+  e->us[2] = us_since(t0);
+  return SFW_OK;
+}
+
+int sfw_ensemble_last_us(sfw_ensemble e, int32_t which, double *us_out) {
+  if (!e || !us_out) return SFW_ERR_INVALID_ARG;
+  if (which < 0 || which > 2) return efail(e, SFW_ERR_INVALID_ARG, "ensemble_last_us: which must be 0..2");
+  *us_out = e->us[which];
   return SFW_OK;
 }
 

@@ -312,6 +312,12 @@ int64_t sfw_rescore_blocks(int64_t T, int K);
 hipError_t sfw_launch_rescore(const double *terms, int64_t T, const sfw_weights *w, int K, const double *linvels,
                               const double *angvels, int32_t nw, int64_t index_base, sfw_sel *partials, double *costs,
                               sfw_sel *sel_host, hipStream_t stream);
+// sfw_ensemble_*: M members' captured terms (terms: device table of M pointers to SoA [5][T]; probs: M doubles, MEAN only —
+// both read wave-uniformly) -> costs[T], rejected[T] (pinned or device) and the record at sel_host (pinned).  partials:
+// sfw_argmin_partials(T) records.
+hipError_t sfw_launch_ensemble(const double *const *terms, const double *probs, int M, int64_t T, int mode, const sfw_weights &w,
+                               const double *linvels, const double *angvels, int32_t nw, double *costs, int32_t *rejected,
+                               sfw_sel *partials, sfw_sel *sel_host, hipStream_t stream);
 // Row r of the [R,5] multi-device exchange table from a selection record (+inf in every other row).
 hipError_t sfw_launch_key_table(const sfw_sel *sel, double *table, int r, int R, hipStream_t stream);
 // Pair table of the flat social kernel for A agents: sfw_pair_table_entries(A) uint16 entries.

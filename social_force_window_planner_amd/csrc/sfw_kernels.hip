@@ -2789,6 +2789,70 @@ __global__ void __launch_bounds__(ARGMIN_BLOCK) sfw_rescore_stage2(const sfw_sel
   if (threadIdx.x == 0) sel_host[blockIdx.x] = best;
 }
 
+// Ensemble (sfw_ensemble_*): M members scored one grid under M crowd hypotheses, with terms captured.  Per sample: the
+// members' distance terms carry the sentinels (skipped in all members -> skipped; `rejected` = members that reject it, any ->
+// invalid), the social work W_m of every member is aggregated (MEAN: acc = acc + p[m] * W_m in member order, no contraction;
+// MAX: the largest), and the cost is formed from member 0's pedestrian-free terms and the aggregate by the scoring kernels'
+// statements (sfw_cost_*).  The member table (M term-buffer pointers, M probabilities) is wave-uniform: s_load through
+// address_space(4).  Costs and `rejected` go straight to where the host reads them (pinned or device); one running
+// selection per thread, block_reduce into partials (a single-block launch writes the record itself).
+__device__ __forceinline__ double sfw_ensemble_mean_step(double acc, double p, double w) {
+#pragma clang fp contract(off)
+  return acc + p * w;
+}
+__global__ void __launch_bounds__(ARGMIN_BLOCK)
+sfw_ensemble_stage1(const double *const *terms, const double *probs, int M, int64_t T, int mode, sfw_weights w,
+                    const double *linvels, const double *angvels, int nw, double *costs, int32_t *rejected,
+                    sfw_sel *partials, sfw_sel *sel_host) {
+  typedef const double *member_terms;
+  typedef const __attribute__((address_space(4))) member_terms *terms_ptr;
+  typedef const __attribute__((address_space(4))) double *probs_ptr;
+  const terms_ptr tp = (terms_ptr)terms;
+  const probs_ptr pp = (probs_ptr)probs;
+  sfw_sel best = sel_empty();
+  for (int64_t t = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; t < T;
+       t += static_cast<int64_t>(gridDim.x) * blockDim.x) {
+    int32_t rej = 0;
+    bool skipped = false;
+    double acc = 0.0, d0 = 0.0;
+    for (int m = 0; m < M; ++m) {
+      const double *const tm = tp[m];
+      const double d = tm[SFW_TERM_DISTANCE * T + t], sw = tm[SFW_TERM_SOCIAL * T + t];
+      if (m == 0) d0 = d;
+      rej += d == SFW_COST_INVALID ? 1 : 0;
+      skipped = skipped || d == SFW_COST_SKIPPED;
+      if (mode == SFW_ENSEMBLE_MEAN) acc = sfw_ensemble_mean_step(acc, pp[m], sw);
+      else acc = (m == 0 || sw > acc) ? sw : acc;
+    }
+    double c;
+    if (skipped) {
+      c = SFW_COST_SKIPPED;
+      rej = 0;
+    } else if (rej > 0) {
+      c = SFW_COST_INVALID;
+    } else {
+      const double *const t0 = tp[0];
+      const double vel = t0[SFW_TERM_VEL * T + t], ang = t0[SFW_TERM_ANGLE * T + t], cm = t0[SFW_TERM_COSTMAP * T + t];
+      c = sfw_cost_add_social(sfw_cost_add_costmap(sfw_cost_base(w.vel, vel, w.distance, d0, w.angle, ang), w.costmap, cm),
+                              w.social, acc);
+    }
+    costs[t] = c;
+    rejected[t] = rej;
+    sel_consider(best, c, linvels, angvels, nw, t, 0);
+  }
+  best = block_reduce(best);
+  if (threadIdx.x == 0) {
+    partials[blockIdx.x] = best;
+    if (sel_host) *sel_host = best;  // (single-block launch: the partial is the result)
+  }
+}
+__global__ void __launch_bounds__(ARGMIN_BLOCK) sfw_ensemble_stage2(const sfw_sel *partials, int n, sfw_sel *sel_host) {
+  sfw_sel best = sel_empty();
+  for (int i = threadIdx.x; i < n; i += blockDim.x) best = sel_merge(best, partials[i]);
+  best = block_reduce(best);
+  if (threadIdx.x == 0) *sel_host = best;
+}
+
 // Multi-device exchange record (sfw_multi_*): row `r` of an [R,5] table = this rank's selection key
 // (cost, -linvel, |angvel|, -index) and its count of valid samples; every other row +inf, so that an
 // element-wise all-reduce(min) over the ranks assembles the table of all local keys.
@@ -3389,6 +3453,19 @@ hipError_t sfw_launch_rescore(const double *terms, int64_t T, const sfw_weights 
   if (blocks > 1)
     hipLaunchKernelGGL(sfw_rescore_stage2, dim3(static_cast<unsigned>(K)), dim3(ARGMIN_BLOCK), 0, stream, partials,
                        static_cast<int>(blocks), sel_host);
+  return hipGetLastError();
+}
+
+hipError_t sfw_launch_ensemble(const double *const *terms, const double *probs, int M, int64_t T, int mode, const sfw_weights &w,
+                               const double *linvels, const double *angvels, int32_t nw, double *costs, int32_t *rejected,
+                               sfw_sel *partials, sfw_sel *sel_host, hipStream_t stream) {
+  if (M < 1 || T < 1) return hipErrorInvalidValue;
+  const int blocks = static_cast<int>(sfw_argmin_partials(T));
+  hipLaunchKernelGGL(sfw_ensemble_stage1, dim3(static_cast<unsigned>(blocks)), dim3(ARGMIN_BLOCK), 0, stream, terms, probs, M, T,
+                     mode, w, linvels, angvels, nw, costs, rejected, partials, blocks == 1 ? sel_host : static_cast<sfw_sel *>(nullptr));
+  if (blocks > 1)
+    hipLaunchKernelGGL(sfw_ensemble_stage2, dim3(1), dim3(ARGMIN_BLOCK), 0, stream, static_cast<const sfw_sel *>(partials), blocks,
+                       sel_host);
   return hipGetLastError();
 }
 

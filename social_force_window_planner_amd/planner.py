@@ -14,6 +14,8 @@ import numpy as np
 
 from ._abi import (
     EXPORTED_SYMBOLS,
+    SFW_ENSEMBLE_MAX,
+    SFW_ENSEMBLE_MEAN,
     SFW_ERR_NO_DEVICE,
     SFW_OK,
     SfwAgent,
@@ -135,6 +137,22 @@ def lib():
         L.sfw_set_terms_capture.argtypes = [vp, C.c_int32]
         L.sfw_grid_rescore.argtypes = [vp, C.POINTER(SfwWeights), C.c_int32, C.POINTER(SfwBest), vp]
         L.sfw_grid_terms.argtypes = [vp, C.c_int64, C.c_int64, vp]
+        L.sfw_ensemble_create.argtypes = [C.POINTER(SfwParams), C.c_int, C.c_int32, C.POINTER(vp)]
+        L.sfw_ensemble_destroy.argtypes = [vp]
+        L.sfw_ensemble_last_error.argtypes = [vp]
+        L.sfw_ensemble_last_error.restype = C.c_char_p
+        L.sfw_ensemble_size.argtypes = [vp]
+        L.sfw_ensemble_size.restype = C.c_int32
+        L.sfw_ensemble_member.argtypes = [vp, C.c_int32]
+        L.sfw_ensemble_member.restype = vp
+        L.sfw_ensemble_set_params.argtypes = [vp, C.POINTER(SfwParams)]
+        L.sfw_ensemble_set_costmap.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.c_double]
+        L.sfw_ensemble_set_footprint.argtypes = [vp, vp, C.c_int32]
+        L.sfw_ensemble_set_hypothesis.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, C.c_int32]
+        L.sfw_ensemble_score_grid.argtypes = [vp, C.POINTER(SfwRobotState), vp, C.c_int32, vp, C.c_int32,
+                                              C.POINTER(SfwGoalArgs), C.c_int32, vp, vp, vp, C.POINTER(SfwBest)]
+        L.sfw_ensemble_aggregate.argtypes = [vp, C.c_int32, vp, vp, vp, C.POINTER(SfwBest)]
+        L.sfw_ensemble_last_us.argtypes = [vp, C.c_int32, C.POINTER(C.c_double)]
         _lib = L
     return _lib
 
@@ -626,5 +644,135 @@ class BatchScorer:
         for which, name in enumerate(("stage", "enqueue", "wait_fetch")):
             v = C.c_double()
             self._check(lib().sfw_batch_last_us(self._b, which, C.byref(v)), "sfw_batch_last_us")
+            out[name] = v.value
+        return out
+
+
+_ENSEMBLE_MODES = {"mean": SFW_ENSEMBLE_MEAN, "max": SFW_ENSEMBLE_MAX}
+
+
+class EnsembleScorer:
+    """One robot's grid under M crowd hypotheses (sfw_ensemble_*): every hypothesis is scored as a standalone handle would
+    score it, in one batch launch, and the per-sample social work is aggregated on the device — "mean" (probability-weighted
+    sum, probs default 1/M each) or "max" (worst case).  A sample any hypothesis rejects is rejected; `rejected` counts the
+    hypotheses that reject each sample."""
+
+    def __init__(self, params: SfwParams | None = None, device: int = 0, M: int = 1):
+        self.params = params if params is not None else default_params()
+        self._e = C.c_void_p()
+        rc = lib().sfw_ensemble_create(C.byref(self.params), device, M, C.byref(self._e))
+        if rc == SFW_ERR_NO_DEVICE:
+            raise SfwError(rc, "sfw_ensemble_create", "no HIP device visible; this library has no CPU fallback")
+        if rc != SFW_OK:
+            raise SfwError(rc, "sfw_ensemble_create")
+        self.M = M
+        self._grid = None
+        self._members = [HipScorer._member_view(lib().sfw_ensemble_member(self._e, m), self.params, self) for m in range(M)]
+
+    def close(self):
+        if getattr(self, "_e", None):
+            for m in self._members:
+                m.close()
+            lib().sfw_ensemble_destroy(self._e)
+            self._e = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc, what):
+        if rc != SFW_OK:
+            raise SfwError(rc, what, (lib().sfw_ensemble_last_error(self._e) or b"").decode())
+
+    def member(self, m):
+        """Hypothesis m's handle as a HipScorer that does not own it (its costs, captured terms, points)."""
+        return self._members[m]
+
+    # -- world state -------------------------------------------------------
+    def set_params(self, params):
+        self._check(lib().sfw_ensemble_set_params(self._e, C.byref(params)), "sfw_ensemble_set_params")
+        self.params = params
+        for m in self._members:
+            m.params = params
+
+    def set_costmap(self, cells, origin_x, origin_y, resolution):
+        cells = np.ascontiguousarray(cells, dtype=np.uint8)
+        sy, sx = cells.shape
+        self._check(lib().sfw_ensemble_set_costmap(self._e, cells.ctypes.data, sx, sy, origin_x, origin_y, resolution),
+                    "sfw_ensemble_set_costmap")
+
+    def set_footprint(self, xy):
+        xy = _f64(xy).reshape(-1, 2)
+        self._check(lib().sfw_ensemble_set_footprint(self._e, xy.ctypes.data if len(xy) else None, len(xy)),
+                    "sfw_ensemble_set_footprint")
+
+    def set_hypothesis(self, m, agents, obstacles=None):
+        n = len(agents)
+        obs = _f64(obstacles if obstacles is not None else np.zeros((0, 2))).reshape(-1, 2)
+        self._check(lib().sfw_ensemble_set_hypothesis(self._e, m, C.addressof(agents) if n else None, n,
+                                                      obs.ctypes.data if len(obs) else None, len(obs)),
+                    "sfw_ensemble_set_hypothesis")
+
+    def load_scene(self, scene, hypotheses):
+        """The scene's costmap and footprint, and hypotheses[m] = agents or (agents, obstacles) for every member (plain
+        agents take the scene's laser points)."""
+        if len(hypotheses) != self.M:
+            raise ValueError(f"load_scene: {len(hypotheses)} hypotheses for an ensemble of {self.M}")
+        self.set_costmap(scene.cells, scene.origin_x, scene.origin_y, scene.resolution)
+        self.set_footprint(scene.footprint)
+        for m, h in enumerate(hypotheses):
+            agents, obs = h if isinstance(h, tuple) else (h, scene.obstacles)
+            self.set_hypothesis(m, agents, obs)
+
+    # -- scoring -----------------------------------------------------------
+    @staticmethod
+    def _mode(mode):
+        return _ENSEMBLE_MODES[mode] if isinstance(mode, str) else int(mode)
+
+    def _probs(self, probs):
+        return None if probs is None else _f64(probs).reshape(-1)
+
+    def _outputs(self):
+        nv, nw = self._grid
+        return np.empty(nv * nw, dtype=np.float64), np.empty(nv * nw, dtype=np.int32), SfwBest()
+
+    def score_grid(self, robot_state, linvels, angvels, goal_args, mode="mean", probs=None):
+        """(costs, rejected, best): the ensemble cost vector, the hypotheses rejecting each sample, the selection."""
+        lin, ang = _f64(linvels), _f64(angvels)
+        rs, ga = SfwRobotState(*robot_state), SfwGoalArgs(*goal_args)
+        p = self._probs(probs)
+        if p is not None and p.size != self.M:
+            raise ValueError(f"score_grid: {p.size} probabilities for an ensemble of {self.M}")
+        self._grid = (len(lin), len(ang))
+        costs, rejected, best = self._outputs()
+        self._check(lib().sfw_ensemble_score_grid(self._e, C.byref(rs), lin.ctypes.data, len(lin), ang.ctypes.data, len(ang),
+                                                  C.byref(ga), self._mode(mode), p.ctypes.data if p is not None else None,
+                                                  costs.ctypes.data, rejected.ctypes.data, C.byref(best)),
+                    "sfw_ensemble_score_grid")
+        for m in self._members:
+            m._grid = self._grid
+        return costs, rejected, best.as_dict()
+
+    def aggregate(self, mode="mean", probs=None):
+        """The last score_grid re-aggregated under another mode / probabilities, no rollout: (costs, rejected, best)."""
+        p = self._probs(probs)
+        if p is not None and p.size != self.M:
+            raise ValueError(f"aggregate: {p.size} probabilities for an ensemble of {self.M}")
+        if self._grid is None:
+            self._grid = (0, 0)  # (the library answers SFW_ERR_STATE)
+        costs, rejected, best = self._outputs()
+        self._check(lib().sfw_ensemble_aggregate(self._e, self._mode(mode), p.ctypes.data if p is not None else None,
+                                                 costs.ctypes.data, rejected.ctypes.data, C.byref(best)),
+                    "sfw_ensemble_aggregate")
+        return costs, rejected, best.as_dict()
+
+    def last_us(self):
+        """Host wall-clock of the last calls: stage (score_grid only), enqueue, wait + copies out (microseconds)."""
+        out = {}
+        for which, name in enumerate(("stage", "enqueue", "wait_fetch")):
+            v = C.c_double()
+            self._check(lib().sfw_ensemble_last_us(self._e, which, C.byref(v)), "sfw_ensemble_last_us")
             out[name] = v.value
         return out
