@@ -243,7 +243,10 @@ int sfw_grid_stage(sfw_handle h, const sfw_robot_state *rs,
                    const double *linvels, int32_t nv, const double *angvels,
                    int32_t nw, const sfw_goal_args *args, int64_t index_base);
 /* Enqueue rollout + social-force + argmin kernels on the handle's stream.
- * Everything stays in HBM; no host sync. */
+ * Everything stays in HBM; no host sync.
+ * Stage and launch are all-or-nothing: a call refused for its arguments
+ * changes nothing; any other failure leaves nothing staged or launched, so a
+ * launch or fetch returns SFW_ERR_STATE until the next successful stage. */
 int sfw_grid_launch(sfw_handle h);
 int sfw_grid_sync(sfw_handle h);
 /* Wait for the launch; the cost vector (nullable) and the local selection (nullable).  Since round 6 the selection kernels

@@ -25,9 +25,13 @@
 
 namespace {
 
+// Owning buffers: not copyable, so that nothing holding one by value can free it twice.
 template <typename T> struct dev_buf {
   T *p = nullptr;
   size_t cap = 0;  // elements
+  dev_buf() = default;
+  dev_buf(const dev_buf &) = delete;
+  dev_buf &operator=(const dev_buf &) = delete;
   hipError_t reserve(size_t n) {
     if (n <= cap) return hipSuccess;
     if (p) (void)hipFree(p);
@@ -54,6 +58,9 @@ struct pinned_buf {
   size_t cap = 0;
   hipEvent_t done = nullptr;
   bool pending = false;
+  pinned_buf() = default;
+  pinned_buf(const pinned_buf &) = delete;
+  pinned_buf &operator=(const pinned_buf &) = delete;
   hipError_t wait() {
     if (!pending) return hipSuccess;
     pending = false;
@@ -86,10 +93,157 @@ struct pinned_buf {
   }
 };
 
+// shared-prefix plan of the staged grid (sfw_device.h: sfw_cls_agent): per chunk of whole rows, the class tables of each level
+struct level_tables {               // offsets (ints) into the plan's class tables
+  int32_t n_row = 0, n_col = 0;     // classes of the level: rows in this chunk x columns
+  size_t o_row_rep = 0, o_col_rep = 0;  // representative chunk-local row / column of a class
+  size_t o_row_src = 0, o_col_src = 0;  // class of the previous level a class resumes from (level > 0)
+};
+struct chunk_plan {
+  std::vector<level_tables> lv;
+  size_t o_row_cls = 0;             // chunk-local row -> row class of the last level
+};
+
+struct map_geometry {
+  uint32_t size_x, size_y;
+  double origin_x, origin_y, resolution;
+};
+
+// An agent set as sfw_set_agents packs it (uploaded with the next stage).  A value: sfw_multi_set_agents copies rank 0's.
+struct agent_set {
+  std::vector<char> blob;  // pos | vel | const | obstacles | grp | off | mem, 16-byte aligned parts
+  size_t ao_vel = 0, ao_cst = 0, ao_obs = 0, ao_grp = 0, ao_off = 0, ao_mem = 0;
+  int A = 0, O = 0, NG = 0, n_grp_mem = 0;
+  bool person_pinned = false;  // some person i >= 1 can never move (desired_velocity == 0): see rest_noise_unreproduced
+  // ordered pairs (i, j) of agents with w x diff == 0 at hand-over (standing people, collinear walkers): see rest_forces
+  std::vector<std::pair<int32_t, int32_t>> rest_pairs;
+};
+
 }  // namespace
 
+// The handle's state, grouped by who owns it:
+//   cfg    fixed by sfw_create (and its environment);
+//   live   switches sfw_set_* change at any time, read by every stage and launch;
+//   world  what sfw_set_costmap / _footprint / _agents hold on the host until the next stage;
+//   st     what the last stage recorded and uploaded: a launch, sfw_grid_plan_info and the points dump read this, never `world`;
+//   last   what the last launch did: fetch, views and the per-launch queries read this.
+// A stage past its argument checks drops `st` and `last` first and sets st.valid last; a launch drops `last` first and sets
+// last.launched last.  A call that fails in between leaves nothing staged (or launched), never a mix of two calls.
 struct sfw_planner_s {
-  sfw_params params;
+  struct config {
+    // shape of the device the launch heuristics are scaled to: compute units (hipDeviceProp_t.multiProcessorCount: 256 on a
+    // whole MI355X, 32 on a CPX partition) and XCDs (32 CUs each); SFW_DEVICE_CUS / SFW_DEVICE_XCDS in the environment of
+    // sfw_create override them (a test pretends 32 CUs: the plan changes, the results may not)
+    int n_cu = SFW_DEFAULT_CUS, n_xcd = SFW_DEFAULT_CUS / SFW_CUS_PER_XCD;
+    std::vector<int> prefix_env;  // SFW_PREFIX: empty automatic, {0} off, else forced split steps
+    bool pin_rest_on = true;      // SFW_PIN_REST=0: no pinned-rest table (tests: what it changes)
+    long spin_us = 20000;         // SFW_SPIN_US: how long a fetch polls the stream before it blocks in hipStreamSynchronize
+                                  // (0: block at once)
+    bool arena_direct_on = true;  // SFW_ARENA_DIRECT=0: always copy the arena at stage time
+    size_t mirror_max_bytes = size_t(64) << 20;  // SFW_MIRROR_MAX_MB; 0: always copy
+    int obs_tasks_force = -1;     // SFW_OBS_TASKS=0|1: the flat form's laser-point pass as one lane per agent / as (agent,
+                                  // segment) tasks, whatever sfw_derive prices (tuning aid)
+    size_t table_budget_bytes = size_t(8) << 30;  // K1->K2 per-step tables per chunk (of 288 GB): BASELINE cfg4 runs in one chunk
+    // a member of a sfw_batch: the batch's streams are borrowed (sfw_destroy refuses the handle; the batch destroys it)
+    bool owns_streams = true;
+    bool batch_member = false;
+  } cfg;
+
+  struct switches {
+    sfw_params params;
+    uint64_t params_epoch = 1;  // bumped by sfw_set_params; st.plan_epoch says which epoch the stage's plan was made for
+    int k2_form = SFW_K2_AUTO;  // sfw_set_k2_form / SFW_FORCE_FLAT
+    bool timing = false;        // sfw_set_timing: record the per-kernel events sfw_last_launch_ms reads
+    // sfw_set_points_capture: a grid small enough for the fused K1 (a control cycle's samples) leaves its Trajectory points,
+    // point counts and contact steps during the scoring launch itself, in one buffer (pin_cap) -> the dump is one memcpy
+    bool capture_points = false;
+    // sfw_set_terms_capture: every grid launch also leaves the five cost terms of every sample in `terms` (SoA [5][T])
+    bool capture_terms = false;
+  } live;
+
+  // Footprint, agents and laser points are small: sfw_set_* keep them on the host and every stage packs them into ONE
+  // pinned arena and issues ONE H2D copy into `arena` — a control cycle is latency-bound and each separate copy costs as
+  // much as a kernel launch.  The costmap's cells wait in pin_map.
+  struct world_state {
+    map_geometry map_new{0, 0, 0, 0, 0};  // what sfw_set_costmap handed over last (pin_map holds its cells)
+    bool have_costmap = false;
+    bool cells_dirty = false;             // ... and the device has not seen yet
+    std::vector<double> footprint;        // 2K
+    int K = 0;
+    agent_set agents;
+  } world;
+
+  struct stage_record {
+    bool valid = false;  // everything below describes what the device holds; false: nothing is staged
+    // the grid
+    std::vector<double> lin, ang;
+    int nv = 0, nw = 0;
+    sfw_robot_state rs{};
+    sfw_goal_args ga{};
+    double vy_samp = 0.0;
+    int skip_zero = 1;
+    int64_t index_base = 0;
+    // the world as uploaded (sfw_set_* after a stage take effect at the next stage; a launch in between must keep
+    // describing the device copy)
+    int K = 0, A = 0, O = 0, NG = 0, n_grp_mem = 0;
+    bool person_pinned = false;       // (agent_set)
+    map_geometry map{0, 0, 0, 0, 0};
+    const uint8_t *d_cells = nullptr;
+    bool cells_in_arena = false;      // the device copy of the cells is the head of `arena` (small maps), else `cells`
+    size_t arena_cells_bytes = 0;     // bytes of that head
+    // device pointers: offsets into `arena`, except d_sel (behind the cost vector in `costs`)
+    const double *d_footprint = nullptr, *d_agent_pos = nullptr, *d_agent_vel = nullptr, *d_obstacles = nullptr;
+    const sfw_agent_const *d_agent_c = nullptr;
+    const int32_t *d_agent_grp = nullptr, *d_grp_off = nullptr, *d_grp_mem = nullptr;
+    const double *d_linvels = nullptr, *d_angvels = nullptr;
+    const double *d_agent_rest = nullptr;  // A x (fx, fy), or null when there is no pair at relative rest
+    const double *d_pin_rest = nullptr;    // see pinned_rest_table: the stage's table, or null
+    sfw_sel *d_sel = nullptr;
+    // what the relative-rest terms and the pinned-rest table were built from (sfw_set_params between stage and launch
+    // rebuilds them)
+    std::vector<std::pair<int32_t, int32_t>> rest_pairs;
+    std::vector<double> rest_pv;      // pos | vel, 4A doubles
+    size_t pin_doubles = 0;           // the pinned-rest table's length (4 + A) when the stage built one
+    std::vector<double> pin_pos;
+    std::vector<sfw_agent_const> pin_cst;
+    // the shared-prefix plan (no levels: not used) and the K1->K2 table size, made for params epoch plan_epoch
+    std::vector<int> prefix_steps;    // P(0) < P(1) < ...: level l integrates steps [P(l-1), P(l))
+    std::vector<chunk_plan> prefix_chunks;
+    size_t prefix_o_col_cls = 0;      // column -> column class of the last level
+    int prefix_S = 0;
+    int64_t prefix_chunk = 0;
+    int64_t prefix_class_steps = 0, prefix_last_classes = 0;
+    std::vector<int32_t> cls_ints;    // the plan's class tables as planned on the host (level_tables offsets index it)
+    int64_t cls_max = 0;              // largest class count of a level (sizes cls_state / cls_dead)
+    bool cls_two = false;             // more than one level: both ping-pong buffers
+    const int32_t *d_cls_tab = nullptr;  // ... on the device: inside `arena` (staged with it) or d_cls (re-planned at launch)
+    int64_t table_chunk = 0;          // samples per chunk the K1 tables hold
+    uint64_t plan_epoch = 0;
+    // the arena left in pin_arena only, for the launch's kernel to fetch (see stage_common / flush_arena)
+    bool arena_pending = false;
+    size_t arena_from = 0, arena_bytes = 0;
+    // K1a of a single-chunk grid is enqueued by the STAGE, before the shared-prefix planning (25..45 us of host work that
+    // the pose rollout does not depend on): early_poses says the staged grid's robot-step table is already in the stream
+    bool early_poses = false;
+    bool early_poses_timed = false;  // ... and the stage recorded ev[0] in front of it (timing was on at stage time)
+    bool early_poses_terms = false;  // ... and it wrote the pedestrian-free terms too
+    bool clock_cleared = false;      // the stage cleared the clock probe in front of the pose rollout it started
+  } st;
+
+  struct launch_record {
+    bool launched = false;  // every kernel of the launch is enqueued; false: nothing to fetch
+    bool timed = false;     // ... with the per-kernel events (sfw_last_launch_ms)
+    bool cycle = false;     // ... as the one-kernel control cycle
+    bool fetched = false;   // a fetch has waited for it (sfw_grid_costs_view)
+    bool mirrored = false;  // its selection kernels left costs + record in pin_mirror (sfw_launch_argmin)
+    bool captured = false;  // it left Trajectory points in pin_cap (sfw_set_points_capture) ...
+    int cap_S = 0;          // ... for this step count (the dump's layout)
+    bool terms = false;     // it left the cost terms in `terms` (sfw_grid_rescore / sfw_grid_terms)
+    int n_chunks = 1;
+  } last;
+  uint64_t launch_seq = 0;  // grid launches so far, never reset (an sfw_ensemble tells its own launch from a member's later one)
+
+  // device, streams, events
   int device = 0;
   hipStream_t stream = nullptr;
   hipStream_t side = nullptr;  // K1b + K1c beside the shared-prefix phase of K2
@@ -98,124 +252,24 @@ struct sfw_planner_s {
   sfw_split_streams split{nullptr, nullptr, nullptr};
   hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   std::vector<hipEvent_t> chunk_ev;  // 3 per chunk of a multi-chunk launch: K1 start, K1 end/K2 start, K2 end
-  int n_chunks = 1;
   std::string err;
+  const void *shared_cols = nullptr;  // axis_classes of the angular targets lent by sfw_multi_score_grid for the stage in
+                                      // progress (every rank has the same column axis), else null
 
-  // world state.  The costmap has its own snapshot buffer (uploaded by sfw_set_costmap).  Footprint,
-  // agents, laser points, groups and the sample vectors are small: sfw_set_* keep them on the host
-  // and every stage packs them into ONE pinned arena and issues ONE H2D copy into `world`
-  // (device pointers below are offsets into it) — a control cycle is latency-bound and each
-  // separate copy costs as much as a kernel launch.
-  dev_buf<uint8_t> cells;               // the snapshot on the device when it is too large to ride in `world`
-  uint32_t size_x = 0, size_y = 0;      // ... as the last stage uploaded it
-  double origin_x = 0, origin_y = 0, resolution = 0;
-  struct map_geometry {
-    uint32_t size_x, size_y;
-    double origin_x, origin_y, resolution;
-  } map_new{0, 0, 0, 0, 0};             // what sfw_set_costmap handed over last (pin_map holds its cells)
-  bool arena_pending = false;           // the last stage left its arena in pin_world only (see stage_common / flush_arena)
-  size_t arena_from = 0, arena_bytes = 0;
-  bool arena_direct_on = true;          // SFW_ARENA_DIRECT=0 in the environment of sfw_create: always copy at stage time
-  bool cells_dirty = false;             // ... and the device has not seen yet
-  bool cells_in_world = false;          // the device copy is the head of `world` (small maps), else `cells`
-  size_t world_cells_bytes = 0;         // bytes of that head
-  const uint8_t *d_cells = nullptr;
-  bool have_costmap = false;
-  std::vector<double> h_footprint;  // 2K
-  int K = 0;
-  std::vector<char> h_agents;       // pos | vel | const | obstacles | grp | off | mem, 16-byte aligned parts
-  size_t ao_vel = 0, ao_cst = 0, ao_obs = 0, ao_grp = 0, ao_off = 0, ao_mem = 0;
-  int A = 0, O = 0, NG = 0, n_grp_mem = 0;
-  // ordered pairs (i, j) of agents with w x diff == 0 at hand-over (standing people, collinear walkers): see rest_forces
-  std::vector<std::pair<int32_t, int32_t>> rest_pairs;
-  const double *d_agent_rest = nullptr;  // A x (fx, fy) in `world`, or null when there is no such pair
-  const double *d_pin_rest = nullptr;  // see pinned_rest_table: the stage's table on the device, or null
-  int obs_tasks_force = -1;            // SFW_OBS_TASKS=0|1 in the environment of sfw_create: the flat form's laser-point pass as
-                                       // one lane per agent / as (agent, segment) tasks, whatever sfw_derive prices (tuning aid)
-  bool clock_cleared = false;          // the stage cleared the clock probe in front of the pose rollout it started
-  bool pin_rest_on = true;             // SFW_PIN_REST=0 in the environment of sfw_create: no such table (tests: what it changes)
-  size_t st_pin_doubles = 0;           // its length (4 + A) when the last stage built one
-  std::vector<double> st_pin_pos;      // ... and what it was built from (sfw_set_params between stage and launch rebuilds it)
-  std::vector<sfw_agent_const> st_pin_cst;
-  std::vector<std::pair<int32_t, int32_t>> st_rest_pairs;  // what the last stage evaluated them from: sfw_set_params
-  std::vector<double> st_rest_pv;                           // between stage and launch re-evaluates (pos | vel, 4A doubles)
-  // what the last stage uploaded (sfw_set_* after a stage take effect at the next stage; a launch
-  // in between must keep describing the device copy)
-  int st_K = 0, st_A = 0, st_O = 0, st_NG = 0, st_n_grp_mem = 0;
-  dev_buf<char> world;
-  const double *d_footprint = nullptr, *d_agent_pos = nullptr, *d_agent_vel = nullptr, *d_obstacles = nullptr;
-  const sfw_agent_const *d_agent_c = nullptr;
-  const int32_t *d_agent_grp = nullptr, *d_grp_off = nullptr, *d_grp_mem = nullptr;
-  const double *d_linvels = nullptr, *d_angvels = nullptr;
+  // owned buffers
+  dev_buf<uint8_t> cells;      // the costmap on the device when it is too large to ride in `arena`
+  dev_buf<char> arena;         // the stage's one H2D copy: [cells] | footprint | agents | sample vectors | rest | class tables
   dev_buf<uint16_t> pair_tab;  // rebuilt when the agent count changes
-  int pair_tab_A = -1;
-
-  // staged grid
-  std::vector<double> h_lin, h_ang;
-  int nv = 0, nw = 0;
-  sfw_robot_state rs{};
-  sfw_goal_args ga{};
-  double vy_samp = 0.0;
-  int skip_zero = 1;
-  int64_t index_base = 0;
-  bool staged = false, launched = false, launched_timed = false;
-  bool launched_cycle = false;        // the last launch was the one-kernel control cycle (sfw_grid_plan_info)
-  dev_buf<unsigned> cycle_counter;    // its "blocks done" word (zero between launches)
-  bool fetched = false;               // ... and a fetch has waited for it (sfw_grid_costs_view)
-  bool mirrored = false;              // the last launch's selection kernels left costs + record in pin_mirror (sfw_launch_argmin)
-  size_t mirror_max_bytes = size_t(64) << 20;  // SFW_MIRROR_MAX_MB in the environment of sfw_create; 0: always copy
-  long spin_us = 20000;               // SFW_SPIN_US in the environment of sfw_create: how long a fetch polls the stream before
-                                      // it blocks in hipStreamSynchronize (0: block at once)
-  bool timing = false;  // sfw_set_timing: record the per-kernel events sfw_last_launch_ms reads
-  int k2_form = SFW_K2_AUTO;     // sfw_set_k2_form / SFW_FORCE_FLAT
-  // shape of the device the launch heuristics are scaled to: compute units (hipDeviceProp_t.multiProcessorCount: 256 on a
-  // whole MI355X, 32 on a CPX partition) and XCDs (32 CUs each); SFW_DEVICE_CUS / SFW_DEVICE_XCDS in the environment of
-  // sfw_create override them (a test pretends 32 CUs: the plan changes, the results may not)
-  int n_cu = SFW_DEFAULT_CUS, n_xcd = SFW_DEFAULT_CUS / SFW_CUS_PER_XCD;
-  // sfw_set_points_capture: a grid small enough for the fused K1 (a control cycle's samples) leaves its Trajectory points,
-  // point counts and contact steps during the scoring launch itself, in one buffer -> the dump is one D2H copy
-  // K1a of a single-chunk grid is enqueued by the STAGE, before the shared-prefix planning (25..45 us of host work that
-  // the pose rollout does not depend on): early_poses says the staged grid's robot-step table is already in the stream
-  bool early_poses = false;
-  bool early_poses_timed = false;  // ... and the stage recorded ev[0] in front of it (timing was on at stage time)
-  bool capture_points = false, captured = false;
-  int cap_S = 0;                 // step count the capturing launch ran with (the dump's layout)
-  pinned_buf pin_cap;            // points (24 S T bytes) | n_points (4 T) | contact steps (4 T), written by the capturing launch
-
-  // shared-prefix plan of the staged grid (sfw_device.h: sfw_cls_agent); no levels: not used
-  struct level_tables {               // offsets (ints) into d_cls
-    int32_t n_row = 0, n_col = 0;     // classes of the level: rows in this chunk x columns
-    size_t o_row_rep = 0, o_col_rep = 0;  // representative chunk-local row / column of a class
-    size_t o_row_src = 0, o_col_src = 0;  // class of the previous level a class resumes from (level > 0)
-  };
-  struct chunk_plan {
-    std::vector<level_tables> lv;
-    size_t o_row_cls = 0;             // chunk-local row -> row class of the last level
-  };
-  std::vector<int> prefix_steps;      // P(0) < P(1) < ...: level l integrates steps [P(l-1), P(l))
-  std::vector<chunk_plan> prefix_chunks;
-  size_t prefix_o_col_cls = 0;        // column -> column class of the last level
-  int prefix_S = 0;
-  int64_t prefix_chunk = 0;
-  int64_t prefix_class_steps = 0, prefix_last_classes = 0;
-  std::vector<int32_t> cls_ints;        // the plan's class tables as planned on the host (level_tables offsets index it)
-  int64_t cls_max = 0;                  // largest class count of a level (sizes cls_state / cls_dead)
-  bool cls_two = false;                 // more than one level: both ping-pong buffers
-  const int32_t *d_cls_tab = nullptr;   // ... on the device: inside `world` (staged with the arena) or d_cls (re-planned at launch)
+  int pair_tab_A = -1;         // ... for this many agents (-1: none)
+  dev_buf<unsigned> cycle_counter;  // the one-kernel control cycle's "blocks done" word (zero between launches)
   dev_buf<int32_t> d_cls, cls_dead[2];
   dev_buf<sfw_cls_agent> cls_state[2];  // ping-pong between levels
-  std::vector<int> prefix_env;          // SFW_PREFIX: empty automatic, {0} off, else forced split steps
-  const void *shared_cols = nullptr;    // axis_classes of the angular targets lent by sfw_multi_score_grid for the stage in
-                                        // progress (every rank has the same column axis), else null
-
   // per-sample outputs + per-chunk table
   dev_buf<int32_t> status, coll_step;
   dev_buf<double> base_cost, costs;  // costs: T doubles followed by the sfw_sel record (one D2H fetches both)
-  dev_buf<sfw_unit> ptab, cs_tab;   // the K1 tables (sfw_device.h sfw_unit), sized for table_chunk samples per step row
-  int64_t table_chunk = 0;          // samples per chunk the tables of the staged grid hold
+  dev_buf<sfw_unit> ptab, cs_tab;   // the K1 tables (sfw_device.h sfw_unit), sized for st.table_chunk samples per step row
   dev_buf<int16_t> fcode;
   dev_buf<sfw_sel> partials;
-  sfw_sel *d_sel = nullptr;
   dev_buf<double> points;
   dev_buf<int32_t> n_points;
   dev_buf<unsigned long long> clock;  // sfw_launch.clock_probe (timing only)
@@ -225,26 +279,15 @@ struct sfw_planner_s {
   dev_buf<double> pts_base, pts_costs;
   dev_buf<sfw_unit> pts_ptab, pts_cs;
   dev_buf<int16_t> pts_fcode;
-  // sfw_set_params bumps params_epoch; the table sizes and the shared-prefix plan carry the epoch they were made for
-  uint64_t params_epoch = 1, plan_epoch = 0;
-  size_t table_budget_bytes = size_t(8) << 30;  // K1->K2 per-step tables per chunk (of 288 GB): BASELINE cfg4 runs in one chunk
-  pinned_buf pin_map, pin_world, pin_out, pin_cls;
+  pinned_buf pin_map, pin_arena, pin_out, pin_cls;
   pinned_buf pin_one;     // sfw_score_one's outputs where the one-launch kernel writes them (cost | n_points | coll_step | points)
   pinned_buf pin_mirror;  // costs + selection record as the selection kernels of the last launch leave them (device writes)
-  // sfw_set_terms_capture: every grid launch also leaves the five cost terms of every sample in `terms` (SoA [5][T]);
-  // sfw_grid_rescore / sfw_grid_terms read them while terms_launched holds (the last launch captured; a stage or
-  // sfw_score_one since clears `launched`)
-  bool capture_terms = false, terms_launched = false;
-  bool early_poses_terms = false;  // the pose rollout the stage enqueued (early_poses) wrote the pedestrian-free terms too
-  dev_buf<double> terms;
+  pinned_buf pin_cap;     // points (24 S T bytes) | n_points (4 T) | contact steps (4 T), written by a capturing launch
+  dev_buf<double> terms;  // the cost terms of a capturing launch (allocated by the first, freed by sfw_set_terms_capture(h, 0))
   dev_buf<sfw_weights> rescore_w;  // sfw_grid_rescore: the weight vectors on the device, its partial records, its cost vectors
   dev_buf<sfw_sel> rescore_partials;
   dev_buf<double> rescore_costs;
   pinned_buf pin_rescore;          // K records (written by the kernels) | K weight vectors (copied from)
-  // a member of a sfw_batch: the batch's streams are borrowed (sfw_destroy refuses the handle; the batch destroys it)
-  bool owns_streams = true;
-  bool batch_member = false;
-  uint64_t launch_seq = 0;  // grid launches so far (an sfw_ensemble tells its own launch from a member's later one)
 };
 
 namespace {
@@ -261,6 +304,16 @@ int hip_fail(sfw_handle h, hipError_t e, const char *what) {
     hipError_t e_ = (call);                                \
     if (e_ != hipSuccess) return hip_fail((h), e_, #call); \
   } while (0)
+
+// A stage past its argument checks, and a launch past its "nothing staged" check, first forget what the last one recorded:
+// a failure from there on leaves nothing staged (or launched), never a record that mixes two calls.
+void drop_launch(sfw_handle h) { h->last = sfw_planner_s::launch_record{}; }
+void drop_stage(sfw_handle h) {
+  h->st.valid = false;
+  h->st.arena_pending = false;
+  h->st.early_poses = false;
+  drop_launch(h);
+}
 
 // K2 through the kernels the precision mode names (SFW_PRECISION_F64_STRICT: the build with the longer polynomials)
 hipError_t launch_social_of(const sfw_launch &L, hipStream_t stream, const sfw_split_streams *sp = nullptr) {
@@ -287,7 +340,7 @@ bool all_finite(const double *v, size_t n) {
 // (one core busy for the duration of the launch, as a caller asking hipDeviceScheduleSpin would have it) for up to spin_us,
 // then blocks.
 hipError_t wait_stream(sfw_handle h) {
-  if (h->spin_us > 0) {
+  if (h->cfg.spin_us > 0) {
     const auto t0 = std::chrono::steady_clock::now();
     bool polled = false;
     for (;;) {
@@ -299,7 +352,7 @@ hipError_t wait_stream(sfw_handle h) {
         return e;
       }
       polled = true;
-      if (std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count() > h->spin_us) break;
+      if (std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count() > h->cfg.spin_us) break;
 #if defined(__x86_64__)
       __builtin_ia32_pause();
 #endif
@@ -309,7 +362,7 @@ hipError_t wait_stream(sfw_handle h) {
   return hipStreamSynchronize(h->stream);
 }
 // ... after which no upload enqueued on it is still reading its pinned staging area
-void stream_is_idle(sfw_handle h) { h->pin_map.pending = h->pin_world.pending = h->pin_cls.pending = false; }
+void stream_is_idle(sfw_handle h) { h->pin_map.pending = h->pin_arena.pending = h->pin_cls.pending = false; }
 
 // the register-form K2 addresses a unit inside a step row of the position / velocity table by a 32-bit byte offset: a row of
 // `chunk` positions and at most chunk + 2 velocities (a one-column grid) must stay below 4 GB
@@ -342,44 +395,44 @@ constexpr size_t kTableBytesPerSampleStep = sizeof(sfw_unit) + sizeof(int16_t);
 // Fill the launch descriptor for samples [begin, begin+count).
 void fill_launch(sfw_handle h, sfw_launch &L, int64_t begin, int64_t count, int64_t stride) {
   std::memset(&L, 0, sizeof(L));
-  L.p = h->params;
-  L.S = num_steps_of(h->params);
-  L.dt = h->params.sim_time / L.S;  // ref :527
-  L.rs = h->rs;
-  L.ga = h->ga;
-  L.vy_samp = h->vy_samp;
-  L.skip_zero_sample = h->skip_zero;
-  L.linvels = h->d_linvels;
-  L.angvels = h->d_angvels;
-  L.nv = h->nv;
-  L.nw = h->nw;
+  L.p = h->live.params;
+  L.S = num_steps_of(h->live.params);
+  L.dt = h->live.params.sim_time / L.S;  // ref :527
+  L.rs = h->st.rs;
+  L.ga = h->st.ga;
+  L.vy_samp = h->st.vy_samp;
+  L.skip_zero_sample = h->st.skip_zero;
+  L.linvels = h->st.d_linvels;
+  L.angvels = h->st.d_angvels;
+  L.nv = h->st.nv;
+  L.nw = h->st.nw;
   L.chunk_begin = begin;
   L.chunk_count = count;
-  L.cells = h->d_cells;
-  L.size_x = h->size_x;
-  L.size_y = h->size_y;
-  L.origin_x = h->origin_x;
-  L.origin_y = h->origin_y;
-  L.resolution = h->resolution;
-  L.footprint = h->d_footprint;
-  L.K = h->st_K;
-  L.agent_pos = h->d_agent_pos;
-  L.agent_vel = h->d_agent_vel;
-  L.agent_c = h->d_agent_c;
-  L.agent_rest = h->d_agent_rest;
-  L.pin_rest = h->d_pin_rest;
-  L.A = h->st_A;
-  L.obstacles = h->d_obstacles;
-  L.O = h->st_O;
-  L.agent_grp = h->d_agent_grp;
-  L.grp_off = h->d_grp_off;
-  L.grp_mem = h->d_grp_mem;
-  L.NG = h->st_NG;
-  L.n_grp_mem = h->st_n_grp_mem;
-  L.n_cu = h->n_cu;
-  L.n_xcd = h->n_xcd;
+  L.cells = h->st.d_cells;
+  L.size_x = h->st.map.size_x;
+  L.size_y = h->st.map.size_y;
+  L.origin_x = h->st.map.origin_x;
+  L.origin_y = h->st.map.origin_y;
+  L.resolution = h->st.map.resolution;
+  L.footprint = h->st.d_footprint;
+  L.K = h->st.K;
+  L.agent_pos = h->st.d_agent_pos;
+  L.agent_vel = h->st.d_agent_vel;
+  L.agent_c = h->st.d_agent_c;
+  L.agent_rest = h->st.d_agent_rest;
+  L.pin_rest = h->st.d_pin_rest;
+  L.A = h->st.A;
+  L.obstacles = h->st.d_obstacles;
+  L.O = h->st.O;
+  L.agent_grp = h->st.d_agent_grp;
+  L.grp_off = h->st.d_grp_off;
+  L.grp_mem = h->st.d_grp_mem;
+  L.NG = h->st.NG;
+  L.n_grp_mem = h->st.n_grp_mem;
+  L.n_cu = h->cfg.n_cu;
+  L.n_xcd = h->cfg.n_xcd;
   sfw_derive(L);
-  if (h->obs_tasks_force >= 0 && L.O > 0) L.k.obs_tasks = h->obs_tasks_force;
+  if (h->cfg.obs_tasks_force >= 0 && L.O > 0) L.k.obs_tasks = h->cfg.obs_tasks_force;
   L.pair_tab = h->pair_tab.p;
   L.status = h->status.p;
   L.base_cost = h->base_cost.p;
@@ -387,7 +440,7 @@ void fill_launch(sfw_handle h, sfw_launch &L, int64_t begin, int64_t count, int6
   L.coll_step = h->coll_step.p;
   L.ptab = h->ptab.p;
   L.cs_tab = h->cs_tab.p;
-  L.row_units = table_row_units(stride, h->nw);
+  L.row_units = table_row_units(stride, h->st.nw);
   L.fcode = h->fcode.p;
   L.rstep_stride = stride;
   L.points = nullptr;
@@ -396,10 +449,10 @@ void fill_launch(sfw_handle h, sfw_launch &L, int64_t begin, int64_t count, int6
   L.step_begin = 0;
   L.step_end = L.S;
   L.resume = 0;
-  L.k2_form = h->k2_form;
-  L.index_base = h->index_base;
+  L.k2_form = h->live.k2_form;
+  L.index_base = h->st.index_base;
   L.cycle_counter = h->cycle_counter.p;
-  L.sel_out = h->d_sel;
+  L.sel_out = h->st.d_sel;
   L.costs_host = nullptr;
   L.sel_host = nullptr;
   L.arena_host = nullptr;
@@ -711,19 +764,19 @@ void plan_row_blocks(const std::vector<double> &lin, const std::vector<double> &
 // Decide the levels of the staged grid's shared-prefix tree and lay the class tables out per chunk of
 // whole rows.
 int plan_prefix(sfw_handle h, int64_t chunk, int S) {
-  h->prefix_steps.clear();
-  h->prefix_chunks.clear();
-  h->cls_ints.clear();
-  h->cls_max = 0;
-  h->prefix_class_steps = h->prefix_last_classes = 0;
-  const int64_t T = static_cast<int64_t>(h->nv) * h->nw;
-  const bool forced = !h->prefix_env.empty();
-  if ((forced && h->prefix_env[0] == 0) || h->st_A < 2 || S < 2 || h->vy_samp != 0.0) return SFW_OK;
+  h->st.prefix_steps.clear();
+  h->st.prefix_chunks.clear();
+  h->st.cls_ints.clear();
+  h->st.cls_max = 0;
+  h->st.prefix_class_steps = h->st.prefix_last_classes = 0;
+  const int64_t T = static_cast<int64_t>(h->st.nv) * h->st.nw;
+  const bool forced = !h->cfg.prefix_env.empty();
+  if ((forced && h->cfg.prefix_env[0] == 0) || h->st.A < 2 || S < 2 || h->st.vy_samp != 0.0) return SFW_OK;
   if (!forced && T < 4096) return SFW_OK;  // the GPU is not full: extra launches cost more than they save
-  const int64_t rows_per_chunk = chunk / h->nw;
+  const int64_t rows_per_chunk = chunk / h->st.nw;
   if (rows_per_chunk < 1) return SFW_OK;  // a single row does not fit the table budget: no sharing
   prefix_classes pc;
-  classes_of_grid(pc, h->h_lin, h->h_ang, h->rs.vx, h->rs.vtheta, h->ga.acc_x, h->ga.acc_theta, h->params.sim_time / S, S,
+  classes_of_grid(pc, h->st.lin, h->st.ang, h->st.rs.vx, h->st.rs.vtheta, h->st.ga.acc_x, h->st.ga.acc_theta, h->live.params.sim_time / S, S,
                   static_cast<const axis_classes *>(h->shared_cols));
   const axis_classes &rc = pc.rows, &cc = *pc.cols;
   const std::vector<int32_t> &nr = pc.rows.n, &nc = pc.cols->n;
@@ -731,19 +784,19 @@ int plan_prefix(sfw_handle h, int64_t chunk, int S) {
   auto count_at = [](const std::vector<int32_t> &n, int p) { return n[std::min<size_t>(static_cast<size_t>(p), n.size()) - 1]; };
   std::vector<int> steps;
   if (forced) {
-    for (int p : h->prefix_env)
+    for (int p : h->cfg.prefix_env)
       if (p >= 1 && p <= pc.max_p) steps.push_back(p);
   } else {
-    steps = choose_levels(pc, T, S, static_cast<double>(sfw_samples_per_wave(h->st_A, std::min<int64_t>(T, rows_per_chunk * h->nw), h->k2_form, h->n_cu)), h->n_cu);
+    steps = choose_levels(pc, T, S, static_cast<double>(sfw_samples_per_wave(h->st.A, std::min<int64_t>(T, rows_per_chunk * h->st.nw), h->live.k2_form, h->cfg.n_cu)), h->cfg.n_cu);
   }
   if (steps.empty()) return SFW_OK;
   const size_t n_lv = steps.size();
 
   // ---- tables: columns (chunk-independent), then rows per chunk
   std::vector<int32_t> ints;
-  ints.swap(h->cls_ints);  // (reuse the last stage's allocation)
+  ints.swap(h->st.cls_ints);  // (reuse the last stage's allocation)
   ints.clear();
-  ints.reserve(static_cast<size_t>(2 * n_lv + 2) * static_cast<size_t>(h->nv + h->nw));
+  ints.reserve(static_cast<size_t>(2 * n_lv + 2) * static_cast<size_t>(h->st.nv + h->st.nw));
   auto append = [&](const std::vector<int32_t> &v) {
     const size_t o = ints.size();
     ints.insert(ints.end(), v.begin(), v.end());
@@ -781,20 +834,20 @@ int plan_prefix(sfw_handle h, int64_t chunk, int S) {
     }
     return out;
   };
-  const std::vector<axis_level> cols = axis_levels(cc, 0, h->nw);
+  const std::vector<axis_level> cols = axis_levels(cc, 0, h->st.nw);
   std::vector<size_t> o_col_rep(n_lv), o_col_src(n_lv);
   for (size_t l = 0; l < n_lv; ++l) {
     o_col_rep[l] = append(cols[l].rep);
     o_col_src[l] = append(cols[l].src);
   }
-  h->prefix_o_col_cls = append(cols[n_lv - 1].local);
+  h->st.prefix_o_col_cls = append(cols[n_lv - 1].local);
   int64_t max_cls = 0;
-  for (int64_t r0 = 0; r0 < h->nv; r0 += rows_per_chunk) {
-    const int64_t r1 = std::min<int64_t>(h->nv, r0 + rows_per_chunk);
+  for (int64_t r0 = 0; r0 < h->st.nv; r0 += rows_per_chunk) {
+    const int64_t r1 = std::min<int64_t>(h->st.nv, r0 + rows_per_chunk);
     const std::vector<axis_level> rows = axis_levels(rc, r0, r1);
-    sfw_planner_s::chunk_plan cp;
+    chunk_plan cp;
     for (size_t l = 0; l < n_lv; ++l) {
-      sfw_planner_s::level_tables t;
+      level_tables t;
       t.n_row = static_cast<int32_t>(rows[l].rep.size());
       t.n_col = static_cast<int32_t>(cols[l].rep.size());
       t.o_row_rep = append(rows[l].rep);
@@ -804,26 +857,26 @@ int plan_prefix(sfw_handle h, int64_t chunk, int S) {
       cp.lv.push_back(t);
       const int64_t n = static_cast<int64_t>(t.n_row) * t.n_col;
       max_cls = std::max(max_cls, n);
-      h->prefix_class_steps += n * (steps[l] - (l ? steps[l - 1] : 0));
-      if (l + 1 == n_lv) h->prefix_last_classes += n;
+      h->st.prefix_class_steps += n * (steps[l] - (l ? steps[l - 1] : 0));
+      if (l + 1 == n_lv) h->st.prefix_last_classes += n;
     }
     cp.o_row_cls = append(rows[n_lv - 1].local);
-    h->prefix_chunks.push_back(cp);
+    h->st.prefix_chunks.push_back(cp);
   }
   // (host only: the tables reach the device with the stage's one arena copy — stage_common — or, when a launch re-plans
   // after sfw_set_params, by a copy of their own: upload_class_tables)
-  h->cls_ints.swap(ints);
-  h->cls_max = max_cls;
-  h->cls_two = n_lv > 1;
+  h->st.cls_ints.swap(ints);
+  h->st.cls_max = max_cls;
+  h->st.cls_two = n_lv > 1;
   if (std::getenv("SFW_DEBUG_PLAN")) {
-    std::fprintf(stderr, "[sfw] shared prefix, %d x %d samples, S=%d, %zu chunk(s):", h->nv, h->nw, S, h->prefix_chunks.size());
+    std::fprintf(stderr, "[sfw] shared prefix, %d x %d samples, S=%d, %zu chunk(s):", h->st.nv, h->st.nw, S, h->st.prefix_chunks.size());
     for (size_t l = 0; l < n_lv; ++l)
       std::fprintf(stderr, " [%d,%d) %d x %d;", l ? steps[l - 1] : 0, steps[l], count_at(nr, steps[l]), count_at(nc, steps[l]));
     std::fprintf(stderr, " [%d,%d) samples\n", steps.back(), S);
   }
-  h->prefix_steps = steps;
-  h->prefix_S = S;
-  h->prefix_chunk = rows_per_chunk * h->nw;
+  h->st.prefix_steps = steps;
+  h->st.prefix_S = S;
+  h->st.prefix_chunk = rows_per_chunk * h->st.nw;
   return SFW_OK;
 }
 
@@ -955,115 +1008,134 @@ bool pinned_rest_table(const sfw_params &p, const sfw_robot_state &rs, const dou
 // §10): a person that can never move next to a robot that moves now and brakes to a stop inside some sample's rollout.
 // Decided from what the stage uploaded, with the device's own velocity recurrence (plain IEEE operations).
 bool rest_noise_unreproduced(sfw_handle h) {
-  if (!h->staged || h->st_A < 2 || (h->rs.vx == 0.0 && h->rs.vy == 0.0)) return false;  // (standing from the start: reproduced)
-  const sfw_agent_const *cst = reinterpret_cast<const sfw_agent_const *>(h->h_agents.data() + h->ao_cst);
-  bool pinned = false;
-  for (int i = 1; i < h->st_A && i < h->A; ++i) pinned |= (cst[i].desired_velocity == 0.0);
-  if (!pinned || h->vy_samp != 0.0) return false;
+  if (!h->st.valid || h->st.A < 2 || (h->st.rs.vx == 0.0 && h->st.rs.vy == 0.0)) return false;  // (standing from the start: reproduced)
+  if (!h->st.person_pinned || h->st.vy_samp != 0.0) return false;
   bool zero_row = false;
-  for (double v : h->h_lin) zero_row |= (v == 0.0);
+  for (double v : h->st.lin) zero_row |= (v == 0.0);
   if (!zero_row) return false;
-  const int S = num_steps_of(h->params);
-  const double dt = h->params.sim_time / S;
-  double vx = h->rs.vx, vy = h->rs.vy;
+  const int S = num_steps_of(h->live.params);
+  const double dt = h->live.params.sim_time / S;
+  double vx = h->st.rs.vx, vy = h->st.rs.vy;
   for (int i = 0; i + 1 < S; ++i) {  // at rest AFTER step i < S - 1: at least one step is integrated from the rest pose
-    vx = new_velocity_host(0.0, vx, h->ga.acc_x, dt);
-    vy = new_velocity_host(0.0, vy, h->ga.acc_y, dt);
+    vx = new_velocity_host(0.0, vx, h->st.ga.acc_x, dt);
+    vy = new_velocity_host(0.0, vy, h->st.ga.acc_y, dt);
     if (vx == 0.0 && vy == 0.0) return true;
   }
   return false;
 }
 
-// Host half: chunk size under the table budget and the shared-prefix plan (class tables in h->cls_ints).  No device call.
+// Host half: chunk size under the table budget and the shared-prefix plan (class tables in h->st.cls_ints).  No device call.
 int64_t plan_tables_host(sfw_handle h, int *err) {
-  const int64_t T = static_cast<int64_t>(h->nv) * h->nw;
-  const int S = num_steps_of(h->params);
-  h->early_poses = false;
+  const int64_t T = static_cast<int64_t>(h->st.nv) * h->st.nw;
+  const int S = num_steps_of(h->live.params);
+  h->st.early_poses = false;
   int64_t chunk = static_cast<int64_t>(
-      h->table_budget_bytes / (kTableBytesPerSampleStep * S));
+      h->cfg.table_budget_bytes / (kTableBytesPerSampleStep * S));
   if (chunk < 1024) chunk = 1024;
   if (chunk > kRowLimit) chunk = kRowLimit;
   if (chunk > T) chunk = T;
   *err = plan_prefix(h, chunk, S);
-  h->plan_epoch = h->params_epoch;
+  h->st.plan_epoch = h->live.params_epoch;
   return chunk;
 }
 // Device half: the K1->K2 tables and the class-record buffers; with may_start_poses the pose rollout of a single-chunk grid
 // is enqueued here, by the STAGE (the robot's poses depend on the sample vectors alone).
 int plan_tables_device(sfw_handle h, int64_t chunk, bool may_start_poses) {
-  const int64_t T = static_cast<int64_t>(h->nv) * h->nw;
-  const int S = num_steps_of(h->params);
-  SFW_HIP(h, h->ptab.reserve(static_cast<size_t>(table_row_units(chunk, h->nw)) * S));
-  SFW_HIP(h, h->cs_tab.reserve(static_cast<size_t>(h->nw) * S));
+  const int64_t T = static_cast<int64_t>(h->st.nv) * h->st.nw;
+  const int S = num_steps_of(h->live.params);
+  SFW_HIP(h, h->ptab.reserve(static_cast<size_t>(table_row_units(chunk, h->st.nw)) * S));
+  SFW_HIP(h, h->cs_tab.reserve(static_cast<size_t>(h->st.nw) * S));
   SFW_HIP(h, h->fcode.reserve(static_cast<size_t>(chunk) * S));
-  h->table_chunk = chunk;
-  if (!h->prefix_steps.empty())
-    for (size_t b = 0; b < (h->cls_two ? 2u : 1u); ++b) {
-      SFW_HIP(h, h->cls_dead[b].reserve(static_cast<size_t>(h->cls_max)));
-      SFW_HIP(h, h->cls_state[b].reserve(static_cast<size_t>(h->cls_max) * h->st_A));
+  h->st.table_chunk = chunk;
+  if (!h->st.prefix_steps.empty())
+    for (size_t b = 0; b < (h->st.cls_two ? 2u : 1u); ++b) {
+      SFW_HIP(h, h->cls_dead[b].reserve(static_cast<size_t>(h->st.cls_max)));
+      SFW_HIP(h, h->cls_state[b].reserve(static_cast<size_t>(h->st.cls_max) * h->st.A));
     }
   if (may_start_poses && chunk >= T) {
     sfw_launch L;
     fill_launch(h, L, 0, T, T);
     if (!sfw_rollout_is_fused(L)) {  // (the fused small-grid K1 is one launch with the costmap part, and may capture points)
-      h->clock_cleared = false;
-      if (h->timing) {  // the clock probe of a timed launch is cleared by the pose rollout itself (clear_clock_probe)
+      h->st.clock_cleared = false;
+      if (h->live.timing) {  // the clock probe of a timed launch is cleared by the pose rollout itself (clear_clock_probe)
         SFW_HIP(h, h->clock.reserve(4));
         L.clock_probe = h->clock.p;
-        h->clock_cleared = true;
+        h->st.clock_cleared = true;
       }
-      if (h->timing) SFW_HIP(h, hipEventRecord(h->ev[0], h->stream));
-      h->early_poses_timed = h->timing;
-      h->early_poses_terms = h->capture_terms;
-      if (h->capture_terms) {
+      if (h->live.timing) SFW_HIP(h, hipEventRecord(h->ev[0], h->stream));
+      h->st.early_poses_timed = h->live.timing;
+      h->st.early_poses_terms = h->live.capture_terms;
+      if (h->live.capture_terms) {
         SFW_HIP(h, h->terms.reserve(static_cast<size_t>(SFW_N_TERMS) * static_cast<size_t>(T)));
         L.terms = h->terms.p;
         L.terms_T = T;
       }
-      if (h->arena_pending) {  // no copy was enqueued: this kernel fetches the arena, and reads its sample vectors at their host addresses
-        L.arena_host = h->pin_world.p + h->arena_from;
-        L.arena_dev = h->world.p + h->arena_from;
-        L.arena_bytes = static_cast<uint32_t>(h->arena_bytes);
-        L.linvels = reinterpret_cast<const double *>(h->pin_world.p + (reinterpret_cast<const char *>(h->d_linvels) - h->world.p));
-        L.angvels = reinterpret_cast<const double *>(h->pin_world.p + (reinterpret_cast<const char *>(h->d_angvels) - h->world.p));
+      if (h->st.arena_pending) {  // no copy was enqueued: this kernel fetches the arena, and reads its sample vectors at their host addresses
+        L.arena_host = h->pin_arena.p + h->st.arena_from;
+        L.arena_dev = h->arena.p + h->st.arena_from;
+        L.arena_bytes = static_cast<uint32_t>(h->st.arena_bytes);
+        L.linvels = reinterpret_cast<const double *>(h->pin_arena.p + (reinterpret_cast<const char *>(h->st.d_linvels) - h->arena.p));
+        L.angvels = reinterpret_cast<const double *>(h->pin_arena.p + (reinterpret_cast<const char *>(h->st.d_angvels) - h->arena.p));
       }
       SFW_HIP(h, sfw_launch_rollout_poses(L, h->stream));
-      if (h->arena_pending) {
-        h->arena_pending = false;
-        SFW_HIP(h, h->pin_world.mark(h->stream));
+      if (h->st.arena_pending) {
+        h->st.arena_pending = false;
+        SFW_HIP(h, h->pin_arena.mark(h->stream));
       }
-      h->early_poses = true;
+      h->st.early_poses = true;
     }
   }
   return SFW_OK;
 }
 // The class tables by a copy of their own (a launch that re-plans after sfw_set_params: the stage's arena is on the device already)
 int upload_class_tables(sfw_handle h) {
-  h->d_cls_tab = nullptr;
-  if (h->cls_ints.empty()) return SFW_OK;
-  const size_t bytes = sizeof(int32_t) * h->cls_ints.size();
-  SFW_HIP(h, h->d_cls.reserve(h->cls_ints.size()));
+  h->st.d_cls_tab = nullptr;
+  if (h->st.cls_ints.empty()) return SFW_OK;
+  const size_t bytes = sizeof(int32_t) * h->st.cls_ints.size();
+  SFW_HIP(h, h->d_cls.reserve(h->st.cls_ints.size()));
   SFW_HIP(h, h->pin_cls.reserve(bytes));
-  std::memcpy(h->pin_cls.p, h->cls_ints.data(), bytes);
+  std::memcpy(h->pin_cls.p, h->st.cls_ints.data(), bytes);
   SFW_HIP(h, hipMemcpyAsync(h->d_cls.p, h->pin_cls.p, bytes, hipMemcpyHostToDevice, h->stream));
   SFW_HIP(h, h->pin_cls.mark(h->stream));
-  h->d_cls_tab = h->d_cls.p;
+  h->st.d_cls_tab = h->d_cls.p;
   return SFW_OK;
 }
+int flush_arena(sfw_handle h);
+
 // Everything of a stage that depends on sfw_params, redone by a launch when sfw_set_params came in between (the reference
-// re-reads its parameters every cycle, :125): a plan made for another dt would merge samples whose robot trajectories now differ.
+// re-reads its parameters every cycle, :125): a plan made for another dt would merge samples whose robot trajectories now
+// differ.  Also drops the poses the stage started: they were rolled out under the old parameters.
 int replan_at_launch(sfw_handle h) {
+  if (int e = flush_arena(h)) return e;  // (the device copy of the rest terms is patched below)
   int err = SFW_OK;
   const int64_t chunk = plan_tables_host(h, &err);
   if (err) return err;
   if (int e = plan_tables_device(h, chunk, false)) return e;
-  return upload_class_tables(h);
+  if (int e = upload_class_tables(h)) return e;
+  if (h->st.d_agent_rest && !h->st.rest_pairs.empty()) {  // the relative-rest terms depend on the sfm parameters too
+    const size_t bytes = sizeof(double) * 2 * static_cast<size_t>(h->st.A);
+    SFW_HIP(h, h->pin_cls.wait());
+    SFW_HIP(h, h->pin_out.reserve(bytes));
+    rest_forces(h->live.params, h->st.rest_pairs, h->st.rest_pv.data(), h->st.rest_pv.data() + 2 * h->st.A, h->st.A,
+                reinterpret_cast<double *>(h->pin_out.p));
+    SFW_HIP(h, hipMemcpyAsync(const_cast<double *>(h->st.d_agent_rest), h->pin_out.p, bytes, hipMemcpyHostToDevice, h->stream));
+    SFW_HIP(h, hipStreamSynchronize(h->stream));  // pin_out is the fetch buffer too: rare path, keep it simple
+  }
+  if (h->st.d_pin_rest && h->st.pin_doubles) {  // ... and so does the pinned-rest table
+    const size_t bytes = sizeof(double) * h->st.pin_doubles;
+    SFW_HIP(h, h->pin_cls.wait());
+    SFW_HIP(h, h->pin_out.reserve(bytes));
+    pinned_rest_table(h->live.params, h->st.rs, h->st.pin_pos.data(), h->st.pin_cst.data(), h->st.A, reinterpret_cast<double *>(h->pin_out.p));
+    SFW_HIP(h, hipMemcpyAsync(const_cast<double *>(h->st.d_pin_rest), h->pin_out.p, bytes, hipMemcpyHostToDevice, h->stream));
+    SFW_HIP(h, hipStreamSynchronize(h->stream));
+  }
+  return SFW_OK;
 }
 
 // The agent / laser-point set must fit one wave's LDS allocation (160 KiB per CU).
-int check_lds(sfw_handle h, int64_t items) {
-  const size_t lds = sfw_social_lds_bytes(h->st_A, h->st_O, h->st_NG, h->st_n_grp_mem, items, h->k2_form, h->n_cu);
-  if (h->st_A > 0 && lds > 160 * 1024)
+int check_lds(sfw_handle h, int A, int O, int NG, int n_grp_mem, int64_t items) {
+  const size_t lds = sfw_social_lds_bytes(A, O, NG, n_grp_mem, items, h->live.k2_form, h->cfg.n_cu);
+  if (A > 0 && lds > 160 * 1024)
     return fail(h, SFW_ERR_UNSUPPORTED, "agent/obstacle set does not fit the 160 KiB LDS of one CU");
   return SFW_OK;
 }
@@ -1096,46 +1168,50 @@ struct host_phases {
   }
 };
 
-int flush_arena(sfw_handle h);
-
 int stage_common(sfw_handle h, const sfw_robot_state *rs, const double *lin, int32_t nv, const double *ang,
                  int32_t nw, const sfw_goal_args *args, double vy_samp, int skip_zero, int64_t index_base,
                  bool grid = false) {
   if (!h) return SFW_ERR_INVALID_ARG;
   if (!rs || !lin || !ang || !args || nv <= 0 || nw <= 0)
     return fail(h, SFW_ERR_INVALID_ARG, "grid_stage: null pointer or non-positive sample count");
-  if (!h->have_costmap) return fail(h, SFW_ERR_STATE, "grid_stage: no costmap set (sfw_set_costmap)");
+  if (!h->world.have_costmap) return fail(h, SFW_ERR_STATE, "grid_stage: no costmap set (sfw_set_costmap)");
   // A NaN would come back as a NaN cost (the header promises sentinels, never NaN) and, in a sample vector, break the
   // ordering the shared-prefix planner sorts by: O(nv + nw) checks
   if (!all_finite(&rs->x, 6) || !all_finite(&args->acc_x, 5) || !std::isfinite(vy_samp))
     return fail(h, SFW_ERR_INVALID_ARG, "grid_stage: non-finite robot state, goal argument or sample velocity");
   if (!all_finite(lin, static_cast<size_t>(nv)) || !all_finite(ang, static_cast<size_t>(nw)))
     return fail(h, SFW_ERR_INVALID_ARG, "grid_stage: non-finite sample velocity");
+  drop_stage(h);  // (valid again at the end of this function, and only there)
   host_phases ph("stage:");
   SFW_HIP(h, hipSetDevice(h->device));
+  const agent_set &ag = h->world.agents;
+  const map_geometry &map = h->world.map_new;
   // a large costmap that has changed goes out first, by a copy of its own that runs while the host plans and packs
-  if (h->cells_dirty && static_cast<size_t>(h->map_new.size_x) * h->map_new.size_y > kMapMergeMax) {
-    const size_t n_cells = static_cast<size_t>(h->map_new.size_x) * h->map_new.size_y;
+  const size_t n_cells = static_cast<size_t>(map.size_x) * map.size_y;
+  const bool merge = n_cells <= kMapMergeMax;
+  if (h->world.cells_dirty && !merge) {
     SFW_HIP(h, h->cells.reserve(n_cells));
     SFW_HIP(h, hipMemcpyAsync(h->cells.p, h->pin_map.p, n_cells, hipMemcpyHostToDevice, h->stream));
     SFW_HIP(h, h->pin_map.mark(h->stream));
-    h->cells_dirty = false;
+    h->world.cells_dirty = false;
   }
   ph.mark("check+setdev");
-  h->h_lin.assign(lin, lin + nv);
-  h->h_ang.assign(ang, ang + nw);
-  h->st_K = h->K;
-  h->st_A = h->A;
-  h->st_O = h->O;
-  h->st_NG = h->NG;
-  h->st_n_grp_mem = h->n_grp_mem;
-  h->nv = nv;
-  h->nw = nw;
-  h->rs = *rs;
-  h->ga = *args;
-  h->vy_samp = vy_samp;
-  h->skip_zero = skip_zero;
-  h->index_base = index_base;
+  h->st.lin.assign(lin, lin + nv);
+  h->st.ang.assign(ang, ang + nw);
+  h->st.K = h->world.K;
+  h->st.A = ag.A;
+  h->st.O = ag.O;
+  h->st.NG = ag.NG;
+  h->st.n_grp_mem = ag.n_grp_mem;
+  h->st.person_pinned = ag.person_pinned;
+  h->st.nv = nv;
+  h->st.nw = nw;
+  h->st.rs = *rs;
+  h->st.ga = *args;
+  h->st.vy_samp = vy_samp;
+  h->st.skip_zero = skip_zero;
+  h->st.index_base = index_base;
+  h->st.map = map;
   // The shared-prefix plan FIRST, on the host (a few microseconds since round 6: axis_classes): its class tables ride in the
   // stage's one arena copy and the levels can be enqueued right behind the pose rollout.  (Rounds 1-5 planned behind the
   // arena copy and the pose rollout, 25-50 us, and sent the tables in a second copy the first level then waited for.)
@@ -1143,131 +1219,127 @@ int stage_common(sfw_handle h, const sfw_robot_state *rs, const double *lin, int
   const int64_t chunk = plan_tables_host(h, &plan_err);
   if (plan_err) return plan_err;
   ph.mark("plan");
+  // a small costmap (<= 64 KB: a control cycle's local costmap of 200 x 200 cells) is the head of the arena and sent with
+  // it when it has changed; a larger one has gone out by a copy of its own (above)
+  auto up16 = [](size_t b) { return (b + 15) & ~size_t(15); };
+  const size_t cells_head = merge ? up16(n_cells) : 0;
   {  // one arena, one copy: footprint | agents blob | linvels | angvels | relative-rest terms | pinned-rest table | class tables
-    auto up16 = [](size_t b) { return (b + 15) & ~size_t(15); };
-    const bool rest = !h->rest_pairs.empty();
-    // a small costmap (<= 64 KB: a control cycle's local costmap of 200 x 200 cells) is the head of the arena and sent with
-    // it when it has changed; a larger one has gone out by a copy of its own at the top of this stage (above)
-    const size_t n_cells = static_cast<size_t>(h->map_new.size_x) * h->map_new.size_y;
-    const bool merge = n_cells <= kMapMergeMax;
-    const size_t cells_head = merge ? up16(n_cells) : 0;
-    const size_t o_fp = cells_head, o_ag = o_fp + up16(sizeof(double) * (h->h_footprint.empty() ? 2 : h->h_footprint.size())),
-                 o_lin = o_ag + up16(h->h_agents.size()), o_ang = o_lin + up16(sizeof(double) * nv),
+    const bool rest = !ag.rest_pairs.empty();
+    const size_t o_fp = cells_head, o_ag = o_fp + up16(sizeof(double) * (h->world.footprint.empty() ? 2 : h->world.footprint.size())),
+                 o_lin = o_ag + up16(ag.blob.size()), o_ang = o_lin + up16(sizeof(double) * nv),
                  o_rest = o_ang + up16(sizeof(double) * nw),
-                 o_pin = o_rest + (rest ? up16(sizeof(double) * 2 * static_cast<size_t>(h->A)) : 0),
-                 pin_doubles = 4 + static_cast<size_t>(h->A > 0 ? h->A : 0),
+                 o_pin = o_rest + (rest ? up16(sizeof(double) * 2 * static_cast<size_t>(ag.A)) : 0),
+                 pin_doubles = 4 + static_cast<size_t>(ag.A > 0 ? ag.A : 0),
                  // (room for the pinned-rest table whenever the robot stands still at hand-over: whether one is needed is known
                  // once the agents' constants have been looked at, below)
-                 o_cls = o_pin + ((h->pin_rest_on && rs->vx == 0.0 && rs->vy == 0.0 && h->A > 1) ? up16(sizeof(double) * pin_doubles) : 0),
-                 total = o_cls + up16(sizeof(int32_t) * h->cls_ints.size());
-    SFW_HIP(h, h->pin_world.reserve(total));
-    // (a `world` that moves, or whose head changes size, has lost its copy of the cells)
-    bool send_cells = h->cells_dirty || (merge && (!h->cells_in_world || h->world_cells_bytes != cells_head || total > h->world.cap));
-    SFW_HIP(h, h->world.reserve(total));
-    char *pb = h->pin_world.p;
-    if (!merge) send_cells = false;  // (sent above)
-    if (merge && send_cells) std::memcpy(pb, h->pin_map.p, n_cells);
-    h->cells_dirty = false;
-    h->cells_in_world = merge;
-    h->world_cells_bytes = cells_head;
-    h->size_x = h->map_new.size_x;
-    h->size_y = h->map_new.size_y;
-    h->origin_x = h->map_new.origin_x;
-    h->origin_y = h->map_new.origin_y;
-    h->resolution = h->map_new.resolution;
-    if (!h->h_footprint.empty()) std::memcpy(pb + o_fp, h->h_footprint.data(), sizeof(double) * h->h_footprint.size());
-    if (!h->h_agents.empty()) std::memcpy(pb + o_ag, h->h_agents.data(), h->h_agents.size());
+                 o_cls = o_pin + ((h->cfg.pin_rest_on && rs->vx == 0.0 && rs->vy == 0.0 && ag.A > 1) ? up16(sizeof(double) * pin_doubles) : 0),
+                 total = o_cls + up16(sizeof(int32_t) * h->st.cls_ints.size());
+    SFW_HIP(h, h->pin_arena.reserve(total));
+    // (an `arena` that moves, or that this stage does not keep the cells at the head of, loses its copy of them)
+    if (!merge || total > h->arena.cap) h->st.cells_in_arena = false;
+    const bool send_cells = merge && (h->world.cells_dirty || !h->st.cells_in_arena || h->st.arena_cells_bytes != cells_head);
+    SFW_HIP(h, h->arena.reserve(total));
+    char *pb = h->pin_arena.p;
+    if (send_cells) std::memcpy(pb, h->pin_map.p, n_cells);
+    if (!h->world.footprint.empty()) std::memcpy(pb + o_fp, h->world.footprint.data(), sizeof(double) * h->world.footprint.size());
+    if (!ag.blob.empty()) std::memcpy(pb + o_ag, ag.blob.data(), ag.blob.size());
     std::memcpy(pb + o_lin, lin, sizeof(double) * nv);
     std::memcpy(pb + o_ang, ang, sizeof(double) * nw);
-    if (!h->cls_ints.empty()) std::memcpy(pb + o_cls, h->cls_ints.data(), sizeof(int32_t) * h->cls_ints.size());
-    h->st_rest_pairs.clear();
+    if (!h->st.cls_ints.empty()) std::memcpy(pb + o_cls, h->st.cls_ints.data(), sizeof(int32_t) * h->st.cls_ints.size());
+    const double *pos = reinterpret_cast<const double *>(ag.blob.data());
+    const double *vel = reinterpret_cast<const double *>(ag.blob.data() + ag.ao_vel);
+    const sfw_agent_const *cst = reinterpret_cast<const sfw_agent_const *>(ag.blob.data() + ag.ao_cst);
+    h->st.rest_pairs.clear();
     if (rest) {
-      const double *pos = reinterpret_cast<const double *>(h->h_agents.data());
-      const double *vel = reinterpret_cast<const double *>(h->h_agents.data() + h->ao_vel);
-      h->st_rest_pairs = h->rest_pairs;
-      h->st_rest_pv.assign(pos, pos + 2 * h->A);
-      h->st_rest_pv.insert(h->st_rest_pv.end(), vel, vel + 2 * h->A);
-      rest_forces(h->params, h->rest_pairs, pos, vel, h->A, reinterpret_cast<double *>(pb + o_rest));
+      h->st.rest_pairs = ag.rest_pairs;
+      h->st.rest_pv.assign(pos, pos + 2 * ag.A);
+      h->st.rest_pv.insert(h->st.rest_pv.end(), vel, vel + 2 * ag.A);
+      rest_forces(h->live.params, ag.rest_pairs, pos, vel, ag.A, reinterpret_cast<double *>(pb + o_rest));
     }
-    bool pinned = false;
-    if (o_cls > o_pin)
-      pinned = pinned_rest_table(h->params, *rs, reinterpret_cast<const double *>(h->h_agents.data()),
-                                 reinterpret_cast<const sfw_agent_const *>(h->h_agents.data() + h->ao_cst), h->A,
-                                 reinterpret_cast<double *>(pb + o_pin));
+    const bool pinned = o_cls > o_pin && pinned_rest_table(h->live.params, *rs, pos, cst, ag.A, reinterpret_cast<double *>(pb + o_pin));
     ph.mark("pack");
     {
       const size_t from = send_cells ? 0 : cells_head;
       // A control cycle's grid whose costmap has not changed: no copy here.  If the launch turns out to be the one-launch kernel
       // its blocks read the (~1 KB) arena from this pinned memory themselves; else the launch enqueues the copy (flush_arena).
-      h->arena_pending = false;
       // ... and a GPU-filling single-chunk grid: the pose rollout this stage enqueues below (plan_tables_device) fetches the
       // arena — with a small costmap that has changed, if any — itself, its thousands of threads 16 bytes each
       const int64_t T_ = static_cast<int64_t>(nv) * nw;
       const bool small = T_ <= 1024 && from == cells_head && total - from <= (size_t(16) << 10);
       const bool early = T_ > 2048 && chunk >= T_ && total - from <= (size_t(1) << 20);
-      if (grid && h->arena_direct_on && (small || early) && (total - from) % 16 == 0 && from % 16 == 0) {
-        h->arena_pending = true;
-        h->arena_from = from;
-        h->arena_bytes = total - from;
+      if (grid && h->cfg.arena_direct_on && (small || early) && (total - from) % 16 == 0 && from % 16 == 0) {
+        h->st.arena_pending = true;
+        h->st.arena_from = from;
+        h->st.arena_bytes = total - from;
       } else {
-        SFW_HIP(h, hipMemcpyAsync(h->world.p + from, pb + from, total - from, hipMemcpyHostToDevice, h->stream));
+        SFW_HIP(h, hipMemcpyAsync(h->arena.p + from, pb + from, total - from, hipMemcpyHostToDevice, h->stream));
       }
     }
-    h->d_cells = merge ? reinterpret_cast<const uint8_t *>(h->world.p) : h->cells.p;
+    h->st.d_cells = merge ? reinterpret_cast<const uint8_t *>(h->arena.p) : h->cells.p;
     ph.mark("h2d");
-    if (!h->arena_pending) SFW_HIP(h, h->pin_world.mark(h->stream));
+    if (!h->st.arena_pending) SFW_HIP(h, h->pin_arena.mark(h->stream));
     ph.mark("evrec");
-    const char *db = h->world.p;
-    h->d_cls_tab = h->cls_ints.empty() ? nullptr : reinterpret_cast<const int32_t *>(db + o_cls);
-    h->d_pin_rest = pinned ? reinterpret_cast<const double *>(db + o_pin) : nullptr;
-    h->st_pin_doubles = pinned ? pin_doubles : 0;
+    const char *db = h->arena.p;
+    h->st.d_cls_tab = h->st.cls_ints.empty() ? nullptr : reinterpret_cast<const int32_t *>(db + o_cls);
+    h->st.d_pin_rest = pinned ? reinterpret_cast<const double *>(db + o_pin) : nullptr;
+    h->st.pin_doubles = pinned ? pin_doubles : 0;
     if (pinned) {
-      const double *pos = reinterpret_cast<const double *>(h->h_agents.data());
-      const sfw_agent_const *cst = reinterpret_cast<const sfw_agent_const *>(h->h_agents.data() + h->ao_cst);
-      h->st_pin_pos.assign(pos, pos + 2 * h->A);
-      h->st_pin_cst.assign(cst, cst + h->A);
+      h->st.pin_pos.assign(pos, pos + 2 * ag.A);
+      h->st.pin_cst.assign(cst, cst + ag.A);
     }
-    h->d_footprint = reinterpret_cast<const double *>(db + o_fp);
-    h->d_agent_pos = reinterpret_cast<const double *>(db + o_ag);
-    h->d_agent_vel = reinterpret_cast<const double *>(db + o_ag + h->ao_vel);
-    h->d_agent_c = reinterpret_cast<const sfw_agent_const *>(db + o_ag + h->ao_cst);
-    h->d_obstacles = reinterpret_cast<const double *>(db + o_ag + h->ao_obs);
-    h->d_agent_grp = reinterpret_cast<const int32_t *>(db + o_ag + h->ao_grp);
-    h->d_grp_off = reinterpret_cast<const int32_t *>(db + o_ag + h->ao_off);
-    h->d_grp_mem = reinterpret_cast<const int32_t *>(db + o_ag + h->ao_mem);
-    h->d_linvels = reinterpret_cast<const double *>(db + o_lin);
-    h->d_angvels = reinterpret_cast<const double *>(db + o_ang);
-    h->d_agent_rest = rest ? reinterpret_cast<const double *>(db + o_rest) : nullptr;
+    h->st.d_footprint = reinterpret_cast<const double *>(db + o_fp);
+    h->st.d_agent_pos = reinterpret_cast<const double *>(db + o_ag);
+    h->st.d_agent_vel = reinterpret_cast<const double *>(db + o_ag + ag.ao_vel);
+    h->st.d_agent_c = reinterpret_cast<const sfw_agent_const *>(db + o_ag + ag.ao_cst);
+    h->st.d_obstacles = reinterpret_cast<const double *>(db + o_ag + ag.ao_obs);
+    h->st.d_agent_grp = reinterpret_cast<const int32_t *>(db + o_ag + ag.ao_grp);
+    h->st.d_grp_off = reinterpret_cast<const int32_t *>(db + o_ag + ag.ao_off);
+    h->st.d_grp_mem = reinterpret_cast<const int32_t *>(db + o_ag + ag.ao_mem);
+    h->st.d_linvels = reinterpret_cast<const double *>(db + o_lin);
+    h->st.d_angvels = reinterpret_cast<const double *>(db + o_ang);
+    h->st.d_agent_rest = rest ? reinterpret_cast<const double *>(db + o_rest) : nullptr;
   }
-  if (h->pair_tab_A != h->A) {
-    SFW_HIP(h, h->pair_tab.reserve(static_cast<size_t>(sfw_pair_table_entries(h->A))));
-    SFW_HIP(h, sfw_launch_pair_table(h->pair_tab.p, h->A, h->stream));
-    h->pair_tab_A = h->A;
+  if (h->pair_tab_A != ag.A) {
+    h->pair_tab_A = -1;  // (until the table for this count is enqueued)
+    SFW_HIP(h, h->pair_tab.reserve(static_cast<size_t>(sfw_pair_table_entries(ag.A))));
+    SFW_HIP(h, sfw_launch_pair_table(h->pair_tab.p, ag.A, h->stream));
+    h->pair_tab_A = ag.A;
   }
   const int64_t T = static_cast<int64_t>(nv) * nw;
   SFW_HIP(h, h->status.reserve(T));
   SFW_HIP(h, h->coll_step.reserve(T));
   SFW_HIP(h, h->base_cost.reserve(T));
   SFW_HIP(h, h->costs.reserve(T + (sizeof(sfw_sel) + sizeof(double) - 1) / sizeof(double)));
-  h->d_sel = reinterpret_cast<sfw_sel *>(h->costs.p + T);
+  h->st.d_sel = reinterpret_cast<sfw_sel *>(h->costs.p + T);
   SFW_HIP(h, h->partials.reserve(sfw_argmin_partials(T)));
   ph.mark("reserve");
   if (int e = plan_tables_device(h, chunk, grid)) return e;
   if (T > 1024)
     if (int e = flush_arena(h)) return e;  // (no pose rollout was enqueued after all: the copy it would have stood in for)
   ph.mark("tables+K1a");
-  h->staged = true;
-  h->launched = false;
+  // commit: everything the arena carries is enqueued (a pending arena never carries cells: `small` keeps the head)
+  if (merge) {
+    h->world.cells_dirty = false;
+    h->st.cells_in_arena = true;
+    h->st.arena_cells_bytes = cells_head;
+  }
+  h->st.valid = true;
   return SFW_OK;
 }
 
 // The arena a stage left in pinned memory only (arena_pending) goes to the device by a copy after all: the launch is not the
-// one-launch kernel, or something is about to patch the device copy.
+// one-launch kernel, or something is about to patch the device copy.  A copy that cannot be enqueued leaves the device
+// without the staged world: nothing is staged any more.
 int flush_arena(sfw_handle h) {
-  if (!h->arena_pending) return SFW_OK;
-  h->arena_pending = false;
-  SFW_HIP(h, hipMemcpyAsync(h->world.p + h->arena_from, h->pin_world.p + h->arena_from, h->arena_bytes, hipMemcpyHostToDevice, h->stream));
-  SFW_HIP(h, h->pin_world.mark(h->stream));
+  if (!h->st.arena_pending) return SFW_OK;
+  h->st.arena_pending = false;
+  hipError_t e = hipMemcpyAsync(h->arena.p + h->st.arena_from, h->pin_arena.p + h->st.arena_from, h->st.arena_bytes,
+                                hipMemcpyHostToDevice, h->stream);
+  if (e == hipSuccess) e = h->pin_arena.mark(h->stream);
+  if (e != hipSuccess) {
+    drop_stage(h);
+    return hip_fail(h, e, "flush_arena: arena copy");
+  }
   return SFW_OK;
 }
 
@@ -1284,49 +1356,33 @@ struct launch_prep {
   double *terms = nullptr;  // sfw_set_terms_capture: the terms buffer, else null
 };
 
-// timing: record the per-kernel events of this launch (h->timing; a batch launch never does)
+// timing: record the per-kernel events of this launch (h->live.timing; a batch launch never does)
 int launch_prepare(sfw_handle h, bool timing, launch_prep &lp) {
   if (!h) return SFW_ERR_INVALID_ARG;
-  if (!h->staged) return fail(h, SFW_ERR_STATE, "grid_launch before grid_stage");
+  if (!h->st.valid) return fail(h, SFW_ERR_STATE, "grid_launch before grid_stage");
+  drop_launch(h);  // (launched again at the end of cycle_commit / launch_kernels, and only there)
   SFW_HIP(h, hipSetDevice(h->device));
-  const int64_t T = static_cast<int64_t>(h->nv) * h->nw;
-  if (h->plan_epoch != h->params_epoch)
-    if (int e = flush_arena(h)) return e;  // (the re-plan below patches the device copy of the rest terms)
+  const int64_t T = static_cast<int64_t>(h->st.nv) * h->st.nw;
   // sfw_set_params since the stage: tables and shared-prefix plan are redone for the live parameters
-  if (h->plan_epoch != h->params_epoch) {
-    if (int e = replan_at_launch(h)) return e;  // (also drops the poses the stage started: they were rolled out under the old parameters)
-    if (h->d_agent_rest && !h->st_rest_pairs.empty()) {  // the relative-rest terms depend on the sfm parameters too
-      const size_t bytes = sizeof(double) * 2 * static_cast<size_t>(h->st_A);
-      SFW_HIP(h, h->pin_cls.wait());
-      SFW_HIP(h, h->pin_out.reserve(bytes));
-      rest_forces(h->params, h->st_rest_pairs, h->st_rest_pv.data(), h->st_rest_pv.data() + 2 * h->st_A, h->st_A,
-                  reinterpret_cast<double *>(h->pin_out.p));
-      SFW_HIP(h, hipMemcpyAsync(const_cast<double *>(h->d_agent_rest), h->pin_out.p, bytes, hipMemcpyHostToDevice, h->stream));
-      SFW_HIP(h, hipStreamSynchronize(h->stream));  // pin_out is the fetch buffer too: rare path, keep it simple
+  if (h->st.plan_epoch != h->live.params_epoch)
+    if (int e = replan_at_launch(h)) {
+      drop_stage(h);  // (a plan half redone fits neither parameter set)
+      return e;
     }
-    if (h->d_pin_rest && h->st_pin_doubles) {  // ... and so does the pinned-rest table
-      const size_t bytes = sizeof(double) * h->st_pin_doubles;
-      SFW_HIP(h, h->pin_cls.wait());
-      SFW_HIP(h, h->pin_out.reserve(bytes));
-      pinned_rest_table(h->params, h->rs, h->st_pin_pos.data(), h->st_pin_cst.data(), h->st_A, reinterpret_cast<double *>(h->pin_out.p));
-      SFW_HIP(h, hipMemcpyAsync(const_cast<double *>(h->d_pin_rest), h->pin_out.p, bytes, hipMemcpyHostToDevice, h->stream));
-      SFW_HIP(h, hipStreamSynchronize(h->stream));
-    }
-  }
-  const int S = num_steps_of(h->params);
-  int64_t chunk = h->table_chunk;  // (plan_tables_device: what the tables were sized for, under the live step count)
+  const int S = num_steps_of(h->live.params);
+  int64_t chunk = h->st.table_chunk;  // (plan_tables_device: what the tables were sized for, under the live step count)
   if (chunk > kRowLimit) chunk = kRowLimit;
   if (chunk > T) chunk = T;
   if (chunk < 1) return fail(h, SFW_ERR_STATE, "robot-step table too small");
-  if (int e = check_lds(h, chunk)) return e;
+  if (int e = check_lds(h, h->st.A, h->st.O, h->st.NG, h->st.n_grp_mem, chunk)) return e;
   // the shared-prefix plan was laid out for the staged step count and for chunks of whole rows
-  const bool prefix = !h->prefix_steps.empty() && h->prefix_S == S && h->prefix_chunk <= chunk;
-  if (prefix) chunk = h->prefix_chunk;
+  const bool prefix = !h->st.prefix_steps.empty() && h->st.prefix_S == S && h->st.prefix_chunk <= chunk;
+  if (prefix) chunk = h->st.prefix_chunk;
   // the stage enqueued K1a of this (single-chunk) grid already — unless sfw_set_timing(1) arrived since: the events of a
   // timed launch bracket its own kernels, so the pose rollout runs again behind a freshly recorded ev[0]
-  const bool poses_done = h->early_poses && chunk >= T && (!timing || h->early_poses_timed) &&
-                          (!h->capture_terms || h->early_poses_terms);  // (capture turned on since the stage: roll out again)
-  h->early_poses = false;                                 // ... once: a second launch of the same stage rolls out again
+  const bool poses_done = h->st.early_poses && chunk >= T && (!timing || h->st.early_poses_timed) &&
+                          (!h->live.capture_terms || h->st.early_poses_terms);  // (capture turned on since the stage: roll out again)
+  h->st.early_poses = false;                                 // ... once: a second launch of the same stage rolls out again
   if (timing) {
     SFW_HIP(h, h->clock.reserve(4));
     // (cleared by the stage already when it started the pose rollout: in front of it, where the GPU waits for the host's
@@ -1335,24 +1391,23 @@ int launch_prepare(sfw_handle h, bool timing, launch_prep &lp) {
     // front of their K2 part) need the memset
     sfw_launch probe0;
     fill_launch(h, probe0, 0, std::min<int64_t>(T, chunk), chunk);
-    if (!(poses_done && h->clock_cleared) && sfw_rollout_is_fused(probe0))
+    if (!(poses_done && h->st.clock_cleared) && sfw_rollout_is_fused(probe0))
       SFW_HIP(h, hipMemsetAsync(h->clock.p, 0, 4 * sizeof(unsigned long long), h->stream));
     if (!poses_done) SFW_HIP(h, hipEventRecord(h->ev[0], h->stream));
   }
-  h->clock_cleared = false;
+  h->st.clock_cleared = false;
   const bool single = chunk >= T;
-  h->n_chunks = static_cast<int>((T + chunk - 1) / chunk);
+  h->last.n_chunks = static_cast<int>((T + chunk - 1) / chunk);
   if (!single && timing) {
-    while (h->chunk_ev.size() < static_cast<size_t>(3 * h->n_chunks)) {
+    while (h->chunk_ev.size() < static_cast<size_t>(3 * h->last.n_chunks)) {
       hipEvent_t e = nullptr;
       SFW_HIP(h, hipEventCreate(&e));
       h->chunk_ev.push_back(e);
     }
   }
   // Trajectory points on request (sfw_set_points_capture), when the whole grid goes through the fused K1
-  h->captured = false;
   char *cap_pts = nullptr, *cap_n = nullptr, *cap_coll = nullptr;
-  if (h->capture_points && single) {
+  if (h->live.capture_points && single) {
     sfw_launch probe;
     fill_launch(h, probe, 0, T, chunk);
     if (sfw_rollout_is_fused(probe)) {
@@ -1364,24 +1419,22 @@ int launch_prepare(sfw_handle h, bool timing, launch_prep &lp) {
       cap_pts = h->pin_cap.p;
       cap_n = cap_pts + pts_bytes;
       cap_coll = cap_n + 4 * static_cast<size_t>(T);
-      h->captured = true;
-      h->cap_S = S;
+      h->last.captured = true;
+      h->last.cap_S = S;
     }
   }
   // the cost vector and the selection record reach the host through the selection kernels themselves (pinned mirror): the
   // fetch then only waits for the stream.  Grids whose vector is larger than SFW_MIRROR_MAX_MB (default 64) keep the copy.
-  h->mirrored = false;
-  h->fetched = false;
   double *costs_host = nullptr;
   sfw_sel *sel_host = nullptr;
-  if (h->mirror_max_bytes > 0 && sizeof(double) * static_cast<size_t>(T) <= h->mirror_max_bytes) {
+  if (h->cfg.mirror_max_bytes > 0 && sizeof(double) * static_cast<size_t>(T) <= h->cfg.mirror_max_bytes) {
     const size_t cost_bytes = sizeof(double) * static_cast<size_t>(T);
     // (growing it frees the old area: no launch still in the stream may be writing there)
     if (cost_bytes + sizeof(sfw_sel) > h->pin_mirror.cap) SFW_HIP(h, hipStreamSynchronize(h->stream));
     SFW_HIP(h, h->pin_mirror.reserve(cost_bytes + sizeof(sfw_sel)));
     costs_host = reinterpret_cast<double *>(h->pin_mirror.p);
     sel_host = reinterpret_cast<sfw_sel *>(h->pin_mirror.p + cost_bytes);
-    h->mirrored = true;
+    h->last.mirrored = true;
   }
   lp.T = T;
   lp.chunk = chunk;
@@ -1395,11 +1448,10 @@ int launch_prepare(sfw_handle h, bool timing, launch_prep &lp) {
   lp.cap_coll = cap_coll;
   lp.costs_host = costs_host;
   lp.sel_host = sel_host;
-  h->terms_launched = false;
-  if (h->capture_terms) {
+  if (h->live.capture_terms) {
     SFW_HIP(h, h->terms.reserve(static_cast<size_t>(SFW_N_TERMS) * static_cast<size_t>(T)));
     lp.terms = h->terms.p;
-    h->terms_launched = true;
+    h->last.terms = true;
   }
   return SFW_OK;
 }
@@ -1409,7 +1461,7 @@ int launch_prepare(sfw_handle h, bool timing, launch_prep &lp) {
 bool cycle_launch_of(sfw_handle h, const launch_prep &lp, sfw_launch &L) {
   if (!(lp.single && !lp.prefix && !lp.poses_done)) return false;
   fill_launch(h, L, 0, lp.T, lp.chunk);
-  if (h->captured) {
+  if (h->last.captured) {
     L.points = reinterpret_cast<double *>(lp.cap_pts);
     L.n_points = reinterpret_cast<int32_t *>(lp.cap_n);
     L.coll_step = reinterpret_cast<int32_t *>(lp.cap_coll);
@@ -1421,27 +1473,27 @@ bool cycle_launch_of(sfw_handle h, const launch_prep &lp, sfw_launch &L) {
   L.terms = lp.terms;
   L.terms_T = lp.T;
   if (!sfw_cycle_applies(L)) return false;
-  if (h->arena_pending) {  // the kernel's blocks fetch the arena from pinned memory themselves: no copy at all this cycle
-    L.arena_host = h->pin_world.p + h->arena_from;
-    L.arena_dev = h->world.p + h->arena_from;
-    L.arena_bytes = static_cast<uint32_t>(h->arena_bytes);
+  if (h->st.arena_pending) {  // the kernel's blocks fetch the arena from pinned memory themselves: no copy at all this cycle
+    L.arena_host = h->pin_arena.p + h->st.arena_from;
+    L.arena_dev = h->arena.p + h->st.arena_from;
+    L.arena_bytes = static_cast<uint32_t>(h->st.arena_bytes);
   }
   return true;
 }
 // Step 2, once the kernel that carries L is enqueued: the handle's state after its launch
 int cycle_commit(sfw_handle h, bool timing) {
-  if (h->arena_pending) {
-    h->arena_pending = false;
-    SFW_HIP(h, h->pin_world.mark(h->stream));
+  if (h->st.arena_pending) {
+    h->st.arena_pending = false;
+    SFW_HIP(h, h->pin_arena.mark(h->stream));
   }
   if (timing) {
     SFW_HIP(h, hipEventRecord(h->ev[2], h->stream));
     SFW_HIP(h, hipEventRecord(h->ev[3], h->stream));
   }
-  h->launched = true;
+  h->last.timed = timing;
+  h->last.cycle = true;
   ++h->launch_seq;
-  h->launched_timed = timing;
-  h->launched_cycle = true;
+  h->last.launched = true;
   return SFW_OK;
 }
 
@@ -1453,14 +1505,13 @@ int launch_kernels(sfw_handle h, const launch_prep &lp) {
   char *const cap_pts = lp.cap_pts, *const cap_n = lp.cap_n, *const cap_coll = lp.cap_coll;
   double *const costs_host = lp.costs_host;
   sfw_sel *const sel_host = lp.sel_host;
-  h->launched_cycle = false;
   if (int e = flush_arena(h)) return e;
   int c = 0;
   for (int64_t b = 0; b < T; b += chunk, ++c) {
     const int64_t n = (T - b < chunk) ? (T - b) : chunk;
     sfw_launch L;
     fill_launch(h, L, b, n, chunk);
-    if (h->captured) {
+    if (h->last.captured) {
       L.points = reinterpret_cast<double *>(cap_pts);
       L.n_points = reinterpret_cast<int32_t *>(cap_n);
       L.coll_step = reinterpret_cast<int32_t *>(cap_coll);
@@ -1481,14 +1532,14 @@ int launch_kernels(sfw_handle h, const launch_prep &lp) {
       if (!poses_done) SFW_HIP(h, sfw_launch_rollout_poses(L, h->stream));
       SFW_HIP(h, hipEventRecord(h->ev_poses, h->stream));
       if (timing) SFW_HIP(h, hipEventRecord(single ? h->ev[1] : h->chunk_ev[3 * c + 1], h->stream));
-      const sfw_planner_s::chunk_plan &cp = h->prefix_chunks[static_cast<size_t>(c)];
-      const int32_t *tab = h->d_cls_tab;
-      const size_t n_lv = h->prefix_steps.size();
+      const chunk_plan &cp = h->st.prefix_chunks[static_cast<size_t>(c)];
+      const int32_t *tab = h->st.d_cls_tab;
+      const size_t n_lv = h->st.prefix_steps.size();
       for (size_t l = 0; l < n_lv; ++l) {  // the tree of shared steps, coarsest classes first
-        const sfw_planner_s::level_tables &t = cp.lv[l];
+        const level_tables &t = cp.lv[l];
         L.phase = SFW_PHASE_PREFIX;
-        L.step_begin = l ? h->prefix_steps[l - 1] : 0;
-        L.step_end = h->prefix_steps[l];
+        L.step_begin = l ? h->st.prefix_steps[l - 1] : 0;
+        L.step_end = h->st.prefix_steps[l];
         L.n_cls = t.n_row * t.n_col;
         L.n_col_cls = t.n_col;
         L.row_rep = tab + t.o_row_rep;
@@ -1514,12 +1565,12 @@ int launch_kernels(sfw_handle h, const launch_prep &lp) {
       }
       SFW_HIP(h, hipStreamWaitEvent(h->stream, h->ev_side, 0));
       L.phase = SFW_PHASE_SUFFIX;
-      L.step_begin = h->prefix_steps.back();
+      L.step_begin = h->st.prefix_steps.back();
       L.step_end = S;
       L.resume = 1;
       L.n_col_src = cp.lv[n_lv - 1].n_col;
       L.row_src = tab + cp.o_row_cls;
-      L.col_src = tab + h->prefix_o_col_cls;
+      L.col_src = tab + h->st.prefix_o_col_cls;
       L.in_state = h->cls_state[(n_lv - 1) & 1].p;
       L.in_dead = h->cls_dead[(n_lv - 1) & 1].p;
       SFW_HIP(h, launch_social_of(L, h->stream, &h->split));  // (`side` is idle: the stream has just waited for it)
@@ -1532,12 +1583,12 @@ int launch_kernels(sfw_handle h, const launch_prep &lp) {
     if (!single && timing) SFW_HIP(h, hipEventRecord(h->chunk_ev[3 * c + 2], h->stream));
   }
   if (timing) SFW_HIP(h, hipEventRecord(h->ev[2], h->stream));
-  SFW_HIP(h, sfw_launch_argmin(h->costs.p, h->d_linvels, h->d_angvels, h->nw, T, h->index_base,
-                               h->partials.p, h->d_sel, h->stream, costs_host, sel_host));
+  SFW_HIP(h, sfw_launch_argmin(h->costs.p, h->st.d_linvels, h->st.d_angvels, h->st.nw, T, h->st.index_base,
+                               h->partials.p, h->st.d_sel, h->stream, costs_host, sel_host));
   if (timing) SFW_HIP(h, hipEventRecord(h->ev[3], h->stream));
-  h->launched = true;
+  h->last.timed = timing;
   ++h->launch_seq;
-  h->launched_timed = timing;
+  h->last.launched = true;
   return SFW_OK;
 }
 
@@ -1547,7 +1598,7 @@ hipError_t launch_cycle_of(const sfw_launch &L, hipStream_t stream) {
 
 int launch_common(sfw_handle h) {
   launch_prep lp;
-  if (int e = launch_prepare(h, h ? h->timing : false, lp)) return e;
+  if (int e = launch_prepare(h, h ? h->live.timing : false, lp)) return e;
   sfw_launch L;
   if (cycle_launch_of(h, lp, L)) {
     if (lp.timing) SFW_HIP(h, hipEventRecord(h->ev[1], h->stream));  // (no K1 of its own: K1 time 0, the launch is "K2")
@@ -1562,12 +1613,12 @@ void sel_to_best(sfw_handle h, const sfw_sel &s, sfw_best *best, sfw_best_key *k
   if (best) {
     best->n_valid = s.n_valid;
     if (found) {
-      const int64_t local = -s.neg_index - h->index_base;
+      const int64_t local = -s.neg_index - h->st.index_base;
       best->index = local;
       best->cost = s.cost;
-      best->vx = h->h_lin[static_cast<size_t>(local / h->nw)];
+      best->vx = h->st.lin[static_cast<size_t>(local / h->st.nw)];
       best->vy = 0.0;
-      best->vtheta = h->h_ang[static_cast<size_t>(local % h->nw)];
+      best->vtheta = h->st.ang[static_cast<size_t>(local % h->st.nw)];
     } else {  // ref :456-468: stop the robot
       best->index = -1;
       best->cost = -1.0;
@@ -1641,51 +1692,51 @@ int create_handle(const sfw_params *params, int device, hipStream_t stream, hipS
 #endif
   sfw_handle h = new (std::nothrow) sfw_planner_s();
   if (!h) return SFW_ERR_HIP;
-  h->params = *params;
+  h->live.params = *params;
   h->device = device;
   if (const char *b = std::getenv("SFW_PREFIX")) {  // "0" off, "10" one split, "3,7,12" several levels
     for (const char *q = b; *q;) {
       char *end = nullptr;
       const long v = std::strtol(q, &end, 10);
       if (end == q) break;
-      if (v >= 0) h->prefix_env.push_back(static_cast<int>(v));
+      if (v >= 0) h->cfg.prefix_env.push_back(static_cast<int>(v));
       q = (*end == ',') ? end + 1 : end;
     }
-    std::sort(h->prefix_env.begin(), h->prefix_env.end());
-    h->prefix_env.erase(std::unique(h->prefix_env.begin(), h->prefix_env.end()), h->prefix_env.end());
+    std::sort(h->cfg.prefix_env.begin(), h->cfg.prefix_env.end());
+    h->cfg.prefix_env.erase(std::unique(h->cfg.prefix_env.begin(), h->cfg.prefix_env.end()), h->cfg.prefix_env.end());
   }
-  if (const char *b = std::getenv("SFW_FORCE_FLAT")) h->k2_form = std::atoi(b) == 1 ? SFW_K2_FLAT : std::atoi(b) == 0 ? SFW_K2_REGISTER : SFW_K2_AUTO;
-  if (const char *b = std::getenv("SFW_PIN_REST")) h->pin_rest_on = std::atoi(b) != 0;
-  if (const char *b = std::getenv("SFW_SPIN_US")) h->spin_us = std::max(0L, std::atol(b));
-  if (const char *b = std::getenv("SFW_ARENA_DIRECT")) h->arena_direct_on = std::atoi(b) != 0;
-  if (const char *b = std::getenv("SFW_MIRROR_MAX_MB")) h->mirror_max_bytes = static_cast<size_t>(std::max(0L, std::atol(b))) << 20;
-  if (const char *b = std::getenv("SFW_OBS_TASKS")) h->obs_tasks_force = std::atoi(b) != 0 ? 1 : 0;
+  if (const char *b = std::getenv("SFW_FORCE_FLAT")) h->live.k2_form = std::atoi(b) == 1 ? SFW_K2_FLAT : std::atoi(b) == 0 ? SFW_K2_REGISTER : SFW_K2_AUTO;
+  if (const char *b = std::getenv("SFW_PIN_REST")) h->cfg.pin_rest_on = std::atoi(b) != 0;
+  if (const char *b = std::getenv("SFW_SPIN_US")) h->cfg.spin_us = std::max(0L, std::atol(b));
+  if (const char *b = std::getenv("SFW_ARENA_DIRECT")) h->cfg.arena_direct_on = std::atoi(b) != 0;
+  if (const char *b = std::getenv("SFW_MIRROR_MAX_MB")) h->cfg.mirror_max_bytes = static_cast<size_t>(std::max(0L, std::atol(b))) << 20;
+  if (const char *b = std::getenv("SFW_OBS_TASKS")) h->cfg.obs_tasks_force = std::atoi(b) != 0 ? 1 : 0;
   if (const char *b = std::getenv("SFW_TABLE_BUDGET_MB")) {
     long mb = std::atol(b);
-    if (mb > 0) h->table_budget_bytes = static_cast<size_t>(mb) << 20;
+    if (mb > 0) h->cfg.table_budget_bytes = static_cast<size_t>(mb) << 20;
   }
   hipError_t e = hipSetDevice(device);
   if (e == hipSuccess) {
     // the launch heuristics (shared-prefix cost model, organisation thresholds, XCD-contiguous block order) scale with the
     // device: a CPX partition of an MI355X shows 32 compute units on one XCD where the whole chip shows 256 on eight
     hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) h->n_cu = prop.multiProcessorCount;
-    h->n_cu = env_device_cus(h->n_cu);
+    if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) h->cfg.n_cu = prop.multiProcessorCount;
+    h->cfg.n_cu = env_device_cus(h->cfg.n_cu);
     // XCDs: what the device says (hipDeviceAttributeNumberOfXccs; 8 on a whole MI355X, 1 on a CPX partition) unless the CU count
     // is pretended (SFW_DEVICE_CUS) or the attribute is not answered — then CUs / 32, right for gfx950's 32-CU XCDs only
     int xccs = 0;
     if (!std::getenv("SFW_DEVICE_CUS") && hipDeviceGetAttribute(&xccs, hipDeviceAttributeNumberOfXccs, device) == hipSuccess && xccs >= 1)
-      h->n_xcd = xccs;
+      h->cfg.n_xcd = xccs;
     else
-      h->n_xcd = std::max(1, h->n_cu / SFW_CUS_PER_XCD);
+      h->cfg.n_xcd = std::max(1, h->cfg.n_cu / SFW_CUS_PER_XCD);
     (void)hipGetLastError();  // (an unanswered attribute is not an error of this call)
     if (const char *b = std::getenv("SFW_DEVICE_XCDS")) {
       const long v = std::atol(b);
-      if (v >= 1 && v <= 64) h->n_xcd = static_cast<int>(v);
+      if (v >= 1 && v <= 64) h->cfg.n_xcd = static_cast<int>(v);
     }
   }
   if (stream) {
-    h->owns_streams = false;
+    h->cfg.owns_streams = false;
     h->stream = stream;
     h->side = side;
   } else {
@@ -1713,7 +1764,7 @@ int destroy_handle(sfw_handle h) {
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   if (h->side) (void)hipStreamSynchronize(h->side);
   h->cells.release();
-  h->world.release();
+  h->arena.release();
   h->pair_tab.release();
   h->status.release();
   h->coll_step.release();
@@ -1742,7 +1793,7 @@ int destroy_handle(sfw_handle h) {
   h->pts_cs.release();
   h->pts_fcode.release();
   h->pin_map.release();
-  h->pin_world.release();
+  h->pin_arena.release();
   h->pin_out.release();
   h->pin_mirror.release();
   h->pin_one.release();
@@ -1758,7 +1809,7 @@ int destroy_handle(sfw_handle h) {
   if (h->ev_side) (void)hipEventDestroy(h->ev_side);
   if (h->split.fork) (void)hipEventDestroy(h->split.fork);
   if (h->split.join) (void)hipEventDestroy(h->split.join);
-  if (h->owns_streams) {
+  if (h->cfg.owns_streams) {
     if (h->side) (void)hipStreamDestroy(h->side);
     if (h->stream) (void)hipStreamDestroy(h->stream);
   }
@@ -1775,15 +1826,15 @@ int sfw_create(const sfw_params *params, int device, sfw_handle *out) {
 
 int sfw_destroy(sfw_handle h) {
   if (!h) return SFW_OK;
-  if (h->batch_member) return fail(h, SFW_ERR_STATE, "destroy: the handle is a member of a batch (sfw_batch_destroy destroys it)");
+  if (h->cfg.batch_member) return fail(h, SFW_ERR_STATE, "destroy: the handle is a member of a batch (sfw_batch_destroy destroys it)");
   return destroy_handle(h);
 }
 
 int sfw_set_params(sfw_handle h, const sfw_params *params) {
   if (!h) return SFW_ERR_INVALID_ARG;
   if (int e = check_params(h, params)) return e;
-  if (std::memcmp(&h->params, params, sizeof(sfw_params)) != 0) ++h->params_epoch;
-  h->params = *params;
+  if (std::memcmp(&h->live.params, params, sizeof(sfw_params)) != 0) ++h->live.params_epoch;
+  h->live.params = *params;
   return SFW_OK;
 }
 
@@ -1801,23 +1852,23 @@ int sfw_set_costmap(sfw_handle h, const uint8_t *cells, uint32_t size_x, uint32_
   // copy per cycle instead of two with the host's call-to-call latency between them), by a copy of its own otherwise.
   // (an unchanged snapshot — a controller hands its local costmap over every cycle, the map changes at the costmap's own
   // rate — is recognised here, ~1 us for 40 KB, and not sent again)
-  if (h->have_costmap && h->pin_map.p && n <= h->pin_map.cap && h->map_new.size_x == size_x && h->map_new.size_y == size_y &&
-      h->map_new.origin_x == origin_x && h->map_new.origin_y == origin_y && h->map_new.resolution == resolution &&
+  if (h->world.have_costmap && h->pin_map.p && n <= h->pin_map.cap && h->world.map_new.size_x == size_x && h->world.map_new.size_y == size_y &&
+      h->world.map_new.origin_x == origin_x && h->world.map_new.origin_y == origin_y && h->world.map_new.resolution == resolution &&
       std::memcmp(h->pin_map.p, cells, n) == 0)
     return SFW_OK;
   SFW_HIP(h, h->pin_map.reserve(n));  // (waits for a copy out of it that is still pending)
   std::memcpy(h->pin_map.p, cells, n);
-  h->map_new = {size_x, size_y, origin_x, origin_y, resolution};
-  h->cells_dirty = true;
-  h->have_costmap = true;
+  h->world.map_new = {size_x, size_y, origin_x, origin_y, resolution};
+  h->world.cells_dirty = true;
+  h->world.have_costmap = true;
   return SFW_OK;
 }
 
 int sfw_set_footprint(sfw_handle h, const double *xy, int32_t K) {
   if (!h) return SFW_ERR_INVALID_ARG;
   if (K < 0 || (K > 0 && !xy)) return fail(h, SFW_ERR_INVALID_ARG, "set_footprint: bad arguments");
-  h->h_footprint.assign(xy, xy + 2 * static_cast<size_t>(K));  // uploaded with the next stage
-  h->K = K;
+  h->world.footprint.assign(xy, xy + 2 * static_cast<size_t>(K));  // uploaded with the next stage
+  h->world.K = K;
   return SFW_OK;
 }
 
@@ -1856,7 +1907,7 @@ int sfw_set_agents(sfw_handle h, const sfw_agent *agents, int32_t A, const doubl
   const int n_mem = off.back();
   // the set has to fit one wave's LDS allocation whatever the grid (the flat form of one sample is the smallest): refused
   // here, before the all-pairs scan below and long before a launch
-  if (A > 0 && sfw_social_lds_bytes(A, O, static_cast<int>(ids.size()), n_mem, 1, SFW_K2_FLAT, h->n_cu) > 160 * 1024)
+  if (A > 0 && sfw_social_lds_bytes(A, O, static_cast<int>(ids.size()), n_mem, 1, SFW_K2_FLAT, h->cfg.n_cu) > 160 * 1024)
     return fail(h, SFW_ERR_UNSUPPORTED, "set_agents: agent/obstacle set does not fit the 160 KiB LDS of one CU");
   if (mem.empty()) mem.push_back(0);
   // host blob (uploaded with the next stage): pos | vel | const | obstacles | grp | off | mem
@@ -1868,10 +1919,12 @@ int sfw_set_agents(sfw_handle h, const sfw_agent *agents, int32_t A, const doubl
                o_grp = o_obs + up16(16 * On) + 64,
                o_off = o_grp + up16(4 * An), o_mem = o_off + up16(4 * off.size()),
                total = o_mem + up16(4 * mem.size());
-  h->h_agents.assign(total, 0);
-  char *base = h->h_agents.data();
+  agent_set &ag = h->world.agents;
+  ag.blob.assign(total, 0);
+  char *base = ag.blob.data();
   double *pos = reinterpret_cast<double *>(base + o_pos), *vel = reinterpret_cast<double *>(base + o_vel);
   sfw_agent_const *cst = reinterpret_cast<sfw_agent_const *>(base + o_cst);
+  ag.person_pinned = false;
   for (int i = 0; i < A; ++i) {
     pos[2 * i] = agents[i].x;
     pos[2 * i + 1] = agents[i].y;
@@ -1885,34 +1938,35 @@ int sfw_set_agents(sfw_handle h, const sfw_agent *agents, int32_t A, const doubl
     c.radius = agents[i].radius;
     c.id = agents[i].id;
     c.has_goal = agents[i].has_goal ? 1 : 0;
+    ag.person_pinned |= i >= 1 && c.desired_velocity == 0.0;
   }
   if (O > 0) std::memcpy(base + o_obs, obstacles_xy, sizeof(double) * 2 * O);
   std::memcpy(base + o_grp, grp.data(), 4 * grp.size());
   std::memcpy(base + o_off, off.data(), 4 * off.size());
   std::memcpy(base + o_mem, mem.data(), 4 * mem.size());
-  h->ao_vel = o_vel;
-  h->ao_cst = o_cst;
-  h->ao_obs = o_obs;
-  h->ao_grp = o_grp;
-  h->ao_off = o_off;
-  h->ao_mem = o_mem;
-  h->NG = static_cast<int>(ids.size());
-  h->n_grp_mem = n_mem;
-  h->A = A;
-  h->O = O;
+  ag.ao_vel = o_vel;
+  ag.ao_cst = o_cst;
+  ag.ao_obs = o_obs;
+  ag.ao_grp = o_grp;
+  ag.ao_off = o_off;
+  ag.ao_mem = o_mem;
+  ag.NG = static_cast<int>(ids.size());
+  ag.n_grp_mem = n_mem;
+  ag.A = A;
+  ag.O = O;
   // Pairs whose w x diff is exactly 0 in the handed-over state — relative rest (w = 0) and motion exactly along the
   // connecting line — are the pairs for which the kernels' sign(theta) = sign(w x diff) is 0 while lightsfm's theta is
   // rounding noise around 0 or exactly +-pi: their angular terms are evaluated on the host (rest_forces).  The test is
   // the kernels' own expression (pair_force_state), IEEE fma on both sides.  All pairs: ~1 ns each, 1275 at 50
   // pedestrians; the scoring that follows costs A^2 per sample-step.
-  h->rest_pairs.clear();
+  ag.rest_pairs.clear();
   for (int i = 0; i < A; ++i)
     for (int j = i + 1; j < A; ++j) {
       const double dx = agents[j].x - agents[i].x, dy = agents[j].y - agents[i].y;
       const double wx = agents[i].vx - agents[j].vx, wy = agents[i].vy - agents[j].vy;
       if (std::fma(wx, dy, -(wy * dx)) == 0.0 && !(dx == 0.0 && dy == 0.0)) {
-        h->rest_pairs.emplace_back(i, j);
-        h->rest_pairs.emplace_back(j, i);
+        ag.rest_pairs.emplace_back(i, j);
+        ag.rest_pairs.emplace_back(j, i);
       }
     }
   return SFW_OK;
@@ -1934,26 +1988,26 @@ int sfw_grid_sync(sfw_handle h) {
 
 int sfw_grid_fetch(sfw_handle h, double *costs_out, sfw_best *best_out, sfw_best_key *key_out) {
   if (!h) return SFW_ERR_INVALID_ARG;
-  if (!h->launched) return fail(h, SFW_ERR_STATE, "grid_fetch before grid_launch");
+  if (!h->last.launched) return fail(h, SFW_ERR_STATE, "grid_fetch before grid_launch");
   SFW_HIP(h, hipSetDevice(h->device));
-  const int64_t T = static_cast<int64_t>(h->nv) * h->nw;
+  const int64_t T = static_cast<int64_t>(h->st.nv) * h->st.nw;
   // costs and the selection record are contiguous on the device: one copy fetches both
   sfw_sel s;
-  if (h->mirrored) {  // the launch's selection kernels wrote both to pin_mirror: nothing to copy, only to wait for
+  if (h->last.mirrored) {  // the launch's selection kernels wrote both to pin_mirror: nothing to copy, only to wait for
     const size_t all_bytes = sizeof(double) * static_cast<size_t>(T);
     SFW_HIP(h, wait_stream(h));
     stream_is_idle(h);
-    h->fetched = true;
+    h->last.fetched = true;
     if (costs_out) std::memcpy(costs_out, h->pin_mirror.p, all_bytes);
     std::memcpy(&s, h->pin_mirror.p + all_bytes, sizeof(s));
   } else {
     const size_t cost_bytes = costs_out ? sizeof(double) * static_cast<size_t>(T) : 0;
     SFW_HIP(h, h->pin_out.reserve(cost_bytes + sizeof(sfw_sel)));
-    const char *src = reinterpret_cast<const char *>(h->d_sel) - cost_bytes;
+    const char *src = reinterpret_cast<const char *>(h->st.d_sel) - cost_bytes;
     SFW_HIP(h, hipMemcpyAsync(h->pin_out.p, src, cost_bytes + sizeof(sfw_sel), hipMemcpyDeviceToHost, h->stream));
     SFW_HIP(h, wait_stream(h));
     stream_is_idle(h);
-    h->fetched = true;
+    h->last.fetched = true;
     if (costs_out) std::memcpy(costs_out, h->pin_out.p, cost_bytes);
     std::memcpy(&s, h->pin_out.p + cost_bytes, sizeof(s));
   }
@@ -1962,7 +2016,7 @@ int sfw_grid_fetch(sfw_handle h, double *costs_out, sfw_best *best_out, sfw_best
 }
 
 const double *sfw_grid_costs_view(sfw_handle h) {
-  if (!h || !h->launched || !h->mirrored || !h->fetched) return nullptr;
+  if (!h || !h->last.launched || !h->last.mirrored || !h->last.fetched) return nullptr;
   return reinterpret_cast<const double *>(h->pin_mirror.p);
 }
 
@@ -1979,9 +2033,15 @@ int sfw_score_one(sfw_handle h, const sfw_robot_state *rs, double vx_samp, doubl
                   int32_t *n_points) {
   if (!h) return SFW_ERR_INVALID_ARG;
   if (!cost_out) return fail(h, SFW_ERR_INVALID_ARG, "score_one: cost_out is NULL");
+  const agent_set &ag = h->world.agents;  // (checked before the stage: a refused call leaves the staged grid alone)
+  if (int e = check_lds(h, ag.A, ag.O, ag.NG, ag.n_grp_mem, 1)) return e;
   if (int e = stage_common(h, rs, &vx_samp, 1, &vtheta_samp, 1, args, vy_samp, 0, 0, true)) return e;
-  if (int e = check_lds(h, 1)) return e;
-  const int S = num_steps_of(h->params);
+  // past the checks the call consumes its one-sample stage, whatever the outcome (no grid to launch or dump)
+  struct consume_stage {
+    sfw_handle h;
+    ~consume_stage() { h->st.valid = false; }
+  } consumed{h};
+  const int S = num_steps_of(h->live.params);
   {
     // The latency path (called on every approach / rotate cycle, ref :204-206, :299-301) as ONE launch and no copy: the
     // one-launch kernel with its outputs — cost, point count, contact step, Trajectory points — in pinned host memory, the
@@ -2000,15 +2060,15 @@ int sfw_score_one(sfw_handle h, const sfw_robot_state *rs, double vx_samp, doubl
       L.n_points = reinterpret_cast<int32_t *>(h->pin_one.p + 8);
       L.coll_step = reinterpret_cast<int32_t *>(h->pin_one.p + 12);
       L.points = reinterpret_cast<double *>(h->pin_one.p + head);
-      if (h->arena_pending) {
-        L.arena_host = h->pin_world.p + h->arena_from;
-        L.arena_dev = h->world.p + h->arena_from;
-        L.arena_bytes = static_cast<uint32_t>(h->arena_bytes);
+      if (h->st.arena_pending) {
+        L.arena_host = h->pin_arena.p + h->st.arena_from;
+        L.arena_dev = h->arena.p + h->st.arena_from;
+        L.arena_bytes = static_cast<uint32_t>(h->st.arena_bytes);
       }
-      SFW_HIP(h, h->params.precision == SFW_PRECISION_F64_STRICT ? sfw_launch_cycle_strict(L, h->stream) : sfw_launch_cycle(L, h->stream));
-      if (h->arena_pending) {
-        h->arena_pending = false;
-        SFW_HIP(h, h->pin_world.mark(h->stream));
+      SFW_HIP(h, h->live.params.precision == SFW_PRECISION_F64_STRICT ? sfw_launch_cycle_strict(L, h->stream) : sfw_launch_cycle(L, h->stream));
+      if (h->st.arena_pending) {
+        h->st.arena_pending = false;
+        SFW_HIP(h, h->pin_arena.mark(h->stream));
       }
       SFW_HIP(h, wait_stream(h));
       stream_is_idle(h);
@@ -2022,8 +2082,6 @@ int sfw_score_one(sfw_handle h, const sfw_robot_state *rs, double vx_samp, doubl
         const int m = n < points_cap ? n : points_cap;
         std::memcpy(points_xyth, h->pin_one.p + head, sizeof(double) * 3 * static_cast<size_t>(m));
       }
-      h->staged = false;  // score_one clobbers the staged grid
-      h->launched = false;
       return SFW_OK;
     }
     if (int e = flush_arena(h)) return e;  // the three-kernel path below reads the device copy
@@ -2058,8 +2116,6 @@ int sfw_score_one(sfw_handle h, const sfw_robot_state *rs, double vx_samp, doubl
     const int m = n < points_cap ? n : points_cap;
     std::memcpy(points_xyth, h->pin_out.p + head, sizeof(double) * 3 * static_cast<size_t>(m));
   }
-  h->staged = false;  // score_one clobbers the staged grid
-  h->launched = false;
   return SFW_OK;
 }
 
@@ -2115,25 +2171,25 @@ int sfw_plan_row_blocks(const double *linvels, int32_t nv, const double *angvels
 
 int sfw_grid_plan_info(sfw_handle h, sfw_plan_info *out) {
   if (!h || !out) return SFW_ERR_INVALID_ARG;
-  if (!h->staged) return fail(h, SFW_ERR_STATE, "grid_plan_info before grid_stage");
-  const int64_t T = static_cast<int64_t>(h->nv) * h->nw;
-  out->split_step = h->prefix_steps.empty() ? 0 : h->prefix_steps.back();
-  out->levels = static_cast<int32_t>(h->prefix_steps.size());
+  if (!h->st.valid) return fail(h, SFW_ERR_STATE, "grid_plan_info before grid_stage");
+  const int64_t T = static_cast<int64_t>(h->st.nv) * h->st.nw;
+  out->split_step = h->st.prefix_steps.empty() ? 0 : h->st.prefix_steps.back();
+  out->levels = static_cast<int32_t>(h->st.prefix_steps.size());
   out->samples = T;
-  out->classes = h->prefix_last_classes;
-  out->class_steps = h->prefix_class_steps;
-  if (!h->prefix_steps.empty()) {
-    out->chunks = static_cast<int32_t>(h->prefix_chunks.size());
+  out->classes = h->st.prefix_last_classes;
+  out->class_steps = h->st.prefix_class_steps;
+  if (!h->st.prefix_steps.empty()) {
+    out->chunks = static_cast<int32_t>(h->st.prefix_chunks.size());
   } else {
-    int64_t chunk = h->table_chunk;
+    int64_t chunk = h->st.table_chunk;
     if (chunk > T) chunk = T;
     out->chunks = chunk > 0 ? static_cast<int32_t>((T + chunk - 1) / chunk) : 0;
   }
-  out->organisation = sfw_social_organisation(h->st_A, out->chunks > 0 ? (T + out->chunks - 1) / out->chunks : T, h->st_O, h->k2_form, h->n_cu);
-  out->flat_samples = sfw_social_flat_items(h->st_A, h->st_O, h->st_NG, out->chunks > 0 ? (T + out->chunks - 1) / out->chunks : T, h->k2_form, h->n_cu);
+  out->organisation = sfw_social_organisation(h->st.A, out->chunks > 0 ? (T + out->chunks - 1) / out->chunks : T, h->st.O, h->live.k2_form, h->cfg.n_cu);
+  out->flat_samples = sfw_social_flat_items(h->st.A, h->st.O, h->st.NG, out->chunks > 0 ? (T + out->chunks - 1) / out->chunks : T, h->live.k2_form, h->cfg.n_cu);
   out->rest_noise_unreproduced = rest_noise_unreproduced(h) ? 1 : 0;
   out->one_launch = 0;
-  if (out->chunks == 1 && h->prefix_steps.empty()) {
+  if (out->chunks == 1 && h->st.prefix_steps.empty()) {
     sfw_launch L;
     fill_launch(h, L, 0, T, T);
     out->one_launch = sfw_cycle_applies(L) ? 1 : 0;
@@ -2145,25 +2201,25 @@ int sfw_set_k2_form(sfw_handle h, int32_t form) {
   if (!h) return SFW_ERR_INVALID_ARG;
   if (form != SFW_K2_AUTO && form != SFW_K2_REGISTER && form != SFW_K2_FLAT)
     return fail(h, SFW_ERR_INVALID_ARG, "set_k2_form: form must be SFW_K2_AUTO, SFW_K2_REGISTER or SFW_K2_FLAT");
-  h->k2_form = form;
+  h->live.k2_form = form;
   return SFW_OK;
 }
 
 int sfw_set_timing(sfw_handle h, int32_t enabled) {
   if (!h) return SFW_ERR_INVALID_ARG;
-  h->timing = enabled != 0;
+  h->live.timing = enabled != 0;
   return SFW_OK;
 }
 
 int sfw_last_launch_ms(sfw_handle h, int32_t which, float *ms_out) {
   if (!h || !ms_out) return SFW_ERR_INVALID_ARG;
-  if (!h->launched) return fail(h, SFW_ERR_STATE, "last_launch_ms before grid_launch");
-  if (!h->launched_timed) return fail(h, SFW_ERR_STATE, "last_launch_ms: timing was off for the last launch (sfw_set_timing)");
+  if (!h->last.launched) return fail(h, SFW_ERR_STATE, "last_launch_ms before grid_launch");
+  if (!h->last.timed) return fail(h, SFW_ERR_STATE, "last_launch_ms: timing was off for the last launch (sfw_set_timing)");
   SFW_HIP(h, hipSetDevice(h->device));
   SFW_HIP(h, hipEventSynchronize(h->ev[3]));
-  if (h->n_chunks > 1 && (which == 1 || which == 2)) {  // sum over the chunks of a multi-chunk launch
+  if (h->last.n_chunks > 1 && (which == 1 || which == 2)) {  // sum over the chunks of a multi-chunk launch
     float total = 0.0f;
-    for (int c = 0; c < h->n_chunks; ++c) {
+    for (int c = 0; c < h->last.n_chunks; ++c) {
       float ms = 0.0f;
       const int a = 3 * c + (which == 1 ? 0 : 1);
       SFW_HIP(h, hipEventElapsedTime(&ms, h->chunk_ev[a], h->chunk_ev[a + 1]));
@@ -2186,16 +2242,16 @@ int sfw_last_launch_ms(sfw_handle h, int32_t which, float *ms_out) {
 
 int sfw_set_points_capture(sfw_handle h, int32_t enabled) {
   if (!h) return SFW_ERR_INVALID_ARG;
-  h->capture_points = enabled != 0;
+  h->live.capture_points = enabled != 0;
   return SFW_OK;
 }
 
 int sfw_set_terms_capture(sfw_handle h, int32_t enabled) {
   if (!h) return SFW_ERR_INVALID_ARG;
-  h->capture_terms = enabled != 0;
-  if (!h->capture_terms) {
-    h->terms_launched = false;
-    h->early_poses_terms = false;
+  h->live.capture_terms = enabled != 0;
+  if (!h->live.capture_terms) {
+    h->last.terms = false;
+    h->st.early_poses_terms = false;
     if (h->terms.p) {
       SFW_HIP(h, hipSetDevice(h->device));
       SFW_HIP(h, hipStreamSynchronize(h->stream));  // (a launch in flight may still be writing there)
@@ -2211,11 +2267,11 @@ int sfw_grid_rescore(sfw_handle h, const sfw_weights *w, int32_t K, sfw_best *be
   if (K < 1 || K > SFW_RESCORE_MAX_K) return fail(h, SFW_ERR_INVALID_ARG, "grid_rescore: K out of [1, SFW_RESCORE_MAX_K]");
   if (!all_finite(reinterpret_cast<const double *>(w), static_cast<size_t>(K) * SFW_N_TERMS))
     return fail(h, SFW_ERR_INVALID_ARG, "grid_rescore: non-finite weight");
-  if (!h->launched || !h->terms_launched)
+  if (!h->last.launched || !h->last.terms)
     return fail(h, SFW_ERR_STATE, "grid_rescore: the last launch did not capture terms (sfw_set_terms_capture), or a stage or "
                                   "sfw_score_one came in since");
   SFW_HIP(h, hipSetDevice(h->device));
-  const int64_t T = static_cast<int64_t>(h->nv) * h->nw;
+  const int64_t T = static_cast<int64_t>(h->st.nv) * h->st.nw;
   const size_t sel_bytes = (sizeof(sfw_sel) * static_cast<size_t>(K) + 15) & ~size_t(15);
   const size_t w_bytes = sizeof(sfw_weights) * static_cast<size_t>(K);
   // (growing the pinned area frees the old one: nothing in the stream may still be writing there)
@@ -2237,7 +2293,7 @@ int sfw_grid_rescore(sfw_handle h, const sfw_weights *w, int32_t K, sfw_best *be
     const int32_t n = std::min(k_step, K - k0);
     const int64_t blocks = sfw_rescore_blocks(T, n);
     SFW_HIP(h, h->rescore_partials.reserve(static_cast<size_t>(blocks) * static_cast<size_t>(n)));
-    SFW_HIP(h, sfw_launch_rescore(h->terms.p, T, h->rescore_w.p + k0, n, h->d_linvels, h->d_angvels, h->nw, h->index_base,
+    SFW_HIP(h, sfw_launch_rescore(h->terms.p, T, h->rescore_w.p + k0, n, h->st.d_linvels, h->st.d_angvels, h->st.nw, h->st.index_base,
                                   h->rescore_partials.p, costs_out ? h->rescore_costs.p : nullptr, sel_host + k0, h->stream));
     if (costs_out)
       SFW_HIP(h, hipMemcpyAsync(costs_out + static_cast<int64_t>(k0) * T, h->rescore_costs.p,
@@ -2253,10 +2309,10 @@ int sfw_grid_rescore(sfw_handle h, const sfw_weights *w, int32_t K, sfw_best *be
 
 int sfw_grid_terms(sfw_handle h, int64_t first, int64_t count, double *terms_out) {
   if (!h) return SFW_ERR_INVALID_ARG;
-  if (!h->launched || !h->terms_launched)
+  if (!h->last.launched || !h->last.terms)
     return fail(h, SFW_ERR_STATE, "grid_terms: the last launch did not capture terms (sfw_set_terms_capture), or a stage or "
                                   "sfw_score_one came in since");
-  const int64_t T = static_cast<int64_t>(h->nv) * h->nw;
+  const int64_t T = static_cast<int64_t>(h->st.nv) * h->st.nw;
   if (count < 0 || first < 0 || first > T || count > T - first) return fail(h, SFW_ERR_INVALID_ARG, "grid_terms: range out of the grid");
   if (count > 0 && !terms_out) return fail(h, SFW_ERR_INVALID_ARG, "grid_terms: terms_out is NULL");
   if (count == 0) return SFW_OK;
@@ -2274,8 +2330,8 @@ int sfw_grid_terms(sfw_handle h, int64_t first, int64_t count, double *terms_out
 
 int sfw_last_clock_ghz(sfw_handle h, double *ghz_out) {
   if (!h || !ghz_out) return SFW_ERR_INVALID_ARG;
-  if (!h->launched) return fail(h, SFW_ERR_STATE, "last_clock_ghz before grid_launch");
-  if (!h->launched_timed) return fail(h, SFW_ERR_STATE, "last_clock_ghz: timing was off for the last launch (sfw_set_timing)");
+  if (!h->last.launched) return fail(h, SFW_ERR_STATE, "last_clock_ghz before grid_launch");
+  if (!h->last.timed) return fail(h, SFW_ERR_STATE, "last_clock_ghz: timing was off for the last launch (sfw_set_timing)");
   SFW_HIP(h, hipSetDevice(h->device));
   SFW_HIP(h, hipEventSynchronize(h->ev[3]));
   unsigned long long v[4] = {0, 0, 0, 0};
@@ -2290,19 +2346,19 @@ int sfw_last_clock_ghz(sfw_handle h, double *ghz_out) {
 
 int sfw_grid_points_batch(sfw_handle h, int64_t first, int64_t count, double *points_xyth, int32_t *n_points) {
   if (!h) return SFW_ERR_INVALID_ARG;
-  if (!h->staged) return fail(h, SFW_ERR_STATE, "grid_points before grid_stage");
-  const int64_t T = static_cast<int64_t>(h->nv) * h->nw;
+  if (!h->st.valid) return fail(h, SFW_ERR_STATE, "grid_points before grid_stage");
+  const int64_t T = static_cast<int64_t>(h->st.nv) * h->st.nw;
   if (first < 0 || count <= 0 || first + count > T || !points_xyth || !n_points)
     return fail(h, SFW_ERR_INVALID_ARG, "grid_points: bad range or buffer");
   SFW_HIP(h, hipSetDevice(h->device));
   if (int e = flush_arena(h)) return e;  // (a dump between stage and launch: the re-run below reads the device copy of the arena)
-  const int S = num_steps_of(h->params);
+  const int S = num_steps_of(h->live.params);
   const size_t n = static_cast<size_t>(count);
-  if (h->launched && h->captured && h->cap_S == S) {  // (sfw_set_params since the launch changed the step count: re-run below)
+  if (h->last.launched && h->last.captured && h->last.cap_S == S) {  // (sfw_set_params since the launch changed the step count: re-run below)
     // the scoring launch left everything in pinned memory (sfw_set_points_capture): points | counts | contact steps, no
     // kernel, no copy — only the wait for the launch, if no fetch has waited for it yet
     const size_t pts_bytes = sizeof(double) * 3 * static_cast<size_t>(S) * static_cast<size_t>(T);
-    if (!h->fetched) {
+    if (!h->last.fetched) {
       SFW_HIP(h, wait_stream(h));
       stream_is_idle(h);
     }
@@ -2324,8 +2380,8 @@ int sfw_grid_points_batch(sfw_handle h, int64_t first, int64_t count, double *po
   hipError_t e = h->pts_status.reserve(n);
   if (e == hipSuccess) e = h->pts_base.reserve(n);
   if (e == hipSuccess) e = h->pts_costs.reserve(n);
-  if (e == hipSuccess) e = h->pts_ptab.reserve(static_cast<size_t>(S) * static_cast<size_t>(table_row_units(count, h->nw)));
-  if (e == hipSuccess) e = h->pts_cs.reserve(static_cast<size_t>(S) * h->nw);
+  if (e == hipSuccess) e = h->pts_ptab.reserve(static_cast<size_t>(S) * static_cast<size_t>(table_row_units(count, h->st.nw)));
+  if (e == hipSuccess) e = h->pts_cs.reserve(static_cast<size_t>(S) * h->st.nw);
   if (e == hipSuccess) e = h->pts_fcode.reserve(static_cast<size_t>(S) * n);
   if (e == hipSuccess) {
     sfw_launch L;
@@ -2344,8 +2400,8 @@ int sfw_grid_points_batch(sfw_handle h, int64_t first, int64_t count, double *po
   std::vector<int32_t> coll(n, -1);
   // a capturing launch wrote its contact steps into the capture buffer, not into coll_step (this path is then only reached
   // when the step count changed since: cap_S != S): the contact steps come from the re-integration below instead
-  const bool coll_elsewhere = h->launched && h->captured;
-  if (e == hipSuccess && h->launched && !coll_elsewhere)
+  const bool coll_elsewhere = h->last.launched && h->last.captured;
+  if (e == hipSuccess && h->last.launched && !coll_elsewhere)
     e = hipMemcpyAsync(coll.data(), h->coll_step.p + first, sizeof(int32_t) * n, hipMemcpyDeviceToHost, h->stream);
   if (e == hipSuccess)
     e = hipMemcpyAsync(n_points, h->n_points.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, h->stream);
@@ -2359,8 +2415,8 @@ int sfw_grid_points_batch(sfw_handle h, int64_t first, int64_t count, double *po
   // contact steps from that run.
   bool rejected = false;
   for (size_t i = 0; i < n && !rejected; ++i) rejected = n_points[i] < S;
-  if ((rejected || coll_elsewhere) && h->st_A > 1) {
-    if (int rc = check_lds(h, count)) return rc;
+  if ((rejected || coll_elsewhere) && h->st.A > 1) {
+    if (int rc = check_lds(h, h->st.A, h->st.O, h->st.NG, h->st.n_grp_mem, count)) return rc;
     SFW_HIP(h, h->pts_coll.reserve(n));
     sfw_launch L;
     fill_launch(h, L, first, count, count);
@@ -2385,7 +2441,7 @@ int sfw_grid_points_batch(sfw_handle h, int64_t first, int64_t count, double *po
 int sfw_grid_points(sfw_handle h, int64_t index, double *points_xyth, int32_t points_cap, int32_t *n_points) {
   if (!h) return SFW_ERR_INVALID_ARG;
   if (!points_xyth || points_cap <= 0) return fail(h, SFW_ERR_INVALID_ARG, "grid_points: bad index or buffer");
-  const int S = num_steps_of(h->params);
+  const int S = num_steps_of(h->live.params);
   std::vector<double> tmp(static_cast<size_t>(3) * S);
   int32_t n = 0;
   if (int rc = sfw_grid_points_batch(h, index, 1, tmp.data(), &n)) return rc;
@@ -2737,13 +2793,7 @@ int sfw_multi_set_agents(sfw_multi_handle m, const sfw_agent *agents, int32_t A,
   // host-side copy — the upload happens per rank with its next stage
   sfw_handle h0 = m->h[0];
   if (int e = sfw_set_agents(h0, agents, A, obstacles_xy, O)) return mrank_fail(m, 0, e, "sfw_set_agents");
-  for (int r = 1; r < m->R; ++r) {
-    sfw_handle h = m->h[static_cast<size_t>(r)];
-    h->h_agents = h0->h_agents;
-    h->ao_vel = h0->ao_vel; h->ao_cst = h0->ao_cst; h->ao_obs = h0->ao_obs; h->ao_grp = h0->ao_grp; h->ao_off = h0->ao_off; h->ao_mem = h0->ao_mem;
-    h->A = h0->A; h->O = h0->O; h->NG = h0->NG; h->n_grp_mem = h0->n_grp_mem;
-    h->rest_pairs = h0->rest_pairs;
-  }
+  for (int r = 1; r < m->R; ++r) m->h[static_cast<size_t>(r)]->world.agents = h0->world.agents;
   return SFW_OK;
 }
 
@@ -2765,25 +2815,25 @@ int sfw_multi_score_grid(sfw_multi_handle m, const sfw_robot_state *rs, const do
       !all_finite(&args->acc_x, 5))
     return mfail(m, SFW_ERR_INVALID_ARG, "multi_score_grid: non-finite robot state, goal argument or sample velocity");
   {  // ref :345: rows are the outer axis — contiguous blocks of equal planned work (equal row counts when nothing is shared)
-    const int S = num_steps_of(h0->params);
-    const bool sharing = h0->prefix_env.empty() || h0->prefix_env[0] != 0;
-    plan_row_blocks(m->lin, m->ang, rs->vx, rs->vtheta, args->acc_x, args->acc_theta, h0->params.sim_time / S, S, sharing ? h0->A : 0, R,
-                    h0->k2_form, h0->n_cu, m->row0);
+    const int S = num_steps_of(h0->live.params);
+    const bool sharing = h0->cfg.prefix_env.empty() || h0->cfg.prefix_env[0] != 0;
+    plan_row_blocks(m->lin, m->ang, rs->vx, rs->vtheta, args->acc_x, args->acc_theta, h0->live.params.sim_time / S, S, sharing ? h0->world.agents.A : 0, R,
+                    h0->live.k2_form, h0->cfg.n_cu, m->row0);
   }
   // (0) what is the same for every rank, once: the agent set must fit a wave's LDS for every rank's item count
   // before anything is launched anywhere, and the classes of the column axis (every rank scores all nw columns)
   for (int r = 0; r < R; ++r) {
     const int64_t items = static_cast<int64_t>(m->row0[static_cast<size_t>(r) + 1] - m->row0[static_cast<size_t>(r)]) * nw;
-    if (items > 0 && h0->A > 0 && sfw_social_lds_bytes(h0->A, h0->O, h0->NG, h0->n_grp_mem, items, h0->k2_form, h0->n_cu) > 160 * 1024)
+    if (items > 0 && h0->world.agents.A > 0 && sfw_social_lds_bytes(h0->world.agents.A, h0->world.agents.O, h0->world.agents.NG, h0->world.agents.n_grp_mem, items, h0->live.k2_form, h0->cfg.n_cu) > 160 * 1024)
       return mfail(m, SFW_ERR_UNSUPPORTED, "agent/obstacle set does not fit the 160 KiB LDS of one CU");
   }
   axis_classes cols;
   const axis_classes *shared = nullptr;
   {
-    const int S = num_steps_of(h0->params);
+    const int S = num_steps_of(h0->live.params);
     const int64_t rows_max = (nv + R - 1) / R;
-    if (R > 1 && h0->A >= 2 && S >= 2 && rows_max * nw >= 4096 && (h0->prefix_env.empty() || h0->prefix_env[0] != 0)) {
-      cols = classes_of_axis(m->ang, rs->vtheta, args->acc_theta, h0->params.sim_time / S, prefix_max_p(S));
+    if (R > 1 && h0->world.agents.A >= 2 && S >= 2 && rows_max * nw >= 4096 && (h0->cfg.prefix_env.empty() || h0->cfg.prefix_env[0] != 0)) {
+      cols = classes_of_axis(m->ang, rs->vtheta, args->acc_theta, h0->live.params.sim_time / S, prefix_max_p(S));
       cols.complete();  // (read by every rank's thread: no level is written lazily from there)
       shared = &cols;
     }
@@ -2813,7 +2863,7 @@ int sfw_multi_score_grid(sfw_multi_handle m, const sfw_robot_state *rs, const do
       }
     }
     // fewer rows than ranks: this rank holds nothing, its row is +inf / 0 valid (null selection record)
-    e = sfw_launch_key_table(n > 0 ? h->d_sel : nullptr, m->d_table[static_cast<size_t>(r)], r, R, h->stream);
+    e = sfw_launch_key_table(n > 0 ? h->st.d_sel : nullptr, m->d_table[static_cast<size_t>(r)], r, R, h->stream);
     if (e != hipSuccess) {
       err = std::string("key table launch: ") + hipGetErrorString(e);
       return SFW_ERR_HIP;
@@ -2960,12 +3010,10 @@ double us_since(std::chrono::steady_clock::time_point t0) {
   return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
 }
 
-int batch_launch(sfw_batch b) {
+// every member staged (batch_launch has checked): one launch per kernel variant for the members that qualify for the
+// one-kernel control cycle, the others' kernels behind them on the same stream
+int batch_enqueue(sfw_batch b) {
   const int32_t B = static_cast<int32_t>(b->h.size());
-  // every member staged, or nothing is enqueued
-  for (int32_t i = 0; i < B; ++i)
-    if (!b->h[static_cast<size_t>(i)]->staged)
-      return bfail(b, SFW_ERR_STATE, "batch_launch: member " + std::to_string(i) + " has no staged grid (sfw_grid_stage; sfw_score_one consumes it)");
   if (hipSetDevice(b->device) != hipSuccess) return bfail(b, SFW_ERR_HIP, "batch_launch: hipSetDevice failed");
   std::vector<launch_prep> lp(static_cast<size_t>(B));
   std::vector<sfw_launch> L(static_cast<size_t>(B));
@@ -3048,10 +3096,21 @@ int batch_launch(sfw_batch b) {
   return SFW_OK;
 }
 
+int batch_launch(sfw_batch b) {
+  // every member staged, or nothing is enqueued
+  for (size_t i = 0; i < b->h.size(); ++i)
+    if (!b->h[i]->st.valid)
+      return bfail(b, SFW_ERR_STATE, "batch_launch: member " + std::to_string(i) + " has no staged grid (sfw_grid_stage; sfw_score_one consumes it)");
+  const int rc = batch_enqueue(b);
+  if (rc != SFW_OK)
+    for (sfw_handle h : b->h) drop_launch(h);  // all or none: the members committed before the failure included
+  return rc;
+}
+
 int batch_fetch(sfw_batch b, sfw_best *best_out) {
   const int32_t B = static_cast<int32_t>(b->h.size());
   for (int32_t i = 0; i < B; ++i)
-    if (!b->h[static_cast<size_t>(i)]->launched)
+    if (!b->h[static_cast<size_t>(i)]->last.launched)
       return bfail(b, SFW_ERR_STATE, "batch_fetch: member " + std::to_string(i) + " has not been launched");
   if (hipSetDevice(b->device) != hipSuccess) return bfail(b, SFW_ERR_HIP, "batch_fetch: hipSetDevice failed");
   // one wait for the whole batch (one stream)
@@ -3060,10 +3119,10 @@ int batch_fetch(sfw_batch b, sfw_best *best_out) {
     sfw_handle h = b->h[static_cast<size_t>(i)];
     stream_is_idle(h);
     sfw_best *const best = best_out ? best_out + i : nullptr;
-    if (h->mirrored) {  // (as sfw_grid_fetch: the selection kernels left vector and record in the pinned mirror)
-      h->fetched = true;
+    if (h->last.mirrored) {  // (as sfw_grid_fetch: the selection kernels left vector and record in the pinned mirror)
+      h->last.fetched = true;
       sfw_sel s;
-      std::memcpy(&s, h->pin_mirror.p + sizeof(double) * static_cast<size_t>(h->nv) * h->nw, sizeof(s));
+      std::memcpy(&s, h->pin_mirror.p + sizeof(double) * static_cast<size_t>(h->st.nv) * h->st.nw, sizeof(s));
       sel_to_best(h, s, best, nullptr);
     } else if (int e = sfw_grid_fetch(h, nullptr, best, nullptr)) {  // (a grid too large for the mirror: its own copy)
       return bmember_fail(b, i, e, "batch_fetch");
@@ -3094,7 +3153,7 @@ int sfw_batch_create(const sfw_params *params, int device, int32_t B, sfw_batch 
     sfw_handle h = nullptr;
     rc = create_handle(params, device, b->stream, b->side, &h);
     if (rc == SFW_OK) {
-      h->batch_member = true;
+      h->cfg.batch_member = true;
       b->h.push_back(h);
     }
   }
@@ -3220,11 +3279,11 @@ int ensemble_check_mode(sfw_ensemble e, int32_t mode, const double *probs, const
 int ensemble_enqueue(sfw_ensemble e, int32_t mode, const double *probs) {
   const int32_t M = static_cast<int32_t>(e->b->h.size());
   sfw_handle h0 = e->b->h[0];
-  const int64_t T = static_cast<int64_t>(h0->nv) * h0->nw;
+  const int64_t T = static_cast<int64_t>(h0->st.nv) * h0->st.nw;
   const size_t cost_bytes = sizeof(double) * static_cast<size_t>(T);
   const size_t rej_bytes = (sizeof(int32_t) * static_cast<size_t>(T) + 15) & ~size_t(15);
   e->T = T;
-  e->mirrored = cost_bytes <= h0->mirror_max_bytes;  // (the handle's rule: pinned up to SFW_MIRROR_MAX_MB of costs)
+  e->mirrored = cost_bytes <= h0->cfg.mirror_max_bytes;  // (the handle's rule: pinned up to SFW_MIRROR_MAX_MB of costs)
   if (e->pin_out.reserve(kEnsRecBytes + (e->mirrored ? cost_bytes + rej_bytes : 0)) != hipSuccess ||
       (!e->mirrored && e->d_out.reserve(cost_bytes + rej_bytes) != hipSuccess) ||
       e->partials.reserve(static_cast<size_t>(sfw_argmin_partials(T))) != hipSuccess)
@@ -3246,7 +3305,7 @@ int ensemble_enqueue(sfw_ensemble e, int32_t mode, const double *probs) {
   char *const out = e->mirrored ? e->pin_out.p + kEnsRecBytes : e->d_out.p;
   const hipError_t he = sfw_launch_ensemble(reinterpret_cast<const double *const *>(e->tab.p),
                                             reinterpret_cast<const double *>(e->tab.p + sizeof(double) * static_cast<size_t>(M)), M, T,
-                                            mode, w, h0->d_linvels, h0->d_angvels, h0->nw, reinterpret_cast<double *>(out),
+                                            mode, w, h0->st.d_linvels, h0->st.d_angvels, h0->st.nw, reinterpret_cast<double *>(out),
                                             reinterpret_cast<int32_t *>(out + cost_bytes), e->partials.p,
                                             reinterpret_cast<sfw_sel *>(e->pin_out.p), e->b->stream);
   if (he != hipSuccess) return efail(e, SFW_ERR_HIP, std::string("ensemble: sfw_ensemble_stage1/2: ") + hipGetErrorString(he));
@@ -3292,7 +3351,7 @@ int sfw_ensemble_create(const sfw_params *params, int device, int32_t M, sfw_ens
   e->b = b;
   e->hyp_set.assign(static_cast<size_t>(M), 0);
   e->seq.assign(static_cast<size_t>(M), 0);
-  for (sfw_handle h : b->h) h->capture_terms = true;
+  for (sfw_handle h : b->h) h->live.capture_terms = true;
   *out = e;
   return SFW_OK;
 }
@@ -3363,9 +3422,9 @@ int sfw_ensemble_score_grid(sfw_ensemble e, const sfw_robot_state *rs, const dou
     const sfw_handle h = e->b->h[static_cast<size_t>(m)];
     if (!e->hyp_set[static_cast<size_t>(m)])
       return efail(e, SFW_ERR_STATE, "ensemble_score_grid: hypothesis " + std::to_string(m) + " was never set");
-    if (std::memcmp(&h->params, &e->params, sizeof(sfw_params)) != 0)
+    if (std::memcmp(&h->live.params, &e->params, sizeof(sfw_params)) != 0)
       return efail(e, SFW_ERR_STATE, "ensemble_score_grid: member " + std::to_string(m) + "'s sfw_params differ from the ensemble's");
-    if (!h->capture_terms)
+    if (!h->live.capture_terms)
       return efail(e, SFW_ERR_STATE, "ensemble_score_grid: member " + std::to_string(m) + "'s terms capture was turned off");
   }
   e->scored = false;
@@ -3378,7 +3437,7 @@ int sfw_ensemble_score_grid(sfw_ensemble e, const sfw_robot_state *rs, const dou
   t0 = std::chrono::steady_clock::now();
   if (int rc = batch_launch(e->b)) return efail(e, rc, "ensemble_score_grid: " + e->b->err);
   for (int32_t m = 0; m < M; ++m)
-    if (!e->b->h[static_cast<size_t>(m)]->terms_launched)
+    if (!e->b->h[static_cast<size_t>(m)]->last.terms)
       return efail(e, SFW_ERR_STATE, "ensemble_score_grid: member " + std::to_string(m) + " did not capture terms");
   if (int rc = ensemble_enqueue(e, mode, probs)) return rc;
   e->us[1] = us_since(t0);
@@ -3398,7 +3457,7 @@ int sfw_ensemble_aggregate(sfw_ensemble e, int32_t mode, const double *probs, do
   if (!e->scored) return efail(e, SFW_ERR_STATE, "ensemble_aggregate: nothing scored (sfw_ensemble_score_grid)");
   for (size_t m = 0; m < e->b->h.size(); ++m) {
     const sfw_handle h = e->b->h[m];
-    if (!h->launched || !h->terms_launched || h->launch_seq != e->seq[m])
+    if (!h->last.launched || !h->last.terms || h->launch_seq != e->seq[m])
       return efail(e, SFW_ERR_STATE, "ensemble_aggregate: member " + std::to_string(m) +
                                          " was staged, launched or used for sfw_score_one since the last score");
   }

@@ -196,6 +196,12 @@ def test_non_finite_inputs_are_refused(hip_mod):
     assert L.sfw_grid_stage(g._h, C.byref(rs), big_l.ctypes.data, 96, big_a.ctypes.data, 96, C.byref(ga), 0) == SFW_ERR_INVALID_ARG
     cost = C.c_double()
     assert L.sfw_score_one(g._h, C.byref(rs), 0.3, float("nan"), 0.1, C.byref(ga), C.byref(cost), None, 0, None) == SFW_ERR_INVALID_ARG
+    # a call refused for its arguments changes nothing: the first grid is still staged and launched (include/sfw_hip.h)
+    cf, bf, _ = g.fetch()
+    assert np.array_equal(cf, c0) and bf == b0
+    g.launch()
+    cf, bf, _ = g.fetch()
+    assert np.array_equal(cf.view(np.uint64), c0.view(np.uint64)) and bf == b0
     c1, b1 = g.score_grid(scene.robot_state, lin, ang, scene.goal_args)
     assert np.array_equal(c0, c1) and b0 == b1 and np.all(np.isfinite(c1))
 

@@ -17,7 +17,7 @@ import numpy as np
 import pytest
 
 from social_force_window_planner_amd import synthetic as syn
-from social_force_window_planner_amd._abi import SFW_PRECISION_F32, default_params
+from social_force_window_planner_amd._abi import SFW_PRECISION_F32, SfwAgent, default_params
 
 from test_parity_gpu import RTOL_F64, RTOL_NORTH_STAR, _assert_parity, _full_size_properties, _params_for
 
@@ -708,6 +708,20 @@ def test_the_braking_robot_hole_is_flagged(oracle_mod, hip_mod):
     _stand(ag[4])
     ag[4].desired_velocity = 0.0
     assert flag() == 1                                   # 0.3 m/s at 1 m/s^2: at rest after 0.3 s of the 1 s horizon
+    # the flag describes the STAGED agents: a set_agents after the stage counts from the next stage on, either way
+    g = hip_mod.HipScorer(default_params(sim_time=1.0))
+    g.load_scene(scene)
+    moving = (SfwAgent * len(ag))(*ag)
+    moving[4].desired_velocity = 1.0
+    for staged, after in ((ag, moving), (moving, ag)):
+        g.set_agents(staged, scene.obstacles)
+        g.stage(scene.robot_state, lin, ang, scene.goal_args)
+        before = g.plan_info()["rest_noise_unreproduced"]
+        assert before == (1 if staged is ag else 0)
+        g.set_agents(after, scene.obstacles)
+        assert g.plan_info()["rest_noise_unreproduced"] == before
+        g.stage(scene.robot_state, lin, ang, scene.goal_args)
+        assert g.plan_info()["rest_noise_unreproduced"] == 1 - before
     assert flag(linvels=lin[1:]) == 0                    # no sample stops the robot
     rs0 = (scene.robot_state[0], scene.robot_state[1], scene.robot_state[2], 0.0, 0.0, 0.0)
     ag[0].vx = ag[0].vy = 0.0
