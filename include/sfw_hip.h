@@ -157,9 +157,9 @@ typedef struct sfw_goal_args {
 
 /* Result of the selection rule (src/sfw_planner.cpp:394-414, :426-468). */
 typedef struct sfw_best {
-  int64_t index;    /* iv*nw+iw of the winner, -1 if no sample is selectable */
+  int64_t index;    /* iv*nw+iw of the winner (a sample list: t), -1 if no sample is selectable */
   double cost;      /* winner's cost, -1.0 if none                           */
-  double vx, vy, vtheta; /* cmd_vel (0,0,0 if none)                          */
+  double vx, vy, vtheta; /* cmd_vel (0,0,0 if none); vy is 0 for a grid      */
   int64_t n_valid;  /* samples with cost >= 0                                */
 } sfw_best;
 
@@ -260,6 +260,66 @@ int sfw_grid_fetch(sfw_handle h, double *costs_out, sfw_best *best_out,
  * pass costs_out).  A caller that only reads the vector — a marker publisher, the tests — saves the memcpy:
  * sfw_grid_fetch(h, NULL, &best, NULL) and this. */
 const double *sfw_grid_costs_view(sfw_handle h);
+
+/* ---- sample lists ------------------------------------------------------ */
+/*
+ * Stage a LIST of n samples instead of a grid: sample t is the command
+ * (vx[t], vy[t], vtheta[t]).  vy may be NULL: every vy is 0.0.  The list
+ * need not be a product of axes: a holonomic (vx, vy, vtheta) window, a set
+ * that is denser around the last winner, random or hand-picked candidates.
+ * The grid loop's (0,0) skip does not apply: the caller chose the samples.
+ *
+ * Cost.  costs[t] is bit for bit what the scalar call sfw_score_one returns for
+ * (rs, vx[t], vy[t], vtheta[t], args): SFW_COST_INVALID exactly where that
+ * call produces it, never SFW_COST_SKIPPED, never NaN.
+ *
+ * After a list stage sfw_grid_launch / _sync / _fetch / _costs_view /
+ * _plan_info, sfw_grid_points(_batch), sfw_set_points_capture,
+ * sfw_set_terms_capture, sfw_grid_terms, sfw_grid_rescore, sfw_set_timing and
+ * sfw_last_launch_ms act on the list, with sample index t in list order (the
+ * cost vector has n entries).  A later sfw_grid_stage replaces the list, a
+ * later list stage replaces the grid; the scalar call consumes either.
+ * All-or-nothing as for sfw_grid_stage: a call refused for its arguments
+ * changes nothing (what was staged before still launches), any other failure
+ * leaves nothing staged.
+ *
+ * SFW_ERR_INVALID_ARG: n < 1; a NULL handle, rs, vx, vtheta or args; a
+ * non-finite value in vx, vy, vtheta, rs or args.  SFW_ERR_STATE: no costmap.
+ *
+ * Selection.  The reference's rule (cost up, linvel down, |angvel| up, later
+ * sample first) with linvel = vx[t] and angvel = vtheta[t]; vy takes no part
+ * in the order; among equal (cost, vx, |vtheta|) the larger index wins, as in
+ * the grid.  sfw_best.index = t and sfw_best.vx / .vy / .vtheta are the
+ * sample's own three values (vy is not always 0 here); n_valid counts costs
+ * >= 0; sfw_best_key.neg_index = -(index_base + t), so a list can be sharded
+ * over ranks as grid rows are.
+ *
+ * sfw_plan_info of a list: samples = n; levels = split_step = classes =
+ * class_steps = 0 — there is NO shared-prefix rollout for lists: a list has
+ * no axes along which samples share their first steps, so every sample is
+ * integrated over the whole horizon.  Where the samples ARE a product of two
+ * axes keep using sfw_grid_stage: at the target configuration (256 x 256
+ * samples, 20 people) the grid's shared prefix integrates about 73 % of the
+ * sample-steps the list does (how much slower the list is there has not been
+ * measured yet, see CHANGELOG.md; examples/sample_list_latency.cpp prints the
+ * ratio).  organisation, chunks and flat_samples are those of
+ * a grid of n x 1; one_launch is 1 exactly where a grid of the same size and
+ * crowd gets it (a refinement list of a few dozen samples is ONE kernel
+ * launch); rest_noise_unreproduced looks at the list's samples as it looks at
+ * a grid's rows (a sample with vx == 0 and vy == 0).
+ *
+ * A member of a sfw_batch may be staged with a list: its results after
+ * sfw_batch_launch / _fetch are bit-identical to its own launch; it does not
+ * join the batched kernel (sfw_batch_desc.own_path_members counts it).
+ * sfw_batch_score_grid, sfw_ensemble_* and sfw_multi_* take grids only.
+ */
+int sfw_samples_stage(sfw_handle h, const sfw_robot_state *rs, const double *vx, const double *vy,
+                      const double *vtheta, int32_t n, const sfw_goal_args *args, int64_t index_base);
+/* sfw_samples_stage (index_base 0) + sfw_grid_launch + sfw_grid_fetch: costs_out (nullable) receives n costs. */
+int sfw_score_samples(sfw_handle h, const sfw_robot_state *rs, const double *vx, const double *vy,
+                      const double *vtheta, int32_t n, const sfw_goal_args *args, double *costs_out,
+                      sfw_best *best_out);
+
 /* How the staged grid will be launched.  levels > 0: the shared-prefix
  * rollout is in use — under the acceleration limits (sfw_planner.hpp:457-463)
  * the robot's first steps are bit-identical for all samples of a class (same

@@ -183,6 +183,10 @@ struct sfw_planner_s {
     double vy_samp = 0.0;
     int skip_zero = 1;
     int64_t index_base = 0;
+    // sfw_samples_stage: a LIST of nv samples (nw = 1).  lin / ang hold vx / vtheta of every sample, vy its vy (empty: all 0.0);
+    // no shared-prefix plan is made, and the cos / sin table holds a unit per sample of a chunk (sfw_device.h sfw_launch.list)
+    bool list = false;
+    std::vector<double> vy;
     // the world as uploaded (sfw_set_* after a stage take effect at the next stage; a launch in between must keep
     // describing the device copy)
     int K = 0, A = 0, O = 0, NG = 0, n_grp_mem = 0;
@@ -196,6 +200,7 @@ struct sfw_planner_s {
     const sfw_agent_const *d_agent_c = nullptr;
     const int32_t *d_agent_grp = nullptr, *d_grp_off = nullptr, *d_grp_mem = nullptr;
     const double *d_linvels = nullptr, *d_angvels = nullptr;
+    const double *d_vy = nullptr;          // the list's vy vector, or null (a grid; a list without one)
     const double *d_agent_rest = nullptr;  // A x (fx, fy), or null when there is no pair at relative rest
     const double *d_pin_rest = nullptr;    // see pinned_rest_table: the stage's table, or null
     sfw_sel *d_sel = nullptr;
@@ -406,6 +411,8 @@ void fill_launch(sfw_handle h, sfw_launch &L, int64_t begin, int64_t count, int6
   L.angvels = h->st.d_angvels;
   L.nv = h->st.nv;
   L.nw = h->st.nw;
+  L.vy_samps = h->st.d_vy;
+  L.list = h->st.list ? 1 : 0;
   L.chunk_begin = begin;
   L.chunk_count = count;
   L.cells = h->st.d_cells;
@@ -771,6 +778,7 @@ int plan_prefix(sfw_handle h, int64_t chunk, int S) {
   h->st.prefix_class_steps = h->st.prefix_last_classes = 0;
   const int64_t T = static_cast<int64_t>(h->st.nv) * h->st.nw;
   const bool forced = !h->cfg.prefix_env.empty();
+  if (h->st.list) return SFW_OK;  // a list has no axes to share a prefix along
   if ((forced && h->cfg.prefix_env[0] == 0) || h->st.A < 2 || S < 2 || h->st.vy_samp != 0.0) return SFW_OK;
   if (!forced && T < 4096) return SFW_OK;  // the GPU is not full: extra launches cost more than they save
   const int64_t rows_per_chunk = chunk / h->st.nw;
@@ -1011,7 +1019,11 @@ bool rest_noise_unreproduced(sfw_handle h) {
   if (!h->st.valid || h->st.A < 2 || (h->st.rs.vx == 0.0 && h->st.rs.vy == 0.0)) return false;  // (standing from the start: reproduced)
   if (!h->st.person_pinned || h->st.vy_samp != 0.0) return false;
   bool zero_row = false;
-  for (double v : h->st.lin) zero_row |= (v == 0.0);
+  if (h->st.list) {  // a sample that decelerates both translations to 0: vx == 0 && vy == 0
+    for (size_t t = 0; t < h->st.lin.size(); ++t) zero_row |= (h->st.lin[t] == 0.0 && (h->st.vy.empty() || h->st.vy[t] == 0.0));
+  } else {
+    for (double v : h->st.lin) zero_row |= (v == 0.0);
+  }
   if (!zero_row) return false;
   const int S = num_steps_of(h->live.params);
   const double dt = h->live.params.sim_time / S;
@@ -1044,7 +1056,7 @@ int plan_tables_device(sfw_handle h, int64_t chunk, bool may_start_poses) {
   const int64_t T = static_cast<int64_t>(h->st.nv) * h->st.nw;
   const int S = num_steps_of(h->live.params);
   SFW_HIP(h, h->ptab.reserve(static_cast<size_t>(table_row_units(chunk, h->st.nw)) * S));
-  SFW_HIP(h, h->cs_tab.reserve(static_cast<size_t>(h->st.nw) * S));
+  SFW_HIP(h, h->cs_tab.reserve((h->st.list ? static_cast<size_t>(chunk) : static_cast<size_t>(h->st.nw)) * S));
   SFW_HIP(h, h->fcode.reserve(static_cast<size_t>(chunk) * S));
   h->st.table_chunk = chunk;
   if (!h->st.prefix_steps.empty())
@@ -1076,6 +1088,7 @@ int plan_tables_device(sfw_handle h, int64_t chunk, bool may_start_poses) {
         L.arena_bytes = static_cast<uint32_t>(h->st.arena_bytes);
         L.linvels = reinterpret_cast<const double *>(h->pin_arena.p + (reinterpret_cast<const char *>(h->st.d_linvels) - h->arena.p));
         L.angvels = reinterpret_cast<const double *>(h->pin_arena.p + (reinterpret_cast<const char *>(h->st.d_angvels) - h->arena.p));
+        if (h->st.d_vy) L.vy_samps = reinterpret_cast<const double *>(h->pin_arena.p + (reinterpret_cast<const char *>(h->st.d_vy) - h->arena.p));
       }
       SFW_HIP(h, sfw_launch_rollout_poses(L, h->stream));
       if (h->st.arena_pending) {
@@ -1168,19 +1181,22 @@ struct host_phases {
   }
 };
 
+// list: sfw_samples_stage — lin / ang are vx / vtheta of nv samples (nw == 1), vy_list their vy (nullable: all 0.0)
 int stage_common(sfw_handle h, const sfw_robot_state *rs, const double *lin, int32_t nv, const double *ang,
                  int32_t nw, const sfw_goal_args *args, double vy_samp, int skip_zero, int64_t index_base,
-                 bool grid = false) {
+                 bool grid = false, bool list = false, const double *vy_list = nullptr) {
   if (!h) return SFW_ERR_INVALID_ARG;
+  const std::string what = list ? "samples_stage" : "grid_stage";
   if (!rs || !lin || !ang || !args || nv <= 0 || nw <= 0)
-    return fail(h, SFW_ERR_INVALID_ARG, "grid_stage: null pointer or non-positive sample count");
-  if (!h->world.have_costmap) return fail(h, SFW_ERR_STATE, "grid_stage: no costmap set (sfw_set_costmap)");
+    return fail(h, SFW_ERR_INVALID_ARG, what + ": null pointer or non-positive sample count");
+  const size_t n_ang = list ? static_cast<size_t>(nv) : static_cast<size_t>(nw);
+  if (!h->world.have_costmap) return fail(h, SFW_ERR_STATE, what + ": no costmap set (sfw_set_costmap)");
   // A NaN would come back as a NaN cost (the header promises sentinels, never NaN) and, in a sample vector, break the
   // ordering the shared-prefix planner sorts by: O(nv + nw) checks
   if (!all_finite(&rs->x, 6) || !all_finite(&args->acc_x, 5) || !std::isfinite(vy_samp))
-    return fail(h, SFW_ERR_INVALID_ARG, "grid_stage: non-finite robot state, goal argument or sample velocity");
-  if (!all_finite(lin, static_cast<size_t>(nv)) || !all_finite(ang, static_cast<size_t>(nw)))
-    return fail(h, SFW_ERR_INVALID_ARG, "grid_stage: non-finite sample velocity");
+    return fail(h, SFW_ERR_INVALID_ARG, what + ": non-finite robot state, goal argument or sample velocity");
+  if (!all_finite(lin, static_cast<size_t>(nv)) || !all_finite(ang, n_ang) || (vy_list && !all_finite(vy_list, static_cast<size_t>(nv))))
+    return fail(h, SFW_ERR_INVALID_ARG, what + ": non-finite sample velocity");
   drop_stage(h);  // (valid again at the end of this function, and only there)
   host_phases ph("stage:");
   SFW_HIP(h, hipSetDevice(h->device));
@@ -1197,7 +1213,10 @@ int stage_common(sfw_handle h, const sfw_robot_state *rs, const double *lin, int
   }
   ph.mark("check+setdev");
   h->st.lin.assign(lin, lin + nv);
-  h->st.ang.assign(ang, ang + nw);
+  h->st.ang.assign(ang, ang + n_ang);
+  h->st.list = list;
+  if (vy_list) h->st.vy.assign(vy_list, vy_list + nv);
+  else h->st.vy.clear();
   h->st.K = h->world.K;
   h->st.A = ag.A;
   h->st.O = ag.O;
@@ -1223,11 +1242,12 @@ int stage_common(sfw_handle h, const sfw_robot_state *rs, const double *lin, int
   // it when it has changed; a larger one has gone out by a copy of its own (above)
   auto up16 = [](size_t b) { return (b + 15) & ~size_t(15); };
   const size_t cells_head = merge ? up16(n_cells) : 0;
-  {  // one arena, one copy: footprint | agents blob | linvels | angvels | relative-rest terms | pinned-rest table | class tables
+  {  // one arena, one copy: footprint | agents blob | linvels | angvels | [a list's vy] | relative-rest terms | pinned-rest table | class tables
     const bool rest = !ag.rest_pairs.empty();
     const size_t o_fp = cells_head, o_ag = o_fp + up16(sizeof(double) * (h->world.footprint.empty() ? 2 : h->world.footprint.size())),
                  o_lin = o_ag + up16(ag.blob.size()), o_ang = o_lin + up16(sizeof(double) * nv),
-                 o_rest = o_ang + up16(sizeof(double) * nw),
+                 o_vy = o_ang + up16(sizeof(double) * n_ang),
+                 o_rest = o_vy + (vy_list ? up16(sizeof(double) * nv) : 0),
                  o_pin = o_rest + (rest ? up16(sizeof(double) * 2 * static_cast<size_t>(ag.A)) : 0),
                  pin_doubles = 4 + static_cast<size_t>(ag.A > 0 ? ag.A : 0),
                  // (room for the pinned-rest table whenever the robot stands still at hand-over: whether one is needed is known
@@ -1244,7 +1264,8 @@ int stage_common(sfw_handle h, const sfw_robot_state *rs, const double *lin, int
     if (!h->world.footprint.empty()) std::memcpy(pb + o_fp, h->world.footprint.data(), sizeof(double) * h->world.footprint.size());
     if (!ag.blob.empty()) std::memcpy(pb + o_ag, ag.blob.data(), ag.blob.size());
     std::memcpy(pb + o_lin, lin, sizeof(double) * nv);
-    std::memcpy(pb + o_ang, ang, sizeof(double) * nw);
+    std::memcpy(pb + o_ang, ang, sizeof(double) * n_ang);
+    if (vy_list) std::memcpy(pb + o_vy, vy_list, sizeof(double) * nv);
     if (!h->st.cls_ints.empty()) std::memcpy(pb + o_cls, h->st.cls_ints.data(), sizeof(int32_t) * h->st.cls_ints.size());
     const double *pos = reinterpret_cast<const double *>(ag.blob.data());
     const double *vel = reinterpret_cast<const double *>(ag.blob.data() + ag.ao_vel);
@@ -1297,6 +1318,7 @@ int stage_common(sfw_handle h, const sfw_robot_state *rs, const double *lin, int
     h->st.d_grp_mem = reinterpret_cast<const int32_t *>(db + o_ag + ag.ao_mem);
     h->st.d_linvels = reinterpret_cast<const double *>(db + o_lin);
     h->st.d_angvels = reinterpret_cast<const double *>(db + o_ang);
+    h->st.d_vy = vy_list ? reinterpret_cast<const double *>(db + o_vy) : nullptr;
     h->st.d_agent_rest = rest ? reinterpret_cast<const double *>(db + o_rest) : nullptr;
   }
   if (h->pair_tab_A != ag.A) {
@@ -1584,7 +1606,7 @@ int launch_kernels(sfw_handle h, const launch_prep &lp) {
   }
   if (timing) SFW_HIP(h, hipEventRecord(h->ev[2], h->stream));
   SFW_HIP(h, sfw_launch_argmin(h->costs.p, h->st.d_linvels, h->st.d_angvels, h->st.nw, T, h->st.index_base,
-                               h->partials.p, h->st.d_sel, h->stream, costs_host, sel_host));
+                               h->partials.p, h->st.d_sel, h->stream, costs_host, sel_host, h->st.list));
   if (timing) SFW_HIP(h, hipEventRecord(h->ev[3], h->stream));
   h->last.timed = timing;
   ++h->launch_seq;
@@ -1616,9 +1638,15 @@ void sel_to_best(sfw_handle h, const sfw_sel &s, sfw_best *best, sfw_best_key *k
       const int64_t local = -s.neg_index - h->st.index_base;
       best->index = local;
       best->cost = s.cost;
-      best->vx = h->st.lin[static_cast<size_t>(local / h->st.nw)];
-      best->vy = 0.0;
-      best->vtheta = h->st.ang[static_cast<size_t>(local % h->st.nw)];
+      if (h->st.list) {  // the sample's own three values
+        best->vx = h->st.lin[static_cast<size_t>(local)];
+        best->vy = h->st.vy.empty() ? 0.0 : h->st.vy[static_cast<size_t>(local)];
+        best->vtheta = h->st.ang[static_cast<size_t>(local)];
+      } else {
+        best->vx = h->st.lin[static_cast<size_t>(local / h->st.nw)];
+        best->vy = 0.0;
+        best->vtheta = h->st.ang[static_cast<size_t>(local % h->st.nw)];
+      }
     } else {  // ref :456-468: stop the robot
       best->index = -1;
       best->cost = -1.0;
@@ -1977,6 +2005,12 @@ int sfw_grid_stage(sfw_handle h, const sfw_robot_state *rs, const double *linvel
   return stage_common(h, rs, linvels, nv, angvels, nw, args, 0.0, 1, index_base, true);
 }
 
+int sfw_samples_stage(sfw_handle h, const sfw_robot_state *rs, const double *vx, const double *vy, const double *vtheta,
+                      int32_t n, const sfw_goal_args *args, int64_t index_base) {
+  // a grid of n rows by one column to everything that counts samples; never the (0,0) skip
+  return stage_common(h, rs, vx, n, vtheta, 1, args, 0.0, 0, index_base, true, true, vy);
+}
+
 int sfw_grid_launch(sfw_handle h) { return launch_common(h); }
 
 int sfw_grid_sync(sfw_handle h) {
@@ -2024,6 +2058,13 @@ int sfw_score_grid(sfw_handle h, const sfw_robot_state *rs, const double *linvel
                    const double *angvels, int32_t nw, const sfw_goal_args *args, double *costs_out,
                    sfw_best *best_out) {
   if (int e = sfw_grid_stage(h, rs, linvels, nv, angvels, nw, args, 0)) return e;
+  if (int e = sfw_grid_launch(h)) return e;
+  return sfw_grid_fetch(h, costs_out, best_out, nullptr);
+}
+
+int sfw_score_samples(sfw_handle h, const sfw_robot_state *rs, const double *vx, const double *vy, const double *vtheta,
+                      int32_t n, const sfw_goal_args *args, double *costs_out, sfw_best *best_out) {
+  if (int e = sfw_samples_stage(h, rs, vx, vy, vtheta, n, args, 0)) return e;
   if (int e = sfw_grid_launch(h)) return e;
   return sfw_grid_fetch(h, costs_out, best_out, nullptr);
 }
@@ -2294,7 +2335,8 @@ int sfw_grid_rescore(sfw_handle h, const sfw_weights *w, int32_t K, sfw_best *be
     const int64_t blocks = sfw_rescore_blocks(T, n);
     SFW_HIP(h, h->rescore_partials.reserve(static_cast<size_t>(blocks) * static_cast<size_t>(n)));
     SFW_HIP(h, sfw_launch_rescore(h->terms.p, T, h->rescore_w.p + k0, n, h->st.d_linvels, h->st.d_angvels, h->st.nw, h->st.index_base,
-                                  h->rescore_partials.p, costs_out ? h->rescore_costs.p : nullptr, sel_host + k0, h->stream));
+                                  h->rescore_partials.p, costs_out ? h->rescore_costs.p : nullptr, sel_host + k0, h->stream,
+                                  h->st.list));
     if (costs_out)
       SFW_HIP(h, hipMemcpyAsync(costs_out + static_cast<int64_t>(k0) * T, h->rescore_costs.p,
                                 sizeof(double) * static_cast<size_t>(n) * static_cast<size_t>(T), hipMemcpyDeviceToHost, h->stream));
@@ -2381,7 +2423,7 @@ int sfw_grid_points_batch(sfw_handle h, int64_t first, int64_t count, double *po
   if (e == hipSuccess) e = h->pts_base.reserve(n);
   if (e == hipSuccess) e = h->pts_costs.reserve(n);
   if (e == hipSuccess) e = h->pts_ptab.reserve(static_cast<size_t>(S) * static_cast<size_t>(table_row_units(count, h->st.nw)));
-  if (e == hipSuccess) e = h->pts_cs.reserve(static_cast<size_t>(S) * h->st.nw);
+  if (e == hipSuccess) e = h->pts_cs.reserve(static_cast<size_t>(S) * (h->st.list ? n : static_cast<size_t>(h->st.nw)));
   if (e == hipSuccess) e = h->pts_fcode.reserve(static_cast<size_t>(S) * n);
   if (e == hipSuccess) {
     sfw_launch L;
@@ -3022,6 +3064,7 @@ int batch_enqueue(sfw_batch b) {
   for (int32_t i = 0; i < B; ++i) {
     const size_t m = static_cast<size_t>(i);
     if (int e = launch_prepare(b->h[m], false, lp[m])) return bmember_fail(b, i, e, "batch_launch");
+    if (b->h[m]->st.list) continue;  // a sample list (sfw_samples_stage) takes its own path: no list form of the batched kernel
     if (cycle_launch_of(b->h[m], lp[m], L[m])) {
       variant[m] = sfw_cycle_batch_variant(L[m]);
       ++n_cycle;
@@ -3088,9 +3131,20 @@ int batch_enqueue(sfw_batch b) {
         return bmember_fail(b, i, SFW_ERR_HIP, "batch_launch");
   }
   // the others on their usual path, behind the batch launches on the same stream
-  for (int32_t i = 0; i < B; ++i)
-    if (variant[static_cast<size_t>(i)] < 0)
-      if (int e = launch_kernels(b->h[static_cast<size_t>(i)], lp[static_cast<size_t>(i)])) return bmember_fail(b, i, e, "batch_launch");
+  // (a list member's own path is what sfw_grid_launch would do: its own one-kernel cycle where that applies)
+  for (int32_t i = 0; i < B; ++i) {
+    const size_t m = static_cast<size_t>(i);
+    if (variant[m] >= 0) continue;
+    if (b->h[m]->st.list && cycle_launch_of(b->h[m], lp[m], L[m])) {
+      if (const hipError_t e = launch_cycle_of(L[m], b->h[m]->stream); e != hipSuccess) {
+        (void)hip_fail(b->h[m], e, "sfw_cycle_list_kernel");
+        return bmember_fail(b, i, SFW_ERR_HIP, "batch_launch");
+      }
+      if (cycle_commit(b->h[m], false) != SFW_OK) return bmember_fail(b, i, SFW_ERR_HIP, "batch_launch");
+      continue;
+    }
+    if (int e = launch_kernels(b->h[m], lp[m])) return bmember_fail(b, i, e, "batch_launch");
+  }
   b->desc = d;
   b->launched = true;
   return SFW_OK;

@@ -205,7 +205,7 @@ struct sfw_launch {
   int32_t *coll_step;    // T : step at which a pedestrian touched the robot (ref :613-627), -1 if none; nullable
   // per-chunk tables (see sfw_unit)
   sfw_unit *ptab;        // [step][row_units]: positions of the chunk's samples, then velocities of its grid rows
-  sfw_unit *cs_tab;      // [step][nw]: cos / sin of the heading before the step, per grid column
+  sfw_unit *cs_tab;      // [step][nw]: cos / sin of the heading before the step, per grid column (a list: [step][rstep_stride])
   int64_t row_units;     // units per step row of ptab (>= rstep_stride + grid rows the chunk touches)
   int16_t *fcode;        // footprint cost per (step, sample): -3,-2,-1 or 0..253, [step][rstep_stride]
   int64_t rstep_stride;  // samples per step row (position units in a ptab row, codes in an fcode row)
@@ -231,6 +231,13 @@ struct sfw_launch {
   // sample index, written where base_cost / costs are (sfw_put_term*); a sentinel cost puts its sentinel into all five
   double *terms;
   int64_t terms_T;
+  // sfw_samples_stage: the samples are a LIST, not a tensor product.  Sample t is the command (linvels[t], vy_samps[t] — 0.0
+  // when vy_samps is null —, angvels[t]); nv = chunk rows = the list's length and nw = 1, so K2, the chunking and the ptab
+  // addressing see a grid of n rows by one column (vel_row_of: one velocity unit per sample).  The list kernels (the *_list
+  // instantiations of K1, the cycle kernel and the selection) never skip a sample and keep cs_tab as [step][rstep_stride]:
+  // one cos / sin unit per sample of the chunk.  (Appended: no other field's offset moves.)
+  const double *vy_samps;
+  int32_t list;
 };
 
 // Writers of the captured cost terms (no-ops when terms is null): term k of sample t, the three pedestrian-free terms, or one
@@ -302,16 +309,17 @@ bool sfw_rollout_is_fused(const sfw_launch &L);
 // hold >= sfw_argmin_partials(T) records.
 int64_t sfw_argmin_partials(int64_t T);
 // costs_host / sel_host (nullable): host-visible pinned memory that receives a copy of the cost vector and of the record
+// list: linvels / angvels hold one value per SAMPLE (sfw_launch.list), nw is not read
 hipError_t sfw_launch_argmin(const double *costs, const double *linvels, const double *angvels,
                              int32_t nw, int64_t T, int64_t index_base, sfw_sel *partials,
                              sfw_sel *out, hipStream_t stream, double *costs_host = nullptr,
-                             sfw_sel *sel_host = nullptr);
+                             sfw_sel *sel_host = nullptr, bool list = false);
 // sfw_grid_rescore: K weight vectors (device copy `w`) over the captured terms (SoA [5][T]) -> K records at sel_host (pinned).
 // partials: K x sfw_rescore_blocks(T, K) records; costs (nullable): K x T doubles, weight-major.
 int64_t sfw_rescore_blocks(int64_t T, int K);
 hipError_t sfw_launch_rescore(const double *terms, int64_t T, const sfw_weights *w, int K, const double *linvels,
                               const double *angvels, int32_t nw, int64_t index_base, sfw_sel *partials, double *costs,
-                              sfw_sel *sel_host, hipStream_t stream);
+                              sfw_sel *sel_host, hipStream_t stream, bool list = false);
 // sfw_ensemble_*: M members' captured terms (terms: device table of M pointers to SoA [5][T]; probs: M doubles, MEAN only —
 // both read wave-uniformly) -> costs[T], rejected[T] (pinned or device) and the record at sel_host (pinned).  partials:
 // sfw_argmin_partials(T) records.

@@ -165,25 +165,55 @@ __device__ __forceinline__ int64_t vel_row_of(const sfw_launch &L, int64_t local
 // One step of one sample as the pose rollout leaves it: the post-step position always; the step's velocity by the first
 // sample of every grid row inside the chunk, cos / sin of the pre-step heading by the chunk's first nw samples (one per
 // column) — the same values whoever writes them.
+// LIST (sfw_launch.list: nw = 1, a sample is its own grid row): velocity and cos / sin are the sample's own, one unit each at
+// the sample's place in the step row — cs_tab is [step][rstep_stride] — so adjacent lanes store adjacent 16-byte units.
+template <bool LIST>
 __device__ __forceinline__ void put_robot_step(const sfw_launch &L, int64_t local, int i, double xn, double yn, double vx,
                                                double vy, double c, double s) {
   sfw_unit *const row = L.ptab + static_cast<int64_t>(i) * L.row_units;
   row[local] = sfw_unit{xn, yn};
-  const int64_t t = L.chunk_begin + local;
-  if (local == 0 || t % L.nw == 0) row[L.rstep_stride + vel_row_of(L, local)] = sfw_unit{vx, vy};
-  if (local < L.nw) L.cs_tab[static_cast<int64_t>(i) * L.nw + t % L.nw] = sfw_unit{c, s};
+  if constexpr (LIST) {
+    row[L.rstep_stride + local] = sfw_unit{vx, vy};  // (= vel_row_of(L, local) for nw = 1)
+    L.cs_tab[static_cast<int64_t>(i) * L.rstep_stride + local] = sfw_unit{c, s};
+  } else {
+    const int64_t t = L.chunk_begin + local;
+    if (local == 0 || t % L.nw == 0) row[L.rstep_stride + vel_row_of(L, local)] = sfw_unit{vx, vy};
+    if (local < L.nw) L.cs_tab[static_cast<int64_t>(i) * L.nw + t % L.nw] = sfw_unit{c, s};
+  }
+}
+// The command of sample t and whether it is scored: the product of the two axes with the grid loop's (0,0) skip (ref :349-352),
+// or entry t of the list — every entry is scored, the caller chose it.
+struct sample_cmd {
+  double vx, vy, vth;
+  bool scored;
+};
+template <bool LIST> __device__ __forceinline__ sample_cmd sample_cmd_of(const sfw_launch &L, int64_t t) {
+  sample_cmd q;
+  if constexpr (LIST) {
+    q.vx = L.linvels[t];
+    q.vth = L.angvels[t];
+    q.vy = L.vy_samps ? L.vy_samps[t] : 0.0;
+    q.scored = true;
+  } else {
+    const int iv = static_cast<int>(t / L.nw), iw = static_cast<int>(t % L.nw);
+    q.vx = L.linvels[iv];
+    q.vth = L.angvels[iw];
+    q.vy = L.vy_samp;
+    q.scored = !(L.skip_zero_sample && q.vx == 0.0 && q.vth == 0.0);
+  }
+  return q;
 }
 
 // Sequential pose integration of one sample (reference :527-:611 without the costmap and the
 // pedestrians): writes the K1 tables (put_robot_step) and the pedestrian-independent cost
 // terms.  Returns false for the never-scored (0,0) sample (whose records are written all the same).
-__device__ __forceinline__ bool rollout_sample(const sfw_launch &L, int64_t local) {
+template <bool LIST> __device__ __forceinline__ bool rollout_sample(const sfw_launch &L, int64_t local) {
   const int64_t t = L.chunk_begin + local;
-  const int iv = static_cast<int>(t / L.nw), iw = static_cast<int>(t % L.nw);
-  const double vx_samp = L.linvels[iv], vth_samp = L.angvels[iw], vy_samp = L.vy_samp;
+  const sample_cmd cmd = sample_cmd_of<LIST>(L, t);
+  const double vx_samp = cmd.vx, vth_samp = cmd.vth, vy_samp = cmd.vy;
   // The never-scored (0,0) sample (ref :349-352) still gets its robot-step records: it can be the
   // representative of a shared-prefix class (sfw_cls_agent) whose other members are scored.
-  const bool scored = !(L.skip_zero_sample && vx_samp == 0.0 && vth_samp == 0.0);
+  const bool scored = cmd.scored;
   if (!scored) {
     L.status[t] = SFW_ST_SKIPPED;
     L.costs[t] = SFW_COST_SKIPPED;
@@ -215,7 +245,7 @@ __device__ __forceinline__ bool rollout_sample(const sfw_launch &L, int64_t loca
     x_i = xn;
     y_i = yn;
     th_i = th_i + vth_i * dt;
-    put_robot_step(L, local, i, x_i, y_i, vx_i, vy_i, c, s);
+    put_robot_step<LIST>(L, local, i, x_i, y_i, vx_i, vy_i, c, s);
   }
   // ref :643-666 without the costmap and social terms (left-to-right sum order kept)
   const double dx = L.ga.wpx - x_i, dy = L.ga.wpy - y_i;
@@ -280,12 +310,14 @@ __device__ __forceinline__ void fetch_arena(const sfw_launch &L) {
   const uint32_t n = L.arena_bytes / 16, stride = gridDim.x * blockDim.x;
   for (uint32_t u = blockIdx.x * blockDim.x + threadIdx.x; u < n; u += stride) dst[u] = __builtin_nontemporal_load(src + u);
 }
-__global__ void __launch_bounds__(64) sfw_rollout_kernel(const sfw_launch L) {
+// (every K1 kernel is one text with the grid form <false> and the list form <true> as its two instantiations, so the
+// arithmetic cannot drift)
+template <bool LIST> __global__ void __launch_bounds__(64) sfw_rollout_kernel(const sfw_launch L) {
   clear_clock_probe(L);
   fetch_arena(L);
   const int64_t local = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
   if (local >= L.chunk_count) return;
-  rollout_sample(L, local);
+  rollout_sample<LIST>(L, local);
 }
 
 // K1a again, for GPU-filling grids: TEAMS of eight lanes per sample, eight samples per wave.  One thread per sample leaves a
@@ -301,7 +333,7 @@ __global__ void __launch_bounds__(64) sfw_rollout_kernel(const sfw_launch L) {
 // values in the same order as rollout_sample (no contraction here either): bit-identical tables and cost terms
 // (tests/test_prefix_sharing_gpu.py::test_team_rollout_equals_the_thread_rollout).
 constexpr int K1A_TEAM = 8;
-__global__ void __launch_bounds__(64) sfw_rollout_team_kernel(const sfw_launch L) {
+template <bool LIST> __global__ void __launch_bounds__(64) sfw_rollout_team_kernel(const sfw_launch L) {
   constexpr int TEAMS = WAVE / K1A_TEAM;
   clear_clock_probe(L);
   fetch_arena(L);
@@ -314,9 +346,9 @@ __global__ void __launch_bounds__(64) sfw_rollout_team_kernel(const sfw_launch L
   const bool live = local_raw < L.chunk_count;
   const int64_t local = live ? local_raw : L.chunk_count - 1;  // a team past the end repeats the last sample and stores nothing
   const int64_t t = L.chunk_begin + local;
-  const int iv = static_cast<int>(t / L.nw), iw = static_cast<int>(t % L.nw);
-  const double vx_samp = L.linvels[iv], vth_samp = L.angvels[iw], vy_samp = L.vy_samp;
-  const bool scored = !(L.skip_zero_sample && vx_samp == 0.0 && vth_samp == 0.0);
+  const sample_cmd cmd = sample_cmd_of<LIST>(L, t);
+  const double vx_samp = cmd.vx, vth_samp = cmd.vth, vy_samp = cmd.vy;
+  const bool scored = cmd.scored;
   if (live && j == 0) {
     if (!scored) {
       L.status[t] = SFW_ST_SKIPPED;
@@ -377,7 +409,7 @@ __global__ void __launch_bounds__(64) sfw_rollout_team_kernel(const sfw_launch L
         pt[1] = r_py[g][j];
         pt[2] = thq;
       }
-      put_robot_step(L, local, i, r_px[g][j + 1], r_py[g][j + 1], vxq, vyq, c, s);
+      put_robot_step<LIST>(L, local, i, r_px[g][j + 1], r_py[g][j + 1], vxq, vyq, c, s);
     }
     // (no barrier here: the next round's phase (1) writes r_th / r_vx / r_vy, which this round read in front of its second
     // barrier, and r_px / r_py are rewritten behind two more)
@@ -401,7 +433,7 @@ __global__ void __launch_bounds__(64) sfw_rollout_team_kernel(const sfw_launch L
 // K1b: footprint legality/cost of one pose, one thread per (step, sample).
 // Independent across steps once the poses are known, so the S*T checks run in
 // parallel instead of serially inside the rollout.
-__global__ void __launch_bounds__(256) sfw_footprint_kernel(const sfw_launch L) {
+template <bool LIST> __global__ void __launch_bounds__(256) sfw_footprint_kernel(const sfw_launch L) {
   const int64_t idx = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
   const int64_t n = L.chunk_count;
   if (idx >= n * L.S) return;
@@ -409,7 +441,8 @@ __global__ void __launch_bounds__(256) sfw_footprint_kernel(const sfw_launch L) 
   if (L.status[L.chunk_begin + local] == SFW_ST_SKIPPED) return;
   // the pose before the step: where the step before it ended (the handed-over pose for step 0), heading by column
   const sfw_unit pos = step == 0 ? sfw_unit{L.rs.x, L.rs.y} : L.ptab[(step - 1) * L.row_units + local];
-  const sfw_unit cs = L.cs_tab[step * L.nw + (L.chunk_begin + local) % L.nw];
+  // (a list: the sample's own unit, next to its neighbour lane's — one coalesced 16-byte load per lane, like `pos`)
+  const sfw_unit cs = LIST ? L.cs_tab[step * L.rstep_stride + local] : L.cs_tab[step * L.nw + (L.chunk_begin + local) % L.nw];
   const double fc = footprint_cost(L, pos.a, pos.b, cs.a, cs.b);  // includes the ref :545 map check
   L.fcode[step * L.rstep_stride + local] = static_cast<int16_t>(fc);
 }
@@ -504,15 +537,15 @@ struct k1s_sample {
   double vx_samp, vy_samp, vth_samp;
   bool scored;
 };
-__device__ __forceinline__ k1s_sample k1s_sample_of(const sfw_launch &L, int64_t local) {
+template <bool LIST> __device__ __forceinline__ k1s_sample k1s_sample_of(const sfw_launch &L, int64_t local) {
   k1s_sample q;
   q.local = local;
   q.t = L.chunk_begin + local;
-  const int iv = static_cast<int>(q.t / L.nw), iw = static_cast<int>(q.t % L.nw);
-  q.vx_samp = L.linvels[iv];
-  q.vth_samp = L.angvels[iw];
-  q.vy_samp = L.vy_samp;
-  q.scored = !(L.skip_zero_sample && q.vx_samp == 0.0 && q.vth_samp == 0.0);
+  const sample_cmd cmd = sample_cmd_of<LIST>(L, q.t);
+  q.vx_samp = cmd.vx;
+  q.vth_samp = cmd.vth;
+  q.vy_samp = cmd.vy;
+  q.scored = cmd.scored;
   return q;
 }
 // the sample's status words (one thread)
@@ -590,7 +623,7 @@ __device__ __forceinline__ void k1s_positions(const sfw_launch &L, const k1s_lds
   st.p = p;
 }
 // (4) records, one step per thread: Trajectory points (ref :578) and — for a K2 that reads them from memory — the robot steps
-template <bool TABLE>
+template <bool TABLE, bool LIST = false>
 __device__ __forceinline__ void k1s_records(const sfw_launch &L, const k1s_lds &a, const k1s_sample &q, int S, int tid, int nthr) {
   for (int i = tid; i < S; i += nthr) {
     if (L.points) {
@@ -599,7 +632,7 @@ __device__ __forceinline__ void k1s_records(const sfw_launch &L, const k1s_lds &
       pt[1] = a.ys[i];
       pt[2] = a.th[i];
     }
-    if constexpr (TABLE) put_robot_step(L, q.local, i, a.xs[i + 1], a.ys[i + 1], a.vxs[i], a.vys[i], a.cs[i].x, a.cs[i].y);
+    if constexpr (TABLE) put_robot_step<LIST>(L, q.local, i, a.xs[i + 1], a.ys[i + 1], a.vxs[i], a.vys[i], a.cs[i].x, a.cs[i].y);
   }
 }
 // ... and the pedestrian-free cost terms (one thread): ref :643-666 without the costmap and social terms (left-to-right sum order kept)
@@ -675,13 +708,13 @@ __device__ __forceinline__ bool k1s_scan(const sfw_launch &L, const k1s_lds &a, 
   return scan_finish(L, q.t, q.local, cm, n_ok, base_out, base_in);
 }
 
-__global__ void __launch_bounds__(K1_SMALL_BLOCK) sfw_rollout_small_kernel(const sfw_launch L) {
+template <bool LIST> __global__ void __launch_bounds__(K1_SMALL_BLOCK) sfw_rollout_small_kernel(const sfw_launch L) {
   __shared__ __attribute__((aligned(16))) char k1s_area[8 * K1_SMALL_MAX_STEPS * 3 + 16 * K1_SMALL_MAX_STEPS * 2 +
                                                         8 * (K1_SMALL_MAX_STEPS + 2) * 2 + 4 * K1_SMALL_MAX_STEPS +
                                                         8 * K1_SMALL_MAX_STEPS + 16];
   const int S = L.S;
   const k1s_lds a(k1s_area, K1_SMALL_MAX_STEPS);
-  const k1s_sample q = k1s_sample_of(L, blockIdx.x);
+  const k1s_sample q = k1s_sample_of<LIST>(L, blockIdx.x);
   const int tid = threadIdx.x, nthr = blockDim.x;
   if (tid == 0) k1s_head(L, q);
   k1s_state st = k1s_begin(L, tid);
@@ -691,7 +724,7 @@ __global__ void __launch_bounds__(K1_SMALL_BLOCK) sfw_rollout_small_kernel(const
   __syncthreads();
   k1s_positions(L, a, 0, S, tid, st);
   __syncthreads();
-  k1s_records<true>(L, a, q, S, tid, nthr);
+  k1s_records<true, LIST>(L, a, q, S, tid, nthr);
   if (tid == 0) k1s_base_cost(L, a, q, S);
   if (!q.scored) {
     if (tid == 0 && L.n_points) L.n_points[q.local] = 0;
@@ -2672,11 +2705,13 @@ __device__ __forceinline__ sfw_sel sel_shfl_down(const sfw_sel &a, int off) {
   return r;
 }
 // one sample's cost against the running best of a thread (ref :394-404; see sel_less)
+// LIST (sfw_launch.list): sample t's own pair (linvels[t], angvels[t]) — vx and vtheta of the list; vy takes no part in the order
+template <bool LIST = false>
 __device__ __forceinline__ void sel_consider(sfw_sel &best, double c, const double *linvels, const double *angvels, int nw,
                                              int64_t t, int64_t index_base) {
   if (!(c >= 0.0)) return;
   best.n_valid += 1;
-  const double lin = linvels[t / nw], ang = angvels[t % nw];
+  const double lin = linvels[LIST ? t : t / nw], ang = angvels[LIST ? t : t % nw];
   const bool selectable = c < 10000.0 || (c == 10000.0 && (lin > 0.0 || (lin == 0.0 && ang == 0.0)));
   if (!selectable) return;
   sfw_sel cand;
@@ -2706,6 +2741,7 @@ __device__ __forceinline__ sfw_sel block_reduce(sfw_sel v) {
 // caller-visible pinned buffer `costs_host` (nullable), and the kernel that forms the final record leaves a copy at
 // `sel_host`.  The blocking call then ends with the stream's completion instead of a device-to-host copy behind it (a blit
 // kernel and two dependency gaps: 15 us of cfg2's step, 9 us of a control cycle; profiles/r06_step_timeline_cfg2.txt).
+template <bool LIST>
 __global__ void __launch_bounds__(ARGMIN_BLOCK)
 sfw_argmin_stage1(const double *costs, const double *linvels, const double *angvels, int nw, int64_t T,
                   int64_t index_base, sfw_sel *partials, double *costs_host, sfw_sel *sel_host) {
@@ -2714,7 +2750,7 @@ sfw_argmin_stage1(const double *costs, const double *linvels, const double *angv
        t += static_cast<int64_t>(gridDim.x) * blockDim.x) {
     const double c = costs[t];
     if (costs_host) costs_host[t] = c;
-    sel_consider(best, c, linvels, angvels, nw, t, index_base);
+    sel_consider<LIST>(best, c, linvels, angvels, nw, t, index_base);
   }
   best = block_reduce(best);
   if (threadIdx.x == 0) {
@@ -2741,9 +2777,21 @@ sfw_argmin_stage2(const sfw_sel *partials, int n, sfw_sel *out, sfw_sel *sel_hos
 // launch with those weights; a sentinel sample's terms all hold its sentinel, which is its cost under every weight vector
 // (the distance term of a scored sample is a sum of squares, never negative).
 constexpr int RESCORE_KT = 8;
+// One text for the grid's kernel and the list's (sfw_launch.list).  The sample form is a TYPE, not a bool: a kernel's symbol
+// spells its template arguments out, and the resource check of tests/test_cost_terms_abi.py finds the grid's stage 1 as the
+// one symbol that contains "sfw_rescore_stage1" — so that is the name of the grid form's tag.  (A body shared through a
+// device function compiles the grid's kernel to other code than it always had: arrays of an inlined function get lifetime
+// markers, thread indices read outside a kernel lose the range its launch bounds give them.)
+struct sfw_rescore_stage1 {
+  static constexpr bool list = false;
+};
+struct sfw_rescore_of_list {
+  static constexpr bool list = true;
+};
+template <typename SAMPLES>
 __global__ void __launch_bounds__(ARGMIN_BLOCK)
-sfw_rescore_stage1(const double *terms, int64_t T, const sfw_weights *w, int K, const double *linvels, const double *angvels,
-                   int nw, int64_t index_base, sfw_sel *partials, double *costs, sfw_sel *sel_host) {
+sfw_rescore_first(const double *terms, int64_t T, const sfw_weights *w, int K, const double *linvels, const double *angvels,
+                  int nw, int64_t index_base, sfw_sel *partials, double *costs, sfw_sel *sel_host) {
   typedef const __attribute__((address_space(4))) sfw_weights *weights_ptr;
   const weights_ptr ws = (weights_ptr)w;
   const int k0 = static_cast<int>(blockIdx.y) * RESCORE_KT;
@@ -2762,7 +2810,7 @@ sfw_rescore_stage1(const double *terms, int64_t T, const sfw_weights *w, int K, 
       const int k = min(k0 + j, K - 1);  // (a partial last tile repeats its last vector; nothing of it is stored)
       const double base = sfw_cost_add_costmap(sfw_cost_base(ws[k].vel, vel, ws[k].distance, d, ws[k].angle, ang), ws[k].costmap, cm);
       c[j] = sentinel ? d : sfw_cost_add_social(base, ws[k].social, sw);
-      sel_consider(best[j], c[j], linvels, angvels, nw, t, index_base);
+      sel_consider<SAMPLES::list>(best[j], c[j], linvels, angvels, nw, t, index_base);
     }
     if (costs) {  // (weight-major)
 #pragma unroll
@@ -2895,7 +2943,9 @@ constexpr int CYCLE_HEAD = 8;  // robot steps handed to the pedestrians' wave ah
 // The block of one sample: the body of sfw_cycle_kernel (L = the kernel arguments; sample blockIdx.x of gridDim.x, read where
 // they are used as before — bid / nblk are unused) and of sfw_batch_cycle_kernel (L = the block's member record `Lb` in the batch
 // table; member-local sample `bid` of `nblk`).
-template <typename R, bool GROUPS, bool OBS, bool BATCH>
+// LIST: the samples are a list (sfw_launch.list) — the sample lookup and the selection's (linvel, angvel) lookup are the list's;
+// everything between them is the same text.
+template <typename R, bool GROUPS, bool OBS, bool BATCH, bool LIST>
 __device__ __forceinline__ void cycle_block(const sfw_launch &L, const late_launch Lb, const int k2_bytes, const unsigned bid,
                                             const unsigned nblk) {
   extern __shared__ __attribute__((aligned(16))) char smem[];  // K2 wave's area (from LDS address 0) | k1s_lds | cycle_result
@@ -2917,7 +2967,7 @@ __device__ __forceinline__ void cycle_block(const sfw_launch &L, const late_laun
   // (the hand-over word starts at 0: written by thread 0, and a block barrier before anybody polls or publishes)
   if (tid == 0) res->ready = res->fdone = 0;
   __syncthreads();
-  const k1s_sample q = k1s_sample_of(L, BATCH ? bid : blockIdx.x);
+  const k1s_sample q = k1s_sample_of<LIST>(L, BATCH ? bid : blockIdx.x);
   // pedestrians to integrate?  (no agents at all, or a robot alone without a laser point: social work identically 0)
   const bool social = q.scored && L.A > 0 && !(L.A == 1 && L.O == 0 && L.NG == 0);
   if (wave == 0 && social) {
@@ -3003,7 +3053,7 @@ __device__ __forceinline__ void cycle_block(const sfw_launch &L, const late_laun
     const int64_t ti = L.chunk_begin + i;
     const double c = __builtin_nontemporal_load(L.costs + ti);
     if (L.costs_host) L.costs_host[ti] = c;
-    sel_consider(best, c, L.linvels, L.angvels, L.nw, ti, L.index_base);
+    sel_consider<LIST>(best, c, L.linvels, L.angvels, L.nw, ti, L.index_base);
   }
   for (int off = WAVE / 2; off > 0; off >>= 1) best = sel_merge(best, sel_shfl_down(best, off));
   if (lane == 0) {
@@ -3014,7 +3064,11 @@ __device__ __forceinline__ void cycle_block(const sfw_launch &L, const late_laun
 }
 template <typename R, bool GROUPS, bool OBS>
 __global__ void __launch_bounds__(CYCLE_BLOCK) sfw_cycle_kernel(const sfw_launch L, const int k2_bytes) {
-  cycle_block<R, GROUPS, OBS, false>(L, nullptr, k2_bytes, 0u, 0u);
+  cycle_block<R, GROUPS, OBS, false, false>(L, nullptr, k2_bytes, 0u, 0u);
+}
+template <typename R, bool GROUPS, bool OBS>
+__global__ void __launch_bounds__(CYCLE_BLOCK) sfw_cycle_list_kernel(const sfw_launch L, const int k2_bytes) {
+  cycle_block<R, GROUPS, OBS, false, true>(L, nullptr, k2_bytes, 0u, 0u);
 }
 // Many handles' control cycles in one launch (sfw_batch_*): a 1-D grid over the samples of all members, member m's T_m blocks
 // from first[m] on.  A block finds its member by a binary search over first[] (scalar loads, uniform) and runs the block of
@@ -3036,7 +3090,7 @@ __global__ void __launch_bounds__(CYCLE_BLOCK) sfw_batch_cycle_kernel(const uint
   }
   const rec_ptr r = (rec_ptr)recs + lo;
   const late_launch Lb = (late_launch)&r->L;
-  cycle_block<R, GROUPS, OBS, true>(*(const sfw_launch *)Lb, Lb, r->k2_bytes, b - f[lo], f[lo + 1] - f[lo]);
+  cycle_block<R, GROUPS, OBS, true, false>(*(const sfw_launch *)Lb, Lb, r->k2_bytes, b - f[lo], f[lo + 1] - f[lo]);
 }
 
 }  // namespace
@@ -3203,18 +3257,20 @@ bool sfw_rollout_is_fused(const sfw_launch &L) { return L.chunk_count <= 2048 &&
 hipError_t sfw_launch_rollout_poses(const sfw_launch &L, hipStream_t stream) {
   if (L.chunk_count <= 0) return hipSuccess;
   if (sfw_rollout_is_fused(L)) {  // latency path: one launch does all of K1
-    hipLaunchKernelGGL(sfw_rollout_small_kernel, dim3(static_cast<unsigned>(L.chunk_count)), dim3(K1_SMALL_BLOCK), 0, stream, L);
+    hipLaunchKernelGGL((L.list ? sfw_rollout_small_kernel<true> : sfw_rollout_small_kernel<false>),
+                       dim3(static_cast<unsigned>(L.chunk_count)), dim3(K1_SMALL_BLOCK), 0, stream, L);
     return hipGetLastError();
   }
   const int block = 64;  // latency-bound serial rollout: spread the waves over all CUs
   if (sfw_k1a_threads()) {  // SFW_K1A_THREADS=1: round 1-5's one thread per sample (A/B and the equality test)
     const unsigned grid = static_cast<unsigned>((L.chunk_count + block - 1) / block);
-    hipLaunchKernelGGL(sfw_rollout_kernel, dim3(grid), dim3(block), 0, stream, L);
+    hipLaunchKernelGGL((L.list ? sfw_rollout_kernel<true> : sfw_rollout_kernel<false>), dim3(grid), dim3(block), 0, stream, L);
     return hipGetLastError();
   }
   constexpr int per_wave = WAVE / K1A_TEAM;
   const unsigned grid = static_cast<unsigned>((L.chunk_count + per_wave - 1) / per_wave);
-  hipLaunchKernelGGL(sfw_rollout_team_kernel, dim3(grid), dim3(block), 0, stream, L);
+  hipLaunchKernelGGL((L.list ? sfw_rollout_team_kernel<true> : sfw_rollout_team_kernel<false>), dim3(grid), dim3(block), 0, stream,
+                     L);
   return hipGetLastError();
 }
 
@@ -3225,7 +3281,7 @@ hipError_t sfw_launch_rollout_costmap(const sfw_launch &L, hipStream_t stream) {
     const int block = 256;
     const int64_t n = L.chunk_count * L.S;
     const unsigned grid = static_cast<unsigned>((n + block - 1) / block);
-    hipLaunchKernelGGL(sfw_footprint_kernel, dim3(grid), dim3(block), 0, stream, L);
+    hipLaunchKernelGGL((L.list ? sfw_footprint_kernel<true> : sfw_footprint_kernel<false>), dim3(grid), dim3(block), 0, stream, L);
   }
   {
     const int block = 256;
@@ -3423,14 +3479,15 @@ int64_t sfw_argmin_partials(int64_t T) {
 
 hipError_t sfw_launch_argmin(const double *costs, const double *linvels, const double *angvels, int32_t nw,
                              int64_t T, int64_t index_base, sfw_sel *partials, sfw_sel *out,
-                             hipStream_t stream, double *costs_host, sfw_sel *sel_host) {
+                             hipStream_t stream, double *costs_host, sfw_sel *sel_host, bool list) {
   const int blocks = static_cast<int>(sfw_argmin_partials(T));
+  const auto stage1 = list ? sfw_argmin_stage1<true> : sfw_argmin_stage1<false>;
   if (blocks == 1) {  // the single block's partial is the result
-    hipLaunchKernelGGL(sfw_argmin_stage1, dim3(1), dim3(ARGMIN_BLOCK), 0, stream, costs, linvels, angvels, nw, T,
+    hipLaunchKernelGGL(stage1, dim3(1), dim3(ARGMIN_BLOCK), 0, stream, costs, linvels, angvels, nw, T,
                        index_base, out, costs_host, sel_host);
     return hipGetLastError();
   }
-  hipLaunchKernelGGL(sfw_argmin_stage1, dim3(blocks), dim3(ARGMIN_BLOCK), 0, stream, costs, linvels,
+  hipLaunchKernelGGL(stage1, dim3(blocks), dim3(ARGMIN_BLOCK), 0, stream, costs, linvels,
                      angvels, nw, T, index_base, partials, costs_host, static_cast<sfw_sel *>(nullptr));
   hipLaunchKernelGGL(sfw_argmin_stage2, dim3(1), dim3(ARGMIN_BLOCK), 0, stream, partials, blocks, out, sel_host);
   return hipGetLastError();
@@ -3444,11 +3501,12 @@ int64_t sfw_rescore_blocks(int64_t T, int K) {
 }
 hipError_t sfw_launch_rescore(const double *terms, int64_t T, const sfw_weights *w, int K, const double *linvels,
                               const double *angvels, int32_t nw, int64_t index_base, sfw_sel *partials, double *costs,
-                              sfw_sel *sel_host, hipStream_t stream) {
+                              sfw_sel *sel_host, hipStream_t stream, bool list) {
   if (K < 1 || T < 1) return hipErrorInvalidValue;
   const int64_t blocks = sfw_rescore_blocks(T, K);
   const dim3 grid(static_cast<unsigned>(blocks), static_cast<unsigned>((K + RESCORE_KT - 1) / RESCORE_KT));
-  hipLaunchKernelGGL(sfw_rescore_stage1, grid, dim3(ARGMIN_BLOCK), 0, stream, terms, T, w, K, linvels, angvels, nw, index_base,
+  const auto stage1 = list ? sfw_rescore_first<sfw_rescore_of_list> : sfw_rescore_first<sfw_rescore_stage1>;
+  hipLaunchKernelGGL(stage1, grid, dim3(ARGMIN_BLOCK), 0, stream, terms, T, w, K, linvels, angvels, nw, index_base,
                      partials, costs, blocks == 1 ? sel_host : static_cast<sfw_sel *>(nullptr));
   if (blocks > 1)
     hipLaunchKernelGGL(sfw_rescore_stage2, dim3(static_cast<unsigned>(K)), dim3(ARGMIN_BLOCK), 0, stream, partials,
@@ -3506,6 +3564,12 @@ template <typename R> static hipError_t launch_cycle_typed(const sfw_launch &L_i
   const size_t lds = k2 + k1_bytes + ((sizeof(cycle_result) + 15) & ~size_t(15));
   const dim3 grid(static_cast<unsigned>(L.chunk_count)), block(CYCLE_BLOCK);
   const int k2i = static_cast<int>(k2);
+  if (L.list) {  // (sfw_samples_stage: the same block over the list's sample lookup and selection)
+    if (L.NG > 0) hipLaunchKernelGGL((sfw_cycle_list_kernel<R, true, true>), grid, block, lds, stream, L, k2i);
+    else if (L.O > 0) hipLaunchKernelGGL((sfw_cycle_list_kernel<R, false, true>), grid, block, lds, stream, L, k2i);
+    else hipLaunchKernelGGL((sfw_cycle_list_kernel<R, false, false>), grid, block, lds, stream, L, k2i);
+    return hipGetLastError();
+  }
   if (L.NG > 0) hipLaunchKernelGGL((sfw_cycle_kernel<R, true, true>), grid, block, lds, stream, L, k2i);
   else if (L.O > 0) hipLaunchKernelGGL((sfw_cycle_kernel<R, false, true>), grid, block, lds, stream, L, k2i);
   else hipLaunchKernelGGL((sfw_cycle_kernel<R, false, false>), grid, block, lds, stream, L, k2i);

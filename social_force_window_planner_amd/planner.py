@@ -153,6 +153,9 @@ def lib():
                                               C.POINTER(SfwGoalArgs), C.c_int32, vp, vp, vp, C.POINTER(SfwBest)]
         L.sfw_ensemble_aggregate.argtypes = [vp, C.c_int32, vp, vp, vp, C.POINTER(SfwBest)]
         L.sfw_ensemble_last_us.argtypes = [vp, C.c_int32, C.POINTER(C.c_double)]
+        L.sfw_samples_stage.argtypes = [vp, C.POINTER(SfwRobotState), vp, vp, vp, C.c_int32, C.POINTER(SfwGoalArgs), C.c_int64]
+        L.sfw_score_samples.argtypes = [vp, C.POINTER(SfwRobotState), vp, vp, vp, C.c_int32, C.POINTER(SfwGoalArgs), vp,
+                                        C.POINTER(SfwBest)]
         _lib = L
     return _lib
 
@@ -265,6 +268,39 @@ class HipScorer:
         self._check(lib().sfw_grid_stage(self._h, C.byref(rs), lin.ctypes.data, len(lin), ang.ctypes.data,
                                          len(ang), C.byref(ga), index_base), "sfw_grid_stage")
         self._grid = (len(lin), len(ang))
+
+    # -- sample lists (sfw_samples_stage / sfw_score_samples) ---------------
+    @staticmethod
+    def _sample_list(vx, vtheta, vy):
+        vx, vth = _f64(vx).reshape(-1), _f64(vtheta).reshape(-1)
+        vyv = None if vy is None else _f64(vy).reshape(-1)
+        if len(vth) != len(vx) or (vyv is not None and len(vyv) != len(vx)):
+            raise ValueError("sample list: vx, vy and vtheta must have the same length")
+        return vx, vth, vyv
+
+    def stage_samples(self, robot_state, vx, vtheta, goal_args, vy=None, index_base=0):
+        """Stage a LIST of samples (vx[t], vy[t], vtheta[t]) — vy=None: all 0 — instead of a grid; launch / fetch / plan_info /
+        grid_points_batch / cost_terms / rescore then act on the list, sample index t in list order."""
+        vx, vth, vyv = self._sample_list(vx, vtheta, vy)
+        rs, ga = SfwRobotState(*robot_state), SfwGoalArgs(*goal_args)
+        self._check(lib().sfw_samples_stage(self._h, C.byref(rs), vx.ctypes.data if len(vx) else None,
+                                            vyv.ctypes.data if vyv is not None and len(vyv) else None,
+                                            vth.ctypes.data if len(vth) else None, len(vx), C.byref(ga), index_base),
+                    "sfw_samples_stage")
+        self._grid = (len(vx), 1)
+
+    def score_samples(self, robot_state, vx, vtheta, goal_args, vy=None):
+        """The blocking call over a sample list: (costs[n], best) — best["vy"] is the winner's own vy."""
+        vx, vth, vyv = self._sample_list(vx, vtheta, vy)
+        rs, ga = SfwRobotState(*robot_state), SfwGoalArgs(*goal_args)
+        costs = np.empty(len(vx), dtype=np.float64)
+        best = SfwBest()
+        self._check(lib().sfw_score_samples(self._h, C.byref(rs), vx.ctypes.data if len(vx) else None,
+                                            vyv.ctypes.data if vyv is not None and len(vyv) else None,
+                                            vth.ctypes.data if len(vth) else None, len(vx), C.byref(ga),
+                                            costs.ctypes.data if len(vx) else None, C.byref(best)), "sfw_score_samples")
+        self._grid = (len(vx), 1)
+        return costs, best.as_dict()
 
     def prepared(self, robot_state, linvels, angvels, goal_args, index_base=0, zero_copy=False):
         """The blocking call with its arguments marshalled ONCE (a C caller builds its structs once too): step() is
