@@ -477,6 +477,40 @@ int sfw_grid_rescore(sfw_handle h, const sfw_weights *w, int32_t K, sfw_best *be
  * same conditions as sfw_grid_rescore.  One device-to-host copy per term. */
 int sfw_grid_terms(sfw_handle h, int64_t first, int64_t count, double *terms_out);
 
+/* ---- the predicted crowd behind a score ------------------------------------
+ * For every sample the scorer integrates the whole crowd forward under the social-force model; these two calls hand that
+ * prediction out for ONE sample: where every person is after every step, who does the social work, whose goal has popped.
+ * One wave integrates the sample once more (K1 + a capturing form of the flat K2 + one device-to-host copy of
+ * 16 + 44 * steps * agents bytes); the values are the scoring kernels' own, in all three precision modes.
+ *
+ * The pedestrian prediction behind ONE scoreTrajectory call.  Row i (0 <= i < *n_steps) is the world AFTER Euler step i:
+ *   state[(i*A + a)*4 + 0..3] = x, y, vx, vy of agent a.  a = 0 is the robot as the reference overwrites it after the step
+ *       (ref :600-604): position = Trajectory pose i+1, velocity = the robot-local twist (vx_i, vy_i);
+ *   work[i*A + a]     a = 0: Wr of step i = |social force| + |obstacle force| on the robot at the PRE-step state (ref :681-682);
+ *                     a >= 1: |force the post-step robot alone exerts on person a| (ref :692-699), 0.0 for a person whose id
+ *                     is the robot's.  Summed over a and i these ARE the sample's social-work term (SFW_TERM_SOCIAL); only a
+ *                     person's entry below 1e-140 (SFW_PRECISION_F32: 1e-12), which that sum's norm cannot resolve, is
+ *                     evaluated apart from it, in double;
+ *   has_goal[i*A + a] 1 while person a's goal has not been popped after step i (a = 0: 0).
+ * *n_steps = steps the reference integrates before it returns = the Trajectory point count sfw_score_one reports for the same
+ * call: S for a valid sample, c + 1 for a pedestrian contact at step c (row c is the contact state), j for a footprint that
+ * turns illegal at pose j (fewer if a contact comes first), 0 without agents.  At most steps_cap rows are written;
+ * *n_steps is the full count.  work / has_goal are nullable.  agents must equal the agent count of the world the call
+ * scores (SFW_ERR_INVALID_ARG otherwise, nothing written).  cost_out is bit for bit sfw_score_one's.
+ * SFW_ERR_INVALID_ARG (before any device call): a NULL handle, cost_out, state_xyvv or n_steps, steps_cap < 1, a wrong
+ * `agents`, and whatever sfw_score_one refuses; SFW_ERR_UNSUPPORTED: an agent set that does not fit one wave's LDS.  The
+ * call consumes the staged grid exactly as sfw_score_one does. */
+int sfw_score_one_crowd(sfw_handle h, const sfw_robot_state *rs, double vx_samp, double vy_samp, double vtheta_samp,
+                        const sfw_goal_args *args, double *cost_out, double *state_xyvv, double *work, int32_t *has_goal,
+                        int32_t agents, int32_t steps_cap, int32_t *n_steps);
+/* The same for sample `index` of the staged grid or list (the winner: sfw_best.index), under the state rules of
+ * sfw_grid_points: needs a stage (SFW_ERR_STATE otherwise), works before or after the launch and on batch / ensemble
+ * members after their fetch, read-only for the launch (cost vector, selection, captured points and terms,
+ * sfw_grid_rescore stay valid).  cost_out is nullable here.
+ * The grid loop's skipped (0,0) sample: *n_steps = 0, *cost_out = SFW_COST_SKIPPED. */
+int sfw_grid_crowd(sfw_handle h, int64_t index, double *cost_out, double *state_xyvv, double *work, int32_t *has_goal,
+                   int32_t agents, int32_t steps_cap, int32_t *n_steps);
+
 /* ---- one process, several devices ---------------------------------------
  * The reference plugin is ONE process (sfw_plugin.xml:1-9; computeVelocityCommands,
  * src/sfw_planner_node.cpp:220-331), so a host that wants the (v,w) grid on several

@@ -217,6 +217,8 @@ EXPORTED_SYMBOLS = (
     "sfw_ensemble_last_us",
     "sfw_samples_stage",
     "sfw_score_samples",
+    "sfw_score_one_crowd",
+    "sfw_grid_crowd",
 )
 # per-term costs (sfw_set_terms_capture / sfw_grid_rescore / sfw_grid_terms)
 SFW_TERM_VEL, SFW_TERM_DISTANCE, SFW_TERM_ANGLE, SFW_TERM_COSTMAP, SFW_TERM_SOCIAL = 0, 1, 2, 3, 4

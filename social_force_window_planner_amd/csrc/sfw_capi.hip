@@ -293,6 +293,12 @@ struct sfw_planner_s {
   dev_buf<sfw_sel> rescore_partials;
   dev_buf<double> rescore_costs;
   pinned_buf pin_rescore;          // K records (written by the kernels) | K weight vectors (copied from)
+  // sfw_score_one_crowd / sfw_grid_crowd: cost | n_points | coll_step | state [S][A][4] | work [S][A] | has_goal [S][A],
+  // contiguous -> one D2H into pin_crowd; the pair table of the kernel with run-time plane capacity (sfw_crowd_kernel)
+  dev_buf<char> crowd_out;
+  pinned_buf pin_crowd;
+  dev_buf<uint16_t> crowd_pair_tab;
+  int crowd_pair_tab_A = -1;
 };
 
 namespace {
@@ -1794,6 +1800,9 @@ int destroy_handle(sfw_handle h) {
   h->cells.release();
   h->arena.release();
   h->pair_tab.release();
+  h->crowd_pair_tab.release();
+  h->crowd_out.release();
+  h->pin_crowd.release();
   h->status.release();
   h->coll_step.release();
   h->base_cost.release();
@@ -2494,6 +2503,114 @@ int sfw_grid_points(sfw_handle h, int64_t index, double *points_xyth, int32_t po
 }
 
 void *sfw_stream(sfw_handle h) { return h ? static_cast<void *>(h->stream) : nullptr; }
+
+}  // extern "C"
+
+namespace {
+// Sample t of the stage once more, alone, with the crowd capture: K1 into scratch outputs (the re-run of
+// sfw_grid_points_batch: the launch's results stay intact), then ONE wave of sfw_crowd_kernel reading the K1 table, then one
+// D2H of cost | point count | contact step | rows.  force_alive: a costmap-rejected sample is integrated too and trimmed here
+// to the steps the reference integrates before it returns.
+int crowd_run(sfw_handle h, int64_t t, double *cost_out, double *state_xyvv, double *work, int32_t *has_goal, int32_t steps_cap,
+              int32_t *n_steps) {
+  SFW_HIP(h, hipSetDevice(h->device));
+  if (int e = flush_arena(h)) return e;  // (the kernels below read the device copy of the arena)
+  const int S = num_steps_of(h->live.params), A = h->st.A;
+  // check_lds prices the score path, not the crowd wave's own layout; it covers it because sfw_social_lds_bytes always
+  // includes the flat form at the score path's plane capacity, and the crowd wave runs the same layout at the run-time
+  // capacity (never larger) without the points' LDS copy.  launch_crowd_typed's own limits (160 KiB, 16-bit plane offsets)
+  // therefore never refuse what passed here; if its layout ever outgrows the flat form's, price it here, so that the caller
+  // sees SFW_ERR_UNSUPPORTED and not a HIP error.
+  if (A > 0)
+    if (int e = check_lds(h, A, h->st.O, h->st.NG, h->st.n_grp_mem, 1)) return e;
+  const size_t SA = static_cast<size_t>(S) * static_cast<size_t>(A);
+  const size_t head = 16, o_work = head + sizeof(double) * 4 * SA, o_hg = o_work + sizeof(double) * SA,
+               total = o_hg + sizeof(int32_t) * SA;
+  SFW_HIP(h, h->crowd_out.reserve(total));
+  SFW_HIP(h, h->pts_status.reserve(1));
+  SFW_HIP(h, h->pts_base.reserve(1));
+  SFW_HIP(h, h->pts_ptab.reserve(static_cast<size_t>(S) * static_cast<size_t>(table_row_units(1, h->st.nw))));
+  SFW_HIP(h, h->pts_cs.reserve(static_cast<size_t>(S) * (h->st.list ? size_t(1) : static_cast<size_t>(h->st.nw))));
+  SFW_HIP(h, h->pts_fcode.reserve(static_cast<size_t>(S)));
+  if (A > 0 && h->crowd_pair_tab_A != A) {
+    h->crowd_pair_tab_A = -1;  // (until the table for this count is enqueued)
+    SFW_HIP(h, h->crowd_pair_tab.reserve(static_cast<size_t>(sfw_pair_table_entries(A))));
+    SFW_HIP(h, sfw_launch_pair_table(h->crowd_pair_tab.p, A, h->stream, true));
+    h->crowd_pair_tab_A = A;
+  }
+  char *const out = h->crowd_out.p;
+  sfw_launch L;
+  fill_launch(h, L, t, 1, 1);
+  // (the kernels index per-sample outputs by the global sample index: the pointers are biased by -t)
+  L.status = h->pts_status.p - t;
+  L.base_cost = h->pts_base.p - t;
+  L.costs = reinterpret_cast<double *>(out) - t;
+  L.coll_step = reinterpret_cast<int32_t *>(out + 12) - t;
+  L.n_points = reinterpret_cast<int32_t *>(out + 8);
+  L.ptab = h->pts_ptab.p;
+  L.cs_tab = h->pts_cs.p;
+  L.fcode = h->pts_fcode.p;
+  L.pair_tab = h->crowd_pair_tab.p;
+  L.force_alive = 1;
+  SFW_HIP(h, sfw_launch_rollout(L, h->stream));
+  if (A > 0) {
+    const sfw_crowd_out cw{reinterpret_cast<double *>(out + head), reinterpret_cast<double *>(out + o_work),
+                           reinterpret_cast<int32_t *>(out + o_hg)};
+    SFW_HIP(h, h->live.params.precision == SFW_PRECISION_F64_STRICT ? sfw_launch_crowd_strict(L, cw, h->stream)
+                                                                     : sfw_launch_crowd(L, cw, h->stream));
+  }
+  SFW_HIP(h, h->pin_crowd.reserve(total));
+  SFW_HIP(h, hipMemcpyAsync(h->pin_crowd.p, out, total, hipMemcpyDeviceToHost, h->stream));
+  SFW_HIP(h, hipStreamSynchronize(h->stream));
+  const char *const pin = h->pin_crowd.p;
+  int32_t n = 0, coll = -1;
+  if (cost_out) std::memcpy(cost_out, pin, sizeof(double));
+  std::memcpy(&n, pin + 8, sizeof(n));
+  std::memcpy(&coll, pin + 12, sizeof(coll));
+  if (coll >= 0 && coll + 1 < n) n = coll + 1;  // rejected by contact at step `coll`: steps 0..coll were integrated
+  if (A <= 0) n = 0;                            // nobody to predict
+  *n_steps = n;
+  const size_t m = static_cast<size_t>(n < steps_cap ? n : steps_cap) * static_cast<size_t>(A > 0 ? A : 0);
+  if (m > 0) {
+    std::memcpy(state_xyvv, pin + head, sizeof(double) * 4 * m);
+    if (work) std::memcpy(work, pin + o_work, sizeof(double) * m);
+    if (has_goal) std::memcpy(has_goal, pin + o_hg, sizeof(int32_t) * m);
+  }
+  return SFW_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int sfw_score_one_crowd(sfw_handle h, const sfw_robot_state *rs, double vx_samp, double vy_samp, double vtheta_samp,
+                        const sfw_goal_args *args, double *cost_out, double *state_xyvv, double *work, int32_t *has_goal,
+                        int32_t agents, int32_t steps_cap, int32_t *n_steps) {
+  if (!h) return SFW_ERR_INVALID_ARG;
+  if (!cost_out || !state_xyvv || !n_steps || steps_cap < 1)
+    return fail(h, SFW_ERR_INVALID_ARG, "score_one_crowd: cost_out, state_xyvv or n_steps is NULL, or steps_cap < 1");
+  const agent_set &ag = h->world.agents;  // (checked before the stage: a refused call leaves the staged grid alone)
+  if (agents != ag.A) return fail(h, SFW_ERR_INVALID_ARG, "score_one_crowd: agents is not the agent count of sfw_set_agents");
+  if (int e = check_lds(h, ag.A, ag.O, ag.NG, ag.n_grp_mem, 1)) return e;
+  if (int e = stage_common(h, rs, &vx_samp, 1, &vtheta_samp, 1, args, vy_samp, 0, 0, true)) return e;
+  // past the checks the call consumes its one-sample stage, whatever the outcome (as sfw_score_one)
+  struct consume_stage {
+    sfw_handle h;
+    ~consume_stage() { h->st.valid = false; }
+  } consumed{h};
+  return crowd_run(h, 0, cost_out, state_xyvv, work, has_goal, steps_cap, n_steps);
+}
+
+int sfw_grid_crowd(sfw_handle h, int64_t index, double *cost_out, double *state_xyvv, double *work, int32_t *has_goal,
+                   int32_t agents, int32_t steps_cap, int32_t *n_steps) {
+  if (!h) return SFW_ERR_INVALID_ARG;
+  if (!state_xyvv || !n_steps || steps_cap < 1)
+    return fail(h, SFW_ERR_INVALID_ARG, "grid_crowd: state_xyvv or n_steps is NULL, or steps_cap < 1");
+  if (!h->st.valid) return fail(h, SFW_ERR_STATE, "grid_crowd before grid_stage");
+  const int64_t T = static_cast<int64_t>(h->st.nv) * h->st.nw;
+  if (index < 0 || index >= T) return fail(h, SFW_ERR_INVALID_ARG, "grid_crowd: bad index");
+  if (agents != h->st.A) return fail(h, SFW_ERR_INVALID_ARG, "grid_crowd: agents is not the agent count of the staged world");
+  return crowd_run(h, index, cost_out, state_xyvv, work, has_goal, steps_cap, n_steps);
+}
 
 }  // extern "C"
 

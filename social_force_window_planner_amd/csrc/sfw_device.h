@@ -257,6 +257,16 @@ __device__ __forceinline__ void sfw_put_terms_sentinel(double *terms, int64_t T,
 }
 
 
+// sfw_score_one_crowd / sfw_grid_crowd: where sfw_crowd_kernel leaves the predicted crowd of its one sample.  Row i (step i)
+// holds one entry per agent slot a (0 = the robot): the post-step state (x, y, vx, vy) — 32 bytes, 16-byte aligned —, the
+// slot's work of the step and its goal flag.  A second kernel argument, not a part of sfw_launch: no other kernel's
+// arguments change.
+struct sfw_crowd_out {
+  double *state;      // [S][A][4]
+  double *work;       // [S][A]
+  int32_t *has_goal;  // [S][A]
+};
+
 // Fills L.k from L.p and L.O (host).
 void sfw_derive(sfw_launch &L);
 
@@ -302,7 +312,11 @@ hipError_t sfw_launch_cycle_batch_strict(int variant, const uint32_t *d_first, c
 int64_t sfw_social_flat_items(int A, int O, int NG, int64_t T, int form, int cus);
 hipError_t sfw_launch_social_strict(const sfw_launch &L, hipStream_t stream, const sfw_split_streams *sp = nullptr);
 hipError_t sfw_launch_cycle_strict(const sfw_launch &L, hipStream_t stream);
+hipError_t sfw_launch_crowd_strict(const sfw_launch &L, const sfw_crowd_out &cw, hipStream_t stream);
 #endif
+// One wave integrates the ONE sample of L (chunk_count 1, whole rollout, K1 tables in place) with the crowd capture
+// (sfw_kernels.hip sfw_crowd_kernel).  L.pair_tab must be a table built with runtime_cap (below); L.A >= 1.
+hipError_t sfw_launch_crowd(const sfw_launch &L, const sfw_crowd_out &cw, hipStream_t stream);
 // true when sfw_launch_rollout_poses runs all of K1 in one launch (small grids): the only form that writes L.points
 bool sfw_rollout_is_fused(const sfw_launch &L);
 // Reduces costs[0..T) to one sfw_sel at *out (device memory).  partials must
@@ -330,7 +344,8 @@ hipError_t sfw_launch_ensemble(const double *const *terms, const double *probs, 
 hipError_t sfw_launch_key_table(const sfw_sel *sel, double *table, int r, int R, hipStream_t stream);
 // Pair table of the flat social kernel for A agents: sfw_pair_table_entries(A) uint16 entries.
 int64_t sfw_pair_table_entries(int A);
-hipError_t sfw_launch_pair_table(uint16_t *tab, int A, hipStream_t stream);
+// runtime_cap: the table of the kernel with run-time plane capacity whatever A is (sfw_crowd_kernel); the dummy slots differ
+hipError_t sfw_launch_pair_table(uint16_t *tab, int A, hipStream_t stream, bool runtime_cap = false);
 // Samples handled by one wave of the social kernel for A agents (form: SFW_K2_*).
 // (cus: compute units of the device, sfw_launch.n_cu)
 int sfw_samples_per_wave(int A, int64_t T, int form, int cus);

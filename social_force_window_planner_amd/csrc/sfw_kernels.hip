@@ -920,6 +920,18 @@ __device__ __forceinline__ double fast_norm(double x, double y) {
   return q * rs;
 }
 
+// |(x, y)| without the clamp: the components are brought to [1/2, 1) by the larger one's exponent first, so the squares
+// neither underflow nor overflow.  For the crowd capture's entries, not for a scoring pass (three issues more than fast_norm).
+__device__ __forceinline__ double scaled_norm(double x, double y) {
+  const double m = fmax(fabs(x), fabs(y));
+  if (!(m > 0.0)) return 0.0;
+  const int e = __builtin_amdgcn_frexp_exp(m);
+  const double sx = __builtin_amdgcn_ldexp(x, -e), sy = __builtin_amdgcn_ldexp(y, -e);
+  double rs, sq;
+  sfwm::rsqrt_sqrt(fma(sx, sx, sy * sy), rs, sq);
+  return __builtin_amdgcn_ldexp(sq, e);
+}
+
 // desiredForce of one person (lightsfm computeDesiredForce), double.
 __device__ __forceinline__ void desired_force(const agent_consts &k, double px, double py, double vx, double vy,
                                               bool has_goal, double gx, double gy, double gr, double dv, double &fx,
@@ -1509,6 +1521,25 @@ __device__ __forceinline__ double agent_step(const sfm_consts<R> &k, const agent
   // The robot's own state is overwritten with its post-step record (ref :600-604) by the caller,
   // after this function: here it would keep the record live across the obstacle loop.
   return work;
+}
+
+// The crowd capture's entry for a Wp the scoring pass cannot resolve.  That pass forms |f| as q rsqrt(q + tiny) with
+// q = ev^2 + ea^2 in the force type (pair_force NORM_ONLY): the regulariser takes tiny / 2|f|^2 of the result, and q
+// underflows for |f| < 1e-154 (double) / 1e-19 (float).  No sum can tell (such an addend is 1e-12 of nothing), but an entry
+// handed out on its own is held to the parity tolerance like any other: a Wp below wp_floor_of<R> (where the regulariser's
+// share is 5e-21 / 5e-7; far above, the addend is the entry, bit for bit) is evaluated again here, in double whatever the
+// force type, as the norm of the full force vector with scaled_norm.  What then lies between an entry and the addend of the
+// sum is what the addend lacked: at most 0.3 sqrt(tiny) (3e-16 in float, at |f|^2 = tiny) below sqrt(tiny / rtol), and the
+// force type's error (1e-5 of at most 1e-12) above it.
+template <typename R> struct wp_floor_of;
+template <> struct wp_floor_of<double> { static constexpr double v = 1e-140; };
+template <> struct wp_floor_of<float> { static constexpr double v = 1e-12; };
+__device__ __forceinline__ double small_wp(const sfwm::poly_consts &pc, late_launch La, const sfw_robot_step &rs, double px,
+                                           double py, double vx, double vy) {
+  sfm_consts<double> kd{pc, La->k.d.lambda, La->k.d.neg_l2e_inv_gamma, La->k.d.l2_f_social, La->k.d.c_vel, La->k.d.c_ang};
+  double fx, fy;
+  pair_force_state<double, false>(kd, px, py, vx, vy, rs.x, rs.y, rs.vx, rs.vy, fx, fy);
+  return scaled_norm(fx, fy);
 }
 
 // Work items of a K2 launch: samples of the chunk (whole rollout, suffix phase) or classes of one
@@ -2136,11 +2167,15 @@ __device__ __forceinline__ int cycle_wait_ready(const cycle_result *res, int nee
 }
 #define K2_SYNC() do { if constexpr (CYCLE) wave_sync(); else __syncthreads(); } while (0)
 // BATCH (CYCLE only): the wave of a batched cycle launch; `Lb` is its member's record (L, read late), no clock probe
-template <typename R, bool GROUPS, int CAP, bool OBS, bool CYCLE, bool BATCH = false>
+// CAPTURE (sfw_crowd_kernel only): every step also leaves each agent slot's post-step state, work and goal flag in `cw`
+// (sfw_crowd_out, rows of A slots per step) — the predicted crowd behind the sample's score.  Every use is under
+// if constexpr: the other instantiations are the code they were.
+template <typename R, bool GROUPS, int CAP, bool OBS, bool CYCLE, bool BATCH = false, bool CAPTURE = false>
 __device__ __forceinline__ void social_flat_wave(const sfw_launch &L, char *const smem, const k1s_lds *const k1, cycle_result *const res,
                                                  const unsigned bid, const unsigned nblk, const int64_t item_base,
-                                                 const late_launch Lb = nullptr) {
+                                                 const late_launch Lb = nullptr, const sfw_crowd_out cw = sfw_crowd_out{}) {
   static_assert(CYCLE || !BATCH, "a batched wave is a cycle kernel's wave");
+  static_assert(!CAPTURE || (!CYCLE && !BATCH), "the crowd capture runs as a kernel of its own");
   const int lane = threadIdx.x;
   const int A = L.A, O = L.O;
   const int NG = GROUPS ? L.NG : 0;
@@ -2451,6 +2486,16 @@ __device__ __forceinline__ void social_flat_wave(const sfw_launch &L, char *cons
         vx = rs.vx;
         vy = rs.vy;
       }
+      if constexpr (CAPTURE) {  // the slot's row entry (the robot's work with laser points: behind their pass)
+        const size_t o = static_cast<size_t>(step) * static_cast<size_t>(A) + static_cast<size_t>(sl);
+        double2 *const st = reinterpret_cast<double2 *>(cw.state) + 2 * o;
+        st[0] = double2{px, py};
+        st[1] = double2{vx, vy};
+        double we = w;  // the addend, but for a Wp under the scoring norm's resolution (small_wp)
+        if (sl != 0 && ak.id != c.robot_id && w < wp_floor_of<R>::v) we = small_wp(k.pc, La, rs, px, py, vx, vy);
+        if (!(sl == 0 && with_obs)) cw.work[o] = we;
+        cw.has_goal[o] = sl == 0 ? 0 : hg;
+      }
       if (!(sl == 0 && with_obs)) {  // with laser points the robot keeps its pre-step position until their pass is done
         s.px[sl] = px;
         s.py[sl] = py;
@@ -2562,7 +2607,11 @@ __device__ __forceinline__ void social_flat_wave(const sfw_launch &L, char *cons
                   // the robot's Wr needs both components: lane 1 (y) hands its to lane 0 (x) — a swap inside the quad
                   const double f_other = swap_pair(f);
                   if (a != 0) *acc = fma(static_cast<double>(t), sc, acc0);
-                  else if (comp == 0) s.swp[0] += wr0 + fast_norm(f, f_other);
+                  else if (comp == 0) {
+                    const double wr = wr0 + fast_norm(f, f_other);
+                    s.swp[0] += wr;
+                    if constexpr (CAPTURE) cw.work[static_cast<size_t>(step) * static_cast<size_t>(A)] = wr;
+                  }
                 }
                 K2_SYNC();
               }
@@ -2579,7 +2628,9 @@ __device__ __forceinline__ void social_flat_wave(const sfw_launch &L, char *cons
           double tx, ty, sc;
           obstacle_sums<R, SFW_FLAT_PIPELINED>(k, c, obs_global(c.obstacles), s.px[a], s.py[a], rad, tx, ty, sc);
           if (a == 0) {
-            s.swp[0] += s.wr[0] + fast_norm(tx * sc, ty * sc);
+            const double wr = s.wr[0] + fast_norm(tx * sc, ty * sc);
+            s.swp[0] += wr;
+            if constexpr (CAPTURE) cw.work[static_cast<size_t>(step) * static_cast<size_t>(A)] = wr;
           } else {
             s.fcx[a] = fma(tx, sc, s.fcx[a]);
             s.fcy[a] = fma(ty, sc, s.fcy[a]);
@@ -2602,6 +2653,8 @@ __device__ __forceinline__ void social_flat_wave(const sfw_launch &L, char *cons
             s.fcy[0] += pin[3];
           } else {
             s.swp[sl] += pin[4 + sl];
+            // (the entry this lane wrote in the agent pass above)
+            if constexpr (CAPTURE) cw.work[static_cast<size_t>(step) * static_cast<size_t>(A) + static_cast<size_t>(sl)] += pin[4 + sl];
           }
         }
     }
@@ -2646,6 +2699,15 @@ __global__ void __launch_bounds__(WAVE, (GROUPS || CAP == 0) ? 1 : OBS ? SFW_FLA
   extern __shared__ __attribute__((aligned(16))) char smem[];
   (void)G_unused;
   social_flat_wave<R, GROUPS, CAP, OBS, false>(L, smem, nullptr, nullptr, blockIdx.x, gridDim.x, L.item_base);
+}
+// sfw_score_one_crowd / sfw_grid_crowd: ONE wave integrates one sample as the flat form does and leaves every step's row of
+// agent slots in `cw`.  The run-time capacity with the laser-point pass serves every crowd (O == 0 included); it runs on a
+// pair table built for that capacity (sfw_launch_pair_table, runtime_cap).  One wave per call.
+template <typename R, bool GROUPS>
+__global__ void __launch_bounds__(WAVE, 1) sfw_crowd_kernel(const sfw_launch L, const sfw_crowd_out cw) {
+  sfwm::fp_mode_for_omod();
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  social_flat_wave<R, GROUPS, 0, true, false, false, true>(L, smem, nullptr, nullptr, blockIdx.x, gridDim.x, 0, nullptr, cw);
 }
 // Both forms in ONE launch (split_point: a register-form launch whose waves do not divide evenly over the SIMDs hands its last
 // items to flat-form waves): the first n_reg blocks run the register form's body on the first `keep` items, the others the flat
@@ -3238,9 +3300,10 @@ int64_t sfw_pair_table_entries(int A) {
   return 2 * (n > 0 ? n : WAVE);
 }
 
-hipError_t sfw_launch_pair_table(uint16_t *tab, int A, hipStream_t stream) {
+hipError_t sfw_launch_pair_table(uint16_t *tab, int A, hipStream_t stream, bool runtime_cap) {
   const int n = static_cast<int>(sfw_pair_table_entries(A) / 2);
-  const int cap = flat_cap(A) > 0 ? flat_cap(A) : flat_cap_runtime(A);  // the capacity the flat kernel will run with
+  // the capacity the flat kernel will run with (runtime_cap: sfw_crowd_kernel's, whatever the agent count)
+  const int cap = (!runtime_cap && flat_cap(A) > 0) ? flat_cap(A) : flat_cap_runtime(A);
   hipLaunchKernelGGL(sfw_pair_table_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, tab, A, n, cap - A);
   return hipGetLastError();
 }
@@ -3462,6 +3525,34 @@ hipError_t sfw_launch_social(const sfw_launch &L, hipStream_t stream, const sfw_
   if (L.p.precision == SFW_PRECISION_F32) return launch_social_typed<float>(L, stream, sp);
 #endif
   return launch_social_typed<double>(L, stream, sp);
+}
+
+// One wave over the one sample of L (a WHOLE-phase launch of chunk_count 1) with the crowd capture; L.pair_tab is a table
+// for the run-time capacity.
+template <typename R> static hipError_t launch_crowd_typed(const sfw_launch &L_in, const sfw_crowd_out &cw, hipStream_t stream) {
+  sfw_launch L = L_in;
+  L.k.obs_lds = 0;  // the points through global memory
+  L.item_base = 0;
+  const bool groups = L.NG > 0;
+  const size_t lds = lds_layout(nullptr, L.A, flat_cap_runtime(L.A), L.A, 1, L.O, L.NG, L.n_grp_mem, groups, true, false).bytes;
+  if (lds > 160 * 1024 || 8 * (static_cast<int64_t>(L.A) + 1) > 65535 || !L.pair_tab) return hipErrorInvalidValue;
+  if (L.chunk_count != 1 || L.phase != SFW_PHASE_WHOLE || L.resume || !cw.state || !cw.work || !cw.has_goal) return hipErrorInvalidValue;
+  auto kernel = groups ? sfw_crowd_kernel<R, true> : sfw_crowd_kernel<R, false>;
+  if (lds > 64 * 1024) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       static_cast<int>(lds));
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(kernel, dim3(1), dim3(WAVE), lds, stream, L, cw);
+  return hipGetLastError();
+}
+
+hipError_t sfw_launch_crowd(const sfw_launch &L, const sfw_crowd_out &cw, hipStream_t stream) {
+  if (L.A <= 0) return hipErrorInvalidValue;
+#ifndef SFW_STRICT_BUILD  // (the strict build of this file holds the f64 kernels only)
+  if (L.p.precision == SFW_PRECISION_F32) return launch_crowd_typed<float>(L, cw, stream);
+#endif
+  return launch_crowd_typed<double>(L, cw, stream);
 }
 
 hipError_t sfw_launch_key_table(const sfw_sel *sel, double *table, int r, int R, hipStream_t stream) {

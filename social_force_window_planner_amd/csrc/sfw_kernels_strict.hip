@@ -3,14 +3,16 @@
 // this build differs by one degree of the angle's polynomial only.  Same source, compiled a second time: the degrees are
 // compile-time constants of the Horner chains (an issue slot each), so the choice between the two is a choice between two
 // sets of kernels, made per launch by sfw_capi.hip.  Every external symbol of sfw_kernels.hip is renamed for this
-// translation unit; only sfw_launch_social_strict, sfw_launch_cycle_strict and sfw_launch_cycle_batch_strict are used (the
-// pose rollout, the footprint check and the selection do not evaluate a polynomial and exist once).
+// translation unit; only sfw_launch_social_strict, sfw_launch_cycle_strict, sfw_launch_cycle_batch_strict and
+// sfw_launch_crowd_strict are used (the pose rollout, the footprint check and the selection do not evaluate a polynomial
+// and exist once).
 #define SFW_STRICT_BUILD 1
 #define SFW_ASIN_DEG 8
 #define SFW_EXP_DEG 9
 #define sfw_launch_social sfw_launch_social_strict
 #define sfw_launch_cycle sfw_launch_cycle_strict
 #define sfw_launch_cycle_batch sfw_launch_cycle_batch_strict
+#define sfw_launch_crowd sfw_launch_crowd_strict
 #define sfw_cycle_batch_variant sfw_strict_unused_cycle_batch_variant
 #define sfw_cycle_batch_record sfw_strict_unused_cycle_batch_record
 #define sfw_cycle_applies sfw_strict_unused_cycle_applies

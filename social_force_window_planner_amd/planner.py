@@ -156,6 +156,11 @@ def lib():
         L.sfw_samples_stage.argtypes = [vp, C.POINTER(SfwRobotState), vp, vp, vp, C.c_int32, C.POINTER(SfwGoalArgs), C.c_int64]
         L.sfw_score_samples.argtypes = [vp, C.POINTER(SfwRobotState), vp, vp, vp, C.c_int32, C.POINTER(SfwGoalArgs), vp,
                                         C.POINTER(SfwBest)]
+        L.sfw_score_one_crowd.argtypes = [vp, C.POINTER(SfwRobotState), C.c_double, C.c_double, C.c_double,
+                                          C.POINTER(SfwGoalArgs), C.POINTER(C.c_double), vp, vp, vp, C.c_int32, C.c_int32,
+                                          C.POINTER(C.c_int32)]
+        L.sfw_grid_crowd.argtypes = [vp, C.c_int64, C.POINTER(C.c_double), vp, vp, vp, C.c_int32, C.c_int32,
+                                     C.POINTER(C.c_int32)]
         _lib = L
     return _lib
 
@@ -182,6 +187,13 @@ class HipScorer:
         if rc != SFW_OK:
             raise SfwError(rc, "sfw_create")
         self._grid = None
+        self._n_agents = self._n_staged_agents = 0  # as handed over last / as the last stage uploaded them
+
+    def _mark_staged(self, grid):
+        """Every stage, by whatever call, ends here: the grid's shape and the agent count that stage uploaded (what
+        grid_crowd sizes its rows by) are recorded in this one place."""
+        self._grid = grid
+        self._n_staged_agents = self._n_agents
 
     @classmethod
     def _member_view(cls, handle, params, owner):
@@ -190,6 +202,7 @@ class HipScorer:
         v.params = params
         v._h = C.c_void_p(handle)
         v._grid = None
+        v._n_agents = v._n_staged_agents = 0
         v._owner = owner  # (keeps the owner, and so the handle, alive as long as the view)
         return v
 
@@ -232,6 +245,7 @@ class HipScorer:
         obs = _f64(obstacles if obstacles is not None else np.zeros((0, 2))).reshape(-1, 2)
         self._check(lib().sfw_set_agents(self._h, C.addressof(agents) if n else None, n,
                                          obs.ctypes.data if len(obs) else None, len(obs)), "sfw_set_agents")
+        self._n_agents = n
 
     def load_scene(self, scene):
         self.set_costmap(scene.cells, scene.origin_x, scene.origin_y, scene.resolution)
@@ -247,7 +261,7 @@ class HipScorer:
         self._check(lib().sfw_score_grid(self._h, C.byref(rs), lin.ctypes.data, len(lin), ang.ctypes.data,
                                          len(ang), C.byref(ga), costs.ctypes.data, C.byref(best)),
                     "sfw_score_grid")
-        self._grid = (len(lin), len(ang))
+        self._mark_staged((len(lin), len(ang)))
         return costs, best.as_dict()
 
     def score_one(self, robot_state, vx_samp, vy_samp, vth_samp, goal_args, points_cap=4096):
@@ -267,7 +281,7 @@ class HipScorer:
         rs, ga = SfwRobotState(*robot_state), SfwGoalArgs(*goal_args)
         self._check(lib().sfw_grid_stage(self._h, C.byref(rs), lin.ctypes.data, len(lin), ang.ctypes.data,
                                          len(ang), C.byref(ga), index_base), "sfw_grid_stage")
-        self._grid = (len(lin), len(ang))
+        self._mark_staged((len(lin), len(ang)))
 
     # -- sample lists (sfw_samples_stage / sfw_score_samples) ---------------
     @staticmethod
@@ -287,7 +301,7 @@ class HipScorer:
                                             vyv.ctypes.data if vyv is not None and len(vyv) else None,
                                             vth.ctypes.data if len(vth) else None, len(vx), C.byref(ga), index_base),
                     "sfw_samples_stage")
-        self._grid = (len(vx), 1)
+        self._mark_staged((len(vx), 1))
 
     def score_samples(self, robot_state, vx, vtheta, goal_args, vy=None):
         """The blocking call over a sample list: (costs[n], best) — best["vy"] is the winner's own vy."""
@@ -299,7 +313,7 @@ class HipScorer:
                                             vyv.ctypes.data if vyv is not None and len(vyv) else None,
                                             vth.ctypes.data if len(vth) else None, len(vx), C.byref(ga),
                                             costs.ctypes.data if len(vx) else None, C.byref(best)), "sfw_score_samples")
-        self._grid = (len(vx), 1)
+        self._mark_staged((len(vx), 1))
         return costs, best.as_dict()
 
     def prepared(self, robot_state, linvels, angvels, goal_args, index_base=0, zero_copy=False):
@@ -384,6 +398,47 @@ class HipScorer:
         self._check(lib().sfw_grid_points(self._h, index, pts.ctypes.data, points_cap, C.byref(n)),
                     "sfw_grid_points")
         return pts[: min(n.value, points_cap)].copy()
+
+    # -- the predicted crowd behind a score ----------------------------------
+    def _num_steps(self):
+        n = int(self.params.sim_time / self.params.sim_granularity + 0.5)  # ref :519-525
+        return n if n != 0 else 1
+
+    @staticmethod
+    def _crowd_buffers(cap, A):
+        """(rows of A slots, at least one byte each: the library refuses a NULL state buffer)"""
+        n = max(cap, 1) * max(A, 1)
+        return (np.zeros(4 * n, dtype=np.float64)[: 4 * max(cap, 1) * A].reshape(max(cap, 1), A, 4),
+                np.zeros(n, dtype=np.float64)[: max(cap, 1) * A].reshape(max(cap, 1), A),
+                np.zeros(n, dtype=np.int32)[: max(cap, 1) * A].reshape(max(cap, 1), A))
+
+    @staticmethod
+    def _crowd_dict(cost, n, state, work, has_goal):
+        m = min(n, state.shape[0])
+        return {"cost": cost, "n_steps": n, "state": state[:m].copy(), "work": work[:m].copy(), "has_goal": has_goal[:m].copy()}
+
+    def score_one_crowd(self, robot_state, vx_samp, vy_samp, vth_samp, goal_args, steps_cap=None):
+        """sfw_score_one_crowd: one scoreTrajectory call and the pedestrian prediction behind it, as
+        dict(cost, n_steps, state[n, A, 4], work[n, A], has_goal[n, A]) — row i is the world after step i, agent 0 the robot."""
+        rs, ga = SfwRobotState(*robot_state), SfwGoalArgs(*goal_args)
+        A, cap = self._n_agents, steps_cap if steps_cap is not None else self._num_steps()
+        state, work, hg = self._crowd_buffers(cap, A)
+        cost, n = C.c_double(), C.c_int32()
+        self._check(lib().sfw_score_one_crowd(self._h, C.byref(rs), vx_samp, vy_samp, vth_samp, C.byref(ga), C.byref(cost),
+                                              state.ctypes.data, work.ctypes.data, hg.ctypes.data, A, cap, C.byref(n)),
+                    "sfw_score_one_crowd")
+        self._grid = None
+        return self._crowd_dict(cost.value, n.value, state, work, hg)
+
+    def grid_crowd(self, index, steps_cap=None):
+        """sfw_grid_crowd: the same for sample `index` of the staged grid or list (the winner: best["index"]); read-only for
+        the launch."""
+        A, cap = self._n_staged_agents, steps_cap if steps_cap is not None else self._num_steps()
+        state, work, hg = self._crowd_buffers(cap, A)
+        cost, n = C.c_double(), C.c_int32()
+        self._check(lib().sfw_grid_crowd(self._h, index, C.byref(cost), state.ctypes.data, work.ctypes.data, hg.ctypes.data,
+                                         A, cap, C.byref(n)), "sfw_grid_crowd")
+        return self._crowd_dict(cost.value, n.value, state, work, hg)
 
     # -- per-term costs ------------------------------------------------------
     def set_terms_capture(self, enabled=True):
@@ -470,7 +525,7 @@ class PreparedGrid:
                             C.byref(self.ga), index_base)
         self._fetch_args = (scorer._h, self.costs.ctypes.data, C.byref(self.best), C.byref(self.key))
         self._fetch_args_nocost = (scorer._h, None, C.byref(self.best), C.byref(self.key))
-        scorer._grid = (len(self.lin), len(self.ang))
+        scorer._mark_staged((len(self.lin), len(self.ang)))
         self.zero_copy = zero_copy
         self._view, self._view_ptr, self._view_arr = L.sfw_grid_costs_view, None, None
 
@@ -666,7 +721,7 @@ class BatchScorer:
         self._check(lib().sfw_batch_score_grid(self._b, rs, lin.ctypes.data, len(lin), ang.ctypes.data, len(ang), ga, best),
                     "sfw_batch_score_grid")
         for m in self._members:
-            m._grid = (len(lin), len(ang))
+            m._mark_staged((len(lin), len(ang)))
         return [(self._costs(i), best[i].as_dict()) for i in range(self.B)]
 
     def describe(self):
@@ -750,6 +805,7 @@ class EnsembleScorer:
         self._check(lib().sfw_ensemble_set_hypothesis(self._e, m, C.addressof(agents) if n else None, n,
                                                       obs.ctypes.data if len(obs) else None, len(obs)),
                     "sfw_ensemble_set_hypothesis")
+        self._members[m]._n_agents = n
 
     def load_scene(self, scene, hypotheses):
         """The scene's costmap and footprint, and hypotheses[m] = agents or (agents, obstacles) for every member (plain
@@ -788,7 +844,7 @@ class EnsembleScorer:
                                                   costs.ctypes.data, rejected.ctypes.data, C.byref(best)),
                     "sfw_ensemble_score_grid")
         for m in self._members:
-            m._grid = self._grid
+            m._mark_staged(self._grid)
         return costs, rejected, best.as_dict()
 
     def aggregate(self, mode="mean", probs=None):
