@@ -320,6 +320,80 @@ int sfw_score_samples(sfw_handle h, const sfw_robot_state *rs, const double *vx,
                       const double *vtheta, int32_t n, const sfw_goal_args *args, double *costs_out,
                       sfw_best *best_out);
 
+/* Command SEQUENCES: samples whose command changes inside the horizon
+ * ("brake for 0.3 s, then swing left", last cycle's plan with a varied tail,
+ * the rollouts of a sampling MPC / MPPI controller).  A sample is K knots;
+ * vx, vy (nullable: all 0.0) and vtheta hold K x n doubles, KNOT-major: knot
+ * k of sample t at [k * n + t].  knot_step[K] is shared by all samples:
+ * knot_step[0] == 0, strictly ascending.  At Euler step i the three targets
+ * of computeNewVelocity are those of knot k(i), the largest k with
+ * knot_step[k] <= i.  Everything else is the reference's scoreTrajectory
+ * statement by statement: the acceleration clip runs from the running
+ * velocity every step, Euler integrates with the old heading, the velocity
+ * term reads the last step's vx, distance and angle come from the final
+ * pose, costmap mean, pedestrian contact and social work as in the
+ * reference.  A knot whose step is >= the step count is never reached and is
+ * no error (sfw_set_params may change the step count between stage and
+ * launch; the knots are looked up by the kernels as the steps go by).
+ *
+ * Contract (tests/test_sequences_gpu.py holds each point):
+ *  1. K == 1 is sfw_samples_stage: costs, sentinels, selection, terms, points
+ *     and crowd are bit-identical (the list's kernels run).
+ *  2. A sequence whose knots all carry the same command has bit for bit the
+ *     cost of that command in a list, whatever knot_step is.
+ *  3. Cutting the knots at the horizon changes nothing: the knots at steps
+ *     >= S may be removed.
+ *  4. Causality: two samples whose knots agree up to the knot active at step
+ *     j have bit-identical Trajectory points 0..j+1 and crowd rows 0..j.
+ *  5. A sample's result does not depend on where it stands in the stage or
+ *     what stands beside it, on whether the one-launch kernel scored it
+ *     (SFW_CYCLE_FUSED), on how the stage is chunked (SFW_TABLE_BUDGET_MB), or
+ *     on which pose-rollout kernel walked it.
+ *  6. Costs are never SFW_COST_SKIPPED and never NaN; SFW_COST_INVALID
+ *     appears exactly where the reference would return -1.0.
+ *
+ * Selection: the reference's rule with linvel = vx[0 * n + t] and angvel =
+ * vtheta[0 * n + t] — the FIRST knot is the command the controller sends
+ * now.  sfw_best.vx / .vy / .vtheta are the winner's first knot, index = t,
+ * sfw_best_key.neg_index = -(index_base + t).
+ *
+ * After a sequence stage everything that acts on a staged list acts on the
+ * sequences in sample order: sfw_grid_launch / _sync / _fetch / _costs_view /
+ * _plan_info, sfw_grid_points(_batch), sfw_set_points_capture,
+ * sfw_set_terms_capture, sfw_grid_terms, sfw_grid_rescore, sfw_grid_crowd,
+ * sfw_set_timing, sfw_last_launch_ms.  Grid, list and sequence stages replace
+ * one another; sfw_score_one consumes any of them.  All-or-nothing as for
+ * every stage: a call refused for its arguments changes nothing, any other
+ * failure leaves nothing staged.
+ *
+ * SFW_ERR_INVALID_ARG (before any device call): n < 1; K < 1 or K >
+ * SFW_SEQ_MAX_KNOTS; a NULL h, rs, vx, vtheta, knot_step or args;
+ * knot_step[0] != 0 or knot_step not strictly ascending; a non-finite value
+ * in any knot, in rs or in args.  SFW_ERR_STATE: no costmap.
+ *
+ * sfw_plan_info reports what a list reports (no shared prefix, one_launch
+ * under the list's conditions).  rest_noise_unreproduced is set when a person
+ * is pinned (desired_velocity == 0), there are at least two agents, and for
+ * some sample the velocity recurrence over its knots REACHES translation
+ * velocity (0, 0) after a step i < S - 1 having been non-zero at hand-over or
+ * after an earlier step.  A robot that stands from hand-over and starts to
+ * move at a later knot is at rest at the handed-over pose only: reproduced,
+ * flag 0.
+ *
+ * A member of a sfw_batch may be staged with sequences: it takes its own
+ * path (sfw_batch_desc.own_path_members), bit-identical to its own launch.
+ * sfw_batch_score_grid, sfw_ensemble_* and sfw_multi_* keep taking grids
+ * only.
+ */
+#define SFW_SEQ_MAX_KNOTS 64
+int sfw_sequences_stage(sfw_handle h, const sfw_robot_state *rs, const double *vx, const double *vy,
+                        const double *vtheta, int32_t n, int32_t K, const int32_t *knot_step,
+                        const sfw_goal_args *args, int64_t index_base);
+/* sfw_sequences_stage (index_base 0) + sfw_grid_launch + sfw_grid_fetch: costs_out (nullable) receives n costs. */
+int sfw_score_sequences(sfw_handle h, const sfw_robot_state *rs, const double *vx, const double *vy,
+                        const double *vtheta, int32_t n, int32_t K, const int32_t *knot_step,
+                        const sfw_goal_args *args, double *costs_out, sfw_best *best_out);
+
 /* How the staged grid will be launched.  levels > 0: the shared-prefix
  * rollout is in use — under the acceleration limits (sfw_planner.hpp:457-463)
  * the robot's first steps are bit-identical for all samples of a class (same

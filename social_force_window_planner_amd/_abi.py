@@ -217,6 +217,8 @@ EXPORTED_SYMBOLS = (
     "sfw_ensemble_last_us",
     "sfw_samples_stage",
     "sfw_score_samples",
+    "sfw_sequences_stage",
+    "sfw_score_sequences",
     "sfw_score_one_crowd",
     "sfw_grid_crowd",
 )

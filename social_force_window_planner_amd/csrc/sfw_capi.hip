@@ -187,6 +187,12 @@ struct sfw_planner_s {
     // no shared-prefix plan is made, and the cos / sin table holds a unit per sample of a chunk (sfw_device.h sfw_launch.list)
     bool list = false;
     std::vector<double> vy;
+    // sfw_sequences_stage: a list whose commands change inside the horizon.  lin / vy / ang then hold nk rows of nv values,
+    // knot-major (row 0 = the first knot: what a list's vectors are to the selection and to sel_to_best); knot_step the nk
+    // steps at which a knot takes over.  nk == 1: a plain list.
+    int nk = 1;
+    std::vector<int32_t> knot_step;
+    const int32_t *d_knot_step = nullptr;
     // the world as uploaded (sfw_set_* after a stage take effect at the next stage; a launch in between must keep
     // describing the device copy)
     int K = 0, A = 0, O = 0, NG = 0, n_grp_mem = 0;
@@ -419,6 +425,9 @@ void fill_launch(sfw_handle h, sfw_launch &L, int64_t begin, int64_t count, int6
   L.nw = h->st.nw;
   L.vy_samps = h->st.d_vy;
   L.list = h->st.list ? 1 : 0;
+  L.n_knots = h->st.nk;
+  L.knot_step = h->st.d_knot_step;
+  L.knot_stride = h->st.nv;  // (a chunk's knot rows are addressed with the whole stage's stride: the kernels index them by the global sample)
   L.chunk_begin = begin;
   L.chunk_count = count;
   L.cells = h->st.d_cells;
@@ -1022,6 +1031,33 @@ bool pinned_rest_table(const sfw_params &p, const sfw_robot_state &rs, const dou
 // §10): a person that can never move next to a robot that moves now and brakes to a stop inside some sample's rollout.
 // Decided from what the stage uploaded, with the device's own velocity recurrence (plain IEEE operations).
 bool rest_noise_unreproduced(sfw_handle h) {
+  if (h->st.valid && h->st.nk > 1) {
+    // Sequences: a sample can come to rest behind a knot, or start to move at one.  The host walks every sample's own
+    // recurrence over the knots — only when a person is pinned — and flags a translation velocity that REACHES (0, 0) after a
+    // step i < S - 1 having been non-zero at hand-over or after an earlier step.  A robot that stands from hand-over and starts
+    // to move at a later knot is at rest only at the handed-over pose, which the pinned-rest table covers step by step.
+    if (h->st.A < 2 || !h->st.person_pinned) return false;
+    const int S = num_steps_of(h->live.params);
+    const double dt = h->live.params.sim_time / S;
+    const size_t n = static_cast<size_t>(h->st.nv);
+    for (size_t t = 0; t < n; ++t) {
+      double vx = h->st.rs.vx, vy = h->st.rs.vy;
+      bool moved = vx != 0.0 || vy != 0.0;
+      int k = 0;
+      for (int i = 0; i + 1 < S; ++i) {
+        if (k + 1 < h->st.nk && h->st.knot_step[static_cast<size_t>(k) + 1] == i) ++k;
+        const size_t at = static_cast<size_t>(k) * n + t;
+        vx = new_velocity_host(h->st.lin[at], vx, h->st.ga.acc_x, dt);
+        vy = new_velocity_host(h->st.vy.empty() ? 0.0 : h->st.vy[at], vy, h->st.ga.acc_y, dt);
+        if (vx == 0.0 && vy == 0.0) {
+          if (moved) return true;
+        } else {
+          moved = true;
+        }
+      }
+    }
+    return false;
+  }
   if (!h->st.valid || h->st.A < 2 || (h->st.rs.vx == 0.0 && h->st.rs.vy == 0.0)) return false;  // (standing from the start: reproduced)
   if (!h->st.person_pinned || h->st.vy_samp != 0.0) return false;
   bool zero_row = false;
@@ -1095,6 +1131,8 @@ int plan_tables_device(sfw_handle h, int64_t chunk, bool may_start_poses) {
         L.linvels = reinterpret_cast<const double *>(h->pin_arena.p + (reinterpret_cast<const char *>(h->st.d_linvels) - h->arena.p));
         L.angvels = reinterpret_cast<const double *>(h->pin_arena.p + (reinterpret_cast<const char *>(h->st.d_angvels) - h->arena.p));
         if (h->st.d_vy) L.vy_samps = reinterpret_cast<const double *>(h->pin_arena.p + (reinterpret_cast<const char *>(h->st.d_vy) - h->arena.p));
+        if (h->st.d_knot_step)
+          L.knot_step = reinterpret_cast<const int32_t *>(h->pin_arena.p + (reinterpret_cast<const char *>(h->st.d_knot_step) - h->arena.p));
       }
       SFW_HIP(h, sfw_launch_rollout_poses(L, h->stream));
       if (h->st.arena_pending) {
@@ -1188,11 +1226,15 @@ struct host_phases {
 };
 
 // list: sfw_samples_stage — lin / ang are vx / vtheta of nv samples (nw == 1), vy_list their vy (nullable: all 0.0)
+// knot_step (list only, nullable): sfw_sequences_stage — lin / ang / vy_list hold nk rows of nv values, knot-major, and
+// knot_step the nk steps at which a knot takes over (checked by the caller: knot_step[0] == 0, strictly ascending)
 int stage_common(sfw_handle h, const sfw_robot_state *rs, const double *lin, int32_t nv, const double *ang,
                  int32_t nw, const sfw_goal_args *args, double vy_samp, int skip_zero, int64_t index_base,
-                 bool grid = false, bool list = false, const double *vy_list = nullptr) {
+                 bool grid = false, bool list = false, const double *vy_list = nullptr, int32_t nk = 1,
+                 const int32_t *knot_step = nullptr) {
   if (!h) return SFW_ERR_INVALID_ARG;
-  const std::string what = list ? "samples_stage" : "grid_stage";
+  const std::string what = knot_step ? "sequences_stage" : list ? "samples_stage" : "grid_stage";
+  const size_t kn = knot_step ? static_cast<size_t>(nk) : size_t(1);  // rows of the sample vectors
   if (!rs || !lin || !ang || !args || nv <= 0 || nw <= 0)
     return fail(h, SFW_ERR_INVALID_ARG, what + ": null pointer or non-positive sample count");
   const size_t n_ang = list ? static_cast<size_t>(nv) : static_cast<size_t>(nw);
@@ -1201,7 +1243,8 @@ int stage_common(sfw_handle h, const sfw_robot_state *rs, const double *lin, int
   // ordering the shared-prefix planner sorts by: O(nv + nw) checks
   if (!all_finite(&rs->x, 6) || !all_finite(&args->acc_x, 5) || !std::isfinite(vy_samp))
     return fail(h, SFW_ERR_INVALID_ARG, what + ": non-finite robot state, goal argument or sample velocity");
-  if (!all_finite(lin, static_cast<size_t>(nv)) || !all_finite(ang, n_ang) || (vy_list && !all_finite(vy_list, static_cast<size_t>(nv))))
+  if (!all_finite(lin, kn * static_cast<size_t>(nv)) || !all_finite(ang, kn * n_ang) ||
+      (vy_list && !all_finite(vy_list, kn * static_cast<size_t>(nv))))
     return fail(h, SFW_ERR_INVALID_ARG, what + ": non-finite sample velocity");
   drop_stage(h);  // (valid again at the end of this function, and only there)
   host_phases ph("stage:");
@@ -1218,11 +1261,14 @@ int stage_common(sfw_handle h, const sfw_robot_state *rs, const double *lin, int
     h->world.cells_dirty = false;
   }
   ph.mark("check+setdev");
-  h->st.lin.assign(lin, lin + nv);
-  h->st.ang.assign(ang, ang + n_ang);
+  h->st.lin.assign(lin, lin + kn * nv);
+  h->st.ang.assign(ang, ang + kn * n_ang);
   h->st.list = list;
-  if (vy_list) h->st.vy.assign(vy_list, vy_list + nv);
+  if (vy_list) h->st.vy.assign(vy_list, vy_list + kn * nv);
   else h->st.vy.clear();
+  h->st.nk = static_cast<int>(kn);
+  if (knot_step) h->st.knot_step.assign(knot_step, knot_step + kn);
+  else h->st.knot_step.clear();
   h->st.K = h->world.K;
   h->st.A = ag.A;
   h->st.O = ag.O;
@@ -1248,12 +1294,13 @@ int stage_common(sfw_handle h, const sfw_robot_state *rs, const double *lin, int
   // it when it has changed; a larger one has gone out by a copy of its own (above)
   auto up16 = [](size_t b) { return (b + 15) & ~size_t(15); };
   const size_t cells_head = merge ? up16(n_cells) : 0;
-  {  // one arena, one copy: footprint | agents blob | linvels | angvels | [a list's vy] | relative-rest terms | pinned-rest table | class tables
+  {  // one arena, one copy: footprint | agents blob | linvels | angvels | [a list's vy] | [knot steps] | relative-rest terms | pinned-rest table | class tables
     const bool rest = !ag.rest_pairs.empty();
     const size_t o_fp = cells_head, o_ag = o_fp + up16(sizeof(double) * (h->world.footprint.empty() ? 2 : h->world.footprint.size())),
-                 o_lin = o_ag + up16(ag.blob.size()), o_ang = o_lin + up16(sizeof(double) * nv),
-                 o_vy = o_ang + up16(sizeof(double) * n_ang),
-                 o_rest = o_vy + (vy_list ? up16(sizeof(double) * nv) : 0),
+                 o_lin = o_ag + up16(ag.blob.size()), o_ang = o_lin + up16(sizeof(double) * kn * nv),
+                 o_vy = o_ang + up16(sizeof(double) * kn * n_ang),
+                 o_knot = o_vy + (vy_list ? up16(sizeof(double) * kn * nv) : 0),
+                 o_rest = o_knot + (knot_step ? up16(sizeof(int32_t) * kn) : 0),
                  o_pin = o_rest + (rest ? up16(sizeof(double) * 2 * static_cast<size_t>(ag.A)) : 0),
                  pin_doubles = 4 + static_cast<size_t>(ag.A > 0 ? ag.A : 0),
                  // (room for the pinned-rest table whenever the robot stands still at hand-over: whether one is needed is known
@@ -1269,9 +1316,10 @@ int stage_common(sfw_handle h, const sfw_robot_state *rs, const double *lin, int
     if (send_cells) std::memcpy(pb, h->pin_map.p, n_cells);
     if (!h->world.footprint.empty()) std::memcpy(pb + o_fp, h->world.footprint.data(), sizeof(double) * h->world.footprint.size());
     if (!ag.blob.empty()) std::memcpy(pb + o_ag, ag.blob.data(), ag.blob.size());
-    std::memcpy(pb + o_lin, lin, sizeof(double) * nv);
-    std::memcpy(pb + o_ang, ang, sizeof(double) * n_ang);
-    if (vy_list) std::memcpy(pb + o_vy, vy_list, sizeof(double) * nv);
+    std::memcpy(pb + o_lin, lin, sizeof(double) * kn * nv);
+    std::memcpy(pb + o_ang, ang, sizeof(double) * kn * n_ang);
+    if (vy_list) std::memcpy(pb + o_vy, vy_list, sizeof(double) * kn * nv);
+    if (knot_step) std::memcpy(pb + o_knot, knot_step, sizeof(int32_t) * kn);
     if (!h->st.cls_ints.empty()) std::memcpy(pb + o_cls, h->st.cls_ints.data(), sizeof(int32_t) * h->st.cls_ints.size());
     const double *pos = reinterpret_cast<const double *>(ag.blob.data());
     const double *vel = reinterpret_cast<const double *>(ag.blob.data() + ag.ao_vel);
@@ -1325,6 +1373,7 @@ int stage_common(sfw_handle h, const sfw_robot_state *rs, const double *lin, int
     h->st.d_linvels = reinterpret_cast<const double *>(db + o_lin);
     h->st.d_angvels = reinterpret_cast<const double *>(db + o_ang);
     h->st.d_vy = vy_list ? reinterpret_cast<const double *>(db + o_vy) : nullptr;
+    h->st.d_knot_step = knot_step ? reinterpret_cast<const int32_t *>(db + o_knot) : nullptr;
     h->st.d_agent_rest = rest ? reinterpret_cast<const double *>(db + o_rest) : nullptr;
   }
   if (h->pair_tab_A != ag.A) {
@@ -2020,6 +2069,19 @@ int sfw_samples_stage(sfw_handle h, const sfw_robot_state *rs, const double *vx,
   return stage_common(h, rs, vx, n, vtheta, 1, args, 0.0, 0, index_base, true, true, vy);
 }
 
+int sfw_sequences_stage(sfw_handle h, const sfw_robot_state *rs, const double *vx, const double *vy, const double *vtheta,
+                        int32_t n, int32_t K, const int32_t *knot_step, const sfw_goal_args *args, int64_t index_base) {
+  if (!h) return SFW_ERR_INVALID_ARG;
+  // (refused before anything is touched: the staged grid, list or sequences stay launchable)
+  if (K < 1 || K > SFW_SEQ_MAX_KNOTS) return fail(h, SFW_ERR_INVALID_ARG, "sequences_stage: K outside 1..SFW_SEQ_MAX_KNOTS");
+  if (!knot_step) return fail(h, SFW_ERR_INVALID_ARG, "sequences_stage: knot_step is NULL");
+  if (knot_step[0] != 0) return fail(h, SFW_ERR_INVALID_ARG, "sequences_stage: knot_step[0] must be 0");
+  for (int32_t k = 1; k < K; ++k)
+    if (knot_step[k] <= knot_step[k - 1]) return fail(h, SFW_ERR_INVALID_ARG, "sequences_stage: knot_step must be strictly ascending");
+  // a list of n samples to everything that counts samples; K rows of n values behind its vectors
+  return stage_common(h, rs, vx, n, vtheta, 1, args, 0.0, 0, index_base, true, true, vy, K, knot_step);
+}
+
 int sfw_grid_launch(sfw_handle h) { return launch_common(h); }
 
 int sfw_grid_sync(sfw_handle h) {
@@ -2074,6 +2136,14 @@ int sfw_score_grid(sfw_handle h, const sfw_robot_state *rs, const double *linvel
 int sfw_score_samples(sfw_handle h, const sfw_robot_state *rs, const double *vx, const double *vy, const double *vtheta,
                       int32_t n, const sfw_goal_args *args, double *costs_out, sfw_best *best_out) {
   if (int e = sfw_samples_stage(h, rs, vx, vy, vtheta, n, args, 0)) return e;
+  if (int e = sfw_grid_launch(h)) return e;
+  return sfw_grid_fetch(h, costs_out, best_out, nullptr);
+}
+
+int sfw_score_sequences(sfw_handle h, const sfw_robot_state *rs, const double *vx, const double *vy, const double *vtheta,
+                        int32_t n, int32_t K, const int32_t *knot_step, const sfw_goal_args *args, double *costs_out,
+                        sfw_best *best_out) {
+  if (int e = sfw_sequences_stage(h, rs, vx, vy, vtheta, n, K, knot_step, args, 0)) return e;
   if (int e = sfw_grid_launch(h)) return e;
   return sfw_grid_fetch(h, costs_out, best_out, nullptr);
 }

@@ -238,6 +238,16 @@ struct sfw_launch {
   // one cos / sin unit per sample of the chunk.  (Appended: no other field's offset moves.)
   const double *vy_samps;
   int32_t list;
+  // sfw_sequences_stage: a list whose commands change inside the horizon.  linvels / vy_samps / angvels hold n_knots rows of
+  // knot_stride (= the stage's sample count) values, knot-major: knot k of sample t at [k * knot_stride + t], so row 0 is where
+  // a list's vectors lie (the selection and the re-score read it as they read a list's).  At step i the targets of
+  // computeNewVelocity are those of the largest k with knot_step[k] <= i (knot_step[0] = 0, strictly ascending, read
+  // wave-uniformly as the steps go by: no per-step table that sfw_set_params could leave stale).  n_knots <= 1: a plain list —
+  // the list kernels run; n_knots > 1: the *_seq instantiations of K1 and of the cycle kernel, which write the list's table
+  // layout.  (Appended: no other field's offset moves.)
+  int32_t n_knots;
+  const int32_t *knot_step;
+  int64_t knot_stride;
 };
 
 // Writers of the captured cost terms (no-ops when terms is null): term k of sample t, the three pedestrian-free terms, or one

@@ -36,6 +36,7 @@
 
 #include <type_traits>
 
+#include <limits.h>
 #include <math.h>
 #include <stdlib.h>
 #include <cmath>
@@ -204,13 +205,35 @@ template <bool LIST> __device__ __forceinline__ sample_cmd sample_cmd_of(const s
   return q;
 }
 
+// SEQ (sfw_sequences_stage, sfw_launch.n_knots > 1): the list form whose targets change inside the horizon.  A cursor over
+// the knots: `next` is the step at which knot `k + 1` takes over (INT_MAX behind the last knot).  knot_step is strictly
+// ascending, so a step advances the cursor at most once, and the compare `i == next` is wave-uniform (scalar loads of
+// knot_step, a uniform step counter).  A knot at a step >= S is never reached.
+struct knot_cursor {
+  int k, next;
+};
+__device__ __forceinline__ int knot_next_step(const sfw_launch &L, int k) { return k + 1 < L.n_knots ? L.knot_step[k + 1] : INT_MAX; }
+// the cursor in front of step i0 (the knot active at i0 - 1, or knot 0: step i0 itself is still to be looked at)
+__device__ __forceinline__ knot_cursor knot_cursor_at(const sfw_launch &L, int i0) {
+  knot_cursor kc{0, 0};
+  while (kc.k + 1 < L.n_knots && L.knot_step[kc.k + 1] < i0) ++kc.k;
+  kc.next = knot_next_step(L, kc.k);
+  return kc;
+}
+// one axis' target of sample t at knot k (axis: the vector of that axis, null for an absent vy: 0.0)
+__device__ __forceinline__ double knot_target(const sfw_launch &L, const double *axis, int k, int64_t t) {
+  return axis ? axis[static_cast<int64_t>(k) * L.knot_stride + t] : 0.0;
+}
+
 // Sequential pose integration of one sample (reference :527-:611 without the costmap and the
 // pedestrians): writes the K1 tables (put_robot_step) and the pedestrian-independent cost
 // terms.  Returns false for the never-scored (0,0) sample (whose records are written all the same).
-template <bool LIST> __device__ __forceinline__ bool rollout_sample(const sfw_launch &L, int64_t local) {
+template <bool LIST, bool SEQ = false> __device__ __forceinline__ bool rollout_sample(const sfw_launch &L, int64_t local) {
+  static_assert(LIST || !SEQ, "sequences are lists");
   const int64_t t = L.chunk_begin + local;
   const sample_cmd cmd = sample_cmd_of<LIST>(L, t);
-  const double vx_samp = cmd.vx, vth_samp = cmd.vth, vy_samp = cmd.vy;
+  double vx_samp = cmd.vx, vth_samp = cmd.vth, vy_samp = cmd.vy;  // (SEQ: the active knot's; knot 0 lies where a list's vectors do)
+  knot_cursor kc{0, SEQ ? knot_next_step(L, 0) : INT_MAX};
   // The never-scored (0,0) sample (ref :349-352) still gets its robot-step records: it can be the
   // representative of a shared-prefix class (sfw_cls_agent) whose other members are scored.
   const bool scored = cmd.scored;
@@ -234,6 +257,15 @@ template <bool LIST> __device__ __forceinline__ bool rollout_sample(const sfw_la
       pt[0] = x_i;
       pt[1] = y_i;
       pt[2] = th_i;
+    }
+    if constexpr (SEQ) {
+      if (i == kc.next) {  // the next knot takes over at this step
+        ++kc.k;
+        vx_samp = knot_target(L, L.linvels, kc.k, t);
+        vy_samp = knot_target(L, L.vy_samps, kc.k, t);
+        vth_samp = knot_target(L, L.angvels, kc.k, t);
+        kc.next = knot_next_step(L, kc.k);
+      }
     }
     vx_i = new_velocity(vx_samp, vx_i, L.ga.acc_x, dt);   // ref :581-583
     vy_i = new_velocity(vy_samp, vy_i, L.ga.acc_y, dt);
@@ -310,14 +342,14 @@ __device__ __forceinline__ void fetch_arena(const sfw_launch &L) {
   const uint32_t n = L.arena_bytes / 16, stride = gridDim.x * blockDim.x;
   for (uint32_t u = blockIdx.x * blockDim.x + threadIdx.x; u < n; u += stride) dst[u] = __builtin_nontemporal_load(src + u);
 }
-// (every K1 kernel is one text with the grid form <false> and the list form <true> as its two instantiations, so the
-// arithmetic cannot drift)
-template <bool LIST> __global__ void __launch_bounds__(64) sfw_rollout_kernel(const sfw_launch L) {
+// (every K1 kernel is one text with the grid form <false>, the list form <true> and the sequence form <true, true> as its
+// instantiations, so the arithmetic cannot drift)
+template <bool LIST, bool SEQ = false> __global__ void __launch_bounds__(64) sfw_rollout_kernel(const sfw_launch L) {
   clear_clock_probe(L);
   fetch_arena(L);
   const int64_t local = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
   if (local >= L.chunk_count) return;
-  rollout_sample<LIST>(L, local);
+  rollout_sample<LIST, SEQ>(L, local);
 }
 
 // K1a again, for GPU-filling grids: TEAMS of eight lanes per sample, eight samples per wave.  One thread per sample leaves a
@@ -333,7 +365,8 @@ template <bool LIST> __global__ void __launch_bounds__(64) sfw_rollout_kernel(co
 // values in the same order as rollout_sample (no contraction here either): bit-identical tables and cost terms
 // (tests/test_prefix_sharing_gpu.py::test_team_rollout_equals_the_thread_rollout).
 constexpr int K1A_TEAM = 8;
-template <bool LIST> __global__ void __launch_bounds__(64) sfw_rollout_team_kernel(const sfw_launch L) {
+template <bool LIST, bool SEQ = false> __global__ void __launch_bounds__(64) sfw_rollout_team_kernel(const sfw_launch L) {
+  static_assert(LIST || !SEQ, "sequences are lists");
   constexpr int TEAMS = WAVE / K1A_TEAM;
   clear_clock_probe(L);
   fetch_arena(L);
@@ -362,7 +395,10 @@ template <bool LIST> __global__ void __launch_bounds__(64) sfw_rollout_team_kern
   const int S = L.S;
   const double dt = L.dt;
   // lanes 0, 1, 2: target, limit and running velocity of "their" recurrence; lane 2 the heading; lanes 0, 1 the position
-  const double target = j == 0 ? vx_samp : j == 1 ? vy_samp : vth_samp;  // ref :581-583
+  double target = j == 0 ? vx_samp : j == 1 ? vy_samp : vth_samp;  // ref :581-583
+  // (SEQ: lanes 0-2 fetch their own axis' target where a knot takes over, inside the round)
+  const double *const axis = j == 0 ? L.linvels : j == 1 ? L.vy_samps : L.angvels;
+  knot_cursor kc{0, SEQ ? knot_next_step(L, 0) : INT_MAX};
   const double a_max = j == 0 ? L.ga.acc_x : j == 1 ? L.ga.acc_y : L.ga.acc_theta;
   double v = j == 0 ? L.rs.vx : j == 1 ? L.rs.vy : L.rs.vtheta;
   double th_i = L.rs.theta;
@@ -373,6 +409,13 @@ template <bool LIST> __global__ void __launch_bounds__(64) sfw_rollout_team_kern
     const int nst = min(K1A_TEAM, S - base);
     if (j < 3) {
       for (int q = 0; q < nst; ++q) {
+        if constexpr (SEQ) {
+          if (base + q == kc.next) {
+            ++kc.k;
+            target = knot_target(L, axis, kc.k, t);
+            kc.next = knot_next_step(L, kc.k);
+          }
+        }
         v = new_velocity(target, v, a_max, dt);
         vel_out[q] = j == 2 ? th_i : v;  // lane 2: the heading BEFORE this step's update (ref :586-588 integrate with the old theta)
         th_i = th_i + v * dt;            // (meaningful on lane 2 only)
@@ -573,15 +616,30 @@ __device__ __forceinline__ k1s_state k1s_begin(const sfw_launch &L, int tid) {
 }
 // (1) velocities and headings of steps [i0, i1): threads 0, 1, 2 walk ONE loop, each with its own target, velocity and limit
 // (as three branches of an if the wave ran the three recurrences one after the other); thread 2 also sums the heading
+// SEQ: the cursor is found again for every range (the knot active in front of step i0), so k1s_state carries nothing new
+template <bool SEQ = false>
 __device__ __forceinline__ void k1s_velocities(const sfw_launch &L, const k1s_lds &a, const k1s_sample &q, int i0, int i1, int S,
                                                int tid, k1s_state &st) {
   if (tid >= 3) return;
   const double dt = L.dt;
-  const double target = tid == 0 ? q.vx_samp : tid == 1 ? q.vy_samp : q.vth_samp;  // ref :581-583
+  double target = tid == 0 ? q.vx_samp : tid == 1 ? q.vy_samp : q.vth_samp;  // ref :581-583
+  const double *const axis = tid == 0 ? L.linvels : tid == 1 ? L.vy_samps : L.angvels;
+  knot_cursor kc{0, INT_MAX};
+  if constexpr (SEQ) {
+    kc = knot_cursor_at(L, i0);
+    if (kc.k > 0) target = knot_target(L, axis, kc.k, q.t);
+  }
   const double a_max = tid == 0 ? L.ga.acc_x : tid == 1 ? L.ga.acc_y : L.ga.acc_theta;
   double v = st.v, th_i = st.th;
   double *const out = tid == 0 ? a.vxs : tid == 1 ? a.vys : a.th;
   for (int i = i0; i < i1; ++i) {
+    if constexpr (SEQ) {
+      if (i == kc.next) {
+        ++kc.k;
+        target = knot_target(L, axis, kc.k, q.t);
+        kc.next = knot_next_step(L, kc.k);
+      }
+    }
     v = new_velocity(target, v, a_max, dt);
     // threads 0, 1: the new velocity; thread 2: the heading BEFORE this step's update (ref :586-588 integrate with the old theta)
     out[i] = tid == 2 ? th_i : v;
@@ -708,7 +766,7 @@ __device__ __forceinline__ bool k1s_scan(const sfw_launch &L, const k1s_lds &a, 
   return scan_finish(L, q.t, q.local, cm, n_ok, base_out, base_in);
 }
 
-template <bool LIST> __global__ void __launch_bounds__(K1_SMALL_BLOCK) sfw_rollout_small_kernel(const sfw_launch L) {
+template <bool LIST, bool SEQ = false> __global__ void __launch_bounds__(K1_SMALL_BLOCK) sfw_rollout_small_kernel(const sfw_launch L) {
   __shared__ __attribute__((aligned(16))) char k1s_area[8 * K1_SMALL_MAX_STEPS * 3 + 16 * K1_SMALL_MAX_STEPS * 2 +
                                                         8 * (K1_SMALL_MAX_STEPS + 2) * 2 + 4 * K1_SMALL_MAX_STEPS +
                                                         8 * K1_SMALL_MAX_STEPS + 16];
@@ -718,7 +776,7 @@ template <bool LIST> __global__ void __launch_bounds__(K1_SMALL_BLOCK) sfw_rollo
   const int tid = threadIdx.x, nthr = blockDim.x;
   if (tid == 0) k1s_head(L, q);
   k1s_state st = k1s_begin(L, tid);
-  k1s_velocities(L, a, q, 0, S, S, tid, st);
+  k1s_velocities<SEQ>(L, a, q, 0, S, S, tid, st);
   __syncthreads();
   k1s_increments(L, a, 0, S, tid, nthr);
   __syncthreads();
@@ -3007,7 +3065,8 @@ constexpr int CYCLE_HEAD = 8;  // robot steps handed to the pedestrians' wave ah
 // table; member-local sample `bid` of `nblk`).
 // LIST: the samples are a list (sfw_launch.list) — the sample lookup and the selection's (linvel, angvel) lookup are the list's;
 // everything between them is the same text.
-template <typename R, bool GROUPS, bool OBS, bool BATCH, bool LIST>
+// SEQ: ... whose targets change inside the horizon (sfw_launch.n_knots > 1): the robot's wave walks the knots (k1s_velocities)
+template <typename R, bool GROUPS, bool OBS, bool BATCH, bool LIST, bool SEQ = false>
 __device__ __forceinline__ void cycle_block(const sfw_launch &L, const late_launch Lb, const int k2_bytes, const unsigned bid,
                                             const unsigned nblk) {
   extern __shared__ __attribute__((aligned(16))) char smem[];  // K2 wave's area (from LDS address 0) | k1s_lds | cycle_result
@@ -3042,7 +3101,7 @@ __device__ __forceinline__ void cycle_block(const sfw_launch &L, const late_laun
       k1s_state st = k1s_begin(L, lane);
       for (int i0 = 0; i0 < S;) {
         const int i1 = i0 == 0 ? min(S, CYCLE_HEAD) : S;
-        k1s_velocities(L, a, q, i0, i1, S, lane, st);
+        k1s_velocities<SEQ>(L, a, q, i0, i1, S, lane, st);
         wave_sync();
         k1s_increments(L, a, i0, i1, lane, WAVE);
         wave_sync();
@@ -3131,6 +3190,10 @@ __global__ void __launch_bounds__(CYCLE_BLOCK) sfw_cycle_kernel(const sfw_launch
 template <typename R, bool GROUPS, bool OBS>
 __global__ void __launch_bounds__(CYCLE_BLOCK) sfw_cycle_list_kernel(const sfw_launch L, const int k2_bytes) {
   cycle_block<R, GROUPS, OBS, false, true>(L, nullptr, k2_bytes, 0u, 0u);
+}
+template <typename R, bool GROUPS, bool OBS>
+__global__ void __launch_bounds__(CYCLE_BLOCK) sfw_cycle_seq_kernel(const sfw_launch L, const int k2_bytes) {
+  cycle_block<R, GROUPS, OBS, false, true, true>(L, nullptr, k2_bytes, 0u, 0u);
 }
 // Many handles' control cycles in one launch (sfw_batch_*): a 1-D grid over the samples of all members, member m's T_m blocks
 // from first[m] on.  A block finds its member by a binary search over first[] (scalar loads, uniform) and runs the block of
@@ -3320,20 +3383,21 @@ bool sfw_rollout_is_fused(const sfw_launch &L) { return L.chunk_count <= 2048 &&
 hipError_t sfw_launch_rollout_poses(const sfw_launch &L, hipStream_t stream) {
   if (L.chunk_count <= 0) return hipSuccess;
   if (sfw_rollout_is_fused(L)) {  // latency path: one launch does all of K1
-    hipLaunchKernelGGL((L.list ? sfw_rollout_small_kernel<true> : sfw_rollout_small_kernel<false>),
+    hipLaunchKernelGGL((L.n_knots > 1 ? sfw_rollout_small_kernel<true, true> : L.list ? sfw_rollout_small_kernel<true> : sfw_rollout_small_kernel<false>),
                        dim3(static_cast<unsigned>(L.chunk_count)), dim3(K1_SMALL_BLOCK), 0, stream, L);
     return hipGetLastError();
   }
   const int block = 64;  // latency-bound serial rollout: spread the waves over all CUs
   if (sfw_k1a_threads()) {  // SFW_K1A_THREADS=1: round 1-5's one thread per sample (A/B and the equality test)
     const unsigned grid = static_cast<unsigned>((L.chunk_count + block - 1) / block);
-    hipLaunchKernelGGL((L.list ? sfw_rollout_kernel<true> : sfw_rollout_kernel<false>), dim3(grid), dim3(block), 0, stream, L);
+    hipLaunchKernelGGL((L.n_knots > 1 ? sfw_rollout_kernel<true, true> : L.list ? sfw_rollout_kernel<true> : sfw_rollout_kernel<false>),
+                       dim3(grid), dim3(block), 0, stream, L);
     return hipGetLastError();
   }
   constexpr int per_wave = WAVE / K1A_TEAM;
   const unsigned grid = static_cast<unsigned>((L.chunk_count + per_wave - 1) / per_wave);
-  hipLaunchKernelGGL((L.list ? sfw_rollout_team_kernel<true> : sfw_rollout_team_kernel<false>), dim3(grid), dim3(block), 0, stream,
-                     L);
+  hipLaunchKernelGGL((L.n_knots > 1 ? sfw_rollout_team_kernel<true, true> : L.list ? sfw_rollout_team_kernel<true> : sfw_rollout_team_kernel<false>),
+                     dim3(grid), dim3(block), 0, stream, L);
   return hipGetLastError();
 }
 
@@ -3655,6 +3719,12 @@ template <typename R> static hipError_t launch_cycle_typed(const sfw_launch &L_i
   const size_t lds = k2 + k1_bytes + ((sizeof(cycle_result) + 15) & ~size_t(15));
   const dim3 grid(static_cast<unsigned>(L.chunk_count)), block(CYCLE_BLOCK);
   const int k2i = static_cast<int>(k2);
+  if (L.n_knots > 1) {  // (sfw_sequences_stage: the list's block with the knot cursor in the robot's wave)
+    if (L.NG > 0) hipLaunchKernelGGL((sfw_cycle_seq_kernel<R, true, true>), grid, block, lds, stream, L, k2i);
+    else if (L.O > 0) hipLaunchKernelGGL((sfw_cycle_seq_kernel<R, false, true>), grid, block, lds, stream, L, k2i);
+    else hipLaunchKernelGGL((sfw_cycle_seq_kernel<R, false, false>), grid, block, lds, stream, L, k2i);
+    return hipGetLastError();
+  }
   if (L.list) {  // (sfw_samples_stage: the same block over the list's sample lookup and selection)
     if (L.NG > 0) hipLaunchKernelGGL((sfw_cycle_list_kernel<R, true, true>), grid, block, lds, stream, L, k2i);
     else if (L.O > 0) hipLaunchKernelGGL((sfw_cycle_list_kernel<R, false, true>), grid, block, lds, stream, L, k2i);

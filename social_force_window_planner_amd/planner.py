@@ -161,6 +161,10 @@ def lib():
                                           C.POINTER(C.c_int32)]
         L.sfw_grid_crowd.argtypes = [vp, C.c_int64, C.POINTER(C.c_double), vp, vp, vp, C.c_int32, C.c_int32,
                                      C.POINTER(C.c_int32)]
+        L.sfw_sequences_stage.argtypes = [vp, C.POINTER(SfwRobotState), vp, vp, vp, C.c_int32, C.c_int32, vp,
+                                          C.POINTER(SfwGoalArgs), C.c_int64]
+        L.sfw_score_sequences.argtypes = [vp, C.POINTER(SfwRobotState), vp, vp, vp, C.c_int32, C.c_int32, vp,
+                                          C.POINTER(SfwGoalArgs), vp, C.POINTER(SfwBest)]
         _lib = L
     return _lib
 
@@ -314,6 +318,43 @@ class HipScorer:
                                             vth.ctypes.data if len(vth) else None, len(vx), C.byref(ga),
                                             costs.ctypes.data if len(vx) else None, C.byref(best)), "sfw_score_samples")
         self._mark_staged((len(vx), 1))
+        return costs, best.as_dict()
+
+    # -- command sequences (sfw_sequences_stage / sfw_score_sequences) -------
+    @staticmethod
+    def _sequences(vx, vtheta, knot_steps, vy):
+        vx, vth = np.ascontiguousarray(_f64(vx)), np.ascontiguousarray(_f64(vtheta))
+        vyv = None if vy is None else np.ascontiguousarray(_f64(vy))
+        ks = np.ascontiguousarray(np.asarray(knot_steps, dtype=np.int32).reshape(-1))
+        if vx.ndim != 2 or vth.shape != vx.shape or (vyv is not None and vyv.shape != vx.shape) or len(ks) != vx.shape[0]:
+            raise ValueError("sequences: vx, vy and vtheta must be (K, n) arrays and knot_steps must hold K steps")
+        return vx, vth, vyv, ks
+
+    def stage_sequences(self, robot_state, vx, vtheta, knot_steps, goal_args, vy=None, index_base=0):
+        """Stage n command SEQUENCES of K knots: vx / vy / vtheta are (K, n) arrays (vy=None: all 0), knot_steps[k] the Euler
+        step at which knot k takes over (knot_steps[0] == 0, strictly ascending).  Everything that acts on a staged list then
+        acts on the sequences, sample index t in column order; best carries the winner's FIRST knot."""
+        vx, vth, vyv, ks = self._sequences(vx, vtheta, knot_steps, vy)
+        rs, ga = SfwRobotState(*robot_state), SfwGoalArgs(*goal_args)
+        K, n = vx.shape
+        self._check(lib().sfw_sequences_stage(self._h, C.byref(rs), vx.ctypes.data if vx.size else None,
+                                              vyv.ctypes.data if vyv is not None and vyv.size else None,
+                                              vth.ctypes.data if vth.size else None, n, K, ks.ctypes.data if len(ks) else None,
+                                              C.byref(ga), index_base), "sfw_sequences_stage")
+        self._mark_staged((n, 1))
+
+    def score_sequences(self, robot_state, vx, vtheta, knot_steps, goal_args, vy=None):
+        """The blocking call over command sequences: (costs[n], best)."""
+        vx, vth, vyv, ks = self._sequences(vx, vtheta, knot_steps, vy)
+        rs, ga = SfwRobotState(*robot_state), SfwGoalArgs(*goal_args)
+        K, n = vx.shape
+        costs = np.empty(n, dtype=np.float64)
+        best = SfwBest()
+        self._check(lib().sfw_score_sequences(self._h, C.byref(rs), vx.ctypes.data if vx.size else None,
+                                              vyv.ctypes.data if vyv is not None and vyv.size else None,
+                                              vth.ctypes.data if vth.size else None, n, K, ks.ctypes.data if len(ks) else None,
+                                              C.byref(ga), costs.ctypes.data if n else None, C.byref(best)), "sfw_score_sequences")
+        self._mark_staged((n, 1))
         return costs, best.as_dict()
 
     def prepared(self, robot_state, linvels, angvels, goal_args, index_base=0, zero_copy=False):

@@ -1,0 +1,73 @@
+"""Command sequences (sfw_sequences_stage, sfw_score_sequences): exported, declared in plain C99, ABI version unchanged, and
+the argument checks that need no GPU."""
+import ctypes as C
+import os
+import re
+import shutil
+import subprocess
+
+import pytest
+
+from social_force_window_planner_amd import planner
+from social_force_window_planner_amd._abi import (EXPORTED_SYMBOLS, SFW_ERR_INVALID_ARG, SfwBest, SfwGoalArgs,
+                                                   SfwRobotState)
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SEQ_SYMBOLS = ("sfw_sequences_stage", "sfw_score_sequences")
+
+
+def _header():
+    return open(os.path.join(ROOT, "include", "sfw_hip.h")).read()
+
+
+def test_sequence_symbols_declared_and_exported():
+    declared = set(re.findall(r"\b(sfw_[a-z_0-9]+)\s*\(", _header()))
+    assert set(SEQ_SYMBOLS) <= declared and set(SEQ_SYMBOLS) <= set(EXPORTED_SYMBOLS)
+    L = planner.lib()
+    assert all(hasattr(L, n) for n in SEQ_SYMBOLS)
+    assert all(planner.exported_symbols()[n] for n in SEQ_SYMBOLS)
+    assert re.search(r"#define SFW_SEQ_MAX_KNOTS 64\b", _header())
+
+
+def test_abi_version_unchanged():
+    assert planner.lib().sfw_abi_version() == 2
+    assert re.search(r"#define SFW_ABI_VERSION 2\b", _header())
+
+
+def test_null_handle_is_invalid_arg_without_gpu():
+    L = planner.lib()
+    rs, ga, best = SfwRobotState(0, 0, 0, 0, 0, 0), SfwGoalArgs(1, 1, 1, 1, 0), SfwBest()
+    v = (C.c_double * 4)(0.1, 0.2, 0.3, 0.1)
+    ks = (C.c_int32 * 2)(0, 12)
+    costs = (C.c_double * 2)()
+    p, k = C.addressof(v), C.addressof(ks)
+    assert L.sfw_sequences_stage(None, C.byref(rs), p, p, p, 2, 2, k, C.byref(ga), 0) == SFW_ERR_INVALID_ARG
+    assert L.sfw_sequences_stage(None, C.byref(rs), p, None, p, 2, 2, k, C.byref(ga), 0) == SFW_ERR_INVALID_ARG
+    assert L.sfw_score_sequences(None, C.byref(rs), p, p, p, 2, 2, k, C.byref(ga), C.addressof(costs), C.byref(best)) == SFW_ERR_INVALID_ARG
+    assert L.sfw_score_sequences(None, None, None, None, None, 0, 0, None, None, None, None) == SFW_ERR_INVALID_ARG
+
+
+def test_python_wrapper_checks_its_shapes():
+    with pytest.raises(ValueError):
+        planner.HipScorer._sequences([0.1, 0.2], [0.0, 0.1], [0], None)  # not (K, n)
+    with pytest.raises(ValueError):
+        planner.HipScorer._sequences([[0.1, 0.2]], [[0.0, 0.1]], [0, 5], None)  # K steps for K rows
+    vx, vth, vy, ks = planner.HipScorer._sequences([[0.1, 0.2], [0.3, 0.4]], [[0.0, 0.1], [0.2, 0.3]], [0, 5], None)
+    assert vx.shape == (2, 2) and vx.flags.c_contiguous and vy is None and ks.dtype.itemsize == 4
+
+
+def test_header_compiles_as_c99_with_the_sequence_calls(tmp_path):
+    gcc = shutil.which("gcc")
+    if not gcc:
+        pytest.skip("no gcc")
+    src = tmp_path / "s.c"
+    src.write_text('#include "sfw_hip.h"\n#include <stddef.h>\n'
+                   "int main(void) { sfw_robot_state rs = {0, 0, 0, 0, 0, 0}; sfw_goal_args ga = {1, 1, 1, 1, 0}; sfw_best b;\n"
+                   "  double vx[4] = {0.1, 0.2, 0.3, 0.1}, vy[4] = {0, 0.1, 0, 0}, vth[4] = {0, 0.3, 0.1, 0.2}, c[2];\n"
+                   "  int32_t ks[SFW_SEQ_MAX_KNOTS] = {0, 12};\n"
+                   "  return sfw_sequences_stage(NULL, &rs, vx, vy, vth, 2, 2, ks, &ga, 0) +\n"
+                   "         sfw_sequences_stage(NULL, &rs, vx, NULL, vth, 2, 2, ks, &ga, 7) +\n"
+                   "         sfw_score_sequences(NULL, &rs, vx, vy, vth, 2, 2, ks, &ga, c, &b); }\n")
+    r = subprocess.run([gcc, "-std=c99", "-pedantic-errors", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.join(ROOT, "include"),
+                        str(src)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
