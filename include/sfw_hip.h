@@ -551,6 +551,60 @@ int sfw_grid_rescore(sfw_handle h, const sfw_weights *w, int32_t K, sfw_best *be
  * same conditions as sfw_grid_rescore.  One device-to-host copy per term. */
 int sfw_grid_terms(sfw_handle h, int64_t first, int64_t count, double *terms_out);
 
+/* ---- softmin blend: the update of a sampling controller (MPPI) ---------------
+ * A sampling controller does not want the argmin of its n rollouts' costs; it wants their softmin weights, the normaliser
+ * and effective sample size, and the weighted mean of the command knots — its next nominal plan.  Costs and knots are on the
+ * device after a launch; this call reduces them there, for L temperatures at once, and returns a few hundred bytes.
+ *
+ * It acts on the handle's last launch, whatever was staged.  T = samples, K = knots per sample: a grid has K = 1 and sample
+ * t = iv*nw+iw the command (linvels[iv], 0.0, angvels[iw]); a list has K = 1; sequences have their K knots.
+ *   valid_t    cost_t >= 0 (the set sfw_best.n_valid counts; sentinels and negative costs are not valid)
+ *   J_t        cost_t + bias_t, one IEEE addition (bias == NULL: cost_t itself).  bias (nullable, T doubles) carries the
+ *              caller's control-cost term lambda * u^T Sigma^-1 eps, or any per-sample prior; at an invalid sample it is ignored
+ *   j_min      the minimum of J over the valid samples; index_min the LARGEST t that holds it (the selection's tie-break);
+ *              j_min = J[index_min]
+ *   a_t        (J_t - j_min) / lambda_l: one IEEE subtraction, one IEEE division
+ *   w_t        exp(-a_t), the device library's double exp; exactly 0.0 at an invalid sample.  The samples at j_min have
+ *              w == 1.0 exactly, a_t = +inf gives exactly 0.0
+ *   eta        sum_t w_t;   sum_w2 = sum_t (w_t * w_t);   effective sample size = eta * eta / sum_w2
+ *   u_out      [l][k][vx, vy, vtheta] = (sum_t w_t * u[k][t]) / eta: every product rounded on its own (no contraction), one
+ *              division at the end.  The vy channel of a grid, or of a stage without vy, is 0.0
+ *   weights_out (nullable) L x T doubles, lambda-major.
+ * No valid sample: every stat_out[l] = {lambda_l, j_min -1.0, eta 0.0, sum_w2 0.0, n_valid 0, index_min -1}, every entry of
+ * u_out 0.0, every weight 0.0, SFW_OK.  j_min, n_valid and index_min do not depend on l.
+ *
+ * Determinism.  eta, sum_w2 and every u channel are sums of T terms x_t (w_t, w_t * w_t, w_t * u[k][t]; an invalid sample's
+ * term is its product with w_t = 0.0).  Each goes through ONE summation tree that is a function of T alone — not of the
+ * device's compute units (SFW_DEVICE_CUS), of how the scoring launch was chunked (SFW_TABLE_BUDGET_MB), of whether the
+ * one-launch kernel scored the stage (SFW_CYCLE_FUSED), of L, or of whether weights_out was asked for.  With C = 256,
+ * B = ceil(T / C) and x_t = +0.0 for T <= t < B * C:
+ *   1. wave:   block b owns samples [b*C, (b+1)*C); lane i of wave v of the block holds x at t = b*C + 64*v + i.  Butterfly:
+ *              for d = 32, 16, 8, 4, 2, 1 in that order every lane replaces its value by (its own + lane (i xor d)'s).
+ *              After the six levels every lane holds the wave's sum s_v.
+ *   2. block:  p_b = ((s_0 + s_1) + s_2) + s_3.
+ *   3. blocks: sum = (...((p_0 + p_1) + p_2) ... ) + p_(B-1), in block order.
+ * Every + is one IEEE double addition; no floating-point atomics.  A term passes through d(T) = 6 + 3 + (B - 1) additions at
+ * most (the depth of the tree).  social_force_window_planner_amd/blend.py restates definition and tree in numpy
+ * (blend.reference, blend.depth); tests/test_blend_gpu.py holds the device to it bit for bit.
+ *
+ * State: read-only for the launch, as sfw_grid_rescore — the cost vector, selection, captured points and terms and
+ * sfw_grid_crowd stay valid; needs no terms capture; works on a batch member after sfw_batch_fetch.  SFW_ERR_STATE when
+ * there is no launch, or a stage or sfw_score_one came in since.  Three small kernels on the handle's stream behind the
+ * launch; blocking.
+ * SFW_ERR_INVALID_ARG (before any device call; a refused call changes nothing): a NULL h, lambda, stat_out or u_out; L
+ * outside [1, SFW_BLEND_MAX_L]; a lambda that is not finite or not > 0; a non-finite bias value. */
+#define SFW_BLEND_MAX_L 16
+typedef struct sfw_blend_stat {
+  double lambda;      /* the temperature this record belongs to                          */
+  double j_min;       /* min over valid samples of J_t; -1.0 when there is none          */
+  double eta;         /* sum of w_t                                                      */
+  double sum_w2;      /* sum of w_t * w_t  (effective sample size = eta * eta / sum_w2)  */
+  int64_t n_valid;    /* samples with cost >= 0: sfw_best.n_valid of the same launch     */
+  int64_t index_min;  /* the LARGEST t with J_t == j_min (the selection's tie-break); -1 */
+} sfw_blend_stat;
+int sfw_grid_blend(sfw_handle h, const double *lambda, int32_t L, const double *bias,
+                   sfw_blend_stat *stat_out, double *u_out, double *weights_out);
+
 /* ---- the predicted crowd behind a score ------------------------------------
  * For every sample the scorer integrates the whole crowd forward under the social-force model; these two calls hand that
  * prediction out for ONE sample: where every person is after every step, who does the social work, whose goal has popped.

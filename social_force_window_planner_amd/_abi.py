@@ -221,6 +221,7 @@ EXPORTED_SYMBOLS = (
     "sfw_score_sequences",
     "sfw_score_one_crowd",
     "sfw_grid_crowd",
+    "sfw_grid_blend",
 )
 # per-term costs (sfw_set_terms_capture / sfw_grid_rescore / sfw_grid_terms)
 SFW_TERM_VEL, SFW_TERM_DISTANCE, SFW_TERM_ANGLE, SFW_TERM_COSTMAP, SFW_TERM_SOCIAL = 0, 1, 2, 3, 4
@@ -233,6 +234,23 @@ class SfwWeights(C.Structure):
 
     _fields_ = [("vel", C.c_double), ("distance", C.c_double), ("angle", C.c_double), ("costmap", C.c_double),
                 ("social", C.c_double)]
+
+
+# softmin blend (sfw_grid_blend)
+SFW_BLEND_MAX_L = 16
+
+
+class SfwBlendStat(C.Structure):
+    """sfw_blend_stat (include/sfw_hip.h): one temperature's record of sfw_grid_blend."""
+
+    _fields_ = [("lambda_", C.c_double), ("j_min", C.c_double), ("eta", C.c_double), ("sum_w2", C.c_double),
+                ("n_valid", C.c_int64), ("index_min", C.c_int64)]
+
+    def as_dict(self):
+        d = {"lambda": self.lambda_, "j_min": self.j_min, "eta": self.eta, "sum_w2": self.sum_w2, "n_valid": self.n_valid,
+             "index_min": self.index_min}
+        d["ess"] = self.eta * self.eta / self.sum_w2 if self.sum_w2 > 0.0 else 0.0
+        return d
 
 
 # one grid under several crowd hypotheses (sfw_ensemble_*)

@@ -299,6 +299,11 @@ struct sfw_planner_s {
   dev_buf<sfw_sel> rescore_partials;
   dev_buf<double> rescore_costs;
   pinned_buf pin_rescore;          // K records (written by the kernels) | K weight vectors (copied from)
+  // sfw_grid_blend: first-pass records, per-block partial sums, the bias and weight vectors on the device; pin_blend receives
+  // the minimum record | eta[L] | sum_w2[L] | u[L][K][3] from the kernels
+  dev_buf<sfw_blend_min> blend_mins;
+  dev_buf<double> blend_partials, blend_bias, blend_weights;
+  pinned_buf pin_blend;
   // sfw_score_one_crowd / sfw_grid_crowd: cost | n_points | coll_step | state [S][A][4] | work [S][A] | has_goal [S][A],
   // contiguous -> one D2H into pin_crowd; the pair table of the kernel with run-time plane capacity (sfw_crowd_kernel)
   dev_buf<char> crowd_out;
@@ -1868,6 +1873,11 @@ int destroy_handle(sfw_handle h) {
   h->rescore_partials.release();
   h->rescore_costs.release();
   h->pin_rescore.release();
+  h->blend_mins.release();
+  h->blend_partials.release();
+  h->blend_bias.release();
+  h->blend_weights.release();
+  h->pin_blend.release();
   h->points.release();
   h->n_points.release();
   h->one_out.release();
@@ -2425,6 +2435,72 @@ int sfw_grid_rescore(sfw_handle h, const sfw_weights *w, int32_t K, sfw_best *be
   h->pin_rescore.pending = false;
   stream_is_idle(h);
   for (int32_t k = 0; k < K; ++k) sel_to_best(h, sel_host[k], best_out + k, nullptr);
+  return SFW_OK;
+}
+
+int sfw_grid_blend(sfw_handle h, const double *lambda, int32_t L, const double *bias, sfw_blend_stat *stat_out, double *u_out,
+                   double *weights_out) {
+  if (!h) return SFW_ERR_INVALID_ARG;
+  if (!lambda || !stat_out || !u_out) return fail(h, SFW_ERR_INVALID_ARG, "grid_blend: lambda, stat_out or u_out is NULL");
+  if (L < 1 || L > SFW_BLEND_MAX_L) return fail(h, SFW_ERR_INVALID_ARG, "grid_blend: L out of [1, SFW_BLEND_MAX_L]");
+  for (int32_t l = 0; l < L; ++l)
+    if (!std::isfinite(lambda[l]) || !(lambda[l] > 0.0)) return fail(h, SFW_ERR_INVALID_ARG, "grid_blend: a lambda is not finite or not > 0");
+  if (!h->last.launched) return fail(h, SFW_ERR_STATE, "grid_blend: no launch, or a stage or sfw_score_one came in since");
+  const int64_t T = static_cast<int64_t>(h->st.nv) * h->st.nw;
+  if (bias && !all_finite(bias, static_cast<size_t>(T))) return fail(h, SFW_ERR_INVALID_ARG, "grid_blend: non-finite bias");
+  SFW_HIP(h, hipSetDevice(h->device));
+  const int K = h->st.list ? h->st.nk : 1;
+  const int64_t n_ch = sfw_blend_channels(L, K), blocks = sfw_blend_blocks(T);
+  const size_t head = (sizeof(sfw_blend_min) + 15) & ~size_t(15), out_bytes = head + sizeof(double) * static_cast<size_t>(n_ch);
+  // (growing the pinned area frees the old one: nothing in the stream may still be writing there)
+  if (out_bytes > h->pin_blend.cap) SFW_HIP(h, hipStreamSynchronize(h->stream));
+  SFW_HIP(h, h->pin_blend.reserve(out_bytes));
+  SFW_HIP(h, h->blend_mins.reserve(static_cast<size_t>(sfw_blend_min_blocks(T))));
+  SFW_HIP(h, h->blend_partials.reserve(static_cast<size_t>(blocks) * static_cast<size_t>(n_ch)));
+  if (bias) {
+    SFW_HIP(h, h->blend_bias.reserve(static_cast<size_t>(T)));
+    SFW_HIP(h, hipMemcpyAsync(h->blend_bias.p, bias, sizeof(double) * static_cast<size_t>(T), hipMemcpyHostToDevice, h->stream));
+  }
+  const double *const d_bias = bias ? h->blend_bias.p : nullptr;
+  // weights_out: all L vectors from the launch that forms the sums, or — beyond 256 MB of them — in slices of as many
+  // temperatures as that holds, each by a launch of its own that is copied out behind it
+  const int64_t fit = std::max<int64_t>(1, (int64_t(256) << 20) / (static_cast<int64_t>(sizeof(double)) * T));
+  const bool sliced = weights_out && fit < L;
+  const int32_t l_step = static_cast<int32_t>(std::min<int64_t>(L, fit));
+  if (weights_out) SFW_HIP(h, h->blend_weights.reserve(static_cast<size_t>(l_step) * static_cast<size_t>(T)));
+  sfw_blend_lambdas lam{};
+  for (int32_t l = 0; l < L; ++l) lam.v[l] = lambda[l];
+  sfw_blend_min *const min_host = reinterpret_cast<sfw_blend_min *>(h->pin_blend.p);
+  double *const out_host = reinterpret_cast<double *>(h->pin_blend.p + head);
+  SFW_HIP(h, sfw_launch_blend(h->costs.p, d_bias, T, lam, L, K, h->st.d_linvels, h->st.d_vy, h->st.d_angvels, h->st.nw, h->st.list,
+                              h->blend_mins.p, h->blend_partials.p, weights_out && !sliced ? h->blend_weights.p : nullptr, min_host,
+                              out_host, h->stream));
+  if (weights_out && !sliced)
+    SFW_HIP(h, hipMemcpyAsync(weights_out, h->blend_weights.p, sizeof(double) * static_cast<size_t>(L) * static_cast<size_t>(T),
+                              hipMemcpyDeviceToHost, h->stream));
+  for (int32_t l0 = 0; sliced && l0 < L; l0 += l_step) {
+    const int32_t n = std::min(l_step, L - l0);
+    sfw_blend_lambdas part{};
+    for (int32_t l = 0; l < n; ++l) part.v[l] = lambda[l0 + l];
+    SFW_HIP(h, sfw_launch_blend_weights(h->costs.p, d_bias, T, part, n, h->blend_mins.p, h->blend_weights.p, h->stream));
+    SFW_HIP(h, hipMemcpyAsync(weights_out + static_cast<int64_t>(l0) * T, h->blend_weights.p,
+                              sizeof(double) * static_cast<size_t>(n) * static_cast<size_t>(T), hipMemcpyDeviceToHost, h->stream));
+  }
+  SFW_HIP(h, h->pin_blend.mark(h->stream));
+  SFW_HIP(h, wait_stream(h));
+  h->pin_blend.pending = false;
+  stream_is_idle(h);
+  const sfw_blend_min m = *min_host;
+  const bool any = m.n_valid > 0;
+  for (int32_t l = 0; l < L; ++l) {
+    stat_out[l].lambda = lambda[l];
+    stat_out[l].j_min = any ? m.j : -1.0;
+    stat_out[l].eta = out_host[l];
+    stat_out[l].sum_w2 = out_host[L + l];
+    stat_out[l].n_valid = m.n_valid;
+    stat_out[l].index_min = any ? m.index : -1;
+  }
+  std::memcpy(u_out, out_host + 2 * L, sizeof(double) * 3 * static_cast<size_t>(K) * static_cast<size_t>(L));
   return SFW_OK;
 }
 

@@ -350,6 +350,30 @@ hipError_t sfw_launch_rescore(const double *terms, int64_t T, const sfw_weights 
 hipError_t sfw_launch_ensemble(const double *const *terms, const double *probs, int M, int64_t T, int mode, const sfw_weights &w,
                                const double *linvels, const double *angvels, int32_t nw, double *costs, int32_t *rejected,
                                sfw_sel *partials, sfw_sel *sel_host, hipStream_t stream);
+// sfw_grid_blend: the cost vector (+ bias, nullable) of a launch over T samples -> softmin weights for L temperatures, their
+// sums and the weighted mean of the K knot rows (list: linvels / vy (nullable) / angvels hold K rows of T values, knot-major;
+// else a grid of T / nw x nw samples, K == 1).  Three launches: `mins` (sfw_blend_min_blocks(T) records), `partials`
+// (sfw_blend_blocks(T) x sfw_blend_channels(L, K) doubles), then *min_host and out_host[sfw_blend_channels(L, K)] = eta[L] |
+// sum_w2[L] | u[L][K][3] in pinned memory.  weights (nullable): L x T doubles, lambda-major.
+struct sfw_blend_min {
+  double j;         // +inf when no sample is valid
+  int64_t index;    // the largest t with J_t == j; -1
+  int64_t n_valid;
+};
+struct sfw_blend_lambdas {
+  double v[SFW_BLEND_MAX_L];
+};
+int64_t sfw_blend_blocks(int64_t T);
+int64_t sfw_blend_min_blocks(int64_t T);
+inline int64_t sfw_blend_channels(int L, int K) { return 2 * static_cast<int64_t>(L) + 3 * static_cast<int64_t>(K) * L; }
+hipError_t sfw_launch_blend(const double *costs, const double *bias, int64_t T, const sfw_blend_lambdas &lam, int L, int K,
+                            const double *linvels, const double *vy, const double *angvels, int32_t nw, bool list,
+                            sfw_blend_min *mins, double *partials, double *weights, sfw_blend_min *min_host, double *out_host,
+                            hipStream_t stream);
+// The weights of L temperatures alone (a slice of a weights_out that does not fit one buffer), behind a sfw_launch_blend
+// with the same costs and bias: `mins` as that launch left it.
+hipError_t sfw_launch_blend_weights(const double *costs, const double *bias, int64_t T, const sfw_blend_lambdas &lam, int L,
+                                    const sfw_blend_min *mins, double *weights, hipStream_t stream);
 // Row r of the [R,5] multi-device exchange table from a selection record (+inf in every other row).
 hipError_t sfw_launch_key_table(const sfw_sel *sel, double *table, int r, int R, hipStream_t stream);
 // Pair table of the flat social kernel for A agents: sfw_pair_table_entries(A) uint16 entries.

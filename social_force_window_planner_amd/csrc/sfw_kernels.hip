@@ -3021,6 +3021,180 @@ __global__ void __launch_bounds__(ARGMIN_BLOCK) sfw_ensemble_stage2(const sfw_se
   if (threadIdx.x == 0) *sel_host = best;
 }
 
+#ifndef SFW_STRICT_BUILD  // (costs are doubles in every precision mode: the blend's kernels exist once)
+// Softmin blend (sfw_grid_blend): the cost vector of a launch -> weights w_t = exp(-(J_t - J_min) / lambda_l) for L
+// temperatures, their sums and the weighted mean of the command knots.  Three launches on the handle's stream:
+//   sfw_blend_min    grid-stride: per block the record (J_min, largest index holding it, valid samples) of its samples.  A
+//                    minimum under a total order and an integer sum: exact, whatever the shape of the reduction;
+//   sfw_blend_first  block b owns samples [b * BLEND_C, (b + 1) * BLEND_C), one per thread.  Every block reduces the (at most
+//                    BLEND_MIN_BLOCKS) records of the first pass itself, forms its sample's L weights in registers (device
+//                    library exp, one IEEE subtraction and division in front of it) and walks the K knot rows: row k of sample t at
+//                    [k * n + t], coalesced over the lanes; a grid's two channels from linvels[t / nw] and angvels[t % nw].  Per row
+//                    3 x L products are summed over the block (blend_wave_sum, then the four waves' sums in wave order through
+//                    LDS, double-buffered: one barrier per row) into partials[b][channel];
+//   sfw_blend_last   one thread per channel adds the blocks' partials in block order, divides the knot channels by eta and
+//                    writes everything into the handle's pinned buffer.
+// The tree every sum goes through is a function of T alone (sfw_hip.h "Determinism"): a sample's place in it is its index,
+// a lane outside T or an invalid sample adds the term +0.0.  No contraction: every product is rounded on its own.
+#pragma clang fp contract(off)
+constexpr int BLEND_C = 256;  // samples per block = threads per block (sfw_hip.h: C)
+constexpr int BLEND_MIN_BLOCKS = 1024;
+// A minimum record in three scalars (j = +inf, index = -1, n = 0: empty).  Take the other record where its J is smaller; among
+// equal J the larger index (the selection's tie-break); the counts add.
+__device__ __forceinline__ void blend_min_take(double &j, long long &index, long long &n, double oj, long long oindex, long long on) {
+  const bool take = (oj < j) | ((oj == j) & (oindex > index));
+  j = take ? oj : j;
+  index = take ? oindex : index;
+  n += on;
+}
+// every thread of the block receives the merge of all threads' records
+__device__ __forceinline__ void blend_min_block(double &j, long long &index, long long &n) {
+  __shared__ double wave_j[BLEND_C / WAVE];
+  __shared__ long long wave_index[BLEND_C / WAVE], wave_n[BLEND_C / WAVE];
+  for (int off = WAVE / 2; off > 0; off >>= 1) {
+    const double oj = __shfl_xor(j, off, WAVE);
+    const long long oindex = __shfl_xor(index, off, WAVE), on = __shfl_xor(n, off, WAVE);
+    blend_min_take(j, index, n, oj, oindex, on);
+  }
+  if ((threadIdx.x & (WAVE - 1)) == 0) {
+    wave_j[threadIdx.x / WAVE] = j;
+    wave_index[threadIdx.x / WAVE] = index;
+    wave_n[threadIdx.x / WAVE] = n;
+  }
+  __syncthreads();
+  j = wave_j[0];
+  index = wave_index[0];
+  n = wave_n[0];
+  for (int w = 1; w < BLEND_C / WAVE; ++w) blend_min_take(j, index, n, wave_j[w], wave_index[w], wave_n[w]);
+}
+// J_t of a valid sample: cost + bias, one IEEE addition; without bias the cost itself
+__device__ __forceinline__ double blend_j(const double *bias, int64_t t, double c) { return bias ? c + bias[t] : c; }
+// The wave's sum as a butterfly: at distance 32, 16, 8, 4, 2, 1 every lane adds its partner's value to its own.  Addition is
+// commutative, so both lanes of a pair hold the same bits and after six levels all 64 lanes hold the wave's sum.
+__device__ __forceinline__ double blend_wave_sum(double v) {
+  for (int off = WAVE / 2; off > 0; off >>= 1) v = v + __shfl_xor(v, off, WAVE);
+  return v;
+}
+
+__global__ void __launch_bounds__(BLEND_C) sfw_blend_min_kernel(const double *costs, const double *bias, int64_t T, sfw_blend_min *out) {
+  double j = INFINITY;
+  long long index = -1, n = 0;
+  for (int64_t t = static_cast<int64_t>(blockIdx.x) * BLEND_C + threadIdx.x; t < T; t += static_cast<int64_t>(gridDim.x) * BLEND_C) {
+    const double c = costs[t];
+    if (c >= 0.0) blend_min_take(j, index, n, blend_j(bias, t, c), t, 1);
+  }
+  blend_min_block(j, index, n);
+  if (threadIdx.x == 0) {
+    out[blockIdx.x].j = j;
+    out[blockIdx.x].index = index;
+    out[blockIdx.x].n_valid = n;
+  }
+}
+
+// LT: lambdas the instantiation holds registers for (L <= LT; the arithmetic does not depend on it).
+// partials == null: the weights only (a slice of a weights_out too large for one buffer).
+template <int LT>
+__global__ void __launch_bounds__(BLEND_C)
+sfw_blend_first(const double *costs, const double *bias, int64_t T, sfw_blend_lambdas lam, int L, int K, const double *linvels,
+                const double *vy, const double *angvels, int nw, int list, const sfw_blend_min *mins, int n_mins, double *partials,
+                double *weights, sfw_blend_min *min_host) {
+  __shared__ double red[2][BLEND_C / WAVE][3 * LT];
+  const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
+  double j_min = INFINITY;
+  long long index_min = -1, n_valid = 0;
+  for (int i = tid; i < n_mins; i += BLEND_C) blend_min_take(j_min, index_min, n_valid, mins[i].j, mins[i].index, mins[i].n_valid);
+  blend_min_block(j_min, index_min, n_valid);
+  if (min_host && blockIdx.x == 0 && tid == 0) {
+    min_host->j = j_min;
+    min_host->index = index_min;
+    min_host->n_valid = n_valid;
+  }
+  const int64_t t = static_cast<int64_t>(blockIdx.x) * BLEND_C + tid;
+  const bool in = t < T;
+  const double c = in ? costs[t] : SFW_COST_INVALID;
+  const bool valid = c >= 0.0;
+  const double j = valid ? blend_j(bias, t, c) : 0.0;
+  double w[LT];
+#pragma unroll
+  for (int l = 0; l < LT; ++l) {
+    w[l] = 0.0;
+    if (l < L) {
+      if (valid) {
+        const double a = (j - j_min) / lam.v[l];
+        w[l] = exp(-a);
+      }
+      if (weights && in) weights[static_cast<int64_t>(l) * T + t] = w[l];
+    }
+  }
+  if (!partials) return;
+  const int n_ch = 2 * L + 3 * K * L;
+  double *const mine = partials + static_cast<int64_t>(blockIdx.x) * n_ch;
+  // row 0: eta and the sum of squares
+#pragma unroll
+  for (int l = 0; l < LT; ++l) {
+    if (l < L) {
+      const double s1 = blend_wave_sum(w[l]), s2 = blend_wave_sum(w[l] * w[l]);
+      if (lane == 0) {
+        red[0][wave][l] = s1;
+        red[0][wave][LT + l] = s2;
+      }
+    }
+  }
+  __syncthreads();
+  if (tid < 2 * LT && tid % LT < L)
+    mine[(tid / LT) * L + tid % LT] = ((red[0][0][tid] + red[0][1][tid]) + red[0][2][tid]) + red[0][3][tid];
+  // rows 1 .. K: the knots
+  const int64_t n = list ? T : 0;
+  for (int k = 0; k < K; ++k) {
+    const int buf = (k + 1) & 1;
+    double u[3] = {0.0, 0.0, 0.0};
+    if (in) {
+      if (list) {
+        u[0] = linvels[k * n + t];
+        if (vy) u[1] = vy[k * n + t];
+        u[2] = angvels[k * n + t];
+      } else {
+        u[0] = linvels[t / nw];
+        u[2] = angvels[t % nw];
+      }
+    }
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+#pragma unroll
+      for (int l = 0; l < LT; ++l) {
+        if (l < L) {
+          const double s = blend_wave_sum(w[l] * u[ch]);
+          if (lane == 0) red[buf][wave][ch * LT + l] = s;
+        }
+      }
+    }
+    __syncthreads();
+    if (tid < 3 * LT && tid % LT < L)
+      mine[2 * L + (static_cast<int64_t>(tid % LT) * K + k) * 3 + tid / LT] =
+          ((red[buf][0][tid] + red[buf][1][tid]) + red[buf][2][tid]) + red[buf][3][tid];
+  }
+}
+
+// out: eta[L] | sum_w2[L] | u[L][K][3]
+__global__ void __launch_bounds__(BLEND_C) sfw_blend_last(const double *__restrict__ partials, int64_t blocks, int L, int K, double *out) {
+  const int n_ch = 2 * L + 3 * K * L;
+  const int ch = static_cast<int>(blockIdx.x) * BLEND_C + threadIdx.x;
+  if (ch >= n_ch) return;
+  double acc = partials[ch];
+#pragma unroll 8
+  for (int64_t b = 1; b < blocks; ++b) acc = acc + partials[b * n_ch + ch];
+  if (ch >= 2 * L) {
+    const int l = (ch - 2 * L) / (3 * K);
+    double eta = partials[l];
+#pragma unroll 8
+    for (int64_t b = 1; b < blocks; ++b) eta = eta + partials[b * n_ch + l];
+    acc = eta > 0.0 ? acc / eta : 0.0;  // (no valid sample: eta == 0, every mean 0.0)
+  }
+  out[ch] = acc;
+}
+#pragma clang fp contract(fast)
+#endif  // SFW_STRICT_BUILD
+
 // Multi-device exchange record (sfw_multi_*): row `r` of an [R,5] table = this rank's selection key
 // (cost, -linvel, |angvel|, -index) and its count of valid samples; every other row +inf, so that an
 // element-wise all-reduce(min) over the ranks assembles the table of all local keys.
@@ -3681,6 +3855,50 @@ hipError_t sfw_launch_ensemble(const double *const *terms, const double *probs, 
                        sel_host);
   return hipGetLastError();
 }
+
+#ifndef SFW_STRICT_BUILD
+int64_t sfw_blend_blocks(int64_t T) { return (T + BLEND_C - 1) / BLEND_C; }
+int64_t sfw_blend_min_blocks(int64_t T) { return std::min<int64_t>(sfw_blend_blocks(T), BLEND_MIN_BLOCKS); }
+template <int LT>
+static void blend_first_typed(dim3 grid, hipStream_t stream, const double *costs, const double *bias, int64_t T,
+                              const sfw_blend_lambdas &lam, int L, int K, const double *linvels, const double *vy,
+                              const double *angvels, int nw, int list, const sfw_blend_min *mins, int n_mins, double *partials,
+                              double *weights, sfw_blend_min *min_host) {
+  hipLaunchKernelGGL(sfw_blend_first<LT>, grid, dim3(BLEND_C), 0, stream, costs, bias, T, lam, L, K, linvels, vy, angvels, nw, list,
+                     mins, n_mins, partials, weights, min_host);
+}
+static hipError_t blend_first(const double *costs, const double *bias, int64_t T, const sfw_blend_lambdas &lam, int L, int K,
+                              const double *linvels, const double *vy, const double *angvels, int nw, int list,
+                              const sfw_blend_min *mins, double *partials, double *weights, sfw_blend_min *min_host,
+                              hipStream_t stream) {
+  const dim3 grid(static_cast<unsigned>(sfw_blend_blocks(T)));
+  const int n_mins = static_cast<int>(sfw_blend_min_blocks(T));
+  const auto launch = L <= 1 ? blend_first_typed<1> : L <= 4 ? blend_first_typed<4> : blend_first_typed<SFW_BLEND_MAX_L>;
+  launch(grid, stream, costs, bias, T, lam, L, K, linvels, vy, angvels, nw, list, mins, n_mins, partials, weights, min_host);
+  return hipGetLastError();
+}
+hipError_t sfw_launch_blend(const double *costs, const double *bias, int64_t T, const sfw_blend_lambdas &lam, int L, int K,
+                            const double *linvels, const double *vy, const double *angvels, int32_t nw, bool list,
+                            sfw_blend_min *mins, double *partials, double *weights, sfw_blend_min *min_host, double *out_host,
+                            hipStream_t stream) {
+  if (T < 1 || L < 1 || L > SFW_BLEND_MAX_L || K < 1 || (!list && (K != 1 || nw < 1)) || sfw_blend_blocks(T) > INT_MAX ||
+      !costs || !linvels || !angvels || !mins || !partials || !min_host || !out_host)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(sfw_blend_min_kernel, dim3(static_cast<unsigned>(sfw_blend_min_blocks(T))), dim3(BLEND_C), 0, stream, costs, bias,
+                     T, mins);
+  hipError_t e = blend_first(costs, bias, T, lam, L, K, linvels, vy, angvels, nw, list ? 1 : 0, mins, partials, weights, min_host, stream);
+  if (e != hipSuccess) return e;
+  const int64_t n_ch = sfw_blend_channels(L, K);
+  hipLaunchKernelGGL(sfw_blend_last, dim3(static_cast<unsigned>((n_ch + BLEND_C - 1) / BLEND_C)), dim3(BLEND_C), 0, stream,
+                     static_cast<const double *>(partials), sfw_blend_blocks(T), L, K, out_host);
+  return hipGetLastError();
+}
+hipError_t sfw_launch_blend_weights(const double *costs, const double *bias, int64_t T, const sfw_blend_lambdas &lam, int L,
+                                    const sfw_blend_min *mins, double *weights, hipStream_t stream) {
+  if (T < 1 || L < 1 || L > SFW_BLEND_MAX_L || sfw_blend_blocks(T) > INT_MAX || !costs || !mins || !weights) return hipErrorInvalidValue;
+  return blend_first(costs, bias, T, lam, L, 1, nullptr, nullptr, nullptr, 1, 1, mins, nullptr, weights, nullptr, stream);
+}
+#endif  // SFW_STRICT_BUILD
 
 // ---- one launch per control cycle ------------------------------------------------------------------------------------
 static size_t cycle_k2_bytes(const sfw_launch &L, bool obs_lds) {

@@ -22,6 +22,8 @@ from ._abi import (
     SfwBatchDesc,
     SfwBest,
     SfwBestKey,
+    SfwBlendStat,
+    SFW_BLEND_MAX_L,
     SfwGoalArgs,
     SfwParams,
     SfwRobotState,
@@ -165,6 +167,7 @@ def lib():
                                           C.POINTER(SfwGoalArgs), C.c_int64]
         L.sfw_score_sequences.argtypes = [vp, C.POINTER(SfwRobotState), vp, vp, vp, C.c_int32, C.c_int32, vp,
                                           C.POINTER(SfwGoalArgs), vp, C.POINTER(SfwBest)]
+        L.sfw_grid_blend.argtypes = [vp, vp, C.c_int32, vp, C.POINTER(SfwBlendStat), vp, vp]
         _lib = L
     return _lib
 
@@ -193,10 +196,11 @@ class HipScorer:
         self._grid = None
         self._n_agents = self._n_staged_agents = 0  # as handed over last / as the last stage uploaded them
 
-    def _mark_staged(self, grid):
-        """Every stage, by whatever call, ends here: the grid's shape and the agent count that stage uploaded (what
-        grid_crowd sizes its rows by) are recorded in this one place."""
+    def _mark_staged(self, grid, knots=1):
+        """Every stage, by whatever call, ends here: the grid's shape, the knots per sample (what blend sizes its mean by)
+        and the agent count that stage uploaded (what grid_crowd sizes its rows by) are recorded in this one place."""
         self._grid = grid
+        self._n_knots = knots
         self._n_staged_agents = self._n_agents
 
     @classmethod
@@ -341,7 +345,7 @@ class HipScorer:
                                               vyv.ctypes.data if vyv is not None and vyv.size else None,
                                               vth.ctypes.data if vth.size else None, n, K, ks.ctypes.data if len(ks) else None,
                                               C.byref(ga), index_base), "sfw_sequences_stage")
-        self._mark_staged((n, 1))
+        self._mark_staged((n, 1), knots=K)
 
     def score_sequences(self, robot_state, vx, vtheta, knot_steps, goal_args, vy=None):
         """The blocking call over command sequences: (costs[n], best)."""
@@ -354,7 +358,7 @@ class HipScorer:
                                               vyv.ctypes.data if vyv is not None and vyv.size else None,
                                               vth.ctypes.data if vth.size else None, n, K, ks.ctypes.data if len(ks) else None,
                                               C.byref(ga), costs.ctypes.data if n else None, C.byref(best)), "sfw_score_sequences")
-        self._mark_staged((n, 1))
+        self._mark_staged((n, 1), knots=K)
         return costs, best.as_dict()
 
     def prepared(self, robot_state, linvels, angvels, goal_args, index_base=0, zero_copy=False):
@@ -508,6 +512,33 @@ class HipScorer:
         self._check(lib().sfw_grid_rescore(self._h, C.cast(w.ctypes.data, C.POINTER(SfwWeights)), K, best,
                                            costs.ctypes.data if costs is not None else None), "sfw_grid_rescore")
         return [best[k].as_dict() for k in range(K)], costs
+
+    # -- softmin blend ---------------------------------------------------------
+    def blend(self, lambdas, bias=None, want_weights=False):
+        """sfw_grid_blend over the last launch (grid, list or sequences): the softmin weights exp(-(J - J_min) / lambda) of
+        L temperatures, reduced on the device.  bias: one value per sample added to its cost (None: none).  Returns
+        (stats: L dicts with lambda, j_min, eta, sum_w2, ess, n_valid, index_min; u[L, K, 3]: the weighted mean of the
+        (vx, vy, vtheta) knots; weights[L, T] or None).  Read-only for the launch."""
+        lam = np.ascontiguousarray(np.asarray(lambdas, dtype=np.float64).reshape(-1))
+        L = len(lam)
+        if L < 1 or L > SFW_BLEND_MAX_L:
+            raise ValueError(f"blend: need 1 .. {SFW_BLEND_MAX_L} lambdas, got {L}")
+        if not np.all(np.isfinite(lam)) or not np.all(lam > 0.0):
+            raise ValueError("blend: every lambda must be finite and > 0")
+        # (no grid staged through this object, e.g. since sfw_score_one: the library answers SFW_ERR_STATE)
+        nv, nw = self._grid if self._grid is not None else (0, 0)
+        T, K = nv * nw, getattr(self, "_n_knots", 1) if self._grid is not None else 64  # (SFW_SEQ_MAX_KNOTS: room for any stage)
+        b = None
+        if bias is not None:
+            b = np.ascontiguousarray(np.asarray(bias, dtype=np.float64).reshape(-1))
+            if len(b) != T:
+                raise ValueError(f"blend: bias must hold one value per sample ({T}), got {len(b)}")
+        stats = (SfwBlendStat * L)()
+        u = np.zeros((L, K, 3), dtype=np.float64)
+        w = np.zeros((L, T), dtype=np.float64) if want_weights else None
+        self._check(lib().sfw_grid_blend(self._h, lam.ctypes.data, L, b.ctypes.data if b is not None and T else None, stats,
+                                         u.ctypes.data, w.ctypes.data if w is not None and T else None), "sfw_grid_blend")
+        return [stats[l].as_dict() for l in range(L)], u, w
 
 
 def plan_row_blocks(linvels, angvels, robot_state, goal_args, sim_time, num_steps, n_agents, n_ranks):
