@@ -912,7 +912,7 @@ int plan_prefix(sfw_handle h, int64_t chunk, int S) {
 // standing person) and motion exactly along the connecting line (two people on one grid-aligned line walking towards
 // or away from each other).  There the model's interaction angle theta is mathematically 0 or +-pi and its angular
 // term -sign(theta) exp(-d/B - (n B theta)^2) leftNormal(Ihat) is discontinuous.  The kernels take sign(theta) from
-// w x diff, exactly 0 here: the sign of a zero (their exact zero in the SFW_SIGN_OF_ZERO=0 build).  lightsfm instead forms theta as the difference of two
+// w x diff, exactly 0 here, and their angular term is then exactly 0.  lightsfm instead forms theta as the difference of two
 // atan2 — of vectors equal up to rounding when I = lambda w + dhat points along dhat (sign(theta) = -1, 0 or +1 by the
 // rounding of the HOST's libm: a full-magnitude lateral force on an ordinary scene), of opposite vectors when the pair
 // separates faster than 1/lambda (theta = +-pi by the sign of a zero).  Such a configuration can only come from the state
@@ -945,22 +945,6 @@ void rest_forces(const sfw_params &p, const std::vector<std::pair<int32_t, int32
       out[2 * i] += p.sfm_force_factor_social * fa * -ey;                             // leftNormal = (-y, x)
       out[2 * i + 1] += p.sfm_force_factor_social * fa * ex;
     }
-#if SFW_SIGN_OF_ZERO
-    // ... minus what the kernels themselves apply to such a pair: their |theta| is 0 or pi by the side I points to, their
-    // exponential a 1e-12 polynomial (the difference to this libm one stays as a 1e-12 share of the term), their sign the
-    // sign bit of w x diff = fma(wx, dy, -(wy dx)) — of a ZERO here, which depends on the order the pair is taken in
-    // (v - v is +0 either way while diff changes sign).  Both K2 organisations evaluate an unordered pair once, as (a, b)
-    // with b = (a + row + 1) mod A, row < A / 2 (the last row of an even A only for a < A / 2), and give b the negative.
-    const int fwd = ((j - i) % A + A) % A, rows = A / 2;
-    const bool i_first = fwd < rows || (fwd == rows && ((A & 1) ? true : i < rows));
-    auto rev = [](double x) { return -x + 0.0; };  // b - a from a - b: the exact negative, a zero difference stays +0
-    const double cw_k = i_first ? std::fma(wx, dy, -(wy * dx)) : std::fma(rev(wx), rev(dy), -(rev(wy) * rev(dx)));
-    const double tk = (ix * ux + iy * uy) < 0.0 ? M_PI : 0.0, sk = p.sfm_n * B * tk;
-    const double s_k = std::signbit(cw_k) ? -1.0 : 1.0;
-    const double fk = -s_k * std::exp(-dn / B - sk * sk);
-    out[2 * i] -= p.sfm_force_factor_social * fk * -ey;
-    out[2 * i + 1] -= p.sfm_force_factor_social * fk * ex;
-#endif
   }
 }
 
@@ -980,12 +964,6 @@ void rest_forces(const sfw_params &p, const std::vector<std::pair<int32_t, int32
 // the device's own pose rollout produced; the rounding noise at that position is not reproduced.
 bool pinned_rest_table(const sfw_params &p, const sfw_robot_state &rs, const double *pos, const sfw_agent_const *cst, int A,
                        double *out) {
-#if SFW_SIGN_OF_ZERO
-  // (round 3's A/B build: its kernels apply a sign-of-zero lateral term of their own to every pair at exact rest, at every
-  // step, which this table does not take back out — ADVICE r5.  No table there: that build is for timing comparisons.)
-  (void)p; (void)rs; (void)pos; (void)cst; (void)A; (void)out;
-  return false;
-#endif
   bool any = false;
   for (int i = 1; i < A; ++i) any |= (cst[i].desired_velocity == 0.0);
   if (!any) return false;
@@ -1769,15 +1747,6 @@ int create_handle(const sfw_params *params, int device, hipStream_t stream, hipS
   int count = 0;
   if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return SFW_ERR_NO_DEVICE;
   if (device < 0 || device >= count) return SFW_ERR_INVALID_ARG;
-#ifdef SFW_ABLATION_BUILD
-  {  // results wrong by construction (sfw_device.h): only a timing script that says so gets a handle
-    const char *ok = std::getenv("SFW_ALLOW_ABLATION");
-    if (!ok || ok[0] != '1') {
-      std::fprintf(stderr, "[sfw] this libsfw_hip.so is an ABLATION build (results wrong by construction); set SFW_ALLOW_ABLATION=1 to time it\n");
-      return SFW_ERR_UNSUPPORTED;
-    }
-  }
-#endif
   sfw_handle h = new (std::nothrow) sfw_planner_s();
   if (!h) return SFW_ERR_HIP;
   h->live.params = *params;

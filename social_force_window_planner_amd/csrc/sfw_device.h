@@ -8,24 +8,9 @@
 
 #include "../../include/sfw_hip.h"
 
-// 0 (default): the pair term's angular part is exactly 0 for a pair whose w x diff is exactly 0 — sign(theta) = 0, as in
-// lightsfm for theta == 0 — at every step (a compare and one integer select per pair evaluation, exp_fast2_gated); the host
-// evaluates the reference's rounding-noise term for such pairs of the handed-over state (rest_forces).
-// 1: round 3's form, kept for A/B: the sign BIT of w x diff decides also for a zero (one v_bfi_b32, 2 issue slots less per
-// pair) and rest_forces takes the kernels' own term back out — right for the handed-over state only: an alignment that
-// persists (a robot driving straight at a person on its axis) then gets a full-magnitude lateral force from step 1 on.
-#ifndef SFW_SIGN_OF_ZERO
-#define SFW_SIGN_OF_ZERO 0
-#endif
-
-// Ablation builds (make EXTRA=-DSFW_ABL_...: a part of a kernel taken out to price it) produce results that are wrong by
-// construction.  Any of those macros marks the whole library: sfw_create refuses to make a handle unless SFW_ALLOW_ABLATION=1
-// is in the environment (the timing scripts under tools/ set it; no test and no bench run does).
-#if defined(SFW_ABL_NOROBOT) || defined(SFW_ABL_NOREAD) || defined(SFW_ABL_NOMATH) || defined(SFW_ABL_NOATOM) ||        \
-    defined(SFW_ABL_NOAGENT) || defined(SFW_ABL_KEEPALIVE) || defined(SFW_ABL_HALF_LDS) || defined(SFW_ABL_NOOBSLOOP) || \
-    defined(SFW_ABL_NOREDUCE)
-#define SFW_ABLATION_BUILD 1
-#endif
+// The pair term's angular part is exactly 0 for a pair whose w x diff is exactly 0 — sign(theta) = 0, as in lightsfm for
+// theta == 0 — at every step (a compare and one integer select per pair evaluation, exp2_fast2_gated); the host evaluates the
+// reference's rounding-noise term for such pairs of the handed-over state (sfw_capi.hip rest_forces).
 
 // Device shape the launch heuristics default to (a whole MI355X: 256 compute units in 8 XCDs of 32); a handle reads its
 // device's own (hipDeviceProp_t.multiProcessorCount) and carries it into every launch (sfw_launch.n_cu / n_xcd).

@@ -828,9 +828,6 @@ __device__ __forceinline__ unsigned xcd_contiguous(unsigned b, unsigned n, unsig
 // and reloads them with v_readlane inside the loop (14 VALU issues per pair in the first version of this layout).
 typedef const __attribute__((address_space(4))) sfw_launch *late_launch;
 __device__ __forceinline__ late_launch late_args() {
-#ifdef SFW_DBG_NO_LAUNDER
-  return (late_launch)__builtin_amdgcn_kernarg_segment_ptr();
-#endif
   const __attribute__((address_space(4))) void *p =
       (const __attribute__((address_space(4))) void *)__builtin_amdgcn_kernarg_segment_ptr();
   asm volatile("" : "+s"(p));
@@ -934,15 +931,11 @@ __device__ __forceinline__ void pair_force(const sfm_consts<R> &k, R dx, R dy, R
   const R a = fmax(fma(dn * rl, k.neg_l2e_inv_gamma, k.l2_f_social), R(-1100));
   const R t2 = l2 * (theta * theta);      // (B theta)^2 = gamma^2 |I|^2 theta^2; gamma^2 sits in c_vel / c_ang
   R ev, ea;  // Fs exp(-|diff|/B - (n' B theta)^2), Fs exp(-|diff|/B - (n B theta)^2)
-#if SFW_SIGN_OF_ZERO
-  exp2_fast2(k.pc, fma(k.c_vel, t2, a), fma(k.c_ang, t2, a), ev, ea);
-#else
   // sign(theta) = sign(w x diff) is 0 for a pair whose w x diff is exactly 0 (relative rest, motion exactly along the
   // connecting line — which PERSISTS over the steps for a robot driving straight at a person on its axis): the angular
   // term is then exactly 0, as lightsfm's is for theta == 0.  The zero enters through the exponent of the term's 2^k
   // scaling (a compare and ONE select on an integer; as a select on the f64 result it was a compare and two).
   exp2_fast2_gated(k.pc, fma(k.c_vel, t2, a), fma(k.c_ang, t2, a), cw, ev, ea);
-#endif
   if constexpr (NORM_ONLY) {
     const R q = fma(ev, ev, ea * ea);
     R rq, nq;
@@ -951,10 +944,7 @@ __device__ __forceinline__ void pair_force(const sfm_consts<R> &k, R dx, R dy, R
     fy = R(0);
     return;
   }
-  // sign(theta) * exp(...): the sign BIT of cw, one v_bfi_b32 (ea is exactly 0 when cw is: its sign is then immaterial).
-  // SFW_SIGN_OF_ZERO=1 (round 3's default, kept for A/B) skips the gate above: the sign of a zero then decides, and the host
-  // takes that term back out for the pairs of the handed-over state (rest_forces, sfw_capi.hip) — but not for an alignment
-  // that persists past it.
+  // sign(theta) * exp(...): the sign BIT of cw, one v_bfi_b32 (ea is exactly 0 when cw is: its sign is then immaterial)
   ea = copysign_from(ea, cw);
   const R gx = ix * rl, gy = iy * rl;    // Ihat
   // f = -ev * Ihat - ea * leftNormal(Ihat),  leftNormal(x,y) = (-y, x)
@@ -1021,10 +1011,7 @@ __device__ __forceinline__ void desired_force(const agent_consts &k, double px, 
 // cycle with 50 people, profiles/r05_cycle_k2.txt.)
 constexpr int OBS_SEG = 16;
 constexpr int OBS_AGENT_LANES = WAVE / OBS_SEG;  // flat form: 4 lanes per segment, each with its own agents
-#ifndef SFW_OBS_KA
-#define SFW_OBS_KA 4
-#endif
-constexpr int OBS_AGENTS_PER_LANE = SFW_OBS_KA;  // ... up to four per round of tasks: 16 agents x 16 segments per round
+constexpr int OBS_AGENTS_PER_LANE = 4;  // ... up to four per round of tasks: 16 agents x 16 segments per round
 // The points a WAVE-UNIFORM loop reads come straight from global memory through the scalar cache (obs_global: the array
 // as a constant-address-space pointer, so that the loads are s_load and cost neither LDS space nor VALU/VMEM issue);
 // the flat form's task loop, whose lanes walk 16 different segments, reads them with per-lane vector loads (the scan is a
@@ -1036,26 +1023,6 @@ __device__ __forceinline__ obs_global_ptr obs_global(const double *obstacles) {
 }
 __device__ __forceinline__ double2 obs_point(const double2 *obs, int o) { return obs[o]; }
 __device__ __forceinline__ double2 obs_point(obs_global_ptr obs, int o) { return double2{obs[2 * o], obs[2 * o + 1]}; }
-// The hand-pipelined scalar loads of obstacle_sums (obs_group_issue / _wait: the next four points' s_load in flight while four
-// are evaluated, across the segment boundaries) — what VERDICT r3 asked for — measured and OFF: their scalar bookkeeping per
-// group of four costs more than the latency they hide, with several waves per SIMD (register form, cfg2 + 240 points: K2 3.33
-// -> 3.56 ms) and for a lone wave alike (flat form's lane-per-agent pass, control cycle with 50 people and 60 points: K2 474
-// -> 499 us, 16 points: 385 -> 409).  -DSFW_FLAT_PIPELINED=true builds them into the flat form's lane-per-agent pass.
-#ifndef SFW_FLAT_PIPELINED
-#define SFW_FLAT_PIPELINED false
-#endif
-#ifndef SFW_OBS_UNIFORM
-#define SFW_OBS_UNIFORM 1  // the task loop of a GPU-filling launch with wave-uniform trip counts (obstacle_segment_multi_uniform)
-#endif
-#ifndef SFW_OBS_UNIFORM_LDS
-#define SFW_OBS_UNIFORM_LDS 1  // ... and of an under-filled one (LDS copy of the points)
-#endif
-#ifndef SFW_SKIP_EMPTY_K2
-#define SFW_SKIP_EMPTY_K2 1  // a robot alone without laser points: sfw_no_social_kernel instead of K2
-#endif
-#ifndef SFW_OBS_UNROLL_SCALAR
-#define SFW_OBS_UNROLL_SCALAR 4  // points per s_load group of a wave-uniform loop (4: one s_load_dwordx16)
-#endif
 // one (agent, point) term: a += exp(-|p - q| / sigma) / |p - q| * (p - q)
 template <typename R>
 __device__ __forceinline__ void obstacle_term(const sfm_consts<R> &k, double2 q, double px, double py, R nis, R &ax, R &ay) {
@@ -1074,66 +1041,28 @@ __device__ __forceinline__ void obstacle_segment(const sfm_consts<R> &k, ObsPtr 
                                                  double px, double py, R nis, R &ax, R &ay) {
   ax = R(0);
   ay = R(0);
-#pragma unroll SFW_OBS_UNROLL_SCALAR
+#pragma unroll 4  // points per s_load group of a wave-uniform loop (4: one s_load_dwordx16)
   for (int o = o_begin; o < o_end; ++o) obstacle_term<R>(k, obs_point(obs, o), px, py, nis, ax, ay);
 }
 // The same segment for NJ agents at once (the flat form's task loop): a point is loaded ONCE per lane — a per-lane vector
 // load, the lanes of a wave walk 16 different segments — and meets the lane's NJ agents.  With one agent per lane the
 // vector memory pipe, not the VALU, set the pace of a 720-point scan (one 16-byte load per 27 issue slots and lane).
 // Every (agent, segment) sum is formed in point order as in obstacle_segment: bit-identical.
-// This version walks the lane's own bounds [o_begin, o_end) — a divergent loop; the kernels run obstacle_segment_multi_uniform
-// below (SFW_OBS_UNIFORM / SFW_OBS_UNIFORM_LDS = 0 build this one back in: profiles/r04_ab_uniform*.txt).
 typedef const __attribute__((address_space(3))) double *obs_lds_ptr;
 __device__ __forceinline__ double2 obs_point(obs_lds_ptr obs, int o) { return double2{obs[2 * o], obs[2 * o + 1]}; }
-template <typename R, int NJ, typename ObsPtr>
-__device__ __forceinline__ void obstacle_segment_multi(const sfm_consts<R> &k, ObsPtr obs, int o_begin, int o_end,
-                                                       const double *px, const double *py, R neg_l2e_inv_sigma, R *ax, R *ay) {
-#pragma unroll
-  for (int j = 0; j < NJ; ++j) ax[j] = ay[j] = R(0);
-  const R nis = neg_l2e_inv_sigma;
-  auto terms = [&](const double2 q) {
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) obstacle_term<R>(k, q, px[j], py[j], nis, ax[j], ay[j]);
-  };
-  // One point ahead, two register sets in turn: the load of the next point is in flight while a point meets the lane's
-  // agents (a lone wave — a control cycle's — otherwise sits out a round trip per point).  The loads run up to two points
-  // past the segment — into the next segment, or into the padding behind the last point (64 bytes in global memory,
-  // sfw_set_agents; two points in the LDS copy, lds_layout): loaded, never evaluated, and no index to clamp.
-  if (o_begin < o_end) {
-    double2 qa = obs_point(obs, o_begin);
-    if constexpr (NJ <= 2) {
-      // one or two agents per lane (small crowds: a control cycle's lone waves): two points per iteration in ONE basic block,
-      // so that the 2 NJ independent chains are interleaved — a lone wave issues a dependent instruction every ~8.5 cycles,
-      // an independent one every ~5 (control cycle with 5 people and 240 points: K2 218 -> 209 us; a robot alone: 123 -> 111)
-      int o = o_begin;
-#pragma unroll 1
-      for (; o + 2 <= o_end; o += 2) {
-        const double2 qb = obs_point(obs, o + 1);
-        const double2 qn = obs_point(obs, o + 2);
-        terms(qa);
-        terms(qb);
-        qa = qn;
-      }
-      if (o < o_end) terms(qa);
-    } else {
-#pragma unroll 1
-      for (int o = o_begin; o < o_end; o += 2) {
-        const double2 qb = obs_point(obs, o + 1);
-        terms(qa);
-        qa = obs_point(obs, o + 2);
-        if (o + 1 < o_end) terms(qb);
-      }
-    }
-  }
-}
-// The task loop of a GPU-FILLING launch (points in global memory): the same sums with wave-uniform trip counts.  A lane's
-// segment holds Lseg points, or the `partial` rest of the scan, or none: written with the lane's own bounds (above) the loop
-// is divergent — index, compare, address and the copies between the two register sets cost 8 vector instructions per point
-// next to the 4 x 24 of the terms (PMC: 26.6 per evaluation).  Here the wave runs `partial` iterations with every lane that
-// has points and Lseg - partial more with the lanes of the full segments: scalar counter, scalar base address + the lane's
-// fixed byte offset (global_load saddr form), loads written as asm one point ahead into two register sets that the
-// unrolled body alternates without copying — the waits are explicit, the compiler does not count an asm load.  Reads up to
-// two points past the range like the loop above.
+// The sums are formed with WAVE-UNIFORM trip counts.  A lane's segment holds Lseg points, or the `partial` rest of the scan, or
+// none: written with the lane's own bounds the loop is divergent — index, compare, address and the copies between the two
+// register sets cost 8 vector instructions per point next to the 4 x 24 of the terms (PMC: 26.6 per evaluation;
+// profiles/r04_ab_uniform*.txt).  Here the wave runs `partial` iterations with every lane that has points and Lseg - partial
+// more with the lanes of the full segments.
+// One point ahead, two register sets in turn: the load of the next point is in flight while a point meets the lane's agents
+// (a lone wave — a control cycle's — otherwise sits out a round trip per point), two points per iteration in ONE basic block,
+// so that the independent chains are interleaved.  The loads run up to two points past the range — into the next segment, or
+// into the padding behind the last point (64 bytes in global memory, sfw_set_agents; two points in the LDS copy, lds_layout):
+// loaded, never evaluated, and no index to clamp.
+// Points in global memory (a GPU-FILLING launch): scalar counter, scalar base address + the lane's fixed byte offset
+// (global_load saddr form), loads written as asm into two register sets that the unrolled body alternates without copying —
+// the waits are explicit, the compiler does not count an asm load.
 typedef double obs_d2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ obs_d2 obs_load_ahead(const double2 *base, uint32_t lane_bytes) {
   obs_d2 q;
@@ -1215,95 +1144,25 @@ template <typename R>
 __device__ __forceinline__ double obstacle_scale(const sfm_consts<R> &k, const agent_consts &c, double radius) {
   return static_cast<double>(sfwm::exp2_fast(k.pc, static_cast<R>(fma(radius, c.l2e_inv_sigma, c.l2_f_obstacle)))) * c.inv_O;
 }
-// Four points = one s_load_dwordx16 into 16 SGPRs, issued and awaited by hand: the loads of a wave-uniform pass are
-// software-pipelined ACROSS the segments — while a group of four points is evaluated (4 x 27 issue slots) the next group's
-// load is in flight, also when that group opens the next segment.  Left to the compiler every s_load was followed at once
-// by s_waitcnt lgkmcnt(0) (scalar loads return out of order: any use needs the counter at zero), so a lone wave — a control
-// cycle, a coarse shared-prefix level — sat out the scalar-cache latency once per four points, sixteen times per agent and
-// step for a 64-point scan.  Two register sets alternate; a set is only read after the wait that follows its load (the asm
-// operands say so: the wait "modifies" the set).
-typedef double obs_group __attribute__((ext_vector_type(8)));  // x0 y0 x1 y1 x2 y2 x3 y3
-__device__ __forceinline__ void obs_group_issue(obs_group &g, obs_global_ptr p) {
-  asm volatile("s_load_dwordx16 %0, %1, 0x0" : "=s"(g) : "s"(p));
-}
-__device__ __forceinline__ void obs_group_wait(obs_group &g) { asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(g)); }
-
 // all sixteen segments on one lane: the agent's raw sums (tx, ty) and the factor they are to be multiplied with.  The
 // callers form the force as ONE explicit fma per component, acc = fma(t, scale, acc), in both organisations: written as a
 // product followed by +=, whether the two are contracted into an fma is the compiler's choice per call site, and the
 // organisations stopped being bit-identical the day it chose differently.
 // The points array is readable 48 bytes past its last point (sfw_set_agents pads it): the last group of a segment is
 // loaded whole and evaluated up to the segment's end.
-// PIPELINED = false (every caller's default, see SFW_FLAT_PIPELINED): the compiler's loop (s_load, wait, four interleaved
-// terms).  Same sums in the same order either way.
-template <typename R, bool PIPELINED>
+// The loop is the compiler's (s_load, wait, four interleaved terms): the next four points' s_load issued by hand while four are
+// evaluated cost more than it hid (cfg2 + 240 points: K2 3.33 -> 3.56 ms; control cycle with 50 people: 474 -> 499 us).
+template <typename R>
 __device__ __forceinline__ void obstacle_sums(const sfm_consts<R> &k, const agent_consts &c, obs_global_ptr obs, double px,
                                               double py, double radius, double &tx_out, double &ty_out, double &scale) {
   const int O = c.O, L = (O + OBS_SEG - 1) / OBS_SEG;
   const R nis = sfwm::vgpr_const(static_cast<R>(-c.l2e_inv_sigma));
   R tx = R(0), ty = R(0);  // the segment sums are added to +0 in segment order (the flat form's reduction does the same)
   R ax = R(0), ay = R(0);
-  if constexpr (!PIPELINED) {
-    for (int b = 0; b < O; b += L) {  // ceil(O / L) <= 16 segments
-      obstacle_segment<R, obs_global_ptr>(k, obs, b, min(b + L, O), px, py, nis, ax, ay);
-      tx += ax;
-      ty += ay;
-    }
-    tx_out = static_cast<double>(tx);
-    ty_out = static_cast<double>(ty);
-    scale = obstacle_scale<R>(k, c, radius);
-    return;
-  }
-  // one group: `cnt` points of set g, then — if the segment ends with it — the segment's sum joins the total
-  auto eval = [&](const obs_group &g, int cnt, bool seg_done) {
-    if (cnt == 4) {
-      obstacle_term<R>(k, double2{g.s0, g.s1}, px, py, nis, ax, ay);
-      obstacle_term<R>(k, double2{g.s2, g.s3}, px, py, nis, ax, ay);
-      obstacle_term<R>(k, double2{g.s4, g.s5}, px, py, nis, ax, ay);
-      obstacle_term<R>(k, double2{g.s6, g.s7}, px, py, nis, ax, ay);
-    } else {
-      asm volatile("" ::: "memory");  // not the same code as above: the compiler must not merge the first term of the two paths
-      obstacle_term<R>(k, double2{g.s0, g.s1}, px, py, nis, ax, ay);  // (the four terms of a full group are to be interleaved)
-      if (cnt > 1) obstacle_term<R>(k, double2{g.s2, g.s3}, px, py, nis, ax, ay);
-      if (cnt > 2) obstacle_term<R>(k, double2{g.s4, g.s5}, px, py, nis, ax, ay);
-    }
-    if (seg_done) {
-      tx += ax;
-      ty += ay;
-      ax = R(0);
-      ay = R(0);
-    }
-  };
-  // the group after the one at o of the segment ending at e: (o, e) advance, false when there is none
-  auto advance = [&](int &o, int &e) {
-    o += 4;
-    if (o >= e) {  // next segment
-      o = e;
-      e = min(e + L, O);
-    }
-    return o < O;
-  };
-  if (O > 0) {
-    int o = 0, e = min(L, O);
-    obs_group ga, gb;
-    obs_group_issue(ga, obs);
-    for (;;) {
-      int o2 = o, e2 = e;
-      const bool more = advance(o2, e2);
-      obs_group_wait(ga);
-      if (more) obs_group_issue(gb, obs + 2 * o2);
-      eval(ga, min(4, e - o), o + 4 >= e);
-      if (!more) break;
-      o = o2;
-      e = e2;
-      const bool more2 = advance(o2, e2);
-      obs_group_wait(gb);
-      if (more2) obs_group_issue(ga, obs + 2 * o2);
-      eval(gb, min(4, e - o), o + 4 >= e);
-      if (!more2) break;
-      o = o2;
-      e = e2;
-    }
+  for (int b = 0; b < O; b += L) {  // ceil(O / L) <= 16 segments
+    obstacle_segment<R, obs_global_ptr>(k, obs, b, min(b + L, O), px, py, nis, ax, ay);
+    tx += ax;
+    ty += ay;
   }
   tx_out = static_cast<double>(tx);
   ty_out = static_cast<double>(ty);
@@ -1856,7 +1715,7 @@ __device__ __forceinline__ void social_reg_wave(const sfw_launch &L, const int G
           desired_force(c0, px, py, vx, vy, hg != 0, ak.gx, ak.gy, ak.gr, ak.dv, fx[r], fy[r]);
           if (O > 0) {
             double tx, ty, sc;
-            obstacle_sums<R, false>(k0, c0, obs_global(L.obstacles), px, py, ak.rad, tx, ty, sc);
+            obstacle_sums<R>(k0, c0, obs_global(L.obstacles), px, py, ak.rad, tx, ty, sc);
             fx[r] = fma(tx, sc, fx[r]);
             fy[r] = fma(ty, sc, fy[r]);
           }
@@ -1930,9 +1789,6 @@ __device__ __forceinline__ void social_reg_wave(const sfw_launch &L, const int G
     // the step's table row (a scalar base) plus its own byte offset, fixed for the rollout (G <= 32, plan_for; forming the address from the item
     // tables every step cost ~90 and, at 80 VGPRs, the scratch spills around it).  The pair pass below holds no
     // compiler-visible DS or VMEM instruction (lds_pair_state, lds_add_pair), so nothing in it waits for this load.
-#if defined(SFW_ABL_NOROBOT)
-    if (step == step_begin)
-#endif
     if (lane < 2 * Gn)
       __builtin_amdgcn_global_load_lds(
           (const __attribute__((address_space(1))) void *)(reinterpret_cast<const char *>(L.ptab + static_cast<int64_t>(step) * L.row_units) + rs_off),
@@ -1942,22 +1798,12 @@ __device__ __forceinline__ void social_reg_wave(const sfw_launch &L, const int G
     auto pair_with = [&](int r, uint32_t jo) {
       R qx, qy;
       double pix, piy, vix, viy, pjx, pjy, vjx, vjy;
-#if defined(SFW_ABL_NOREAD)
-      pix = fx[r]; piy = fy[r]; vix = sw[r] + 1.0; viy = 0.5; pjx = fx[r] + static_cast<double>(jo); pjy = fy[r] - 3.0; vjx = 0.25; vjy = static_cast<double>(jo) * 0.001;
-#else
       lds_pair_state<PY, VX, VY>(io_[r], jo, pix, piy, vix, viy, pjx, pjy, vjx, vjy);
-#endif
-#if defined(SFW_ABL_NOMATH)
-      qx = R(pix + pjy - vjx); qy = R(piy - pjx + vix * viy + vjy);
-#else
       pair_force_state<R>(k, pix, piy, vix, viy, pjx, pjy, vjx, vjy, qx, qy);
-#endif
       fx[r] += static_cast<double>(qx);
       fy[r] += static_cast<double>(qy);
       // the partner receives -q: accumulated with the opposite sign, subtracted in the agent pass
-#if !defined(SFW_ABL_NOATOM)
       lds_add_pair<FJX, FJY>(jo, static_cast<double>(qx), static_cast<double>(qy));
-#endif
     };
     // the partner offset advances by one word per row, so it can only MEET the bound
     auto next_partner = [&](int r) {
@@ -2000,11 +1846,7 @@ __device__ __forceinline__ void social_reg_wave(const sfw_launch &L, const int G
     const bool with_obs = c.O > 0;
 #pragma unroll
     for (int r = 0; r < NS; ++r) {
-#if defined(SFW_ABL_NOAGENT)
-      if (false) {
-#else
       if (ok_[r] && lds_at<int>(smem, off::DEAD + g4_[r]) == 0) {
-#endif
         const uint32_t io = io_[r], ci = ci_[r];
         const bool robot = i_[r] == 0;
         const sfw_robot_step rs = lds_at<sfw_robot_step>(smem, off::RSB + 8u * g4_[r]);
@@ -2019,9 +1861,7 @@ __device__ __forceinline__ void social_reg_wave(const sfw_launch &L, const int G
         const double w = agent_step<R>(k, c, rs, ak, robot, (cell.y & 1) != 0, hg, contact, px, py, vx, vy,
                                        fx[r] - lds_at<double>(smem, io + FJX), fy[r] - lds_at<double>(smem, io + FJY), nfx, nfy);
         if (hg != cell.x) lds_at<int>(smem, io + off::HG) = hg;  // goal reached: popped
-#if !defined(SFW_ABL_NOATOM) && !defined(SFW_ABL_NOREAD) && !defined(SFW_ABL_NOMATH) && !defined(SFW_ABL_KEEPALIVE)
         if (contact) lds_at<int>(smem, off::DEAD + g4_[r]) = 2 + step;  // >= 2: rejected by contact at `step`
-#endif
         fx[r] = nfx;
         fy[r] = nfy;
         if (robot && with_obs) {
@@ -2053,7 +1893,7 @@ __device__ __forceinline__ void social_reg_wave(const sfw_launch &L, const int G
         if (ok_[r] && lds_at<int>(smem, off::DEAD + g4_[r]) == 0) {
           const uint32_t io = io_[r];
           double tx, ty, sc;
-          obstacle_sums<R, false>(k, c, obs_global(c.obstacles), lds_at<double>(smem, io), lds_at<double>(smem, io + PY),
+          obstacle_sums<R>(k, c, obs_global(c.obstacles), lds_at<double>(smem, io), lds_at<double>(smem, io + PY),
                            lds_at<double>(smem, ci_[r] + 32u), tx, ty, sc);
           if (i_[r] == 0) {
             sw[r] += lds_at<double>(smem, io + off::SW) + fast_norm(tx * sc, ty * sc);
@@ -2167,11 +2007,6 @@ __global__ void __launch_bounds__(256) sfw_pair_table_kernel(uint16_t *tab, int 
 
 __device__ __forceinline__ void load_pair_entries(const uint16_t *ti, const uint16_t *tj, uint32_t lane_off, uint32_t &io,
                                                   uint32_t &jo) {
-#ifdef SFW_DBG_C_LOADS
-  io = ti[lane_off / 2];
-  jo = tj[lane_off / 2];
-  return;
-#endif
   // s_nop 4: the table addresses may have just been reloaded from a spill lane (v_readlane: VALU writes an SGPR), and a
   // VMEM instruction reading such an SGPR needs 5 wait states — the compiler's hazard recogniser does not look inside
   // an asm block (found as a memory fault that only showed with many waves per SIMD)
@@ -2183,9 +2018,6 @@ __device__ __forceinline__ void wait_pair_entries(uint32_t &io, uint32_t &jo) {
   asm volatile("s_waitcnt vmcnt(0)" : "+v"(io), "+v"(jo));
 }
 
-#ifndef SFW_FIRST_PAIRS_IN_REGS
-#define SFW_FIRST_PAIRS_IN_REGS 1  // flat form: the first 64 pairs' table entries stay in registers across the rollout
-#endif
 #ifndef SFW_FLAT_WAVES
 #define SFW_FLAT_WAVES 5  // waves per SIMD the flat kernel is compiled for (<= 96 VGPRs; tuning knob, csrc/Makefile EXTRA)
 #endif
@@ -2305,7 +2137,7 @@ __device__ __forceinline__ void social_flat_wave(const sfw_launch &L, char *cons
         desired_force(c0, px, py, vx, vy, c.has_goal != 0, c.goal_x, c.goal_y, c.goal_radius, c.desired_velocity, fx, fy);
         if (OBS && O > 0) {
           double tx, ty, sc;
-          obstacle_sums<R, SFW_FLAT_PIPELINED>(k0, c0, obs_global(L.obstacles), px, py, c.radius, tx, ty, sc);
+          obstacle_sums<R>(k0, c0, obs_global(L.obstacles), px, py, c.radius, tx, ty, sc);
           fx = fma(tx, sc, fx);
           fy = fma(ty, sc, fy);
         }
@@ -2374,9 +2206,10 @@ __device__ __forceinline__ void social_flat_wave(const sfw_launch &L, char *cons
     }
   };
   if (step_begin < step_end) fetch_robot(L.ptab, L.row_units, step_begin, step_begin & 1);
+  // The first 64 pairs' table entries stay in registers across the rollout
   // (the 64-double planes only — crowds of up to 63 agents, every control cycle —: the larger capacities' kernels have no
   // registers to spare, tests/test_kernel_resources.py)
-  constexpr bool FIRST_IN_REGS = SFW_FIRST_PAIRS_IN_REGS && CAP == 64;
+  constexpr bool FIRST_IN_REGS = CAP == 64;
   uint32_t i0 = 0, j0 = 0;  // the first iteration's pair-table entries (see the pair loop)
   if constexpr (FIRST_IN_REGS) {
     if (n_it > 0) {
@@ -2385,48 +2218,23 @@ __device__ __forceinline__ void social_flat_wave(const sfw_launch &L, char *cons
     }
   }
 
-#if defined(SFW_ABL_HALF_LDS)
-  double abl_ix = s.px[lane < A ? lane : 0], abl_iy = s.py[lane < A ? lane : 0], abl_fx = 0.0, abl_fy = 0.0;
-#endif
   // one pair per lane: both agents from LDS, the force into both agents' accumulators
   auto pair_at = [&](const sfm_consts<R> &k, uint32_t io, uint32_t jo) {
     R qx, qy;
     if constexpr (CAP > 0) {
       double pix, piy, vix, viy, pjx, pjy, vjx, vjy;
-#if defined(SFW_ABL_NOREAD)
-      pix = static_cast<double>(io); piy = 1.0; vix = 0.3; viy = 0.5; pjx = static_cast<double>(jo) * 0.37; pjy = -3.0; vjx = 0.25; vjy = static_cast<double>(jo) * 0.001;
-#elif defined(SFW_ABL_HALF_LDS)
-      // upper bound of a lane-stationary organisation: the i side from registers, only the partner's state from LDS
-      pix = abl_ix; piy = abl_iy; vix = 0.3; viy = 0.5;
-      asm volatile("ds_read_b64 %0, %4\n\tds_read_b64 %1, %4 offset:%5\n\tds_read_b64 %2, %4 offset:%6\n\tds_read_b64 %3, %4 offset:%7\n\ts_waitcnt lgkmcnt(0)"
-                   : "=&v"(pjx), "=&v"(pjy), "=&v"(vjx), "=&v"(vjy) : "v"(jo), "n"(8 * CAP), "n"(16 * CAP), "n"(24 * CAP) : "memory");
-#else
       lds_pair_state<8 * CAP, 16 * CAP, 24 * CAP>(io, jo, pix, piy, vix, viy, pjx, pjy, vjx, vjy);
-#endif
-#if defined(SFW_ABL_NOMATH)
-      qx = R(pix + pjy - vjx); qy = R(piy - pjx + vix * viy + vjy);
-#else
       pair_force_state<R>(k, pix, piy, vix, viy, pjx, pjy, vjx, vjy, qx, qy);
-#endif
     } else {
       pair_force_state<R>(k, lds_at<double>(smem, io), lds_at<double>(smem, io + PY), lds_at<double>(smem, io + VX),
                           lds_at<double>(smem, io + VY), lds_at<double>(smem, jo), lds_at<double>(smem, jo + PY),
                           lds_at<double>(smem, jo + VX), lds_at<double>(smem, jo + VY), qx, qy);
     }
-#if defined(SFW_ABL_NOATOM)
-    asm volatile("" :: "v"(qx), "v"(qy));
-#elif defined(SFW_ABL_HALF_LDS)
-    abl_fx += static_cast<double>(qx);
-    abl_fy += static_cast<double>(qy);
-    atomicAdd(&lds_at<double>(smem, jo + FJX), static_cast<double>(qx));
-    atomicAdd(&lds_at<double>(smem, jo + FJY), static_cast<double>(qy));
-#else
     atomicAdd(&lds_at<double>(smem, io + FCX), static_cast<double>(qx));
     atomicAdd(&lds_at<double>(smem, io + FCY), static_cast<double>(qy));
     // j receives -q: accumulated with the opposite sign, subtracted in the agent pass
     atomicAdd(&lds_at<double>(smem, jo + FJX), static_cast<double>(qx));
     atomicAdd(&lds_at<double>(smem, jo + FJY), static_cast<double>(qy));
-#endif
   };
 
   // The kernel exists twice: with and without the laser-point pass (OBS).  With it, the pair term's constants pinned to VGPRs
@@ -2495,9 +2303,6 @@ __device__ __forceinline__ void social_flat_wave(const sfw_launch &L, char *cons
     }
     }
     K2_SYNC();
-#if defined(SFW_ABL_HALF_LDS)
-    if (lane < A) { s.fcx[lane] += abl_fx; s.fcy[lane] += abl_fy; abl_ix = s.px[lane] + 1e-3; abl_iy = s.py[lane]; abl_fx = abl_fy = 0.0; }
-#endif
     // ---- per-agent pass: its parameters are read here, not held across the pair loop -----------
     const late_launch La = late_args_of<BATCH>(Lb);
     const agent_consts c = load_agent_consts(La, F32);
@@ -2516,11 +2321,7 @@ __device__ __forceinline__ void social_flat_wave(const sfw_launch &L, char *cons
     // here (two instructions) instead of being held — in scratch, for the 104- and 208-double capacities — across the pair loop
     int lane_s = lane;
     asm volatile("" : "+v"(lane_s));
-#if defined(SFW_ABL_NOAGENT)
-    for (int sl = lane_s; sl < 0; sl += WAVE) {
-#else
     for (int sl = lane_s; sl < A; sl += WAVE) {
-#endif
       const agent_k ak = CONSTS_IN_LDS ? agent_k_lds(s, sl) : agent_k_global(agent_c, sl);
       double px = s.px[sl], py = s.py[sl], vx = s.vx[sl], vy = s.vy[sl];
       double nfx, nfy;
@@ -2530,9 +2331,7 @@ __device__ __forceinline__ void social_flat_wave(const sfw_launch &L, char *cons
       const double w = agent_step<R>(k, c, rs, ak, sl == 0, ak.id != c.robot_id, hg, contact, px, py, vx, vy,
                                      s.fcx[sl] - s.fjx[sl], s.fcy[sl] - s.fjy[sl], nfx, nfy);
       if (sl != 0 && hg0) s.hasgoal8[sl] = static_cast<unsigned char>(hg);
-#if !defined(SFW_ABL_NOATOM) && !defined(SFW_ABL_NOREAD) && !defined(SFW_ABL_NOMATH) && !defined(SFW_ABL_KEEPALIVE) && !defined(SFW_ABL_HALF_LDS)
       if (contact) s.dead[0] = 2 + step;  // >= 2: rejected by contact at `step`
-#endif
       if (sl == 0 && with_obs) {
         s.wr[0] = w;  // Wr = social part + obstacle part: summed below, then added to the robot's social work
       } else {
@@ -2572,9 +2371,8 @@ __device__ __forceinline__ void social_flat_wave(const sfw_launch &L, char *cons
         // Every (agent, segment) pair is a task; the wave walks them 256 at a time, 16 agents x 16 segments per round (same
         // sums in the same order as obstacle_sums).  Lane l: segment l / 4 of the agents a0 + l % 4 + {0, 4, 8, 12} — four
         // neighbouring lanes read the same point — the points through per-lane loads from global memory (L1), one load per
-        // point and lane for up to four agents (obstacle_segment_multi).
+        // point and lane for up to four agents (obstacle_segment_multi_uniform).
         const int Lseg = (c.O + OBS_SEG - 1) / OBS_SEG, seg = lane >> 2, sub = lane & (OBS_AGENT_LANES - 1);
-        const int ob = min(seg * Lseg, c.O), oe = min(ob + Lseg, c.O);
         const R nis = sfwm::vgpr_const(static_cast<R>(-c.l2e_inv_sigma));
         // The wave's LDS copy in an under-filled launch, else global memory — as two instantiations of the loop, not one
         // over a generic pointer: a flat load counts on vmcnt too, and waiting for it a lone wave also waited, in front of
@@ -2600,15 +2398,6 @@ __device__ __forceinline__ void social_flat_wave(const sfw_launch &L, char *cons
           }
 #pragma unroll
           for (int j = 0; j <= KA; ++j) axj[j] = ayj[j] = R(0);
-          auto run = [&](auto pts) {
-            switch (nj) {
-              case 1: obstacle_segment_multi<R, 1>(k, pts, ob, oe, pxj, pyj, nis, axj, ayj); break;
-              case 2: obstacle_segment_multi<R, 2>(k, pts, ob, oe, pxj, pyj, nis, axj, ayj); break;
-              case (KA > 3 ? 3 : -1): obstacle_segment_multi<R, 3>(k, pts, ob, oe, pxj, pyj, nis, axj, ayj); break;
-              default: obstacle_segment_multi<R, KA>(k, pts, ob, oe, pxj, pyj, nis, axj, ayj); break;
-            }
-          };
-          // (a GPU-filling launch — points in global memory — runs the loop with wave-uniform trip counts)
           auto run_uniform = [&](auto pts) {
             switch (nj) {
               case 1: obstacle_segment_multi_uniform<R, 1>(k, pts, c.O, Lseg, seg, pxj, pyj, nis, axj, ayj); break;
@@ -2617,13 +2406,8 @@ __device__ __forceinline__ void social_flat_wave(const sfw_launch &L, char *cons
               default: obstacle_segment_multi_uniform<R, KA>(k, pts, c.O, Lseg, seg, pxj, pyj, nis, axj, ayj); break;
             }
           };
-#if !defined(SFW_ABL_NOOBSLOOP)  // (ablation builds: time only, results wrong by construction)
-          if (in_lds) {
-            if (SFW_OBS_UNIFORM_LDS) run_uniform(pts_l);
-            else run(pts_l);
-          } else if (SFW_OBS_UNIFORM) run_uniform(pts_g);
-          else run(pts_g);
-#endif
+          if (in_lds) run_uniform(pts_l);
+          else run_uniform(pts_g);
           // The sixteen segment sums of an agent slot are added in segment order by one lane per (slot, component) out of LDS.  SL slots go through LDS at a time: two in a GPU-filling launch
           // (2 KB: what the wave can spare without losing a wave per SIMD at the target crowd), all four in a launch that leaves
           // the GPU under-filled (the ones that also keep the points in LDS) when the round has more than two — there a phase is
@@ -2633,15 +2417,10 @@ __device__ __forceinline__ void social_flat_wave(const sfw_launch &L, char *cons
           auto reduce = [&](auto sl_tag) {
             constexpr int SL = decltype(sl_tag)::value;
             // (the slots of a round go through LDS SL at a time: axj / opart are sized for KA <= 4 and a whole number of phases)
-            static_assert(KA <= 4 && (SL == 2 || KA % SL == 0), "SFW_OBS_KA: at most four agent slots per lane");
+            static_assert(KA <= 4 && (SL == 2 || KA % SL == 0), "OBS_AGENTS_PER_LANE: at most four agent slots per lane");
 #pragma unroll
             for (int j0 = 0; j0 < KA; j0 += SL) {
-#if defined(SFW_ABL_NOREDUCE)
-              asm volatile("" :: "v"(axj[j0]), "v"(ayj[j0]), "v"(axj[j0 + 1]), "v"(ayj[j0 + 1]));
-              if (false) {
-#else
               if (j0 < nj) {
-#endif
 #pragma unroll
                 for (int u = 0; u < SL; ++u)
                   s.opart[u * WAVE + lane] = double2{static_cast<double>(axj[j0 + u]), static_cast<double>(ayj[j0 + u])};
@@ -2684,7 +2463,7 @@ __device__ __forceinline__ void social_flat_wave(const sfw_launch &L, char *cons
         for (int a = lane; a < A; a += WAVE) {
           const double rad = CONSTS_IN_LDS ? s.ac[a].radius : agent_c[a].radius;
           double tx, ty, sc;
-          obstacle_sums<R, SFW_FLAT_PIPELINED>(k, c, obs_global(c.obstacles), s.px[a], s.py[a], rad, tx, ty, sc);
+          obstacle_sums<R>(k, c, obs_global(c.obstacles), s.px[a], s.py[a], rad, tx, ty, sc);
           if (a == 0) {
             const double wr = s.wr[0] + fast_norm(tx * sc, ty * sc);
             s.swp[0] += wr;
@@ -3438,10 +3217,7 @@ static wave_plan plan_for(int A, int64_t T, int O, int form, int cus) {
   }
   // ... and a robot alone among laser points: the flat form spreads the points' sixteen segments over sixteen lanes
   // (the item thresholds were measured on 256 compute units and scale with the device: 6 / 12 / 16 items per CU)
-#ifndef SFW_FLAT_ITEMS_PER_CU
-#define SFW_FLAT_ITEMS_PER_CU 16
-#endif
-  if (T <= static_cast<int64_t>(A <= 8 ? 6 : A <= 12 ? 12 : SFW_FLAT_ITEMS_PER_CU) * cus && (A >= 2 || O > 0)) best = flat;
+  if (T <= static_cast<int64_t>(A <= 8 ? 6 : A <= 12 ? 12 : 16) * cus && (A >= 2 || O > 0)) best = flat;
   if (form == SFW_K2_FLAT && (A >= 2 || O > 0)) best = flat;
   if (form == SFW_K2_REGISTER && A <= 2 * WAVE) best = reg;
   return best;
@@ -3624,14 +3400,8 @@ template <int CAP> static bool reg_layout_matches() {
 // register-form waves per SIMD: cfg2's 16 384 samples = 5 x 1024 x 3 in the register form + 1024 flat waves, one per SIMD.
 // Returns how many of the `items` stay in the register form (all of them when a split would not pay; the costs are plan_for's
 // instruction counts per sample and step, plus 24 per laser-point evaluation).
-#ifndef SFW_SPLIT_FORMS
-#define SFW_SPLIT_FORMS 1
-#endif
-#ifndef SFW_MIXED_LAUNCH
-#define SFW_MIXED_LAUNCH 1  // 0: the split launch as two launches on two streams whatever the scan (rounds 4-5; A/B)
-#endif
 static int64_t split_point(const wave_plan &pl, int A, int O, int NG, int form, int64_t items, int cus) {
-  if (!SFW_SPLIT_FORMS || form != SFW_K2_AUTO || pl.flat || pl.ns != 1 || A < 2 || A > WAVE || NG > 0) return items;
+  if (form != SFW_K2_AUTO || pl.flat || pl.ns != 1 || A < 2 || A > WAVE || NG > 0) return items;
   const int64_t S = 4LL * cus, W = (items + pl.G - 1) / pl.G, q = W / S;
   if (q < 1 || q > 5 || W % S == 0) return items;  // (six waves per SIMD are resident at once; beyond that the waves queue)
   const int64_t reg_items = q * S * pl.G, rest = items - reg_items;
@@ -3658,7 +3428,7 @@ template <typename R> static hipError_t launch_social_typed(const sfw_launch &L_
   const wave_plan pl = plan_for(L_in.A, items, L_in.O, L_in.k2_form, cus);
   if (sp && sp->side && item_base == 0) {
     const int64_t keep = L_in.pair_tab ? split_point(pl, L_in.A, L_in.O, L_in.NG, L_in.k2_form, items, cus) : items;
-    if (keep < items && L_in.O == 0 && flat_cap(L_in.A) == 64 && SFW_MIXED_LAUNCH) {
+    if (keep < items && L_in.O == 0 && flat_cap(L_in.A) == 64) {
       // both forms in one launch (sfw_social_kernel_mixed): no second stream, no fork, no join
       const unsigned n_reg = static_cast<unsigned>((keep + pl.G - 1) / pl.G), n_flat = static_cast<unsigned>(items - keep);
       const wave_plan fl{1, 0, true};
@@ -3755,7 +3525,7 @@ __global__ void __launch_bounds__(256) sfw_no_social_kernel(const sfw_launch L) 
 
 hipError_t sfw_launch_social(const sfw_launch &L, hipStream_t stream, const sfw_split_streams *sp) {
   if (L.chunk_count <= 0 || L.A <= 0) return hipSuccess;
-  if (SFW_SKIP_EMPTY_K2 && L.A == 1 && L.O == 0 && L.NG == 0 && L.phase != SFW_PHASE_PREFIX && !L.out_state) {
+  if (L.A == 1 && L.O == 0 && L.NG == 0 && L.phase != SFW_PHASE_PREFIX && !L.out_state) {
     hipLaunchKernelGGL(sfw_no_social_kernel, dim3(static_cast<unsigned>((L.chunk_count + 255) / 256)), dim3(256), 0, stream, L);
     return hipGetLastError();
   }

@@ -189,22 +189,8 @@ __device__ __forceinline__ double exp2_scaled(const poly_consts &pc, double u, d
 }
 // Two exponentials at once, their Horner chains interleaved: a lone wave per SIMD (shared-prefix levels, control-cycle
 // grids) pays the ~8-cycle dependent-issue latency of every link of a chain, two independent chains hide each other's.
-// Same operations on the same values as two exp2_fast calls: bit-identical.
-__device__ __forceinline__ void exp2_fast2(const poly_consts &pc, double x1, double x2, double &e1, double &e2) {
-  const double shift = 6755399441055744.0;  // 1.5 * 2^52
-  const double t1 = x1 + shift, t2 = x2 + shift;
-  const double k1 = t1 - shift, k2 = t2 - shift;
-  const double r1 = x1 - k1, r2 = x2 - k2;
-  double p1 = pc.ex[SFW_EXP_DEG], p2 = pc.ex[SFW_EXP_DEG];
-#pragma unroll
-  for (int n = SFW_EXP_DEG - 1; n >= 0; --n) {
-    p1 = fma(p1, r1, pc.ex[n]);
-    p2 = fma(p2, r2, pc.ex[n]);
-  }
-  e1 = __builtin_amdgcn_ldexp(p1, __double2loint(t1));
-  e2 = __builtin_amdgcn_ldexp(p2, __double2loint(t2));
-}
-// The same with the second exponential exactly 0 in the lanes whose `cw` is zero: the integer exponent of its 2^k scaling is replaced by one far below the denormals
+// Same operations on the same values as two exp2_fast calls, except that the second exponential is exactly 0 in the lanes
+// whose `cw` is zero: the integer exponent of its 2^k scaling is replaced by one far below the denormals
 // (v_ldexp_f64 then returns +0) — one v_cndmask_b32 on the integer instead of two on the result.  The replacement is the bit
 // pattern of -4.0f read as an integer (-1 065 353 216): an INLINE constant of the instruction, so it costs neither a VGPR
 // (the register form sits exactly at its 80-VGPR budget) nor the constant bus (a literal next to the vcc mask does not
@@ -265,10 +251,6 @@ __device__ __forceinline__ float rcp_nr(float x) { return __builtin_amdgcn_rcpf(
 // 2^x in float: v_exp_f32; below -150 the result is 0 (clamped so that no denormal-handling mode decides)
 __device__ __forceinline__ float exp2_fast(const poly_consts &, float x) { return __builtin_amdgcn_exp2f(fmaxf(x, -150.0f)); }
 __device__ __forceinline__ float exp2_scaled(const poly_consts &pc, float u, float c) { return exp2_fast(pc, u * c); }
-__device__ __forceinline__ void exp2_fast2(const poly_consts &pc, float x1, float x2, float &e1, float &e2) {
-  e1 = exp2_fast(pc, x1);
-  e2 = exp2_fast(pc, x2);
-}
 __device__ __forceinline__ void exp2_fast2_gated(const poly_consts &pc, float x1, float x2, double cw, float &e1, float &e2) {
   e1 = exp2_fast(pc, x1);
   const float e = exp2_fast(pc, x2);

@@ -28,7 +28,7 @@ ab)
     ARGS="--workload $w --no-cpu-baseline --no-extra --no-verify --steps ${STEPS:-30} --warmup 3"
     if [ "$v" = "-" ]; then python bench.py $ARGS 2>/dev/null | tail -1 | line "this tree"
     elif [ -d "$v" ]; then (cd $v && python bench.py $ARGS 2>/dev/null | tail -1) | line "$v"
-    else SFW_ALLOW_ABLATION=1 SFW_HIP_LIB=$PWD/$v python bench.py $ARGS 2>/dev/null | tail -1 | line "$v"; fi
+    else SFW_HIP_LIB=$PWD/$v python bench.py $ARGS 2>/dev/null | tail -1 | line "$v"; fi
   done; done; done | tee $OUT/${TAG}_ab.txt ;;
 timeline)
   bash tools/step_timeline.sh ${1:-cfg2} > $OUT/${TAG}_step_timeline_${1:-cfg2}.txt 2>&1; cat $OUT/${TAG}_step_timeline_${1:-cfg2}.txt ;;
