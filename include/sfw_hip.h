@@ -394,6 +394,89 @@ int sfw_score_sequences(sfw_handle h, const sfw_robot_state *rs, const double *v
                         const double *vtheta, int32_t n, int32_t K, const int32_t *knot_step,
                         const sfw_goal_args *args, double *costs_out, sfw_best *best_out);
 
+/* PERTURBED sequences: the rollouts of a sampling controller (MPPI) drawn on
+ * the device.  sfw_sequences_perturb_stage is sfw_sequences_stage whose K x n
+ * knots are not handed over but computed by a kernel from a nominal plan of K
+ * knots, a standard deviation and a clamp box per channel, and a seed: under
+ * 2 KB go to the device instead of 24 K n bytes.
+ *
+ * Definition.  For sample t, knot k and channel c (0 vx, 1 vy, 2 vtheta), with
+ * g = index_base + t as an unsigned 64-bit number:
+ *   (w0, w1, w2, w3) = Philox4x32-10(counter = (g & 0xffffffff, g >> 32, k, c),
+ *                                    key = (seed & 0xffffffff, seed >> 32))
+ *     — the Random123 generator: multipliers 0xD2511F53 and 0xCD9E8D57, Weyl
+ *     constants 0x9E3779B9 and 0xBB67AE85, ten rounds;
+ *   m1 = ((w1 << 32) | w0) >> 11,  u1 = (m1 + 1) * 2^-53   in (0, 1];
+ *   m2 = ((w3 << 32) | w2) >> 11,  u2 = m2 * 2^-53         in [0, 1);
+ *   r = sqrt(-2.0 * log(u1)),  z = r * cos(6.283185307179586 * u2)
+ *     — the argument of cos is one IEEE product; log and cos are the device
+ *     library's double functions (as the blend's exp is), sqrt is IEEE; the
+ *     sine branch of Box-Muller is discarded;
+ *   under SFW_PERTURB_KEEP_NOMINAL z = 0.0 where g == 0;
+ *   u = fmin(fmax(nominal[k][c] + sigma[c] * z, lo[c]), hi[c])
+ *     — the product and the sum are each rounded on their own (no
+ *     contraction).
+ * social_force_window_planner_amd/perturb.py restates this in numpy
+ * (perturb.reference); tests/test_perturb_gpu.py holds the device to it.
+ *
+ * Consequences.  r <= sqrt(106 ln 2) < 8.58, so every knot is finite.  A
+ * value depends on (seed, g, k, c, nominal[k][c], sigma[c], lo[c], hi[c]) and
+ * on nothing else: not on n, not on K beyond k, not on the neighbouring
+ * samples, not on SFW_DEVICE_CUS, SFW_TABLE_BUDGET_MB or SFW_CYCLE_FUSED, and
+ * not on how a list is sharded over ranks — shards that pass their index_base
+ * draw what the unsharded stage draws.  The same seed draws the same
+ * perturbations: the caller changes `seed` from cycle to cycle.
+ *
+ * Under SFW_PERTURB_NO_VY the stage has no vy vector (vy == NULL in
+ * sfw_sequences_stage): channel 1 of every knot is 0.0 whatever the box says.
+ *
+ * The stage is a sequence stage in every respect: sfw_grid_launch / _sync /
+ * _fetch / _costs_view / _plan_info, sfw_grid_points(_batch), the terms and
+ * points capture, sfw_grid_rescore, sfw_grid_crowd, sfw_grid_blend, timing and
+ * a batch member's own path act on it as on sfw_sequences_stage, and a second
+ * stage by sfw_sequences_stage with the knots sfw_sequences_knots returns is
+ * BIT FOR BIT the perturbed stage in everything it produces.  K == 1 runs the
+ * list's kernels.  sfw_best.vx / .vy / .vtheta are bitwise the winner's first
+ * knot as sfw_sequences_knots reports it (one small copy from the device
+ * behind the fetch's wait: the host never holds the knots).
+ *
+ * rest_noise_unreproduced of a perturbed stage is CONSERVATIVE, because the
+ * host never sees the knots: 1 when a person is pinned, there are at least two
+ * agents and the clamp box admits a zero translation command — lo[0] <= 0 <=
+ * hi[0] and (SFW_PERTURB_NO_VY or lo[1] <= 0 <= hi[1]) — else 0.
+ *
+ * SFW_ERR_INVALID_ARG (before any device call; a refused call changes
+ * nothing): a NULL h, rs, p, p->nominal, knot_step or args; n < 1; K outside
+ * [1, SFW_SEQ_MAX_KNOTS]; knot_step[0] != 0 or not strictly ascending;
+ * index_base < 0; a non-finite value in nominal, sigma, lo, hi, rs or args;
+ * sigma[c] < 0; lo[c] > hi[c]; unknown flag bits or reserved != 0;
+ * SFW_PERTURB_NO_VY with sigma[1] != 0 or some nominal[k][1] != 0.
+ * SFW_ERR_STATE: no costmap.  All-or-nothing as every stage is.
+ */
+#define SFW_PERTURB_KEEP_NOMINAL 1  /* the sample with GLOBAL index index_base + t == 0 gets z = 0 in every channel */
+#define SFW_PERTURB_NO_VY        2  /* stage without a vy vector, as vy == NULL in sfw_sequences_stage */
+#define SFW_PERTURB_KEEP_NORMALS 4  /* also keep every z on the device for sfw_sequences_normals */
+typedef struct sfw_perturb {
+  uint64_t seed;
+  const double *nominal;  /* K x 3 doubles: [k][vx, vy, vtheta] */
+  double sigma[3];        /* per channel, finite, >= 0 */
+  double lo[3], hi[3];    /* clamp box per channel, finite, lo <= hi */
+  int32_t flags, reserved;
+} sfw_perturb;
+int sfw_sequences_perturb_stage(sfw_handle h, const sfw_robot_state *rs, const sfw_perturb *p, int32_t n, int32_t K,
+                                const int32_t *knot_step, const sfw_goal_args *args, int64_t index_base);
+/* sfw_sequences_perturb_stage (index_base 0) + sfw_grid_launch + sfw_grid_fetch: costs_out (nullable) receives n costs. */
+int sfw_score_perturbed(sfw_handle h, const sfw_robot_state *rs, const sfw_perturb *p, int32_t n, int32_t K,
+                        const int32_t *knot_step, const sfw_goal_args *args, double *costs_out, sfw_best *best_out);
+/* The knots of samples [first, first + count) of the staged list or sequences (host-staged or perturbed), knot-major within
+ * the range: out[k * count + i] is knot k of sample first + i.  vy_out is nullable; a stage without a vy vector reports 0.0.
+ * SFW_ERR_STATE: nothing staged, or a grid.  SFW_ERR_INVALID_ARG: a range outside [0, n), count < 1, a NULL vx_out or
+ * vtheta_out. */
+int sfw_sequences_knots(sfw_handle h, int64_t first, int64_t count, double *vx_out, double *vy_out, double *vtheta_out);
+/* The normals z of the same range of a perturbed stage: z_out[(k * 3 + c) * count + i] (all three channels, whatever
+ * SFW_PERTURB_NO_VY says).  SFW_ERR_STATE unless the stage was perturbed with SFW_PERTURB_KEEP_NORMALS. */
+int sfw_sequences_normals(sfw_handle h, int64_t first, int64_t count, double *z_out);
+
 /* How the staged grid will be launched.  levels > 0: the shared-prefix
  * rollout is in use — under the acceleration limits (sfw_planner.hpp:457-463)
  * the robot's first steps are bit-identical for all samples of a class (same

@@ -222,6 +222,10 @@ EXPORTED_SYMBOLS = (
     "sfw_score_one_crowd",
     "sfw_grid_crowd",
     "sfw_grid_blend",
+    "sfw_sequences_perturb_stage",
+    "sfw_score_perturbed",
+    "sfw_sequences_knots",
+    "sfw_sequences_normals",
 )
 # per-term costs (sfw_set_terms_capture / sfw_grid_rescore / sfw_grid_terms)
 SFW_TERM_VEL, SFW_TERM_DISTANCE, SFW_TERM_ANGLE, SFW_TERM_COSTMAP, SFW_TERM_SOCIAL = 0, 1, 2, 3, 4
@@ -251,6 +255,18 @@ class SfwBlendStat(C.Structure):
              "index_min": self.index_min}
         d["ess"] = self.eta * self.eta / self.sum_w2 if self.sum_w2 > 0.0 else 0.0
         return d
+
+
+# perturbed sequences (sfw_sequences_perturb_stage)
+SFW_SEQ_MAX_KNOTS = 64
+SFW_PERTURB_KEEP_NOMINAL, SFW_PERTURB_NO_VY, SFW_PERTURB_KEEP_NORMALS = 1, 2, 4
+
+
+class SfwPerturb(C.Structure):
+    """sfw_perturb (include/sfw_hip.h): what a perturbed stage draws its knots from."""
+
+    _fields_ = [("seed", C.c_uint64), ("nominal", C.c_void_p), ("sigma", C.c_double * 3), ("lo", C.c_double * 3),
+                ("hi", C.c_double * 3), ("flags", C.c_int32), ("reserved", C.c_int32)]
 
 
 # one grid under several crowd hypotheses (sfw_ensemble_*)

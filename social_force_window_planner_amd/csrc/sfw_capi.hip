@@ -193,6 +193,10 @@ struct sfw_planner_s {
     int nk = 1;
     std::vector<int32_t> knot_step;
     const int32_t *d_knot_step = nullptr;
+    // sfw_sequences_perturb_stage: the knot rows were drawn on the device (sfw_perturb_kernel) — lin / vy / ang stay EMPTY, the
+    // arena's knot regions are never filled or sent from the host, and such a stage is never left arena_pending.  zero_admitted:
+    // the clamp box admits a zero translation command (rest_noise_unreproduced); normals_kept: `normals` holds 3 nk nv doubles
+    bool perturbed = false, zero_admitted = false, normals_kept = false;
     // the world as uploaded (sfw_set_* after a stage take effect at the next stage; a launch in between must keep
     // describing the device copy)
     int K = 0, A = 0, O = 0, NG = 0, n_grp_mem = 0;
@@ -304,6 +308,10 @@ struct sfw_planner_s {
   dev_buf<sfw_blend_min> blend_mins;
   dev_buf<double> blend_partials, blend_bias, blend_weights;
   pinned_buf pin_blend;
+  // sfw_sequences_perturb_stage: the normals of a stage with SFW_PERTURB_KEEP_NORMALS; pin_knots receives the winner's first knot
+  // (sel_to_best) and the ranges sfw_sequences_knots / _normals read back
+  dev_buf<double> normals;
+  pinned_buf pin_knots;
   // sfw_score_one_crowd / sfw_grid_crowd: cost | n_points | coll_step | state [S][A][4] | work [S][A] | has_goal [S][A],
   // contiguous -> one D2H into pin_crowd; the pair table of the kernel with run-time plane capacity (sfw_crowd_kernel)
   dev_buf<char> crowd_out;
@@ -1014,6 +1022,9 @@ bool pinned_rest_table(const sfw_params &p, const sfw_robot_state &rs, const dou
 // §10): a person that can never move next to a robot that moves now and brakes to a stop inside some sample's rollout.
 // Decided from what the stage uploaded, with the device's own velocity recurrence (plain IEEE operations).
 bool rest_noise_unreproduced(sfw_handle h) {
+  // A perturbed stage: the host never sees the knots, so the answer is conservative — some sample may be commanded to rest
+  // wherever the clamp box admits a zero translation command.
+  if (h->st.valid && h->st.perturbed) return h->st.person_pinned && h->st.A >= 2 && h->st.zero_admitted;
   if (h->st.valid && h->st.nk > 1) {
     // Sequences: a sample can come to rest behind a knot, or start to move at one.  The host walks every sample's own
     // recurrence over the knots — only when a person is pinned — and flags a translation velocity that REACHES (0, 0) after a
@@ -1208,17 +1219,25 @@ struct host_phases {
   }
 };
 
+// What a perturbed stage draws its knots from (sfw_sequences_perturb_stage, checked there): stage_common reserves the knot
+// regions of the arena and enqueues sfw_perturb_kernel to fill them instead of copying lin / ang / vy_list (all null then)
+struct perturb_source {
+  sfw_perturb_dev args;
+  bool vy, keep_normals, zero_admitted;
+};
+
 // list: sfw_samples_stage — lin / ang are vx / vtheta of nv samples (nw == 1), vy_list their vy (nullable: all 0.0)
 // knot_step (list only, nullable): sfw_sequences_stage — lin / ang / vy_list hold nk rows of nv values, knot-major, and
 // knot_step the nk steps at which a knot takes over (checked by the caller: knot_step[0] == 0, strictly ascending)
 int stage_common(sfw_handle h, const sfw_robot_state *rs, const double *lin, int32_t nv, const double *ang,
                  int32_t nw, const sfw_goal_args *args, double vy_samp, int skip_zero, int64_t index_base,
                  bool grid = false, bool list = false, const double *vy_list = nullptr, int32_t nk = 1,
-                 const int32_t *knot_step = nullptr) {
+                 const int32_t *knot_step = nullptr, const perturb_source *dev = nullptr) {
   if (!h) return SFW_ERR_INVALID_ARG;
-  const std::string what = knot_step ? "sequences_stage" : list ? "samples_stage" : "grid_stage";
+  const std::string what = dev ? "sequences_perturb_stage" : knot_step ? "sequences_stage" : list ? "samples_stage" : "grid_stage";
   const size_t kn = knot_step ? static_cast<size_t>(nk) : size_t(1);  // rows of the sample vectors
-  if (!rs || !lin || !ang || !args || nv <= 0 || nw <= 0)
+  const bool has_vy = dev ? dev->vy : vy_list != nullptr;
+  if (!rs || (!dev && (!lin || !ang)) || !args || nv <= 0 || nw <= 0)
     return fail(h, SFW_ERR_INVALID_ARG, what + ": null pointer or non-positive sample count");
   const size_t n_ang = list ? static_cast<size_t>(nv) : static_cast<size_t>(nw);
   if (!h->world.have_costmap) return fail(h, SFW_ERR_STATE, what + ": no costmap set (sfw_set_costmap)");
@@ -1226,8 +1245,8 @@ int stage_common(sfw_handle h, const sfw_robot_state *rs, const double *lin, int
   // ordering the shared-prefix planner sorts by: O(nv + nw) checks
   if (!all_finite(&rs->x, 6) || !all_finite(&args->acc_x, 5) || !std::isfinite(vy_samp))
     return fail(h, SFW_ERR_INVALID_ARG, what + ": non-finite robot state, goal argument or sample velocity");
-  if (!all_finite(lin, kn * static_cast<size_t>(nv)) || !all_finite(ang, kn * n_ang) ||
-      (vy_list && !all_finite(vy_list, kn * static_cast<size_t>(nv))))
+  if (!dev && (!all_finite(lin, kn * static_cast<size_t>(nv)) || !all_finite(ang, kn * n_ang) ||
+               (vy_list && !all_finite(vy_list, kn * static_cast<size_t>(nv)))))
     return fail(h, SFW_ERR_INVALID_ARG, what + ": non-finite sample velocity");
   drop_stage(h);  // (valid again at the end of this function, and only there)
   host_phases ph("stage:");
@@ -1244,8 +1263,16 @@ int stage_common(sfw_handle h, const sfw_robot_state *rs, const double *lin, int
     h->world.cells_dirty = false;
   }
   ph.mark("check+setdev");
-  h->st.lin.assign(lin, lin + kn * nv);
-  h->st.ang.assign(ang, ang + kn * n_ang);
+  h->st.perturbed = dev != nullptr;
+  h->st.zero_admitted = dev && dev->zero_admitted;
+  h->st.normals_kept = false;  // (until the kernel that writes them is enqueued)
+  if (dev) {  // the knots exist on the device only
+    h->st.lin.clear();
+    h->st.ang.clear();
+  } else {
+    h->st.lin.assign(lin, lin + kn * nv);
+    h->st.ang.assign(ang, ang + kn * n_ang);
+  }
   h->st.list = list;
   if (vy_list) h->st.vy.assign(vy_list, vy_list + kn * nv);
   else h->st.vy.clear();
@@ -1282,7 +1309,7 @@ int stage_common(sfw_handle h, const sfw_robot_state *rs, const double *lin, int
     const size_t o_fp = cells_head, o_ag = o_fp + up16(sizeof(double) * (h->world.footprint.empty() ? 2 : h->world.footprint.size())),
                  o_lin = o_ag + up16(ag.blob.size()), o_ang = o_lin + up16(sizeof(double) * kn * nv),
                  o_vy = o_ang + up16(sizeof(double) * kn * n_ang),
-                 o_knot = o_vy + (vy_list ? up16(sizeof(double) * kn * nv) : 0),
+                 o_knot = o_vy + (has_vy ? up16(sizeof(double) * kn * nv) : 0),
                  o_rest = o_knot + (knot_step ? up16(sizeof(int32_t) * kn) : 0),
                  o_pin = o_rest + (rest ? up16(sizeof(double) * 2 * static_cast<size_t>(ag.A)) : 0),
                  pin_doubles = 4 + static_cast<size_t>(ag.A > 0 ? ag.A : 0),
@@ -1299,9 +1326,11 @@ int stage_common(sfw_handle h, const sfw_robot_state *rs, const double *lin, int
     if (send_cells) std::memcpy(pb, h->pin_map.p, n_cells);
     if (!h->world.footprint.empty()) std::memcpy(pb + o_fp, h->world.footprint.data(), sizeof(double) * h->world.footprint.size());
     if (!ag.blob.empty()) std::memcpy(pb + o_ag, ag.blob.data(), ag.blob.size());
-    std::memcpy(pb + o_lin, lin, sizeof(double) * kn * nv);
-    std::memcpy(pb + o_ang, ang, sizeof(double) * kn * n_ang);
-    if (vy_list) std::memcpy(pb + o_vy, vy_list, sizeof(double) * kn * nv);
+    if (!dev) {
+      std::memcpy(pb + o_lin, lin, sizeof(double) * kn * nv);
+      std::memcpy(pb + o_ang, ang, sizeof(double) * kn * n_ang);
+      if (vy_list) std::memcpy(pb + o_vy, vy_list, sizeof(double) * kn * nv);
+    }
     if (knot_step) std::memcpy(pb + o_knot, knot_step, sizeof(int32_t) * kn);
     if (!h->st.cls_ints.empty()) std::memcpy(pb + o_cls, h->st.cls_ints.data(), sizeof(int32_t) * h->st.cls_ints.size());
     const double *pos = reinterpret_cast<const double *>(ag.blob.data());
@@ -1325,7 +1354,13 @@ int stage_common(sfw_handle h, const sfw_robot_state *rs, const double *lin, int
       const int64_t T_ = static_cast<int64_t>(nv) * nw;
       const bool small = T_ <= 1024 && from == cells_head && total - from <= (size_t(16) << 10);
       const bool early = T_ > 2048 && chunk >= T_ && total - from <= (size_t(1) << 20);
-      if (grid && h->cfg.arena_direct_on && (small || early) && (total - from) % 16 == 0 && from % 16 == 0) {
+      if (dev) {
+        // The knot regions [o_lin, o_knot) hold nothing on the host: the copy goes around them, and the kernel that fills them
+        // on the device is enqueued behind it (below).  Never pending: a kernel that fetched the arena from pinned memory
+        // would read its sample vectors there.
+        if (o_lin > from) SFW_HIP(h, hipMemcpyAsync(h->arena.p + from, pb + from, o_lin - from, hipMemcpyHostToDevice, h->stream));
+        if (total > o_knot) SFW_HIP(h, hipMemcpyAsync(h->arena.p + o_knot, pb + o_knot, total - o_knot, hipMemcpyHostToDevice, h->stream));
+      } else if (grid && h->cfg.arena_direct_on && (small || early) && (total - from) % 16 == 0 && from % 16 == 0) {
         h->st.arena_pending = true;
         h->st.arena_from = from;
         h->st.arena_bytes = total - from;
@@ -1355,7 +1390,7 @@ int stage_common(sfw_handle h, const sfw_robot_state *rs, const double *lin, int
     h->st.d_grp_mem = reinterpret_cast<const int32_t *>(db + o_ag + ag.ao_mem);
     h->st.d_linvels = reinterpret_cast<const double *>(db + o_lin);
     h->st.d_angvels = reinterpret_cast<const double *>(db + o_ang);
-    h->st.d_vy = vy_list ? reinterpret_cast<const double *>(db + o_vy) : nullptr;
+    h->st.d_vy = has_vy ? reinterpret_cast<const double *>(db + o_vy) : nullptr;
     h->st.d_knot_step = knot_step ? reinterpret_cast<const int32_t *>(db + o_knot) : nullptr;
     h->st.d_agent_rest = rest ? reinterpret_cast<const double *>(db + o_rest) : nullptr;
   }
@@ -1373,6 +1408,17 @@ int stage_common(sfw_handle h, const sfw_robot_state *rs, const double *lin, int
   h->st.d_sel = reinterpret_cast<sfw_sel *>(h->costs.p + T);
   SFW_HIP(h, h->partials.reserve(sfw_argmin_partials(T)));
   ph.mark("reserve");
+  if (dev) {  // the knots, before anything that reads them (plan_tables_device may enqueue the pose rollout)
+    double *z = nullptr;
+    if (dev->keep_normals) {
+      SFW_HIP(h, h->normals.reserve(3 * kn * static_cast<size_t>(nv)));
+      z = h->normals.p;
+    }
+    SFW_HIP(h, sfw_launch_perturb(dev->args, nv, static_cast<int>(kn), index_base, const_cast<double *>(h->st.d_linvels),
+                                  const_cast<double *>(h->st.d_vy), const_cast<double *>(h->st.d_angvels), z, h->stream));
+    h->st.normals_kept = dev->keep_normals;
+    ph.mark("perturb");
+  }
   if (int e = plan_tables_device(h, chunk, grid)) return e;
   if (T > 1024)
     if (int e = flush_arena(h)) return e;  // (no pose rollout was enqueued after all: the copy it would have stood in for)
@@ -1668,7 +1714,28 @@ int launch_common(sfw_handle h) {
   return launch_kernels(h, lp);
 }
 
-void sel_to_best(sfw_handle h, const sfw_sel &s, sfw_best *best, sfw_best_key *key) {
+// Knots of samples [first, first + count) of a stage whose knots the device holds, into pin_knots: rows[c][k * count + i] for
+// the channels c the stage has (vy: null without a vy vector), behind everything enqueued on the stream.  Waits for the stream.
+int knots_from_device(sfw_handle h, int64_t first, int64_t count, const double *rows[3]) {
+  const size_t K = static_cast<size_t>(h->st.nk), row = sizeof(double) * static_cast<size_t>(count);
+  SFW_HIP(h, hipSetDevice(h->device));
+  if (3 * K * row > h->pin_knots.cap) SFW_HIP(h, hipStreamSynchronize(h->stream));  // (growing the area frees the old one)
+  SFW_HIP(h, h->pin_knots.reserve(3 * K * row));
+  const double *src[3] = {h->st.d_linvels, h->st.d_vy, h->st.d_angvels};
+  for (int c = 0; c < 3; ++c) {
+    rows[c] = nullptr;
+    if (!src[c]) continue;
+    char *dst = h->pin_knots.p + static_cast<size_t>(c) * K * row;
+    SFW_HIP(h, hipMemcpy2DAsync(dst, row, src[c] + first, sizeof(double) * static_cast<size_t>(h->st.nv), row, K, hipMemcpyDeviceToHost,
+                                h->stream));
+    rows[c] = reinterpret_cast<const double *>(dst);
+  }
+  SFW_HIP(h, wait_stream(h));
+  stream_is_idle(h);
+  return SFW_OK;
+}
+
+int sel_to_best(sfw_handle h, const sfw_sel &s, sfw_best *best, sfw_best_key *key) {
   const bool found = std::isfinite(s.cost);
   if (best) {
     best->n_valid = s.n_valid;
@@ -1676,7 +1743,13 @@ void sel_to_best(sfw_handle h, const sfw_sel &s, sfw_best *best, sfw_best_key *k
       const int64_t local = -s.neg_index - h->st.index_base;
       best->index = local;
       best->cost = s.cost;
-      if (h->st.list) {  // the sample's own three values
+      if (h->st.perturbed) {  // the winner's first knot, from the device: the host holds no knots of a perturbed stage
+        const double *rows[3];
+        if (int e = knots_from_device(h, local, 1, rows)) return e;
+        best->vx = rows[0][0];
+        best->vy = rows[1] ? rows[1][0] : 0.0;
+        best->vtheta = rows[2][0];
+      } else if (h->st.list) {  // the sample's own three values
         best->vx = h->st.lin[static_cast<size_t>(local)];
         best->vy = h->st.vy.empty() ? 0.0 : h->st.vy[static_cast<size_t>(local)];
         best->vtheta = h->st.ang[static_cast<size_t>(local)];
@@ -1697,6 +1770,7 @@ void sel_to_best(sfw_handle h, const sfw_sel &s, sfw_best *best, sfw_best_key *k
     key->abs_angvel = found ? s.abs_angvel : std::numeric_limits<double>::infinity();
     key->neg_index = found ? static_cast<double>(s.neg_index) : std::numeric_limits<double>::infinity();
   }
+  return SFW_OK;
 }
 
 }  // namespace
@@ -1847,6 +1921,8 @@ int destroy_handle(sfw_handle h) {
   h->blend_bias.release();
   h->blend_weights.release();
   h->pin_blend.release();
+  h->normals.release();
+  h->pin_knots.release();
   h->points.release();
   h->n_points.release();
   h->one_out.release();
@@ -2095,8 +2171,7 @@ int sfw_grid_fetch(sfw_handle h, double *costs_out, sfw_best *best_out, sfw_best
     if (costs_out) std::memcpy(costs_out, h->pin_out.p, cost_bytes);
     std::memcpy(&s, h->pin_out.p + cost_bytes, sizeof(s));
   }
-  sel_to_best(h, s, best_out, key_out);
-  return SFW_OK;
+  return sel_to_best(h, s, best_out, key_out);
 }
 
 const double *sfw_grid_costs_view(sfw_handle h) {
@@ -2125,6 +2200,105 @@ int sfw_score_sequences(sfw_handle h, const sfw_robot_state *rs, const double *v
   if (int e = sfw_sequences_stage(h, rs, vx, vy, vtheta, n, K, knot_step, args, 0)) return e;
   if (int e = sfw_grid_launch(h)) return e;
   return sfw_grid_fetch(h, costs_out, best_out, nullptr);
+}
+
+int sfw_sequences_perturb_stage(sfw_handle h, const sfw_robot_state *rs, const sfw_perturb *p, int32_t n, int32_t K,
+                                const int32_t *knot_step, const sfw_goal_args *args, int64_t index_base) {
+  if (!h) return SFW_ERR_INVALID_ARG;
+  // (refused before anything is touched: the staged grid, list or sequences stay launchable)
+  const char *const what = "sequences_perturb_stage: ";
+  auto refuse = [&](const char *why) { return fail(h, SFW_ERR_INVALID_ARG, std::string(what) + why); };
+  if (!rs || !p || !p->nominal || !knot_step || !args) return refuse("rs, p, p->nominal, knot_step or args is NULL");
+  if (n < 1) return refuse("n < 1");
+  if (K < 1 || K > SFW_SEQ_MAX_KNOTS) return refuse("K outside 1..SFW_SEQ_MAX_KNOTS");
+  if (knot_step[0] != 0) return refuse("knot_step[0] must be 0");
+  for (int32_t k = 1; k < K; ++k)
+    if (knot_step[k] <= knot_step[k - 1]) return refuse("knot_step must be strictly ascending");
+  if (index_base < 0) return refuse("index_base < 0");
+  constexpr int32_t known = SFW_PERTURB_KEEP_NOMINAL | SFW_PERTURB_NO_VY | SFW_PERTURB_KEEP_NORMALS;
+  if ((p->flags & ~known) != 0 || p->reserved != 0) return refuse("unknown flag bits, or reserved != 0");
+  if (!all_finite(p->nominal, 3 * static_cast<size_t>(K)) || !all_finite(p->sigma, 3) || !all_finite(p->lo, 3) || !all_finite(p->hi, 3))
+    return refuse("non-finite nominal, sigma, lo or hi");
+  for (int c = 0; c < 3; ++c) {
+    if (p->sigma[c] < 0.0) return refuse("a sigma is negative");
+    if (p->lo[c] > p->hi[c]) return refuse("lo > hi");
+  }
+  const bool no_vy = (p->flags & SFW_PERTURB_NO_VY) != 0;
+  if (no_vy) {
+    if (p->sigma[1] != 0.0) return refuse("SFW_PERTURB_NO_VY with sigma[1] != 0");
+    for (int32_t k = 0; k < K; ++k)
+      if (p->nominal[3 * k + 1] != 0.0) return refuse("SFW_PERTURB_NO_VY with a nominal vy != 0");
+  }
+  perturb_source src{};
+  src.args.key0 = static_cast<uint32_t>(p->seed & 0xffffffffu);
+  src.args.key1 = static_cast<uint32_t>(p->seed >> 32);
+  src.args.keep_nominal = (p->flags & SFW_PERTURB_KEEP_NOMINAL) ? 1 : 0;
+  for (int c = 0; c < 3; ++c) {
+    src.args.sigma[c] = p->sigma[c];
+    src.args.lo[c] = p->lo[c];
+    src.args.hi[c] = p->hi[c];
+  }
+  std::memcpy(src.args.nominal, p->nominal, sizeof(double) * 3 * static_cast<size_t>(K));
+  src.vy = !no_vy;
+  src.keep_normals = (p->flags & SFW_PERTURB_KEEP_NORMALS) != 0;
+  src.zero_admitted = p->lo[0] <= 0.0 && 0.0 <= p->hi[0] && (no_vy || (p->lo[1] <= 0.0 && 0.0 <= p->hi[1]));
+  return stage_common(h, rs, nullptr, n, nullptr, 1, args, 0.0, 0, index_base, true, true, nullptr, K, knot_step, &src);
+}
+
+int sfw_score_perturbed(sfw_handle h, const sfw_robot_state *rs, const sfw_perturb *p, int32_t n, int32_t K,
+                        const int32_t *knot_step, const sfw_goal_args *args, double *costs_out, sfw_best *best_out) {
+  if (int e = sfw_sequences_perturb_stage(h, rs, p, n, K, knot_step, args, 0)) return e;
+  if (int e = sfw_grid_launch(h)) return e;
+  return sfw_grid_fetch(h, costs_out, best_out, nullptr);
+}
+
+int sfw_sequences_knots(sfw_handle h, int64_t first, int64_t count, double *vx_out, double *vy_out, double *vtheta_out) {
+  if (!h) return SFW_ERR_INVALID_ARG;
+  if (!h->st.valid || !h->st.list) return fail(h, SFW_ERR_STATE, "sequences_knots: no list or sequences are staged");
+  const int64_t n = h->st.nv;
+  if (first < 0 || count < 1 || first >= n || count > n - first) return fail(h, SFW_ERR_INVALID_ARG, "sequences_knots: range outside [0, n)");
+  if (!vx_out || !vtheta_out) return fail(h, SFW_ERR_INVALID_ARG, "sequences_knots: vx_out or vtheta_out is NULL");
+  const size_t K = static_cast<size_t>(h->st.nk), cnt = static_cast<size_t>(count);
+  double *const out[3] = {vx_out, vy_out, vtheta_out};
+  if (h->st.perturbed) {
+    const double *rows[3];
+    if (int e = knots_from_device(h, first, count, rows)) return e;
+    for (int c = 0; c < 3; ++c) {
+      if (!out[c]) continue;
+      if (rows[c]) std::memcpy(out[c], rows[c], sizeof(double) * K * cnt);
+      else std::fill(out[c], out[c] + K * cnt, 0.0);
+    }
+    return SFW_OK;
+  }
+  // a host-staged list or sequences: the stage's own record of what it uploaded
+  const std::vector<double> *const src[3] = {&h->st.lin, h->st.vy.empty() ? nullptr : &h->st.vy, &h->st.ang};
+  for (int c = 0; c < 3; ++c) {
+    if (!out[c]) continue;
+    for (size_t k = 0; k < K; ++k) {
+      if (src[c]) std::memcpy(out[c] + k * cnt, src[c]->data() + k * static_cast<size_t>(n) + first, sizeof(double) * cnt);
+      else std::fill(out[c] + k * cnt, out[c] + (k + 1) * cnt, 0.0);
+    }
+  }
+  return SFW_OK;
+}
+
+int sfw_sequences_normals(sfw_handle h, int64_t first, int64_t count, double *z_out) {
+  if (!h) return SFW_ERR_INVALID_ARG;
+  if (!h->st.valid || !h->st.perturbed || !h->st.normals_kept)
+    return fail(h, SFW_ERR_STATE, "sequences_normals: no perturbed stage with SFW_PERTURB_KEEP_NORMALS is staged");
+  const int64_t n = h->st.nv;
+  if (first < 0 || count < 1 || first >= n || count > n - first) return fail(h, SFW_ERR_INVALID_ARG, "sequences_normals: range outside [0, n)");
+  if (!z_out) return fail(h, SFW_ERR_INVALID_ARG, "sequences_normals: z_out is NULL");
+  const size_t rows = 3 * static_cast<size_t>(h->st.nk), row = sizeof(double) * static_cast<size_t>(count);
+  SFW_HIP(h, hipSetDevice(h->device));
+  if (rows * row > h->pin_knots.cap) SFW_HIP(h, hipStreamSynchronize(h->stream));  // (growing the area frees the old one)
+  SFW_HIP(h, h->pin_knots.reserve(rows * row));
+  SFW_HIP(h, hipMemcpy2DAsync(h->pin_knots.p, row, h->normals.p + first, sizeof(double) * static_cast<size_t>(n), row, rows,
+                              hipMemcpyDeviceToHost, h->stream));
+  SFW_HIP(h, wait_stream(h));
+  stream_is_idle(h);
+  std::memcpy(z_out, h->pin_knots.p, rows * row);
+  return SFW_OK;
 }
 
 int sfw_score_one(sfw_handle h, const sfw_robot_state *rs, double vx_samp, double vy_samp, double vtheta_samp,
@@ -2403,7 +2577,8 @@ int sfw_grid_rescore(sfw_handle h, const sfw_weights *w, int32_t K, sfw_best *be
   SFW_HIP(h, wait_stream(h));
   h->pin_rescore.pending = false;
   stream_is_idle(h);
-  for (int32_t k = 0; k < K; ++k) sel_to_best(h, sel_host[k], best_out + k, nullptr);
+  for (int32_t k = 0; k < K; ++k)
+    if (int e = sel_to_best(h, sel_host[k], best_out + k, nullptr)) return e;
   return SFW_OK;
 }
 
@@ -3409,7 +3584,7 @@ int batch_fetch(sfw_batch b, sfw_best *best_out) {
       h->last.fetched = true;
       sfw_sel s;
       std::memcpy(&s, h->pin_mirror.p + sizeof(double) * static_cast<size_t>(h->st.nv) * h->st.nw, sizeof(s));
-      sel_to_best(h, s, best, nullptr);
+      if (int e = sel_to_best(h, s, best, nullptr)) return bmember_fail(b, i, e, "batch_fetch");
     } else if (int e = sfw_grid_fetch(h, nullptr, best, nullptr)) {  // (a grid too large for the mirror: its own copy)
       return bmember_fail(b, i, e, "batch_fetch");
     }
@@ -3613,7 +3788,7 @@ int ensemble_finish(sfw_ensemble e, double *costs_out, int32_t *rejected_out, sf
   }
   sfw_sel s;
   std::memcpy(&s, e->pin_out.p, sizeof(s));
-  sel_to_best(e->b->h[0], s, best_out, nullptr);
+  (void)sel_to_best(e->b->h[0], s, best_out, nullptr);  // (an ensemble stages grids: the host holds the axes)
   return SFW_OK;
 }
 }  // namespace

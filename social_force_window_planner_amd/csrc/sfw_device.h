@@ -359,6 +359,17 @@ hipError_t sfw_launch_blend(const double *costs, const double *bias, int64_t T, 
 // with the same costs and bias: `mins` as that launch left it.
 hipError_t sfw_launch_blend_weights(const double *costs, const double *bias, int64_t T, const sfw_blend_lambdas &lam, int L,
                                     const sfw_blend_min *mins, double *weights, hipStream_t stream);
+// sfw_sequences_perturb_stage: the K x n knot rows of a perturbed stage, drawn on the device (sfw_kernels.hip
+// sfw_perturb_kernel).  vx / vy (nullable: SFW_PERTURB_NO_VY) / vtheta: K rows of n doubles, knot-major; z_out (nullable): the
+// normals, [(k * 3 + c) * n + t].
+struct sfw_perturb_dev {
+  uint32_t key0, key1;  // the seed's low and high half
+  int32_t keep_nominal, pad;
+  double sigma[3], lo[3], hi[3];
+  double nominal[SFW_SEQ_MAX_KNOTS * 3];  // [k][vx, vy, vtheta]; rows >= K are not read
+};
+hipError_t sfw_launch_perturb(const sfw_perturb_dev &a, int64_t n, int K, int64_t index_base, double *vx, double *vy, double *vtheta,
+                              double *z_out, hipStream_t stream);
 // Row r of the [R,5] multi-device exchange table from a selection record (+inf in every other row).
 hipError_t sfw_launch_key_table(const sfw_sel *sel, double *table, int r, int R, hipStream_t stream);
 // Pair table of the flat social kernel for A agents: sfw_pair_table_entries(A) uint16 entries.

@@ -2974,6 +2974,65 @@ __global__ void __launch_bounds__(BLEND_C) sfw_blend_last(const double *__restri
 #pragma clang fp contract(fast)
 #endif  // SFW_STRICT_BUILD
 
+#ifndef SFW_STRICT_BUILD  // (knots are doubles in every precision mode: the kernel exists once)
+// Perturbed command sequences (sfw_sequences_perturb_stage): knot k, channel c of sample t is the nominal plan's value plus
+// sigma[c] times a standard normal variate that is a function of (seed, index_base + t, k, c) alone — one Philox4x32-10 block
+// per value (Random123: counter = (g lo, g hi, k, c), key = the seed's halves), its four words two 53-bit uniforms, Box-Muller's
+// cosine branch, then the clamp box (sfw_hip.h "Definition"; social_force_window_planner_amd/perturb.py restates it in numpy).
+// Thread = sample, blockIdx.y = knot: the three knot rows (and the kept normals) are written at [k * n + t], coalesced over the
+// lanes.  No LDS, no atomics; nominal, sigma and the box are kernel arguments (wave-uniform scalar loads).  No contraction: the
+// product and the sum of the affine map are each rounded on their own.
+#pragma clang fp contract(off)
+constexpr int PERTURB_C = 256;
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
+                                              uint32_t w[4]) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint64_t p0 = static_cast<uint64_t>(0xD2511F53u) * c0, p1 = static_cast<uint64_t>(0xCD9E8D57u) * c2;
+    const uint32_t n0 = static_cast<uint32_t>(p1 >> 32) ^ c1 ^ k0, n2 = static_cast<uint32_t>(p0 >> 32) ^ c3 ^ k1;
+    c1 = static_cast<uint32_t>(p1);
+    c3 = static_cast<uint32_t>(p0);
+    c0 = n0;
+    c2 = n2;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  w[0] = c0;
+  w[1] = c1;
+  w[2] = c2;
+  w[3] = c3;
+}
+// vy == null: a stage without a vy row (SFW_PERTURB_NO_VY); z_out == null: the normals are not kept
+__global__ void __launch_bounds__(PERTURB_C)
+sfw_perturb_kernel(sfw_perturb_dev a, int64_t n, int64_t index_base, double *vx, double *vy, double *vtheta, double *z_out) {
+  const int64_t t = static_cast<int64_t>(blockIdx.x) * PERTURB_C + threadIdx.x;
+  if (t >= n) return;
+  const int k = blockIdx.y;
+  const uint64_t g = static_cast<uint64_t>(index_base + t);
+  double *const row[3] = {vx, vy, vtheta};
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    if (!row[c] && !z_out) continue;
+    uint32_t w[4];
+    philox4x32_10(static_cast<uint32_t>(g), static_cast<uint32_t>(g >> 32), static_cast<uint32_t>(k), static_cast<uint32_t>(c), a.key0,
+                  a.key1, w);
+    const uint64_t m1 = ((static_cast<uint64_t>(w[1]) << 32) | w[0]) >> 11, m2 = ((static_cast<uint64_t>(w[3]) << 32) | w[2]) >> 11;
+    const double u1 = static_cast<double>(m1 + 1) * 0x1p-53, u2 = static_cast<double>(m2) * 0x1p-53;  // (0, 1] and [0, 1): exact
+    const double r = sqrt(-2.0 * log(u1));
+    const double angle = 6.283185307179586 * u2;
+    double z = r * cos(angle);
+    if (a.keep_nominal && g == 0) z = 0.0;
+    const int64_t at = static_cast<int64_t>(k) * n + t;
+    if (z_out) z_out[(static_cast<int64_t>(k) * 3 + c) * n + t] = z;
+    if (row[c]) {
+      const double step = a.sigma[c] * z;
+      row[c][at] = fmin(fmax(a.nominal[k * 3 + c] + step, a.lo[c]), a.hi[c]);
+    }
+  }
+}
+#pragma clang fp contract(fast)
+#endif  // SFW_STRICT_BUILD
+
 // Multi-device exchange record (sfw_multi_*): row `r` of an [R,5] table = this rank's selection key
 // (cost, -linvel, |angvel|, -index) and its count of valid samples; every other row +inf, so that an
 // element-wise all-reduce(min) over the ranks assembles the table of all local keys.
@@ -3667,6 +3726,14 @@ hipError_t sfw_launch_blend_weights(const double *costs, const double *bias, int
                                     const sfw_blend_min *mins, double *weights, hipStream_t stream) {
   if (T < 1 || L < 1 || L > SFW_BLEND_MAX_L || sfw_blend_blocks(T) > INT_MAX || !costs || !mins || !weights) return hipErrorInvalidValue;
   return blend_first(costs, bias, T, lam, L, 1, nullptr, nullptr, nullptr, 1, 1, mins, nullptr, weights, nullptr, stream);
+}
+hipError_t sfw_launch_perturb(const sfw_perturb_dev &a, int64_t n, int K, int64_t index_base, double *vx, double *vy, double *vtheta,
+                              double *z_out, hipStream_t stream) {
+  const int64_t blocks = (n + PERTURB_C - 1) / PERTURB_C;
+  if (n < 1 || K < 1 || K > SFW_SEQ_MAX_KNOTS || index_base < 0 || blocks > INT_MAX || !vx || !vtheta) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(sfw_perturb_kernel, dim3(static_cast<unsigned>(blocks), static_cast<unsigned>(K)), dim3(PERTURB_C), 0, stream, a, n,
+                     index_base, vx, vy, vtheta, z_out);
+  return hipGetLastError();
 }
 #endif  // SFW_STRICT_BUILD
 

@@ -26,6 +26,7 @@ from ._abi import (
     SFW_BLEND_MAX_L,
     SfwGoalArgs,
     SfwParams,
+    SfwPerturb,
     SfwRobotState,
     SfwPlanInfo,
     SfwWeights,
@@ -168,6 +169,12 @@ def lib():
         L.sfw_score_sequences.argtypes = [vp, C.POINTER(SfwRobotState), vp, vp, vp, C.c_int32, C.c_int32, vp,
                                           C.POINTER(SfwGoalArgs), vp, C.POINTER(SfwBest)]
         L.sfw_grid_blend.argtypes = [vp, vp, C.c_int32, vp, C.POINTER(SfwBlendStat), vp, vp]
+        L.sfw_sequences_perturb_stage.argtypes = [vp, C.POINTER(SfwRobotState), C.POINTER(SfwPerturb), C.c_int32, C.c_int32, vp,
+                                                  C.POINTER(SfwGoalArgs), C.c_int64]
+        L.sfw_score_perturbed.argtypes = [vp, C.POINTER(SfwRobotState), C.POINTER(SfwPerturb), C.c_int32, C.c_int32, vp,
+                                          C.POINTER(SfwGoalArgs), vp, C.POINTER(SfwBest)]
+        L.sfw_sequences_knots.argtypes = [vp, C.c_int64, C.c_int64, vp, vp, vp]
+        L.sfw_sequences_normals.argtypes = [vp, C.c_int64, C.c_int64, vp]
         _lib = L
     return _lib
 
@@ -360,6 +367,60 @@ class HipScorer:
                                               C.byref(ga), costs.ctypes.data if n else None, C.byref(best)), "sfw_score_sequences")
         self._mark_staged((n, 1), knots=K)
         return costs, best.as_dict()
+
+    # -- perturbed sequences (sfw_sequences_perturb_stage / sfw_score_perturbed) ----
+    @staticmethod
+    def _perturb(seed, nominal, sigma, lo, hi, knot_steps, flags):
+        nom = np.ascontiguousarray(_f64(nominal))
+        ks = np.ascontiguousarray(np.asarray(knot_steps, dtype=np.int32).reshape(-1))
+        if nom.ndim != 2 or nom.shape[1] != 3 or len(ks) != nom.shape[0]:
+            raise ValueError("perturbed: nominal must be a (K, 3) array and knot_steps must hold K steps")
+        p = SfwPerturb()
+        p.seed = int(seed)
+        p.nominal = nom.ctypes.data if nom.size else None
+        for name, v in (("sigma", sigma), ("lo", lo), ("hi", hi)):
+            setattr(p, name, (C.c_double * 3)(*[float(x) for x in np.asarray(v, dtype=np.float64).reshape(3)]))
+        p.flags = int(flags)
+        return p, nom, ks  # (nom and ks are kept alive by the caller for the duration of the call)
+
+    def stage_perturbed(self, robot_state, n, seed, nominal, sigma, lo, hi, knot_steps, goal_args, flags=0, index_base=0):
+        """Stage n command sequences whose knots the DEVICE draws: knot k, channel c of sample t is
+        clamp(nominal[k, c] + sigma[c] * z, lo[c], hi[c]) with z a standard normal that depends on (seed, index_base + t, k, c)
+        alone (perturb.reference restates it).  nominal is (K, 3); flags: SFW_PERTURB_*.  A sequence stage in every respect."""
+        p, nom, ks = self._perturb(seed, nominal, sigma, lo, hi, knot_steps, flags)
+        rs, ga = SfwRobotState(*robot_state), SfwGoalArgs(*goal_args)
+        K = nom.shape[0]
+        self._check(lib().sfw_sequences_perturb_stage(self._h, C.byref(rs), C.byref(p), n, K, ks.ctypes.data if len(ks) else None,
+                                                      C.byref(ga), index_base), "sfw_sequences_perturb_stage")
+        self._mark_staged((n, 1), knots=K)
+
+    def score_perturbed(self, robot_state, n, seed, nominal, sigma, lo, hi, knot_steps, goal_args, flags=0):
+        """The blocking call over perturbed sequences: (costs[n], best)."""
+        p, nom, ks = self._perturb(seed, nominal, sigma, lo, hi, knot_steps, flags)
+        rs, ga = SfwRobotState(*robot_state), SfwGoalArgs(*goal_args)
+        K = nom.shape[0]
+        costs = np.empty(max(n, 0), dtype=np.float64)
+        best = SfwBest()
+        self._check(lib().sfw_score_perturbed(self._h, C.byref(rs), C.byref(p), n, K, ks.ctypes.data if len(ks) else None,
+                                              C.byref(ga), costs.ctypes.data if n > 0 else None, C.byref(best)), "sfw_score_perturbed")
+        self._mark_staged((n, 1), knots=K)
+        return costs, best.as_dict()
+
+    def knots(self, first, count):
+        """The knots of samples [first, first + count) of the staged list or sequences as a (K, 3, count) array (vx, vy, vtheta;
+        vy 0.0 for a stage without one) — after a perturbed stage, what the device drew."""
+        K = getattr(self, "_n_knots", 1) if self._grid is not None else 1
+        out = np.zeros((3, K, max(count, 1)), dtype=np.float64)
+        self._check(lib().sfw_sequences_knots(self._h, first, count, out[0].ctypes.data, out[1].ctypes.data, out[2].ctypes.data),
+                    "sfw_sequences_knots")
+        return np.ascontiguousarray(out.transpose(1, 0, 2))
+
+    def normals(self, first, count):
+        """The standard normals of the same range of a perturbed stage staged with SFW_PERTURB_KEEP_NORMALS: (K, 3, count)."""
+        K = getattr(self, "_n_knots", 1) if self._grid is not None else 1
+        out = np.zeros((K, 3, max(count, 1)), dtype=np.float64)
+        self._check(lib().sfw_sequences_normals(self._h, first, count, out.ctypes.data), "sfw_sequences_normals")
+        return out
 
     def prepared(self, robot_state, linvels, angvels, goal_args, index_base=0, zero_copy=False):
         """The blocking call with its arguments marshalled ONCE (a C caller builds its structs once too): step() is
