@@ -311,7 +311,8 @@ const double *sfw_grid_costs_view(sfw_handle h);
  * A member of a sfw_batch may be staged with a list: its results after
  * sfw_batch_launch / _fetch are bit-identical to its own launch; it does not
  * join the batched kernel (sfw_batch_desc.own_path_members counts it).
- * sfw_batch_score_grid, sfw_ensemble_* and sfw_multi_* take grids only.
+ * sfw_batch_score_grid and sfw_multi_* take grids only; an ensemble scores
+ * a list as sequences of one knot (sfw_ensemble_score_sequences, K == 1).
  */
 int sfw_samples_stage(sfw_handle h, const sfw_robot_state *rs, const double *vx, const double *vy,
                       const double *vtheta, int32_t n, const sfw_goal_args *args, int64_t index_base);
@@ -382,8 +383,8 @@ int sfw_score_samples(sfw_handle h, const sfw_robot_state *rs, const double *vx,
  *
  * A member of a sfw_batch may be staged with sequences: it takes its own
  * path (sfw_batch_desc.own_path_members), bit-identical to its own launch.
- * sfw_batch_score_grid, sfw_ensemble_* and sfw_multi_* keep taking grids
- * only.
+ * sfw_batch_score_grid and sfw_multi_* keep taking grids only; an ensemble
+ * scores sequences through sfw_ensemble_score_sequences / _score_perturbed.
  */
 #define SFW_SEQ_MAX_KNOTS 64
 int sfw_sequences_stage(sfw_handle h, const sfw_robot_state *rs, const double *vx, const double *vy,
@@ -872,8 +873,41 @@ int sfw_ensemble_score_grid(sfw_ensemble e, const sfw_robot_state *rs, const dou
  * sfw_score_one since (the rule of sfw_grid_rescore). */
 int sfw_ensemble_aggregate(sfw_ensemble e, int32_t mode, const double *probs, double *costs_out,
                            int32_t *rejected_out, sfw_best *best_out);
-/* Host wall-clock of the last calls, microseconds: which = 0 staging of the members (score_grid only), 1 the enqueue of the
- * launch and the aggregation, 2 the wait and the copies out. */
+/* The same over n command SEQUENCES of K knots instead of a grid (MPPI rollouts under crowd uncertainty).  Every member
+ * stages the same sequences as sfw_sequences_stage would (vx / vy (nullable) / vtheta: K rows of n values, knot-major;
+ * index_base 0), one batch launch, the aggregation behind it, one wait: the shape of sfw_ensemble_score_grid.  K == 1 is a
+ * sample list (sfw_samples_stage).  Afterwards member m is as after its own sfw_score_sequences: costs view, terms, points,
+ * sfw_grid_crowd, sfw_sequences_knots.  The aggregation is the definition above, unchanged; a list has no skipped sample, so
+ * SFW_COST_SKIPPED never appears.  Selection is the LIST's rule over the ensemble cost vector: the first knot's vx and
+ * vtheta are the key's velocities (vy takes no part), the larger index wins among equals; best_out carries the winner's
+ * first knot.  costs_out (n doubles), rejected_out (n int32) and best_out are nullable.
+ * Refusals, in this order: mode and probabilities as sfw_ensemble_score_grid; then every argument rule of
+ * sfw_sequences_stage (SFW_ERR_INVALID_ARG) — before any member is staged, so the previous score stays usable by
+ * sfw_ensemble_aggregate and sfw_ensemble_blend; then SFW_ERR_STATE when a hypothesis was never set, a member's sfw_params
+ * differ, its terms capture was turned off or no costmap was set.  A failure from there on leaves nothing scored.
+ * sfw_ensemble_aggregate after this call re-aggregates with the list's selection. */
+int sfw_ensemble_score_sequences(sfw_ensemble e, const sfw_robot_state *rs, const double *vx, const double *vy,
+                                 const double *vtheta, int32_t n, int32_t K, const int32_t *knot_step,
+                                 const sfw_goal_args *args, int32_t mode, const double *probs, double *costs_out,
+                                 int32_t *rejected_out, sfw_best *best_out);
+/* ... with the knots drawn on the device: every member stages as sfw_sequences_perturb_stage would with the same *p and
+ * index_base 0, so all members hold bitwise the same knots (sfw_sequences_knots on any member) and the results are those of
+ * sfw_ensemble_score_sequences fed these knots.  best_out's command is read from the device.  The argument rules are those
+ * of sfw_sequences_perturb_stage, in the same place. */
+int sfw_ensemble_score_perturbed(sfw_ensemble e, const sfw_robot_state *rs, const sfw_perturb *p, int32_t n, int32_t K,
+                                 const int32_t *knot_step, const sfw_goal_args *args, int32_t mode, const double *probs,
+                                 double *costs_out, int32_t *rejected_out, sfw_best *best_out);
+/* sfw_grid_blend over the ENSEMBLE cost vector: its definition, its outputs and its summation tree ("Determinism" above),
+ * with J_t the cost vector of the last aggregation (a score call or sfw_ensemble_aggregate) and the knots of member 0 — after
+ * sfw_ensemble_score_grid K = 1 and sample t = iv * nw + iw, as the handle's blend over a grid.  Read-only for the score: it
+ * may be repeated and alternate with sfw_ensemble_aggregate.  stat.n_valid is best.n_valid of that aggregation; with no valid
+ * sample the all-zero record of sfw_grid_blend comes back with SFW_OK.  The cost vector is read on the device wherever the
+ * aggregation left it for the host.  Argument refusals are sfw_grid_blend's (before any device call); SFW_ERR_STATE by the
+ * rule of sfw_ensemble_aggregate.  Member 0's own sfw_grid_blend is not disturbed: the ensemble has buffers of its own. */
+int sfw_ensemble_blend(sfw_ensemble e, const double *lambda, int32_t L, const double *bias, sfw_blend_stat *stat_out,
+                       double *u_out, double *weights_out);
+/* Host wall-clock of the last calls, microseconds: which = 0 staging of the members (the score calls only), 1 the enqueue of
+ * the launch and the aggregation, 2 the wait and the copies out. */
 int sfw_ensemble_last_us(sfw_ensemble e, int32_t which, double *us_out);
 
 #ifdef __cplusplus

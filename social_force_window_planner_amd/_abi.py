@@ -226,6 +226,9 @@ EXPORTED_SYMBOLS = (
     "sfw_score_perturbed",
     "sfw_sequences_knots",
     "sfw_sequences_normals",
+    "sfw_ensemble_score_sequences",
+    "sfw_ensemble_score_perturbed",
+    "sfw_ensemble_blend",
 )
 # per-term costs (sfw_set_terms_capture / sfw_grid_rescore / sfw_grid_terms)
 SFW_TERM_VEL, SFW_TERM_DISTANCE, SFW_TERM_ANGLE, SFW_TERM_COSTMAP, SFW_TERM_SOCIAL = 0, 1, 2, 3, 4

@@ -1226,6 +1226,26 @@ struct perturb_source {
   bool vy, keep_normals, zero_admitted;
 };
 
+// stage_common's argument rules as texts of their own (null: accepted), in two parts because the costmap's state check stands
+// between them: an ensemble's score calls read the same ones before ANY member is staged.  drawn: the device draws the sample
+// vectors (lin == ang == null); n_ang: values per row of ang; kn: rows of the sample vectors.
+const char *stage_null_refusal(const sfw_robot_state *rs, const double *lin, int32_t nv, const double *ang, int32_t nw,
+                               const sfw_goal_args *args, bool drawn) {
+  if (!rs || (!drawn && (!lin || !ang)) || !args || nv <= 0 || nw <= 0) return "null pointer or non-positive sample count";
+  return nullptr;
+}
+// A NaN would come back as a NaN cost (the header promises sentinels, never NaN) and, in a sample vector, break the
+// ordering the shared-prefix planner sorts by: O(nv + nw) checks
+const char *stage_finite_refusal(const sfw_robot_state *rs, const double *lin, int32_t nv, const double *ang, size_t n_ang,
+                                 const sfw_goal_args *args, double vy_samp, const double *vy_list, size_t kn, bool drawn) {
+  if (!all_finite(&rs->x, 6) || !all_finite(&args->acc_x, 5) || !std::isfinite(vy_samp))
+    return "non-finite robot state, goal argument or sample velocity";
+  if (!drawn && (!all_finite(lin, kn * static_cast<size_t>(nv)) || !all_finite(ang, kn * n_ang) ||
+                 (vy_list && !all_finite(vy_list, kn * static_cast<size_t>(nv)))))
+    return "non-finite sample velocity";
+  return nullptr;
+}
+
 // list: sfw_samples_stage — lin / ang are vx / vtheta of nv samples (nw == 1), vy_list their vy (nullable: all 0.0)
 // knot_step (list only, nullable): sfw_sequences_stage — lin / ang / vy_list hold nk rows of nv values, knot-major, and
 // knot_step the nk steps at which a knot takes over (checked by the caller: knot_step[0] == 0, strictly ascending)
@@ -1237,17 +1257,12 @@ int stage_common(sfw_handle h, const sfw_robot_state *rs, const double *lin, int
   const std::string what = dev ? "sequences_perturb_stage" : knot_step ? "sequences_stage" : list ? "samples_stage" : "grid_stage";
   const size_t kn = knot_step ? static_cast<size_t>(nk) : size_t(1);  // rows of the sample vectors
   const bool has_vy = dev ? dev->vy : vy_list != nullptr;
-  if (!rs || (!dev && (!lin || !ang)) || !args || nv <= 0 || nw <= 0)
-    return fail(h, SFW_ERR_INVALID_ARG, what + ": null pointer or non-positive sample count");
+  if (const char *why = stage_null_refusal(rs, lin, nv, ang, nw, args, dev != nullptr))
+    return fail(h, SFW_ERR_INVALID_ARG, what + ": " + why);
   const size_t n_ang = list ? static_cast<size_t>(nv) : static_cast<size_t>(nw);
   if (!h->world.have_costmap) return fail(h, SFW_ERR_STATE, what + ": no costmap set (sfw_set_costmap)");
-  // A NaN would come back as a NaN cost (the header promises sentinels, never NaN) and, in a sample vector, break the
-  // ordering the shared-prefix planner sorts by: O(nv + nw) checks
-  if (!all_finite(&rs->x, 6) || !all_finite(&args->acc_x, 5) || !std::isfinite(vy_samp))
-    return fail(h, SFW_ERR_INVALID_ARG, what + ": non-finite robot state, goal argument or sample velocity");
-  if (!dev && (!all_finite(lin, kn * static_cast<size_t>(nv)) || !all_finite(ang, kn * n_ang) ||
-               (vy_list && !all_finite(vy_list, kn * static_cast<size_t>(nv)))))
-    return fail(h, SFW_ERR_INVALID_ARG, what + ": non-finite sample velocity");
+  if (const char *why = stage_finite_refusal(rs, lin, nv, ang, n_ang, args, vy_samp, vy_list, kn, dev != nullptr))
+    return fail(h, SFW_ERR_INVALID_ARG, what + ": " + why);
   drop_stage(h);  // (valid again at the end of this function, and only there)
   host_phases ph("stage:");
   SFW_HIP(h, hipSetDevice(h->device));
@@ -1773,6 +1788,118 @@ int sel_to_best(sfw_handle h, const sfw_sel &s, sfw_best *best, sfw_best_key *ke
   return SFW_OK;
 }
 
+// The argument rules of the sequence stages as texts of their own: null when the arguments are accepted, else why not.  The
+// handle's stages and the ensemble's score calls (which must refuse before ANY member is staged) read the same ones.
+const char *sequences_refusal(int32_t K, const int32_t *knot_step) {
+  if (K < 1 || K > SFW_SEQ_MAX_KNOTS) return "K outside 1..SFW_SEQ_MAX_KNOTS";
+  if (!knot_step) return "knot_step is NULL";
+  if (knot_step[0] != 0) return "knot_step[0] must be 0";
+  for (int32_t k = 1; k < K; ++k)
+    if (knot_step[k] <= knot_step[k - 1]) return "knot_step must be strictly ascending";
+  return nullptr;
+}
+const char *perturb_refusal(const sfw_robot_state *rs, const sfw_perturb *p, int32_t n, int32_t K, const int32_t *knot_step,
+                            const sfw_goal_args *args, int64_t index_base) {
+  if (!rs || !p || !p->nominal || !knot_step || !args) return "rs, p, p->nominal, knot_step or args is NULL";
+  if (n < 1) return "n < 1";
+  if (K < 1 || K > SFW_SEQ_MAX_KNOTS) return "K outside 1..SFW_SEQ_MAX_KNOTS";
+  if (knot_step[0] != 0) return "knot_step[0] must be 0";
+  for (int32_t k = 1; k < K; ++k)
+    if (knot_step[k] <= knot_step[k - 1]) return "knot_step must be strictly ascending";
+  if (index_base < 0) return "index_base < 0";
+  constexpr int32_t known = SFW_PERTURB_KEEP_NOMINAL | SFW_PERTURB_NO_VY | SFW_PERTURB_KEEP_NORMALS;
+  if ((p->flags & ~known) != 0 || p->reserved != 0) return "unknown flag bits, or reserved != 0";
+  if (!all_finite(p->nominal, 3 * static_cast<size_t>(K)) || !all_finite(p->sigma, 3) || !all_finite(p->lo, 3) || !all_finite(p->hi, 3))
+    return "non-finite nominal, sigma, lo or hi";
+  for (int c = 0; c < 3; ++c) {
+    if (p->sigma[c] < 0.0) return "a sigma is negative";
+    if (p->lo[c] > p->hi[c]) return "lo > hi";
+  }
+  if ((p->flags & SFW_PERTURB_NO_VY) != 0) {
+    if (p->sigma[1] != 0.0) return "SFW_PERTURB_NO_VY with sigma[1] != 0";
+    for (int32_t k = 0; k < K; ++k)
+      if (p->nominal[3 * k + 1] != 0.0) return "SFW_PERTURB_NO_VY with a nominal vy != 0";
+  }
+  return nullptr;
+}
+// ... and stage_common's own (stage_null_refusal, stage_finite_refusal) for a list of n samples with kn knot rows
+const char *list_stage_refusal(const sfw_robot_state *rs, const double *lin, const double *vy_list, const double *ang, int32_t n,
+                               size_t kn, const sfw_goal_args *args, bool drawn) {
+  if (const char *why = stage_null_refusal(rs, lin, n, ang, 1, args, drawn)) return why;
+  return stage_finite_refusal(rs, lin, n, ang, static_cast<size_t>(n), args, 0.0, vy_list, kn, drawn);
+}
+const char *blend_refusal(const double *lambda, int32_t L, const sfw_blend_stat *stat_out, const double *u_out) {
+  if (!lambda || !stat_out || !u_out) return "lambda, stat_out or u_out is NULL";
+  if (L < 1 || L > SFW_BLEND_MAX_L) return "L out of [1, SFW_BLEND_MAX_L]";
+  for (int32_t l = 0; l < L; ++l)
+    if (!std::isfinite(lambda[l]) || !(lambda[l] > 0.0)) return "a lambda is not finite or not > 0";
+  return nullptr;
+}
+
+// The buffers of a softmin blend (the handle's own; an sfw_ensemble's) and the blend itself over a device cost vector of T
+// samples with the knot rows at lin / vy / ang: ONE text for sfw_grid_blend and sfw_ensemble_blend, on h's stream.  Arguments
+// and state are the caller's to check.
+struct blend_area {
+  dev_buf<sfw_blend_min> &mins;
+  dev_buf<double> &partials, &bias, &weights;
+  pinned_buf &pin;
+};
+int blend_run(sfw_handle h, const blend_area &a, const double *d_costs, int64_t T, int K, const double *d_lin, const double *d_vy,
+              const double *d_ang, int nw, bool list, const double *lambda, int32_t L, const double *bias, sfw_blend_stat *stat_out,
+              double *u_out, double *weights_out) {
+  const int64_t n_ch = sfw_blend_channels(L, K), blocks = sfw_blend_blocks(T);
+  const size_t head = (sizeof(sfw_blend_min) + 15) & ~size_t(15), out_bytes = head + sizeof(double) * static_cast<size_t>(n_ch);
+  // (growing the pinned area frees the old one: nothing in the stream may still be writing there)
+  if (out_bytes > a.pin.cap) SFW_HIP(h, hipStreamSynchronize(h->stream));
+  SFW_HIP(h, a.pin.reserve(out_bytes));
+  SFW_HIP(h, a.mins.reserve(static_cast<size_t>(sfw_blend_min_blocks(T))));
+  SFW_HIP(h, a.partials.reserve(static_cast<size_t>(blocks) * static_cast<size_t>(n_ch)));
+  if (bias) {
+    SFW_HIP(h, a.bias.reserve(static_cast<size_t>(T)));
+    SFW_HIP(h, hipMemcpyAsync(a.bias.p, bias, sizeof(double) * static_cast<size_t>(T), hipMemcpyHostToDevice, h->stream));
+  }
+  const double *const d_bias = bias ? a.bias.p : nullptr;
+  // weights_out: all L vectors from the launch that forms the sums, or — beyond 256 MB of them — in slices of as many
+  // temperatures as that holds, each by a launch of its own that is copied out behind it
+  const int64_t fit = std::max<int64_t>(1, (int64_t(256) << 20) / (static_cast<int64_t>(sizeof(double)) * T));
+  const bool sliced = weights_out && fit < L;
+  const int32_t l_step = static_cast<int32_t>(std::min<int64_t>(L, fit));
+  if (weights_out) SFW_HIP(h, a.weights.reserve(static_cast<size_t>(l_step) * static_cast<size_t>(T)));
+  sfw_blend_lambdas lam{};
+  for (int32_t l = 0; l < L; ++l) lam.v[l] = lambda[l];
+  sfw_blend_min *const min_host = reinterpret_cast<sfw_blend_min *>(a.pin.p);
+  double *const out_host = reinterpret_cast<double *>(a.pin.p + head);
+  SFW_HIP(h, sfw_launch_blend(d_costs, d_bias, T, lam, L, K, d_lin, d_vy, d_ang, nw, list, a.mins.p, a.partials.p,
+                              weights_out && !sliced ? a.weights.p : nullptr, min_host, out_host, h->stream));
+  if (weights_out && !sliced)
+    SFW_HIP(h, hipMemcpyAsync(weights_out, a.weights.p, sizeof(double) * static_cast<size_t>(L) * static_cast<size_t>(T),
+                              hipMemcpyDeviceToHost, h->stream));
+  for (int32_t l0 = 0; sliced && l0 < L; l0 += l_step) {
+    const int32_t n = std::min(l_step, L - l0);
+    sfw_blend_lambdas part{};
+    for (int32_t l = 0; l < n; ++l) part.v[l] = lambda[l0 + l];
+    SFW_HIP(h, sfw_launch_blend_weights(d_costs, d_bias, T, part, n, a.mins.p, a.weights.p, h->stream));
+    SFW_HIP(h, hipMemcpyAsync(weights_out + static_cast<int64_t>(l0) * T, a.weights.p,
+                              sizeof(double) * static_cast<size_t>(n) * static_cast<size_t>(T), hipMemcpyDeviceToHost, h->stream));
+  }
+  SFW_HIP(h, a.pin.mark(h->stream));
+  SFW_HIP(h, wait_stream(h));
+  a.pin.pending = false;
+  stream_is_idle(h);
+  const sfw_blend_min m = *min_host;
+  const bool any = m.n_valid > 0;
+  for (int32_t l = 0; l < L; ++l) {
+    stat_out[l].lambda = lambda[l];
+    stat_out[l].j_min = any ? m.j : -1.0;
+    stat_out[l].eta = out_host[l];
+    stat_out[l].sum_w2 = out_host[L + l];
+    stat_out[l].n_valid = m.n_valid;
+    stat_out[l].index_min = any ? m.index : -1;
+  }
+  std::memcpy(u_out, out_host + 2 * L, sizeof(double) * 3 * static_cast<size_t>(K) * static_cast<size_t>(L));
+  return SFW_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2128,11 +2255,7 @@ int sfw_sequences_stage(sfw_handle h, const sfw_robot_state *rs, const double *v
                         int32_t n, int32_t K, const int32_t *knot_step, const sfw_goal_args *args, int64_t index_base) {
   if (!h) return SFW_ERR_INVALID_ARG;
   // (refused before anything is touched: the staged grid, list or sequences stay launchable)
-  if (K < 1 || K > SFW_SEQ_MAX_KNOTS) return fail(h, SFW_ERR_INVALID_ARG, "sequences_stage: K outside 1..SFW_SEQ_MAX_KNOTS");
-  if (!knot_step) return fail(h, SFW_ERR_INVALID_ARG, "sequences_stage: knot_step is NULL");
-  if (knot_step[0] != 0) return fail(h, SFW_ERR_INVALID_ARG, "sequences_stage: knot_step[0] must be 0");
-  for (int32_t k = 1; k < K; ++k)
-    if (knot_step[k] <= knot_step[k - 1]) return fail(h, SFW_ERR_INVALID_ARG, "sequences_stage: knot_step must be strictly ascending");
+  if (const char *why = sequences_refusal(K, knot_step)) return fail(h, SFW_ERR_INVALID_ARG, std::string("sequences_stage: ") + why);
   // a list of n samples to everything that counts samples; K rows of n values behind its vectors
   return stage_common(h, rs, vx, n, vtheta, 1, args, 0.0, 0, index_base, true, true, vy, K, knot_step);
 }
@@ -2206,29 +2329,9 @@ int sfw_sequences_perturb_stage(sfw_handle h, const sfw_robot_state *rs, const s
                                 const int32_t *knot_step, const sfw_goal_args *args, int64_t index_base) {
   if (!h) return SFW_ERR_INVALID_ARG;
   // (refused before anything is touched: the staged grid, list or sequences stay launchable)
-  const char *const what = "sequences_perturb_stage: ";
-  auto refuse = [&](const char *why) { return fail(h, SFW_ERR_INVALID_ARG, std::string(what) + why); };
-  if (!rs || !p || !p->nominal || !knot_step || !args) return refuse("rs, p, p->nominal, knot_step or args is NULL");
-  if (n < 1) return refuse("n < 1");
-  if (K < 1 || K > SFW_SEQ_MAX_KNOTS) return refuse("K outside 1..SFW_SEQ_MAX_KNOTS");
-  if (knot_step[0] != 0) return refuse("knot_step[0] must be 0");
-  for (int32_t k = 1; k < K; ++k)
-    if (knot_step[k] <= knot_step[k - 1]) return refuse("knot_step must be strictly ascending");
-  if (index_base < 0) return refuse("index_base < 0");
-  constexpr int32_t known = SFW_PERTURB_KEEP_NOMINAL | SFW_PERTURB_NO_VY | SFW_PERTURB_KEEP_NORMALS;
-  if ((p->flags & ~known) != 0 || p->reserved != 0) return refuse("unknown flag bits, or reserved != 0");
-  if (!all_finite(p->nominal, 3 * static_cast<size_t>(K)) || !all_finite(p->sigma, 3) || !all_finite(p->lo, 3) || !all_finite(p->hi, 3))
-    return refuse("non-finite nominal, sigma, lo or hi");
-  for (int c = 0; c < 3; ++c) {
-    if (p->sigma[c] < 0.0) return refuse("a sigma is negative");
-    if (p->lo[c] > p->hi[c]) return refuse("lo > hi");
-  }
+  if (const char *why = perturb_refusal(rs, p, n, K, knot_step, args, index_base))
+    return fail(h, SFW_ERR_INVALID_ARG, std::string("sequences_perturb_stage: ") + why);
   const bool no_vy = (p->flags & SFW_PERTURB_NO_VY) != 0;
-  if (no_vy) {
-    if (p->sigma[1] != 0.0) return refuse("SFW_PERTURB_NO_VY with sigma[1] != 0");
-    for (int32_t k = 0; k < K; ++k)
-      if (p->nominal[3 * k + 1] != 0.0) return refuse("SFW_PERTURB_NO_VY with a nominal vy != 0");
-  }
   perturb_source src{};
   src.args.key0 = static_cast<uint32_t>(p->seed & 0xffffffffu);
   src.args.key1 = static_cast<uint32_t>(p->seed >> 32);
@@ -2585,67 +2688,14 @@ int sfw_grid_rescore(sfw_handle h, const sfw_weights *w, int32_t K, sfw_best *be
 int sfw_grid_blend(sfw_handle h, const double *lambda, int32_t L, const double *bias, sfw_blend_stat *stat_out, double *u_out,
                    double *weights_out) {
   if (!h) return SFW_ERR_INVALID_ARG;
-  if (!lambda || !stat_out || !u_out) return fail(h, SFW_ERR_INVALID_ARG, "grid_blend: lambda, stat_out or u_out is NULL");
-  if (L < 1 || L > SFW_BLEND_MAX_L) return fail(h, SFW_ERR_INVALID_ARG, "grid_blend: L out of [1, SFW_BLEND_MAX_L]");
-  for (int32_t l = 0; l < L; ++l)
-    if (!std::isfinite(lambda[l]) || !(lambda[l] > 0.0)) return fail(h, SFW_ERR_INVALID_ARG, "grid_blend: a lambda is not finite or not > 0");
+  if (const char *why = blend_refusal(lambda, L, stat_out, u_out)) return fail(h, SFW_ERR_INVALID_ARG, std::string("grid_blend: ") + why);
   if (!h->last.launched) return fail(h, SFW_ERR_STATE, "grid_blend: no launch, or a stage or sfw_score_one came in since");
   const int64_t T = static_cast<int64_t>(h->st.nv) * h->st.nw;
   if (bias && !all_finite(bias, static_cast<size_t>(T))) return fail(h, SFW_ERR_INVALID_ARG, "grid_blend: non-finite bias");
   SFW_HIP(h, hipSetDevice(h->device));
-  const int K = h->st.list ? h->st.nk : 1;
-  const int64_t n_ch = sfw_blend_channels(L, K), blocks = sfw_blend_blocks(T);
-  const size_t head = (sizeof(sfw_blend_min) + 15) & ~size_t(15), out_bytes = head + sizeof(double) * static_cast<size_t>(n_ch);
-  // (growing the pinned area frees the old one: nothing in the stream may still be writing there)
-  if (out_bytes > h->pin_blend.cap) SFW_HIP(h, hipStreamSynchronize(h->stream));
-  SFW_HIP(h, h->pin_blend.reserve(out_bytes));
-  SFW_HIP(h, h->blend_mins.reserve(static_cast<size_t>(sfw_blend_min_blocks(T))));
-  SFW_HIP(h, h->blend_partials.reserve(static_cast<size_t>(blocks) * static_cast<size_t>(n_ch)));
-  if (bias) {
-    SFW_HIP(h, h->blend_bias.reserve(static_cast<size_t>(T)));
-    SFW_HIP(h, hipMemcpyAsync(h->blend_bias.p, bias, sizeof(double) * static_cast<size_t>(T), hipMemcpyHostToDevice, h->stream));
-  }
-  const double *const d_bias = bias ? h->blend_bias.p : nullptr;
-  // weights_out: all L vectors from the launch that forms the sums, or — beyond 256 MB of them — in slices of as many
-  // temperatures as that holds, each by a launch of its own that is copied out behind it
-  const int64_t fit = std::max<int64_t>(1, (int64_t(256) << 20) / (static_cast<int64_t>(sizeof(double)) * T));
-  const bool sliced = weights_out && fit < L;
-  const int32_t l_step = static_cast<int32_t>(std::min<int64_t>(L, fit));
-  if (weights_out) SFW_HIP(h, h->blend_weights.reserve(static_cast<size_t>(l_step) * static_cast<size_t>(T)));
-  sfw_blend_lambdas lam{};
-  for (int32_t l = 0; l < L; ++l) lam.v[l] = lambda[l];
-  sfw_blend_min *const min_host = reinterpret_cast<sfw_blend_min *>(h->pin_blend.p);
-  double *const out_host = reinterpret_cast<double *>(h->pin_blend.p + head);
-  SFW_HIP(h, sfw_launch_blend(h->costs.p, d_bias, T, lam, L, K, h->st.d_linvels, h->st.d_vy, h->st.d_angvels, h->st.nw, h->st.list,
-                              h->blend_mins.p, h->blend_partials.p, weights_out && !sliced ? h->blend_weights.p : nullptr, min_host,
-                              out_host, h->stream));
-  if (weights_out && !sliced)
-    SFW_HIP(h, hipMemcpyAsync(weights_out, h->blend_weights.p, sizeof(double) * static_cast<size_t>(L) * static_cast<size_t>(T),
-                              hipMemcpyDeviceToHost, h->stream));
-  for (int32_t l0 = 0; sliced && l0 < L; l0 += l_step) {
-    const int32_t n = std::min(l_step, L - l0);
-    sfw_blend_lambdas part{};
-    for (int32_t l = 0; l < n; ++l) part.v[l] = lambda[l0 + l];
-    SFW_HIP(h, sfw_launch_blend_weights(h->costs.p, d_bias, T, part, n, h->blend_mins.p, h->blend_weights.p, h->stream));
-    SFW_HIP(h, hipMemcpyAsync(weights_out + static_cast<int64_t>(l0) * T, h->blend_weights.p,
-                              sizeof(double) * static_cast<size_t>(n) * static_cast<size_t>(T), hipMemcpyDeviceToHost, h->stream));
-  }
-  SFW_HIP(h, h->pin_blend.mark(h->stream));
-  SFW_HIP(h, wait_stream(h));
-  h->pin_blend.pending = false;
-  stream_is_idle(h);
-  const sfw_blend_min m = *min_host;
-  const bool any = m.n_valid > 0;
-  for (int32_t l = 0; l < L; ++l) {
-    stat_out[l].lambda = lambda[l];
-    stat_out[l].j_min = any ? m.j : -1.0;
-    stat_out[l].eta = out_host[l];
-    stat_out[l].sum_w2 = out_host[L + l];
-    stat_out[l].n_valid = m.n_valid;
-    stat_out[l].index_min = any ? m.index : -1;
-  }
-  std::memcpy(u_out, out_host + 2 * L, sizeof(double) * 3 * static_cast<size_t>(K) * static_cast<size_t>(L));
-  return SFW_OK;
+  const blend_area area{h->blend_mins, h->blend_partials, h->blend_bias, h->blend_weights, h->pin_blend};
+  return blend_run(h, area, h->costs.p, T, h->st.list ? h->st.nk : 1, h->st.d_linvels, h->st.d_vy, h->st.d_angvels, h->st.nw,
+                   h->st.list, lambda, L, bias, stat_out, u_out, weights_out);
 }
 
 int sfw_grid_terms(sfw_handle h, int64_t first, int64_t count, double *terms_out) {
@@ -3712,6 +3762,14 @@ struct sfw_ensemble_s {
   std::vector<uint64_t> seq;
   int64_t T = 0;
   double us[3] = {0.0, 0.0, 0.0};
+  // sfw_ensemble_blend: the last aggregation's cost vector ON THE DEVICE — d_out when it went there, d_cost when it went to
+  // the pinned mirror (a list's aggregation writes both; a grid's is uploaded by the first blend that asks: cost_dev null) —
+  // and the blend's own buffers (member 0's belong to its sfw_grid_blend)
+  dev_buf<double> d_cost;
+  const double *cost_dev = nullptr;
+  dev_buf<sfw_blend_min> blend_mins;
+  dev_buf<double> blend_partials, blend_bias, blend_weights;
+  pinned_buf pin_blend;
 };
 
 namespace {
@@ -3745,8 +3803,11 @@ int ensemble_enqueue(sfw_ensemble e, int32_t mode, const double *probs) {
   const size_t rej_bytes = (sizeof(int32_t) * static_cast<size_t>(T) + 15) & ~size_t(15);
   e->T = T;
   e->mirrored = cost_bytes <= h0->cfg.mirror_max_bytes;  // (the handle's rule: pinned up to SFW_MIRROR_MAX_MB of costs)
+  const bool list = h0->st.list;  // the members staged sequences (a list): the list form of stage 1
+  e->cost_dev = nullptr;
   if (e->pin_out.reserve(kEnsRecBytes + (e->mirrored ? cost_bytes + rej_bytes : 0)) != hipSuccess ||
       (!e->mirrored && e->d_out.reserve(cost_bytes + rej_bytes) != hipSuccess) ||
+      (e->mirrored && list && e->d_cost.reserve(static_cast<size_t>(T)) != hipSuccess) ||
       e->partials.reserve(static_cast<size_t>(sfw_argmin_partials(T))) != hipSuccess)
     return efail(e, SFW_ERR_HIP, "ensemble: output allocation failed");
   const size_t tab_bytes = 2 * sizeof(double) * static_cast<size_t>(M);
@@ -3764,12 +3825,19 @@ int ensemble_enqueue(sfw_ensemble e, int32_t mode, const double *probs) {
   const sfw_weights w{e->params.vel_weight, e->params.distance_weight, e->params.angle_weight, e->params.costmap_weight,
                       e->params.social_weight};
   char *const out = e->mirrored ? e->pin_out.p + kEnsRecBytes : e->d_out.p;
-  const hipError_t he = sfw_launch_ensemble(reinterpret_cast<const double *const *>(e->tab.p),
-                                            reinterpret_cast<const double *>(e->tab.p + sizeof(double) * static_cast<size_t>(M)), M, T,
-                                            mode, w, h0->st.d_linvels, h0->st.d_angvels, h0->st.nw, reinterpret_cast<double *>(out),
-                                            reinterpret_cast<int32_t *>(out + cost_bytes), e->partials.p,
-                                            reinterpret_cast<sfw_sel *>(e->pin_out.p), e->b->stream);
-  if (he != hipSuccess) return efail(e, SFW_ERR_HIP, std::string("ensemble: sfw_ensemble_stage1/2: ") + hipGetErrorString(he));
+  const double *const *const d_terms = reinterpret_cast<const double *const *>(e->tab.p);
+  const double *const d_probs = reinterpret_cast<const double *>(e->tab.p + sizeof(double) * static_cast<size_t>(M));
+  const hipError_t he =
+      list ? sfw_launch_ensemble_list(d_terms, d_probs, M, T, mode, w, h0->st.d_linvels, h0->st.d_angvels, reinterpret_cast<double *>(out),
+                                      e->mirrored ? e->d_cost.p : nullptr, reinterpret_cast<int32_t *>(out + cost_bytes),
+                                      e->partials.p, reinterpret_cast<sfw_sel *>(e->pin_out.p), e->b->stream)
+           : sfw_launch_ensemble(d_terms, d_probs, M, T, mode, w, h0->st.d_linvels, h0->st.d_angvels, h0->st.nw,
+                                 reinterpret_cast<double *>(out), reinterpret_cast<int32_t *>(out + cost_bytes), e->partials.p,
+                                 reinterpret_cast<sfw_sel *>(e->pin_out.p), e->b->stream);
+  if (he != hipSuccess)
+    return efail(e, SFW_ERR_HIP, std::string(list ? "ensemble: sfw_ens_list_first / sfw_ensemble_stage2: " : "ensemble: sfw_ensemble_stage1/2: ") +
+                                     hipGetErrorString(he));
+  e->cost_dev = !e->mirrored ? reinterpret_cast<const double *>(e->d_out.p) : list ? e->d_cost.p : nullptr;
   return SFW_OK;
 }
 
@@ -3788,7 +3856,53 @@ int ensemble_finish(sfw_ensemble e, double *costs_out, int32_t *rejected_out, sf
   }
   sfw_sel s;
   std::memcpy(&s, e->pin_out.p, sizeof(s));
-  (void)sel_to_best(e->b->h[0], s, best_out, nullptr);  // (an ensemble stages grids: the host holds the axes)
+  // (member 0 holds what the record refers to: a grid's axes, a list's first knot row — on the device after a perturbed stage)
+  if (int rc = sel_to_best(e->b->h[0], s, best_out, nullptr)) return emember_fail(e, 0, rc, "ensemble: winner's first knot");
+  return SFW_OK;
+}
+
+// The state rules every ensemble score shares, after the arguments and before any member is staged
+int ensemble_check_members(sfw_ensemble e, const char *what) {
+  for (size_t m = 0; m < e->b->h.size(); ++m) {
+    const sfw_handle h = e->b->h[m];
+    if (!e->hyp_set[m]) return efail(e, SFW_ERR_STATE, std::string(what) + ": hypothesis " + std::to_string(m) + " was never set");
+    if (std::memcmp(&h->live.params, &e->params, sizeof(sfw_params)) != 0)
+      return efail(e, SFW_ERR_STATE, std::string(what) + ": member " + std::to_string(m) + "'s sfw_params differ from the ensemble's");
+    if (!h->live.capture_terms)
+      return efail(e, SFW_ERR_STATE, std::string(what) + ": member " + std::to_string(m) + "'s terms capture was turned off");
+    if (!h->world.have_costmap) return efail(e, SFW_ERR_STATE, std::string(what) + ": no costmap set (sfw_ensemble_set_costmap)");
+  }
+  return SFW_OK;
+}
+
+// The state rule of sfw_ensemble_aggregate and sfw_ensemble_blend: something was scored, and no member has moved since
+int ensemble_check_scored(sfw_ensemble e, const char *what) {
+  if (!e->scored) return efail(e, SFW_ERR_STATE, std::string(what) + ": nothing scored (sfw_ensemble_score_grid / _sequences / _perturbed)");
+  for (size_t m = 0; m < e->b->h.size(); ++m) {
+    const sfw_handle h = e->b->h[m];
+    if (!h->last.launched || !h->last.terms || h->launch_seq != e->seq[m])
+      return efail(e, SFW_ERR_STATE, std::string(what) + ": member " + std::to_string(m) +
+                                         " was staged, launched or used for sfw_score_one since the last score");
+  }
+  return SFW_OK;
+}
+
+// Every member is staged: one batch launch, the aggregation behind it, one wait (the shape of sfw_ensemble_score_grid)
+int ensemble_launch_and_finish(sfw_ensemble e, int32_t mode, const double *probs, double *costs_out, int32_t *rejected_out,
+                               sfw_best *best_out, const std::string &what) {
+  const size_t M = e->b->h.size();
+  auto t0 = std::chrono::steady_clock::now();
+  if (int rc = batch_launch(e->b)) return efail(e, rc, what + ": " + e->b->err);
+  for (size_t m = 0; m < M; ++m)
+    if (!e->b->h[m]->last.terms) return efail(e, SFW_ERR_STATE, what + ": member " + std::to_string(m) + " did not capture terms");
+  if (int rc = ensemble_enqueue(e, mode, probs)) return rc;
+  e->us[1] = us_since(t0);
+  t0 = std::chrono::steady_clock::now();
+  if (int rc = batch_fetch(e->b, nullptr)) return efail(e, rc, what + ": " + e->b->err);  // (one wait, all members)
+  if (int rc = ensemble_finish(e, costs_out, rejected_out, best_out)) return rc;
+  e->us[2] = us_since(t0);
+  for (size_t m = 0; m < M; ++m) e->seq[m] = e->b->h[m]->launch_seq;
+  e->scored = true;
   return SFW_OK;
 }
 }  // namespace
@@ -3826,6 +3940,12 @@ int sfw_ensemble_destroy(sfw_ensemble e) {
   e->tab.release();
   e->d_out.release();
   e->partials.release();
+  e->d_cost.release();
+  e->blend_mins.release();
+  e->blend_partials.release();
+  e->blend_bias.release();
+  e->blend_weights.release();
+  e->pin_blend.release();
   delete e;
   return SFW_OK;
 }
@@ -3878,36 +3998,80 @@ int sfw_ensemble_score_grid(sfw_ensemble e, const sfw_robot_state *rs, const dou
   if (int rc = ensemble_check_mode(e, mode, probs, "ensemble_score_grid")) return rc;
   if (!rs || !args || !linvels || !angvels || nv <= 0 || nw <= 0)
     return efail(e, SFW_ERR_INVALID_ARG, "ensemble_score_grid: null robot state, goal arguments or sample vectors");
-  const int32_t M = static_cast<int32_t>(e->b->h.size());
-  for (int32_t m = 0; m < M; ++m) {
-    const sfw_handle h = e->b->h[static_cast<size_t>(m)];
-    if (!e->hyp_set[static_cast<size_t>(m)])
-      return efail(e, SFW_ERR_STATE, "ensemble_score_grid: hypothesis " + std::to_string(m) + " was never set");
-    if (std::memcmp(&h->live.params, &e->params, sizeof(sfw_params)) != 0)
-      return efail(e, SFW_ERR_STATE, "ensemble_score_grid: member " + std::to_string(m) + "'s sfw_params differ from the ensemble's");
-    if (!h->live.capture_terms)
-      return efail(e, SFW_ERR_STATE, "ensemble_score_grid: member " + std::to_string(m) + "'s terms capture was turned off");
-  }
+  const char *const what = "ensemble_score_grid";
+  if (int rc = ensemble_check_members(e, what)) return rc;
   e->scored = false;
   if (hipSetDevice(e->device) != hipSuccess) return efail(e, SFW_ERR_HIP, "ensemble_score_grid: hipSetDevice failed");
-  auto t0 = std::chrono::steady_clock::now();
-  for (int32_t m = 0; m < M; ++m)
-    if (int rc = sfw_grid_stage(e->b->h[static_cast<size_t>(m)], rs, linvels, nv, angvels, nw, args, 0))
-      return emember_fail(e, m, rc, "ensemble_score_grid: stage");
+  const auto t0 = std::chrono::steady_clock::now();
+  for (size_t m = 0; m < e->b->h.size(); ++m)
+    if (int rc = sfw_grid_stage(e->b->h[m], rs, linvels, nv, angvels, nw, args, 0))
+      return emember_fail(e, static_cast<int32_t>(m), rc, "ensemble_score_grid: stage");
   e->us[0] = us_since(t0);
-  t0 = std::chrono::steady_clock::now();
-  if (int rc = batch_launch(e->b)) return efail(e, rc, "ensemble_score_grid: " + e->b->err);
-  for (int32_t m = 0; m < M; ++m)
-    if (!e->b->h[static_cast<size_t>(m)]->last.terms)
-      return efail(e, SFW_ERR_STATE, "ensemble_score_grid: member " + std::to_string(m) + " did not capture terms");
-  if (int rc = ensemble_enqueue(e, mode, probs)) return rc;
-  e->us[1] = us_since(t0);
-  t0 = std::chrono::steady_clock::now();
-  if (int rc = batch_fetch(e->b, nullptr)) return efail(e, rc, "ensemble_score_grid: " + e->b->err);  // (one wait, all members)
-  if (int rc = ensemble_finish(e, costs_out, rejected_out, best_out)) return rc;
-  e->us[2] = us_since(t0);
-  for (int32_t m = 0; m < M; ++m) e->seq[static_cast<size_t>(m)] = e->b->h[static_cast<size_t>(m)]->launch_seq;
-  e->scored = true;
+  return ensemble_launch_and_finish(e, mode, probs, costs_out, rejected_out, best_out, what);
+}
+
+int sfw_ensemble_score_sequences(sfw_ensemble e, const sfw_robot_state *rs, const double *vx, const double *vy, const double *vtheta,
+                                 int32_t n, int32_t K, const int32_t *knot_step, const sfw_goal_args *args, int32_t mode,
+                                 const double *probs, double *costs_out, int32_t *rejected_out, sfw_best *best_out) {
+  if (!e) return SFW_ERR_INVALID_ARG;
+  const char *const what = "ensemble_score_sequences";
+  if (int rc = ensemble_check_mode(e, mode, probs, what)) return rc;
+  // (the stage's argument rules, before any member is staged: a refused call leaves the previous score as it was)
+  const char *why = sequences_refusal(K, knot_step);
+  if (!why) why = list_stage_refusal(rs, vx, vy, vtheta, n, static_cast<size_t>(K), args, false);
+  if (why) return efail(e, SFW_ERR_INVALID_ARG, std::string(what) + ": " + why);
+  if (int rc = ensemble_check_members(e, what)) return rc;
+  e->scored = false;
+  if (hipSetDevice(e->device) != hipSuccess) return efail(e, SFW_ERR_HIP, std::string(what) + ": hipSetDevice failed");
+  const auto t0 = std::chrono::steady_clock::now();
+  for (size_t m = 0; m < e->b->h.size(); ++m)
+    if (int rc = sfw_sequences_stage(e->b->h[m], rs, vx, vy, vtheta, n, K, knot_step, args, 0))
+      return emember_fail(e, static_cast<int32_t>(m), rc, "ensemble_score_sequences: stage");
+  e->us[0] = us_since(t0);
+  return ensemble_launch_and_finish(e, mode, probs, costs_out, rejected_out, best_out, what);
+}
+
+int sfw_ensemble_score_perturbed(sfw_ensemble e, const sfw_robot_state *rs, const sfw_perturb *p, int32_t n, int32_t K,
+                                 const int32_t *knot_step, const sfw_goal_args *args, int32_t mode, const double *probs,
+                                 double *costs_out, int32_t *rejected_out, sfw_best *best_out) {
+  if (!e) return SFW_ERR_INVALID_ARG;
+  const char *const what = "ensemble_score_perturbed";
+  if (int rc = ensemble_check_mode(e, mode, probs, what)) return rc;
+  const char *why = perturb_refusal(rs, p, n, K, knot_step, args, 0);
+  if (!why) why = list_stage_refusal(rs, nullptr, nullptr, nullptr, n, static_cast<size_t>(K), args, true);
+  if (why) return efail(e, SFW_ERR_INVALID_ARG, std::string(what) + ": " + why);
+  if (int rc = ensemble_check_members(e, what)) return rc;
+  e->scored = false;
+  if (hipSetDevice(e->device) != hipSuccess) return efail(e, SFW_ERR_HIP, std::string(what) + ": hipSetDevice failed");
+  const auto t0 = std::chrono::steady_clock::now();
+  // (every member draws the knots itself: a function of (seed, index, knot, channel) alone, so bitwise the same M times)
+  for (size_t m = 0; m < e->b->h.size(); ++m)
+    if (int rc = sfw_sequences_perturb_stage(e->b->h[m], rs, p, n, K, knot_step, args, 0))
+      return emember_fail(e, static_cast<int32_t>(m), rc, "ensemble_score_perturbed: stage");
+  e->us[0] = us_since(t0);
+  return ensemble_launch_and_finish(e, mode, probs, costs_out, rejected_out, best_out, what);
+}
+
+int sfw_ensemble_blend(sfw_ensemble e, const double *lambda, int32_t L, const double *bias, sfw_blend_stat *stat_out, double *u_out,
+                       double *weights_out) {
+  if (!e) return SFW_ERR_INVALID_ARG;
+  if (const char *why = blend_refusal(lambda, L, stat_out, u_out)) return efail(e, SFW_ERR_INVALID_ARG, std::string("ensemble_blend: ") + why);
+  if (int rc = ensemble_check_scored(e, "ensemble_blend")) return rc;
+  if (bias && !all_finite(bias, static_cast<size_t>(e->T))) return efail(e, SFW_ERR_INVALID_ARG, "ensemble_blend: non-finite bias");
+  if (hipSetDevice(e->device) != hipSuccess) return efail(e, SFW_ERR_HIP, "ensemble_blend: hipSetDevice failed");
+  sfw_handle h0 = e->b->h[0];
+  if (!e->cost_dev) {  // a grid's aggregation left the vector in the pinned mirror only: the blend's kernels read a device copy
+    if (!e->mirrored) return efail(e, SFW_ERR_STATE, "ensemble_blend: the last aggregation left no cost vector");
+    if (e->d_cost.reserve(static_cast<size_t>(e->T)) != hipSuccess ||
+        hipMemcpyAsync(e->d_cost.p, e->pin_out.p + kEnsRecBytes, sizeof(double) * static_cast<size_t>(e->T), hipMemcpyHostToDevice,
+                       e->b->stream) != hipSuccess)
+      return efail(e, SFW_ERR_HIP, "ensemble_blend: cost vector upload failed");
+    e->cost_dev = e->d_cost.p;  // (the blend waits for the stream before it returns: the mirror is free again by then)
+  }
+  const blend_area area{e->blend_mins, e->blend_partials, e->blend_bias, e->blend_weights, e->pin_blend};
+  if (int rc = blend_run(h0, area, e->cost_dev, e->T, h0->st.list ? h0->st.nk : 1, h0->st.d_linvels, h0->st.d_vy, h0->st.d_angvels,
+                         h0->st.nw, h0->st.list, lambda, L, bias, stat_out, u_out, weights_out))
+    return emember_fail(e, 0, rc, "ensemble_blend");
   return SFW_OK;
 }
 
@@ -3915,16 +4079,13 @@ int sfw_ensemble_aggregate(sfw_ensemble e, int32_t mode, const double *probs, do
                            sfw_best *best_out) {
   if (!e) return SFW_ERR_INVALID_ARG;
   if (int rc = ensemble_check_mode(e, mode, probs, "ensemble_aggregate")) return rc;
-  if (!e->scored) return efail(e, SFW_ERR_STATE, "ensemble_aggregate: nothing scored (sfw_ensemble_score_grid)");
-  for (size_t m = 0; m < e->b->h.size(); ++m) {
-    const sfw_handle h = e->b->h[m];
-    if (!h->last.launched || !h->last.terms || h->launch_seq != e->seq[m])
-      return efail(e, SFW_ERR_STATE, "ensemble_aggregate: member " + std::to_string(m) +
-                                         " was staged, launched or used for sfw_score_one since the last score");
-  }
+  if (int rc = ensemble_check_scored(e, "ensemble_aggregate")) return rc;
   if (hipSetDevice(e->device) != hipSuccess) return efail(e, SFW_ERR_HIP, "ensemble_aggregate: hipSetDevice failed");
   auto t0 = std::chrono::steady_clock::now();
-  if (int rc = ensemble_enqueue(e, mode, probs)) return rc;
+  if (int rc = ensemble_enqueue(e, mode, probs)) {
+    e->scored = false;  // (the outputs of the last aggregation are gone: nothing for sfw_ensemble_blend to read)
+    return rc;
+  }
   e->us[1] = us_since(t0);
   t0 = std::chrono::steady_clock::now();
   if (const hipError_t he = wait_stream(e->b->h[0]); he != hipSuccess)

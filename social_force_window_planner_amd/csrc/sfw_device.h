@@ -335,6 +335,11 @@ hipError_t sfw_launch_rescore(const double *terms, int64_t T, const sfw_weights 
 hipError_t sfw_launch_ensemble(const double *const *terms, const double *probs, int M, int64_t T, int mode, const sfw_weights &w,
                                const double *linvels, const double *angvels, int32_t nw, double *costs, int32_t *rejected,
                                sfw_sel *partials, sfw_sel *sel_host, hipStream_t stream);
+// ... over a LIST the members staged (sfw_launch.list): linvels / angvels hold one value per sample (the first knot row), the
+// selection is the list's, no sample is skipped.  costs_dev (nullable): a second, device-resident copy of the cost vector.
+hipError_t sfw_launch_ensemble_list(const double *const *terms, const double *probs, int M, int64_t T, int mode,
+                                    const sfw_weights &w, const double *linvels, const double *angvels, double *costs,
+                                    double *costs_dev, int32_t *rejected, sfw_sel *partials, sfw_sel *sel_host, hipStream_t stream);
 // sfw_grid_blend: the cost vector (+ bias, nullable) of a launch over T samples -> softmin weights for L temperatures, their
 // sums and the weighted mean of the K knot rows (list: linvels / vy (nullable) / angvels hold K rows of T values, knot-major;
 // else a grid of T / nw x nw samples, K == 1).  Three launches: `mins` (sfw_blend_min_blocks(T) records), `partials`

@@ -2799,6 +2799,55 @@ __global__ void __launch_bounds__(ARGMIN_BLOCK) sfw_ensemble_stage2(const sfw_se
   best = block_reduce(best);
   if (threadIdx.x == 0) *sel_host = best;
 }
+#ifndef SFW_STRICT_BUILD  // (terms and costs are doubles in every precision mode: the list form exists once)
+// The same first stage over a LIST (sfw_ensemble_score_sequences / _perturbed: the members staged n samples, sfw_launch.list):
+// sample t's selection key is its own pair (linvels[t], angvels[t]) — the first knot row — under the list rule, and a list has
+// no skipped sample.  costs_dev (nullable): a second, device-resident copy of the cost vector for sfw_ensemble_blend when
+// `costs` is the pinned mirror.  A kernel of its own, and not a second instantiation of the grid's: that one is found by the
+// resource checks as the only symbol that contains its name, and keeps the code it always had (see sfw_rescore_stage1).
+__global__ void __launch_bounds__(ARGMIN_BLOCK)
+sfw_ens_list_first(const double *const *terms, const double *probs, int M, int64_t T, int mode, sfw_weights w,
+                   const double *linvels, const double *angvels, double *costs, double *costs_dev, int32_t *rejected,
+                   sfw_sel *partials, sfw_sel *sel_host) {
+  typedef const double *member_terms;
+  typedef const __attribute__((address_space(4))) member_terms *terms_ptr;
+  typedef const __attribute__((address_space(4))) double *probs_ptr;
+  const terms_ptr tp = (terms_ptr)terms;
+  const probs_ptr pp = (probs_ptr)probs;
+  sfw_sel best = sel_empty();
+  for (int64_t t = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; t < T;
+       t += static_cast<int64_t>(gridDim.x) * blockDim.x) {
+    int32_t rej = 0;
+    double acc = 0.0, d0 = 0.0;
+    for (int m = 0; m < M; ++m) {
+      const double *const tm = tp[m];
+      const double d = tm[SFW_TERM_DISTANCE * T + t], sw = tm[SFW_TERM_SOCIAL * T + t];
+      if (m == 0) d0 = d;
+      rej += d == SFW_COST_INVALID ? 1 : 0;
+      if (mode == SFW_ENSEMBLE_MEAN) acc = sfw_ensemble_mean_step(acc, pp[m], sw);
+      else acc = (m == 0 || sw > acc) ? sw : acc;
+    }
+    double c;
+    if (rej > 0) {
+      c = SFW_COST_INVALID;
+    } else {
+      const double *const t0 = tp[0];
+      const double vel = t0[SFW_TERM_VEL * T + t], ang = t0[SFW_TERM_ANGLE * T + t], cm = t0[SFW_TERM_COSTMAP * T + t];
+      c = sfw_cost_add_social(sfw_cost_add_costmap(sfw_cost_base(w.vel, vel, w.distance, d0, w.angle, ang), w.costmap, cm),
+                              w.social, acc);
+    }
+    costs[t] = c;
+    if (costs_dev) costs_dev[t] = c;
+    rejected[t] = rej;
+    sel_consider<true>(best, c, linvels, angvels, 1, t, 0);
+  }
+  best = block_reduce(best);
+  if (threadIdx.x == 0) {
+    partials[blockIdx.x] = best;
+    if (sel_host) *sel_host = best;  // (single-block launch: the partial is the result)
+  }
+}
+#endif  // SFW_STRICT_BUILD
 
 #ifndef SFW_STRICT_BUILD  // (costs are doubles in every precision mode: the blend's kernels exist once)
 // Softmin blend (sfw_grid_blend): the cost vector of a launch -> weights w_t = exp(-(J_t - J_min) / lambda_l) for L
@@ -3686,6 +3735,19 @@ hipError_t sfw_launch_ensemble(const double *const *terms, const double *probs, 
 }
 
 #ifndef SFW_STRICT_BUILD
+hipError_t sfw_launch_ensemble_list(const double *const *terms, const double *probs, int M, int64_t T, int mode,
+                                    const sfw_weights &w, const double *linvels, const double *angvels, double *costs,
+                                    double *costs_dev, int32_t *rejected, sfw_sel *partials, sfw_sel *sel_host, hipStream_t stream) {
+  if (M < 1 || T < 1) return hipErrorInvalidValue;
+  const int blocks = static_cast<int>(sfw_argmin_partials(T));
+  hipLaunchKernelGGL(sfw_ens_list_first, dim3(static_cast<unsigned>(blocks)), dim3(ARGMIN_BLOCK), 0, stream, terms, probs, M, T,
+                     mode, w, linvels, angvels, costs, costs_dev, rejected, partials,
+                     blocks == 1 ? sel_host : static_cast<sfw_sel *>(nullptr));
+  if (blocks > 1)
+    hipLaunchKernelGGL(sfw_ensemble_stage2, dim3(1), dim3(ARGMIN_BLOCK), 0, stream, static_cast<const sfw_sel *>(partials), blocks,
+                       sel_host);
+  return hipGetLastError();
+}
 int64_t sfw_blend_blocks(int64_t T) { return (T + BLEND_C - 1) / BLEND_C; }
 int64_t sfw_blend_min_blocks(int64_t T) { return std::min<int64_t>(sfw_blend_blocks(T), BLEND_MIN_BLOCKS); }
 template <int LT>

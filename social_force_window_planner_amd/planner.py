@@ -175,6 +175,11 @@ def lib():
                                           C.POINTER(SfwGoalArgs), vp, C.POINTER(SfwBest)]
         L.sfw_sequences_knots.argtypes = [vp, C.c_int64, C.c_int64, vp, vp, vp]
         L.sfw_sequences_normals.argtypes = [vp, C.c_int64, C.c_int64, vp]
+        L.sfw_ensemble_score_sequences.argtypes = [vp, C.POINTER(SfwRobotState), vp, vp, vp, C.c_int32, C.c_int32, vp,
+                                                   C.POINTER(SfwGoalArgs), C.c_int32, vp, vp, vp, C.POINTER(SfwBest)]
+        L.sfw_ensemble_score_perturbed.argtypes = [vp, C.POINTER(SfwRobotState), C.POINTER(SfwPerturb), C.c_int32, C.c_int32, vp,
+                                                   C.POINTER(SfwGoalArgs), C.c_int32, vp, vp, vp, C.POINTER(SfwBest)]
+        L.sfw_ensemble_blend.argtypes = [vp, vp, C.c_int32, vp, C.POINTER(SfwBlendStat), vp, vp]
         _lib = L
     return _lib
 
@@ -959,42 +964,114 @@ class EnsembleScorer:
     def _probs(self, probs):
         return None if probs is None else _f64(probs).reshape(-1)
 
-    def _outputs(self):
-        nv, nw = self._grid
+    def _outputs(self, grid=None):
+        nv, nw = self._grid if grid is None else grid
         return np.empty(nv * nw, dtype=np.float64), np.empty(nv * nw, dtype=np.int32), SfwBest()
+
+    def _mark_scored(self, grid, knots=1):
+        """Every score that succeeded ends here: the shape aggregate() and blend() size their outputs by, and the members'
+        views staged with the same samples (their cost_terms(), knots() and grid_crowd() then work)."""
+        self._grid = grid
+        self._n_knots = knots
+        for m in self._members:
+            m._mark_staged(grid, knots=knots)
+
+    def _checked_probs(self, probs, what):
+        p = self._probs(probs)
+        if p is not None and p.size != self.M:
+            raise ValueError(f"{what}: {p.size} probabilities for an ensemble of {self.M}")
+        return p
 
     def score_grid(self, robot_state, linvels, angvels, goal_args, mode="mean", probs=None):
         """(costs, rejected, best): the ensemble cost vector, the hypotheses rejecting each sample, the selection."""
         lin, ang = _f64(linvels), _f64(angvels)
         rs, ga = SfwRobotState(*robot_state), SfwGoalArgs(*goal_args)
-        p = self._probs(probs)
-        if p is not None and p.size != self.M:
-            raise ValueError(f"score_grid: {p.size} probabilities for an ensemble of {self.M}")
-        self._grid = (len(lin), len(ang))
-        costs, rejected, best = self._outputs()
+        p = self._checked_probs(probs, "score_grid")
+        grid = (len(lin), len(ang))
+        costs, rejected, best = self._outputs(grid)
         self._check(lib().sfw_ensemble_score_grid(self._e, C.byref(rs), lin.ctypes.data, len(lin), ang.ctypes.data, len(ang),
                                                   C.byref(ga), self._mode(mode), p.ctypes.data if p is not None else None,
                                                   costs.ctypes.data, rejected.ctypes.data, C.byref(best)),
                     "sfw_ensemble_score_grid")
-        for m in self._members:
-            m._mark_staged(self._grid)
+        self._mark_scored(grid)
+        return costs, rejected, best.as_dict()
+
+    def score_sequences(self, robot_state, vx, vtheta, knot_steps, goal_args, vy=None, mode="mean", probs=None):
+        """n command sequences of K knots ((K, n) arrays as HipScorer.score_sequences takes them; K == 1: a sample list) under
+        every hypothesis: (costs[n], rejected[n], best) — best carries the winner's first knot."""
+        vx, vth, vyv, ks = HipScorer._sequences(vx, vtheta, knot_steps, vy)
+        rs, ga = SfwRobotState(*robot_state), SfwGoalArgs(*goal_args)
+        p = self._checked_probs(probs, "score_sequences")
+        K, n = vx.shape
+        costs, rejected, best = self._outputs((n, 1))
+        self._check(lib().sfw_ensemble_score_sequences(self._e, C.byref(rs), vx.ctypes.data if vx.size else None,
+                                                       vyv.ctypes.data if vyv is not None and vyv.size else None,
+                                                       vth.ctypes.data if vth.size else None, n, K,
+                                                       ks.ctypes.data if len(ks) else None, C.byref(ga), self._mode(mode),
+                                                       p.ctypes.data if p is not None else None, costs.ctypes.data if n else None,
+                                                       rejected.ctypes.data if n else None, C.byref(best)),
+                    "sfw_ensemble_score_sequences")
+        self._mark_scored((n, 1), knots=K)
+        return costs, rejected, best.as_dict()
+
+    def score_perturbed(self, robot_state, n, seed, nominal, sigma, lo, hi, knot_steps, goal_args, flags=0, mode="mean",
+                        probs=None):
+        """n sequences whose knots the device draws (HipScorer.score_perturbed's arguments; every member holds the same
+        knots): (costs[n], rejected[n], best)."""
+        pt, nom, ks = HipScorer._perturb(seed, nominal, sigma, lo, hi, knot_steps, flags)
+        rs, ga = SfwRobotState(*robot_state), SfwGoalArgs(*goal_args)
+        p = self._checked_probs(probs, "score_perturbed")
+        K = nom.shape[0]
+        costs, rejected, best = self._outputs((max(n, 0), 1))
+        self._check(lib().sfw_ensemble_score_perturbed(self._e, C.byref(rs), C.byref(pt), n, K, ks.ctypes.data if len(ks) else None,
+                                                       C.byref(ga), self._mode(mode), p.ctypes.data if p is not None else None,
+                                                       costs.ctypes.data if n > 0 else None,
+                                                       rejected.ctypes.data if n > 0 else None, C.byref(best)),
+                    "sfw_ensemble_score_perturbed")
+        self._mark_scored((n, 1), knots=K)
         return costs, rejected, best.as_dict()
 
     def aggregate(self, mode="mean", probs=None):
-        """The last score_grid re-aggregated under another mode / probabilities, no rollout: (costs, rejected, best)."""
-        p = self._probs(probs)
-        if p is not None and p.size != self.M:
-            raise ValueError(f"aggregate: {p.size} probabilities for an ensemble of {self.M}")
-        if self._grid is None:
-            self._grid = (0, 0)  # (the library answers SFW_ERR_STATE)
-        costs, rejected, best = self._outputs()
+        """The last score (grid, sequences or perturbed) re-aggregated under another mode / probabilities, no rollout:
+        (costs, rejected, best)."""
+        p = self._checked_probs(probs, "aggregate")
+        # (nothing scored: the library answers SFW_ERR_STATE)
+        costs, rejected, best = self._outputs(self._grid if self._grid is not None else (0, 0))
         self._check(lib().sfw_ensemble_aggregate(self._e, self._mode(mode), p.ctypes.data if p is not None else None,
                                                  costs.ctypes.data, rejected.ctypes.data, C.byref(best)),
                     "sfw_ensemble_aggregate")
         return costs, rejected, best.as_dict()
 
+    def blend(self, lambdas, bias=None, want_weights=False):
+        """sfw_ensemble_blend: HipScorer.blend over the ENSEMBLE cost vector of the last aggregation and member 0's knots —
+        (stats, u[L, K, 3], weights[L, n] or None)."""
+        lam = np.ascontiguousarray(np.asarray(lambdas, dtype=np.float64).reshape(-1))
+        L = len(lam)
+        if L < 1 or L > SFW_BLEND_MAX_L:
+            raise ValueError(f"blend: need 1 .. {SFW_BLEND_MAX_L} lambdas, got {L}")
+        if not np.all(np.isfinite(lam)) or not np.all(lam > 0.0):
+            raise ValueError("blend: every lambda must be finite and > 0")
+        nv, nw = self._grid if self._grid is not None else (0, 0)  # (nothing scored: the library answers SFW_ERR_STATE)
+        T, K = nv * nw, getattr(self, "_n_knots", 1)
+        b = None
+        if bias is not None:
+            b = np.ascontiguousarray(np.asarray(bias, dtype=np.float64).reshape(-1))
+            if len(b) != T:
+                raise ValueError(f"blend: bias must hold one value per sample ({T}), got {len(b)}")
+        stats = (SfwBlendStat * L)()
+        u = np.zeros((L, K, 3), dtype=np.float64)
+        w = np.zeros((L, T), dtype=np.float64) if want_weights else None
+        self._check(lib().sfw_ensemble_blend(self._e, lam.ctypes.data, L, b.ctypes.data if b is not None and T else None, stats,
+                                             u.ctypes.data, w.ctypes.data if w is not None and T else None), "sfw_ensemble_blend")
+        return [stats[l].as_dict() for l in range(L)], u, w
+
+    def knots(self, first, count):
+        """The knots of samples [first, first + count) of the last sequence score as (K, 3, count): member 0's (every member
+        holds the same)."""
+        return self._members[0].knots(first, count)
+
     def last_us(self):
-        """Host wall-clock of the last calls: stage (score_grid only), enqueue, wait + copies out (microseconds)."""
+        """Host wall-clock of the last calls: stage (the score calls only), enqueue, wait + copies out (microseconds)."""
         out = {}
         for which, name in enumerate(("stage", "enqueue", "wait_fetch")):
             v = C.c_double()
