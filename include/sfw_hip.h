@@ -689,6 +689,69 @@ typedef struct sfw_blend_stat {
 int sfw_grid_blend(sfw_handle h, const double *lambda, int32_t L, const double *bias,
                    sfw_blend_stat *stat_out, double *u_out, double *weights_out);
 
+/* ---- MPPI on the device: the control cost, and chained iterations ------------
+ * Control cost.  MPPI's importance weight carries u_nom^T Sigma^-1 eps_t, the control-cost term of sample t's perturbation.
+ * After sfw_sequences_perturb_stage the host holds no perturbations; these calls form the term on the device from what the
+ * stage was drawn from.  For sample t of the staged PERTURBED sequences, z[k][c] is bit for bit the normal of the stage's
+ * Definition (the value sfw_sequences_normals reports; 0.0 at g == 0 under SFW_PERTURB_KEEP_NOMINAL):
+ *   acc = +0.0
+ *   for k = 0 .. K-1:  for c = 0, 1, 2 with sigma[c] > 0:
+ *       q   = nominal[k][c] / sigma[c]      one IEEE division
+ *       acc = acc + q * z[k][c]             product and sum each rounded on their own (no contraction)
+ *   c_t = acc;   bias_t = gamma * c_t       one IEEE product
+ * A channel with sigma[c] == 0 is skipped (under SFW_PERTURB_NO_VY channel 1 always is: its sigma is 0).  This is
+ * u_nom^T Sigma^-1 eps_t with the UNCLAMPED eps = sigma * z.  The value depends on (seed, g, K, nominal, sigma, flags) alone:
+ * not on SFW_PERTURB_KEEP_NORMALS (the kept normals are read where the stage kept them, else drawn again: the same bits),
+ * not on n, on chunking, on SFW_DEVICE_CUS or on SFW_CYCLE_FUSED.  social_force_window_planner_amd/mppi.py restates it in
+ * numpy (mppi.control_cost); tests/test_mppi_gpu.py holds the device to it bit for bit.
+ *
+ * sfw_sequences_control_cost: bias_out[t] = gamma * c_t, n doubles.  One kernel and one copy on the handle's stream; blocking.
+ * It needs a valid perturbed stage (sfw_sequences_perturb_stage, sfw_score_perturbed, sfw_mppi_run), before or after its
+ * launch, and leaves stage and launch as they are.  SFW_ERR_STATE: nothing staged, a grid, a host-staged list or sequences.
+ * SFW_ERR_INVALID_ARG (before any device call): a NULL h or bias_out, a gamma that is not finite.
+ *
+ * sfw_grid_blend_control: sfw_grid_blend with J_t = cost_t + b_t, where b_t = gamma * c_t (bias == NULL) or
+ * (gamma * c_t) + bias_t, each + one IEEE addition; nothing else differs — the definition, the outputs, the summation tree
+ * and the state rule are sfw_grid_blend's.  The bias vector never leaves the device.  gamma == 0 is bit for bit
+ * sfw_grid_blend with the same `bias`.  SFW_ERR_STATE: as sfw_sequences_control_cost, and sfw_grid_blend's own rule (no
+ * launch).  SFW_ERR_INVALID_ARG (before any device call; a refused call changes nothing): what sfw_grid_blend refuses, and
+ * a gamma that is not finite. */
+int sfw_sequences_control_cost(sfw_handle h, double gamma, double *bias_out);
+int sfw_grid_blend_control(sfw_handle h, const double *lambda, int32_t L, double gamma, const double *bias,
+                           sfw_blend_stat *stat_out, double *u_out, double *weights_out);
+
+/* sfw_mppi_run: I = m->iterations iterations of perturb -> score -> control cost -> blend -> new nominal plan, enqueued
+ * back to back behind ONE wait.  It is defined as this loop of the calls above and equals it BIT FOR BIT in every output:
+ *   nom_0 = p->nominal
+ *   for i = 0 .. I-1:
+ *       pt = *p;  pt.seed = p->seed + i (mod 2^64);  pt.nominal = nom_i
+ *       sfw_sequences_perturb_stage(h, rs, &pt, n, K, knot_step, args, 0);  sfw_grid_launch(h);
+ *       sfw_grid_fetch(h, NULL, &best_i, NULL)
+ *       sfw_grid_blend_control(h, &m->lambda, 1, m->gamma, NULL, &stat_out[i], u_i, NULL)
+ *       nom_(i+1) = stat_out[i].n_valid > 0 ? u_i : nom_i
+ *       plans_out[i] = nom_(i+1)                                      (K x 3 doubles: [k][vx, vy, vtheta])
+ *   *best_out = best_(I-1)                                             (nullable)
+ * Between iterations nothing goes through the host: a perturb kernel reads the plan from device memory, where the blend's
+ * last kernel leaves the next one.  Afterwards the handle is exactly as after iteration I-1 of that loop — it holds a
+ * perturbed stage drawn around nom_(I-1) with seed p->seed + I - 1, launched and fetched — and sfw_grid_costs_view,
+ * sfw_grid_fetch, sfw_sequences_knots / _normals, sfw_grid_crowd, the terms and points capture, sfw_grid_rescore,
+ * sfw_grid_blend(_control), sfw_sequences_control_cost, sfw_grid_plan_info and a re-launch act on that iteration.  Under
+ * SFW_PERTURB_KEEP_NOMINAL sample 0 of iteration i is nom_i itself, so its cost is in the cost vector.  The plan is always
+ * finite: a weighted mean of clamped knots, or the caller's checked nominal.
+ * SFW_ERR_INVALID_ARG (before any device call; a refused call changes nothing): a NULL h, m, stat_out or plans_out;
+ * iterations outside [1, SFW_MPPI_MAX_ITER]; reserved != 0; a lambda that is not finite or not > 0; a gamma that is not
+ * finite; everything sfw_sequences_perturb_stage refuses at index_base 0.  SFW_ERR_STATE: no costmap.  Any later failure
+ * leaves nothing staged or launched, as for every stage. */
+#define SFW_MPPI_MAX_ITER 32
+typedef struct sfw_mppi {
+  int32_t iterations, reserved; /* 1 .. SFW_MPPI_MAX_ITER; 0 */
+  double lambda;                /* the blend's temperature, finite, > 0 */
+  double gamma;                 /* the control cost's factor, finite; 0: no control cost */
+} sfw_mppi;
+int sfw_mppi_run(sfw_handle h, const sfw_robot_state *rs, const sfw_perturb *p, int32_t n, int32_t K,
+                 const int32_t *knot_step, const sfw_goal_args *args, const sfw_mppi *m,
+                 sfw_blend_stat *stat_out /* I */, double *plans_out /* I x K x 3 */, sfw_best *best_out /* nullable */);
+
 /* ---- the predicted crowd behind a score ------------------------------------
  * For every sample the scorer integrates the whole crowd forward under the social-force model; these two calls hand that
  * prediction out for ONE sample: where every person is after every step, who does the social work, whose goal has popped.

@@ -229,6 +229,9 @@ EXPORTED_SYMBOLS = (
     "sfw_ensemble_score_sequences",
     "sfw_ensemble_score_perturbed",
     "sfw_ensemble_blend",
+    "sfw_sequences_control_cost",
+    "sfw_grid_blend_control",
+    "sfw_mppi_run",
 )
 # per-term costs (sfw_set_terms_capture / sfw_grid_rescore / sfw_grid_terms)
 SFW_TERM_VEL, SFW_TERM_DISTANCE, SFW_TERM_ANGLE, SFW_TERM_COSTMAP, SFW_TERM_SOCIAL = 0, 1, 2, 3, 4
@@ -270,6 +273,16 @@ class SfwPerturb(C.Structure):
 
     _fields_ = [("seed", C.c_uint64), ("nominal", C.c_void_p), ("sigma", C.c_double * 3), ("lo", C.c_double * 3),
                 ("hi", C.c_double * 3), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+# chained MPPI iterations (sfw_mppi_run)
+SFW_MPPI_MAX_ITER = 32
+
+
+class SfwMppi(C.Structure):
+    """sfw_mppi (include/sfw_hip.h): iterations, the blend's temperature and the control cost's factor."""
+
+    _fields_ = [("iterations", C.c_int32), ("reserved", C.c_int32), ("lambda_", C.c_double), ("gamma", C.c_double)]
 
 
 # one grid under several crowd hypotheses (sfw_ensemble_*)

@@ -197,6 +197,9 @@ struct sfw_planner_s {
     // arena's knot regions are never filled or sent from the host, and such a stage is never left arena_pending.  zero_admitted:
     // the clamp box admits a zero translation command (rest_noise_unreproduced); normals_kept: `normals` holds 3 nk nv doubles
     bool perturbed = false, zero_admitted = false, normals_kept = false;
+    // ... and what they were drawn from (seed, sigma, box, KEEP_NOMINAL, the nominal rows), for sfw_sequences_control_cost.
+    // Host memory only: the stage pays a struct copy for it
+    sfw_perturb_dev pert{};
     // the world as uploaded (sfw_set_* after a stage take effect at the next stage; a launch in between must keep
     // describing the device copy)
     int K = 0, A = 0, O = 0, NG = 0, n_grp_mem = 0;
@@ -312,6 +315,11 @@ struct sfw_planner_s {
   // (sel_to_best) and the ranges sfw_sequences_knots / _normals read back
   dev_buf<double> normals;
   pinned_buf pin_knots;
+  // sfw_sequences_control_cost / sfw_grid_blend_control: the bias vector gamma * c_t on the device.  sfw_mppi_run: the nominal
+  // plan on the device (SFW_SEQ_MAX_KNOTS x 3 doubles, moved on by every iteration's update kernel) and pin_mppi = one blend
+  // slot per iteration | the caller's nominal (the source of the copy that starts the chain)
+  dev_buf<double> ctrl_bias, mppi_plan;
+  pinned_buf pin_mppi;
   // sfw_score_one_crowd / sfw_grid_crowd: cost | n_points | coll_step | state [S][A][4] | work [S][A] | has_goal [S][A],
   // contiguous -> one D2H into pin_crowd; the pair table of the kernel with run-time plane capacity (sfw_crowd_kernel)
   dev_buf<char> crowd_out;
@@ -1280,6 +1288,7 @@ int stage_common(sfw_handle h, const sfw_robot_state *rs, const double *lin, int
   ph.mark("check+setdev");
   h->st.perturbed = dev != nullptr;
   h->st.zero_admitted = dev && dev->zero_admitted;
+  if (dev) h->st.pert = dev->args;
   h->st.normals_kept = false;  // (until the kernel that writes them is enqueued)
   if (dev) {  // the knots exist on the device only
     h->st.lin.clear();
@@ -1844,21 +1853,19 @@ struct blend_area {
   dev_buf<double> &partials, &bias, &weights;
   pinned_buf &pin;
 };
-int blend_run(sfw_handle h, const blend_area &a, const double *d_costs, int64_t T, int K, const double *d_lin, const double *d_vy,
-              const double *d_ang, int nw, bool list, const double *lambda, int32_t L, const double *bias, sfw_blend_stat *stat_out,
-              double *u_out, double *weights_out) {
+// What a blend leaves in pinned memory (a "slot"): the minimum record | eta[L] | sum_w2[L] | u[L][K][3]
+constexpr size_t kBlendHead = (sizeof(sfw_blend_min) + 15) & ~size_t(15);
+size_t blend_slot_bytes(int L, int K) { return kBlendHead + sizeof(double) * static_cast<size_t>(sfw_blend_channels(L, K)); }
+
+// The blend in two parts.  blend_enqueue: the kernels (and the copies of weights_out) on h's stream, no wait — d_bias
+// (nullable) is ON THE DEVICE and `slot` is pinned memory of blend_slot_bytes(L, K) that stays put until the stream has been
+// waited for.  plan (sfw_mppi_run, L == 1): see sfw_launch_blend.  blend_finish: the outputs from a slot the stream is done with.
+int blend_enqueue(sfw_handle h, const blend_area &a, const double *d_costs, int64_t T, int K, const double *d_lin, const double *d_vy,
+                  const double *d_ang, int nw, bool list, const double *lambda, int32_t L, const double *d_bias, double *weights_out,
+                  char *slot, double *plan = nullptr) {
   const int64_t n_ch = sfw_blend_channels(L, K), blocks = sfw_blend_blocks(T);
-  const size_t head = (sizeof(sfw_blend_min) + 15) & ~size_t(15), out_bytes = head + sizeof(double) * static_cast<size_t>(n_ch);
-  // (growing the pinned area frees the old one: nothing in the stream may still be writing there)
-  if (out_bytes > a.pin.cap) SFW_HIP(h, hipStreamSynchronize(h->stream));
-  SFW_HIP(h, a.pin.reserve(out_bytes));
   SFW_HIP(h, a.mins.reserve(static_cast<size_t>(sfw_blend_min_blocks(T))));
   SFW_HIP(h, a.partials.reserve(static_cast<size_t>(blocks) * static_cast<size_t>(n_ch)));
-  if (bias) {
-    SFW_HIP(h, a.bias.reserve(static_cast<size_t>(T)));
-    SFW_HIP(h, hipMemcpyAsync(a.bias.p, bias, sizeof(double) * static_cast<size_t>(T), hipMemcpyHostToDevice, h->stream));
-  }
-  const double *const d_bias = bias ? a.bias.p : nullptr;
   // weights_out: all L vectors from the launch that forms the sums, or — beyond 256 MB of them — in slices of as many
   // temperatures as that holds, each by a launch of its own that is copied out behind it
   const int64_t fit = std::max<int64_t>(1, (int64_t(256) << 20) / (static_cast<int64_t>(sizeof(double)) * T));
@@ -1867,10 +1874,10 @@ int blend_run(sfw_handle h, const blend_area &a, const double *d_costs, int64_t 
   if (weights_out) SFW_HIP(h, a.weights.reserve(static_cast<size_t>(l_step) * static_cast<size_t>(T)));
   sfw_blend_lambdas lam{};
   for (int32_t l = 0; l < L; ++l) lam.v[l] = lambda[l];
-  sfw_blend_min *const min_host = reinterpret_cast<sfw_blend_min *>(a.pin.p);
-  double *const out_host = reinterpret_cast<double *>(a.pin.p + head);
+  sfw_blend_min *const min_host = reinterpret_cast<sfw_blend_min *>(slot);
+  double *const out_host = reinterpret_cast<double *>(slot + kBlendHead);
   SFW_HIP(h, sfw_launch_blend(d_costs, d_bias, T, lam, L, K, d_lin, d_vy, d_ang, nw, list, a.mins.p, a.partials.p,
-                              weights_out && !sliced ? a.weights.p : nullptr, min_host, out_host, h->stream));
+                              weights_out && !sliced ? a.weights.p : nullptr, min_host, out_host, h->stream, plan));
   if (weights_out && !sliced)
     SFW_HIP(h, hipMemcpyAsync(weights_out, a.weights.p, sizeof(double) * static_cast<size_t>(L) * static_cast<size_t>(T),
                               hipMemcpyDeviceToHost, h->stream));
@@ -1882,11 +1889,12 @@ int blend_run(sfw_handle h, const blend_area &a, const double *d_costs, int64_t 
     SFW_HIP(h, hipMemcpyAsync(weights_out + static_cast<int64_t>(l0) * T, a.weights.p,
                               sizeof(double) * static_cast<size_t>(n) * static_cast<size_t>(T), hipMemcpyDeviceToHost, h->stream));
   }
-  SFW_HIP(h, a.pin.mark(h->stream));
-  SFW_HIP(h, wait_stream(h));
-  a.pin.pending = false;
-  stream_is_idle(h);
-  const sfw_blend_min m = *min_host;
+  return SFW_OK;
+}
+void blend_finish(const char *slot, const double *lambda, int32_t L, int K, sfw_blend_stat *stat_out, double *u_out) {
+  sfw_blend_min m;
+  std::memcpy(&m, slot, sizeof(m));
+  const double *const out_host = reinterpret_cast<const double *>(slot + kBlendHead);
   const bool any = m.n_valid > 0;
   for (int32_t l = 0; l < L; ++l) {
     stat_out[l].lambda = lambda[l];
@@ -1897,9 +1905,97 @@ int blend_run(sfw_handle h, const blend_area &a, const double *d_costs, int64_t 
     stat_out[l].index_min = any ? m.index : -1;
   }
   std::memcpy(u_out, out_host + 2 * L, sizeof(double) * 3 * static_cast<size_t>(K) * static_cast<size_t>(L));
+}
+// The blocking blend: the area's pinned slot, the enqueue, one wait, the finish.  bias (nullable, host) goes up first; d_bias
+// (nullable) is a bias vector the device holds already, read instead.
+int blend_run(sfw_handle h, const blend_area &a, const double *d_costs, int64_t T, int K, const double *d_lin, const double *d_vy,
+              const double *d_ang, int nw, bool list, const double *lambda, int32_t L, const double *bias, sfw_blend_stat *stat_out,
+              double *u_out, double *weights_out, const double *d_bias = nullptr) {
+  const size_t out_bytes = blend_slot_bytes(L, K);
+  // (growing the pinned area frees the old one: nothing in the stream may still be writing there)
+  if (out_bytes > a.pin.cap) SFW_HIP(h, hipStreamSynchronize(h->stream));
+  SFW_HIP(h, a.pin.reserve(out_bytes));
+  if (bias) {
+    SFW_HIP(h, a.bias.reserve(static_cast<size_t>(T)));
+    SFW_HIP(h, hipMemcpyAsync(a.bias.p, bias, sizeof(double) * static_cast<size_t>(T), hipMemcpyHostToDevice, h->stream));
+    d_bias = a.bias.p;
+  }
+  if (int e = blend_enqueue(h, a, d_costs, T, K, d_lin, d_vy, d_ang, nw, list, lambda, L, d_bias, weights_out, a.pin.p)) return e;
+  SFW_HIP(h, a.pin.mark(h->stream));
+  SFW_HIP(h, wait_stream(h));
+  a.pin.pending = false;
+  stream_is_idle(h);
+  blend_finish(a.pin.p, lambda, L, K, stat_out, u_out);
   return SFW_OK;
 }
 
+// The bias vector gamma * c_t (+ bias[t], nullable: T host doubles, uploaded to the blend's bias buffer first) of the staged
+// perturbed stage into h->ctrl_bias, on h's stream.  plan (nullable): the nominal rows in device memory (sfw_mppi_run).
+int control_cost_enqueue(sfw_handle h, double gamma, const double *bias, const double *plan) {
+  const int64_t n = h->st.nv;
+  SFW_HIP(h, h->ctrl_bias.reserve(static_cast<size_t>(n)));
+  const double *d_add = nullptr;
+  if (bias) {
+    SFW_HIP(h, h->blend_bias.reserve(static_cast<size_t>(n)));
+    SFW_HIP(h, hipMemcpyAsync(h->blend_bias.p, bias, sizeof(double) * static_cast<size_t>(n), hipMemcpyHostToDevice, h->stream));
+    d_add = h->blend_bias.p;
+  }
+  SFW_HIP(h, sfw_launch_control_cost(h->st.pert, plan, h->st.nk, n, h->st.index_base, h->st.normals_kept ? h->normals.p : nullptr, gamma,
+                                     d_add, h->ctrl_bias.p, h->stream));
+  return SFW_OK;
+}
+const char *control_state_refusal(sfw_handle h) {
+  return h->st.valid && h->st.perturbed ? nullptr : "no perturbed stage (sfw_sequences_perturb_stage, sfw_mppi_run) is staged";
+}
+
+
+// sfw_mppi_run behind its stage of iteration 0: everything enqueued, one wait, the outputs.  A failure is the caller's to clean up.
+int mppi_chain(sfw_handle h, const sfw_perturb *p, int K, const sfw_mppi *m, sfw_blend_stat *stat_out, double *plans_out,
+               sfw_best *best_out) {
+  const int I = m->iterations;
+  const int64_t n = h->st.nv;
+  const size_t slot = (blend_slot_bytes(1, K) + 15) & ~size_t(15), plan_bytes = sizeof(double) * 3 * static_cast<size_t>(K);
+  SFW_HIP(h, hipSetDevice(h->device));
+  // every buffer the chain writes is in place before its first kernel is enqueued: nothing in flight is ever freed
+  if (I * slot + plan_bytes > h->pin_mppi.cap) SFW_HIP(h, hipStreamSynchronize(h->stream));
+  SFW_HIP(h, h->pin_mppi.reserve(I * slot + plan_bytes));
+  SFW_HIP(h, h->mppi_plan.reserve(3 * static_cast<size_t>(SFW_SEQ_MAX_KNOTS)));
+  if (m->gamma != 0.0) SFW_HIP(h, h->ctrl_bias.reserve(static_cast<size_t>(n)));
+  SFW_HIP(h, h->blend_mins.reserve(static_cast<size_t>(sfw_blend_min_blocks(n))));
+  SFW_HIP(h, h->blend_partials.reserve(static_cast<size_t>(sfw_blend_blocks(n)) * static_cast<size_t>(sfw_blend_channels(1, K))));
+  const blend_area area{h->blend_mins, h->blend_partials, h->blend_bias, h->blend_weights, h->pin_blend};
+  char *const pin = h->pin_mppi.p;
+  std::memcpy(pin + I * slot, p->nominal, plan_bytes);
+  SFW_HIP(h, hipMemcpyAsync(h->mppi_plan.p, pin + I * slot, plan_bytes, hipMemcpyHostToDevice, h->stream));
+  double *const plan = h->mppi_plan.p;
+  for (int i = 0; i < I; ++i) {
+    if (i > 0) {  // the stage of iteration i: its seed, and the knots drawn around the plan the last update left
+      const uint64_t seed = p->seed + static_cast<uint64_t>(i);
+      h->st.pert.key0 = static_cast<uint32_t>(seed & 0xffffffffu);
+      h->st.pert.key1 = static_cast<uint32_t>(seed >> 32);
+      SFW_HIP(h, sfw_launch_perturb_plan(h->st.pert, plan, n, K, 0, const_cast<double *>(h->st.d_linvels), const_cast<double *>(h->st.d_vy),
+                                         const_cast<double *>(h->st.d_angvels), h->st.normals_kept ? h->normals.p : nullptr, h->stream));
+    }
+    if (int e = launch_common(h)) return e;
+    const double *d_bias = nullptr;
+    if (m->gamma != 0.0) {  // (as sfw_grid_blend_control: gamma == 0 is the plain blend)
+      if (int e = control_cost_enqueue(h, m->gamma, nullptr, plan)) return e;
+      d_bias = h->ctrl_bias.p;
+    }
+    if (int e = blend_enqueue(h, area, h->costs.p, n, K, h->st.d_linvels, h->st.d_vy, h->st.d_angvels, 1, true, &m->lambda, 1, d_bias,
+                              nullptr, pin + i * slot, plan))
+      return e;
+  }
+  SFW_HIP(h, h->pin_mppi.mark(h->stream));
+  sfw_best best;
+  if (int e = sfw_grid_fetch(h, nullptr, &best, nullptr)) return e;  // THE wait (and the winner's first knot behind it)
+  h->pin_mppi.pending = false;
+  for (int i = 0; i < I; ++i) blend_finish(pin + i * slot, &m->lambda, 1, K, stat_out + i, plans_out + static_cast<size_t>(i) * 3 * K);
+  // the stage the handle holds is iteration I - 1's: drawn around nom_(I-1)
+  if (I > 1) std::memcpy(h->st.pert.nominal, plans_out + static_cast<size_t>(I - 2) * 3 * K, plan_bytes);
+  if (best_out) *best_out = best;
+  return SFW_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -2048,6 +2144,9 @@ int destroy_handle(sfw_handle h) {
   h->blend_bias.release();
   h->blend_weights.release();
   h->pin_blend.release();
+  h->ctrl_bias.release();
+  h->mppi_plan.release();
+  h->pin_mppi.release();
   h->normals.release();
   h->pin_knots.release();
   h->points.release();
@@ -2696,6 +2795,66 @@ int sfw_grid_blend(sfw_handle h, const double *lambda, int32_t L, const double *
   const blend_area area{h->blend_mins, h->blend_partials, h->blend_bias, h->blend_weights, h->pin_blend};
   return blend_run(h, area, h->costs.p, T, h->st.list ? h->st.nk : 1, h->st.d_linvels, h->st.d_vy, h->st.d_angvels, h->st.nw,
                    h->st.list, lambda, L, bias, stat_out, u_out, weights_out);
+}
+
+int sfw_sequences_control_cost(sfw_handle h, double gamma, double *bias_out) {
+  if (!h) return SFW_ERR_INVALID_ARG;
+  if (!bias_out || !std::isfinite(gamma)) return fail(h, SFW_ERR_INVALID_ARG, "sequences_control_cost: bias_out is NULL, or gamma is not finite");
+  if (const char *why = control_state_refusal(h)) return fail(h, SFW_ERR_STATE, std::string("sequences_control_cost: ") + why);
+  SFW_HIP(h, hipSetDevice(h->device));
+  const size_t bytes = sizeof(double) * static_cast<size_t>(h->st.nv);
+  if (bytes > h->pin_knots.cap) SFW_HIP(h, hipStreamSynchronize(h->stream));  // (growing the area frees the old one)
+  SFW_HIP(h, h->pin_knots.reserve(bytes));
+  if (int e = control_cost_enqueue(h, gamma, nullptr, nullptr)) return e;
+  SFW_HIP(h, hipMemcpyAsync(h->pin_knots.p, h->ctrl_bias.p, bytes, hipMemcpyDeviceToHost, h->stream));
+  SFW_HIP(h, wait_stream(h));
+  stream_is_idle(h);
+  std::memcpy(bias_out, h->pin_knots.p, bytes);
+  return SFW_OK;
+}
+
+int sfw_grid_blend_control(sfw_handle h, const double *lambda, int32_t L, double gamma, const double *bias, sfw_blend_stat *stat_out,
+                           double *u_out, double *weights_out) {
+  if (!h) return SFW_ERR_INVALID_ARG;
+  if (const char *why = blend_refusal(lambda, L, stat_out, u_out))
+    return fail(h, SFW_ERR_INVALID_ARG, std::string("grid_blend_control: ") + why);
+  if (!std::isfinite(gamma)) return fail(h, SFW_ERR_INVALID_ARG, "grid_blend_control: gamma is not finite");
+  if (const char *why = control_state_refusal(h)) return fail(h, SFW_ERR_STATE, std::string("grid_blend_control: ") + why);
+  if (!h->last.launched) return fail(h, SFW_ERR_STATE, "grid_blend_control: no launch, or a stage or sfw_score_one came in since");
+  const int64_t T = h->st.nv;
+  if (bias && !all_finite(bias, static_cast<size_t>(T))) return fail(h, SFW_ERR_INVALID_ARG, "grid_blend_control: non-finite bias");
+  SFW_HIP(h, hipSetDevice(h->device));
+  const blend_area area{h->blend_mins, h->blend_partials, h->blend_bias, h->blend_weights, h->pin_blend};
+  // gamma == 0: sfw_grid_blend itself (a bias of gamma * c_t = +-0.0 would turn a cost of -0.0 into +0.0)
+  const double *d_bias = nullptr;
+  if (gamma != 0.0) {
+    if (int e = control_cost_enqueue(h, gamma, bias, nullptr)) return e;
+    d_bias = h->ctrl_bias.p;
+    bias = nullptr;
+  }
+  return blend_run(h, area, h->costs.p, T, h->st.nk, h->st.d_linvels, h->st.d_vy, h->st.d_angvels, 1, true, lambda, L, bias, stat_out,
+                   u_out, weights_out, d_bias);
+}
+
+int sfw_mppi_run(sfw_handle h, const sfw_robot_state *rs, const sfw_perturb *p, int32_t n, int32_t K, const int32_t *knot_step,
+                 const sfw_goal_args *args, const sfw_mppi *m, sfw_blend_stat *stat_out, double *plans_out, sfw_best *best_out) {
+  if (!h) return SFW_ERR_INVALID_ARG;
+  // (refused before anything is touched: the staged grid, list or sequences stay launchable)
+  if (!m || !stat_out || !plans_out) return fail(h, SFW_ERR_INVALID_ARG, "mppi_run: m, stat_out or plans_out is NULL");
+  if (m->iterations < 1 || m->iterations > SFW_MPPI_MAX_ITER || m->reserved != 0)
+    return fail(h, SFW_ERR_INVALID_ARG, "mppi_run: iterations outside 1..SFW_MPPI_MAX_ITER, or reserved != 0");
+  if (!std::isfinite(m->lambda) || !(m->lambda > 0.0) || !std::isfinite(m->gamma))
+    return fail(h, SFW_ERR_INVALID_ARG, "mppi_run: lambda is not finite or not > 0, or gamma is not finite");
+  if (const char *why = perturb_refusal(rs, p, n, K, knot_step, args, 0)) return fail(h, SFW_ERR_INVALID_ARG, std::string("mppi_run: ") + why);
+  if (int e = sfw_sequences_perturb_stage(h, rs, p, n, K, knot_step, args, 0)) return e;
+  if (int e = mppi_chain(h, p, K, m, stat_out, plans_out, best_out)) {
+    if (h->pin_mppi.done) (void)h->pin_mppi.mark(h->stream);  // (kernels of the chain may still be writing there)
+    const std::string why = h->err;
+    drop_stage(h);
+    h->err = why;
+    return e;
+  }
+  return SFW_OK;
 }
 
 int sfw_grid_terms(sfw_handle h, int64_t first, int64_t count, double *terms_out) {

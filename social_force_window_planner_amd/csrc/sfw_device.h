@@ -345,6 +345,8 @@ hipError_t sfw_launch_ensemble_list(const double *const *terms, const double *pr
 // else a grid of T / nw x nw samples, K == 1).  Three launches: `mins` (sfw_blend_min_blocks(T) records), `partials`
 // (sfw_blend_blocks(T) x sfw_blend_channels(L, K) doubles), then *min_host and out_host[sfw_blend_channels(L, K)] = eta[L] |
 // sum_w2[L] | u[L][K][3] in pinned memory.  weights (nullable): L x T doubles, lambda-major.
+// plan (nullable; sfw_mppi_run: L == 1, K x 3 doubles on the device): the last kernel is sfw_mppi_update_kernel — out_host
+// receives eta | sum_w2 | the NEXT nominal plan, and `plan` becomes it: the blended knots, or unchanged when no sample is valid.
 struct sfw_blend_min {
   double j;         // +inf when no sample is valid
   int64_t index;    // the largest t with J_t == j; -1
@@ -359,7 +361,7 @@ inline int64_t sfw_blend_channels(int L, int K) { return 2 * static_cast<int64_t
 hipError_t sfw_launch_blend(const double *costs, const double *bias, int64_t T, const sfw_blend_lambdas &lam, int L, int K,
                             const double *linvels, const double *vy, const double *angvels, int32_t nw, bool list,
                             sfw_blend_min *mins, double *partials, double *weights, sfw_blend_min *min_host, double *out_host,
-                            hipStream_t stream);
+                            hipStream_t stream, double *plan = nullptr);
 // The weights of L temperatures alone (a slice of a weights_out that does not fit one buffer), behind a sfw_launch_blend
 // with the same costs and bias: `mins` as that launch left it.
 hipError_t sfw_launch_blend_weights(const double *costs, const double *bias, int64_t T, const sfw_blend_lambdas &lam, int L,
@@ -375,6 +377,21 @@ struct sfw_perturb_dev {
 };
 hipError_t sfw_launch_perturb(const sfw_perturb_dev &a, int64_t n, int K, int64_t index_base, double *vx, double *vy, double *vtheta,
                               double *z_out, hipStream_t stream);
+// sfw_perturb_dev up to the nominal rows: what a kernel that reads the plan from device memory takes as its argument
+struct sfw_perturb_head {
+  uint32_t key0, key1;
+  int32_t keep_nominal, pad;
+  double sigma[3], lo[3], hi[3];
+};
+static_assert(sizeof(sfw_perturb_head) == offsetof(sfw_perturb_dev, nominal), "sfw_perturb_head is the head of sfw_perturb_dev");
+// The same draw around `plan` (K x 3 doubles in device memory; a.nominal is not read): sfw_perturb_plan_kernel
+hipError_t sfw_launch_perturb_plan(const sfw_perturb_dev &a, const double *plan, int64_t n, int K, int64_t index_base, double *vx,
+                                   double *vy, double *vtheta, double *z_out, hipStream_t stream);
+// sfw_sequences_control_cost: bias[t] = gamma * c_t (+ bias_add[t], nullable) of the perturbed stage `a` describes, n doubles
+// on the device.  plan (nullable): the nominal rows in device memory instead of a.nominal; z_kept (nullable): the stage's kept
+// normals, else they are drawn again.
+hipError_t sfw_launch_control_cost(const sfw_perturb_dev &a, const double *plan, int K, int64_t n, int64_t index_base,
+                                   const double *z_kept, double gamma, const double *bias_add, double *bias, hipStream_t stream);
 // Row r of the [R,5] multi-device exchange table from a selection record (+inf in every other row).
 hipError_t sfw_launch_key_table(const sfw_sel *sel, double *table, int r, int R, hipStream_t stream);
 // Pair table of the flat social kernel for A agents: sfw_pair_table_entries(A) uint16 entries.

@@ -3003,11 +3003,10 @@ sfw_blend_first(const double *costs, const double *bias, int64_t T, sfw_blend_la
   }
 }
 
-// out: eta[L] | sum_w2[L] | u[L][K][3]
-__global__ void __launch_bounds__(BLEND_C) sfw_blend_last(const double *__restrict__ partials, int64_t blocks, int L, int K, double *out) {
+// Channel ch of eta[L] | sum_w2[L] | u[L][K][3]: the blocks' partials in block order, a knot channel divided by its eta.
+// any (knot channels only): that eta is > 0, i.e. some sample is valid (the samples at j_min have w == 1.0)
+__device__ __forceinline__ double blend_channel(const double *__restrict__ partials, int64_t blocks, int L, int K, int ch, bool &any) {
   const int n_ch = 2 * L + 3 * K * L;
-  const int ch = static_cast<int>(blockIdx.x) * BLEND_C + threadIdx.x;
-  if (ch >= n_ch) return;
   double acc = partials[ch];
 #pragma unroll 8
   for (int64_t b = 1; b < blocks; ++b) acc = acc + partials[b * n_ch + ch];
@@ -3016,9 +3015,17 @@ __global__ void __launch_bounds__(BLEND_C) sfw_blend_last(const double *__restri
     double eta = partials[l];
 #pragma unroll 8
     for (int64_t b = 1; b < blocks; ++b) eta = eta + partials[b * n_ch + l];
-    acc = eta > 0.0 ? acc / eta : 0.0;  // (no valid sample: eta == 0, every mean 0.0)
+    any = eta > 0.0;
+    acc = any ? acc / eta : 0.0;  // (no valid sample: eta == 0, every mean 0.0)
   }
-  out[ch] = acc;
+  return acc;
+}
+// out: eta[L] | sum_w2[L] | u[L][K][3]
+__global__ void __launch_bounds__(BLEND_C) sfw_blend_last(const double *__restrict__ partials, int64_t blocks, int L, int K, double *out) {
+  const int ch = static_cast<int>(blockIdx.x) * BLEND_C + threadIdx.x;
+  if (ch >= 2 * L + 3 * K * L) return;
+  bool any = false;
+  out[ch] = blend_channel(partials, blocks, L, K, ch, any);
 }
 #pragma clang fp contract(fast)
 #endif  // SFW_STRICT_BUILD
@@ -3051,9 +3058,34 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
   w[2] = c2;
   w[3] = c3;
 }
-// vy == null: a stage without a vy row (SFW_PERTURB_NO_VY); z_out == null: the normals are not kept
-__global__ void __launch_bounds__(PERTURB_C)
-sfw_perturb_kernel(sfw_perturb_dev a, int64_t n, int64_t index_base, double *vx, double *vy, double *vtheta, double *z_out) {
+// The normal of (sample g, knot k, channel c) under the seed (key0, key1): sfw_hip.h "Definition" up to z.  ONE text for every
+// kernel that draws or re-draws a perturbation (sfw_perturb_kernel, sfw_perturb_plan_kernel, sfw_control_cost_kernel).
+__device__ __forceinline__ double perturb_normal(uint32_t key0, uint32_t key1, int keep_nominal, uint64_t g, int k, int c) {
+  uint32_t w[4];
+  philox4x32_10(static_cast<uint32_t>(g), static_cast<uint32_t>(g >> 32), static_cast<uint32_t>(k), static_cast<uint32_t>(c), key0, key1,
+                w);
+  const uint64_t m1 = ((static_cast<uint64_t>(w[1]) << 32) | w[0]) >> 11, m2 = ((static_cast<uint64_t>(w[3]) << 32) | w[2]) >> 11;
+  const double u1 = static_cast<double>(m1 + 1) * 0x1p-53, u2 = static_cast<double>(m2) * 0x1p-53;  // (0, 1] and [0, 1): exact
+  const double r = sqrt(-2.0 * log(u1));
+  const double angle = 6.283185307179586 * u2;
+  double z = r * cos(angle);
+  if (keep_nominal && g == 0) z = 0.0;
+  return z;
+}
+// A wave-uniform table of doubles in device memory, read through the scalar cache (s_load) as sfw_ens_list_first reads its
+// member table.  The kernel arguments are such memory too: the nominal rows of an sfw_perturb_dev that is the FIRST argument.
+typedef const __attribute__((address_space(4))) double *uniform_doubles;
+__device__ __forceinline__ uniform_doubles uniform_of(const double *p) {
+  return (uniform_doubles)(const __attribute__((address_space(1))) double *)p;
+}
+__device__ __forceinline__ uniform_doubles nominal_of_first_arg() {
+  return (uniform_doubles)((const __attribute__((address_space(4))) char *)__builtin_amdgcn_kernarg_segment_ptr() +
+                           offsetof(sfw_perturb_dev, nominal));
+}
+// One thread's work of a perturb kernel: sample t, knot blockIdx.y, the three channels.  ARGS: sfw_perturb_dev or its head.
+template <typename ARGS>
+__device__ __forceinline__ void perturb_sample(const ARGS &a, const uniform_doubles nominal, int64_t n, int64_t index_base, double *vx,
+                                               double *vy, double *vtheta, double *z_out) {
   const int64_t t = static_cast<int64_t>(blockIdx.x) * PERTURB_C + threadIdx.x;
   if (t >= n) return;
   const int k = blockIdx.y;
@@ -3062,22 +3094,69 @@ sfw_perturb_kernel(sfw_perturb_dev a, int64_t n, int64_t index_base, double *vx,
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     if (!row[c] && !z_out) continue;
-    uint32_t w[4];
-    philox4x32_10(static_cast<uint32_t>(g), static_cast<uint32_t>(g >> 32), static_cast<uint32_t>(k), static_cast<uint32_t>(c), a.key0,
-                  a.key1, w);
-    const uint64_t m1 = ((static_cast<uint64_t>(w[1]) << 32) | w[0]) >> 11, m2 = ((static_cast<uint64_t>(w[3]) << 32) | w[2]) >> 11;
-    const double u1 = static_cast<double>(m1 + 1) * 0x1p-53, u2 = static_cast<double>(m2) * 0x1p-53;  // (0, 1] and [0, 1): exact
-    const double r = sqrt(-2.0 * log(u1));
-    const double angle = 6.283185307179586 * u2;
-    double z = r * cos(angle);
-    if (a.keep_nominal && g == 0) z = 0.0;
+    const double z = perturb_normal(a.key0, a.key1, a.keep_nominal, g, k, c);
     const int64_t at = static_cast<int64_t>(k) * n + t;
     if (z_out) z_out[(static_cast<int64_t>(k) * 3 + c) * n + t] = z;
     if (row[c]) {
       const double step = a.sigma[c] * z;
-      row[c][at] = fmin(fmax(a.nominal[k * 3 + c] + step, a.lo[c]), a.hi[c]);
+      row[c][at] = fmin(fmax(nominal[k * 3 + c] + step, a.lo[c]), a.hi[c]);
     }
   }
+}
+// vy == null: a stage without a vy row (SFW_PERTURB_NO_VY); z_out == null: the normals are not kept
+__global__ void __launch_bounds__(PERTURB_C)
+sfw_perturb_kernel(sfw_perturb_dev a, int64_t n, int64_t index_base, double *vx, double *vy, double *vtheta, double *z_out) {
+  perturb_sample(a, nominal_of_first_arg(), n, index_base, vx, vy, vtheta, z_out);
+}
+// sfw_mppi_run, iterations > 0: the same draw around the plan the last update left in device memory (K x 3 doubles) instead
+// of around a kernel argument, into the knot rows the stage reserved.  Same thread layout, same stores.
+__global__ void __launch_bounds__(PERTURB_C)
+sfw_perturb_plan_kernel(sfw_perturb_head a, const double *plan, int64_t n, int64_t index_base, double *vx, double *vy, double *vtheta,
+                        double *z_out) {
+  perturb_sample(a, uniform_of(plan), n, index_base, vx, vy, vtheta, z_out);
+}
+
+// The control-cost term of a perturbed stage (sfw_sequences_control_cost, sfw_hip.h "Control cost"): c_t = sum over k, then
+// over the channels with sigma > 0, of (nominal[k][c] / sigma[c]) * z[k][c] — acc = acc + q * z from +0.0, every operation
+// rounded on its own — and bias[t] = gamma * c_t, plus bias_add[t] where the caller has a bias of its own.  Thread = sample.
+// z comes from the kept normals (z_kept, [(k * 3 + c) * n + t]: coalesced) or is drawn again by perturb_normal: the same bits.
+// plan: the nominal rows in device memory (sfw_mppi_run), or null: those of the kernel argument.  No LDS, no atomics.
+constexpr int CONTROL_C = 256;
+__global__ void __launch_bounds__(CONTROL_C)
+sfw_control_cost_kernel(sfw_perturb_dev a, const double *plan, int K, int64_t n, int64_t index_base, const double *z_kept,
+                        double gamma, const double *bias_add, double *bias) {
+  const int64_t t = static_cast<int64_t>(blockIdx.x) * CONTROL_C + threadIdx.x;
+  if (t >= n) return;
+  const uniform_doubles nominal = plan ? uniform_of(plan) : nominal_of_first_arg();
+  const uint64_t g = static_cast<uint64_t>(index_base + t);
+  double acc = 0.0;
+  for (int k = 0; k < K; ++k) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      if (!(a.sigma[c] > 0.0)) continue;
+      const double q = nominal[k * 3 + c] / a.sigma[c];
+      const double z = z_kept ? z_kept[(static_cast<int64_t>(k) * 3 + c) * n + t] : perturb_normal(a.key0, a.key1, a.keep_nominal, g, k, c);
+      acc = acc + q * z;
+    }
+  }
+  const double b = gamma * acc;
+  bias[t] = bias_add ? b + bias_add[t] : b;
+}
+
+// The last kernel of a blend inside sfw_mppi_run (L == 1), in place of sfw_blend_last: the same sums and the same division
+// (blend_channel), then the plan update.  slot (pinned) receives eta | sum_w2 | nom_next[K][3] and `plan` (device, K x 3)
+// becomes nom_next: the blended knots, or — no valid sample: eta == 0 — the plan as it stands.  One thread per channel.
+__global__ void __launch_bounds__(BLEND_C) sfw_mppi_update_kernel(const double *__restrict__ partials, int64_t blocks, int K, double *plan,
+                                                                  double *slot) {
+  const int ch = static_cast<int>(blockIdx.x) * BLEND_C + threadIdx.x;
+  if (ch >= 2 + 3 * K) return;
+  bool any = false;
+  double v = blend_channel(partials, blocks, 1, K, ch, any);
+  if (ch >= 2) {
+    if (any) plan[ch - 2] = v;
+    else v = plan[ch - 2];
+  }
+  slot[ch] = v;
 }
 #pragma clang fp contract(fast)
 #endif  // SFW_STRICT_BUILD
@@ -3771,15 +3850,20 @@ static hipError_t blend_first(const double *costs, const double *bias, int64_t T
 hipError_t sfw_launch_blend(const double *costs, const double *bias, int64_t T, const sfw_blend_lambdas &lam, int L, int K,
                             const double *linvels, const double *vy, const double *angvels, int32_t nw, bool list,
                             sfw_blend_min *mins, double *partials, double *weights, sfw_blend_min *min_host, double *out_host,
-                            hipStream_t stream) {
+                            hipStream_t stream, double *plan) {
   if (T < 1 || L < 1 || L > SFW_BLEND_MAX_L || K < 1 || (!list && (K != 1 || nw < 1)) || sfw_blend_blocks(T) > INT_MAX ||
-      !costs || !linvels || !angvels || !mins || !partials || !min_host || !out_host)
+      !costs || !linvels || !angvels || !mins || !partials || !min_host || !out_host || (plan && (L != 1 || K > SFW_SEQ_MAX_KNOTS)))
     return hipErrorInvalidValue;
   hipLaunchKernelGGL(sfw_blend_min_kernel, dim3(static_cast<unsigned>(sfw_blend_min_blocks(T))), dim3(BLEND_C), 0, stream, costs, bias,
                      T, mins);
   hipError_t e = blend_first(costs, bias, T, lam, L, K, linvels, vy, angvels, nw, list ? 1 : 0, mins, partials, weights, min_host, stream);
   if (e != hipSuccess) return e;
   const int64_t n_ch = sfw_blend_channels(L, K);
+  if (plan) {  // sfw_mppi_run: the last kernel also moves the plan on
+    hipLaunchKernelGGL(sfw_mppi_update_kernel, dim3(static_cast<unsigned>((n_ch + BLEND_C - 1) / BLEND_C)), dim3(BLEND_C), 0, stream,
+                       static_cast<const double *>(partials), sfw_blend_blocks(T), K, plan, out_host);
+    return hipGetLastError();
+  }
   hipLaunchKernelGGL(sfw_blend_last, dim3(static_cast<unsigned>((n_ch + BLEND_C - 1) / BLEND_C)), dim3(BLEND_C), 0, stream,
                      static_cast<const double *>(partials), sfw_blend_blocks(T), L, K, out_host);
   return hipGetLastError();
@@ -3795,6 +3879,28 @@ hipError_t sfw_launch_perturb(const sfw_perturb_dev &a, int64_t n, int K, int64_
   if (n < 1 || K < 1 || K > SFW_SEQ_MAX_KNOTS || index_base < 0 || blocks > INT_MAX || !vx || !vtheta) return hipErrorInvalidValue;
   hipLaunchKernelGGL(sfw_perturb_kernel, dim3(static_cast<unsigned>(blocks), static_cast<unsigned>(K)), dim3(PERTURB_C), 0, stream, a, n,
                      index_base, vx, vy, vtheta, z_out);
+  return hipGetLastError();
+}
+hipError_t sfw_launch_perturb_plan(const sfw_perturb_dev &a, const double *plan, int64_t n, int K, int64_t index_base, double *vx,
+                                   double *vy, double *vtheta, double *z_out, hipStream_t stream) {
+  const int64_t blocks = (n + PERTURB_C - 1) / PERTURB_C;
+  if (n < 1 || K < 1 || K > SFW_SEQ_MAX_KNOTS || index_base < 0 || blocks > INT_MAX || !vx || !vtheta || !plan) return hipErrorInvalidValue;
+  sfw_perturb_head head{a.key0, a.key1, a.keep_nominal, 0, {}, {}, {}};
+  for (int c = 0; c < 3; ++c) {
+    head.sigma[c] = a.sigma[c];
+    head.lo[c] = a.lo[c];
+    head.hi[c] = a.hi[c];
+  }
+  hipLaunchKernelGGL(sfw_perturb_plan_kernel, dim3(static_cast<unsigned>(blocks), static_cast<unsigned>(K)), dim3(PERTURB_C), 0, stream,
+                     head, plan, n, index_base, vx, vy, vtheta, z_out);
+  return hipGetLastError();
+}
+hipError_t sfw_launch_control_cost(const sfw_perturb_dev &a, const double *plan, int K, int64_t n, int64_t index_base,
+                                   const double *z_kept, double gamma, const double *bias_add, double *bias, hipStream_t stream) {
+  const int64_t blocks = (n + CONTROL_C - 1) / CONTROL_C;
+  if (n < 1 || K < 1 || K > SFW_SEQ_MAX_KNOTS || index_base < 0 || blocks > INT_MAX || !bias) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(sfw_control_cost_kernel, dim3(static_cast<unsigned>(blocks)), dim3(CONTROL_C), 0, stream, a, plan, K, n, index_base,
+                     z_kept, gamma, bias_add, bias);
   return hipGetLastError();
 }
 #endif  // SFW_STRICT_BUILD

@@ -25,6 +25,8 @@ from ._abi import (
     SfwBlendStat,
     SFW_BLEND_MAX_L,
     SfwGoalArgs,
+    SfwMppi,
+    SFW_MPPI_MAX_ITER,
     SfwParams,
     SfwPerturb,
     SfwRobotState,
@@ -180,6 +182,10 @@ def lib():
         L.sfw_ensemble_score_perturbed.argtypes = [vp, C.POINTER(SfwRobotState), C.POINTER(SfwPerturb), C.c_int32, C.c_int32, vp,
                                                    C.POINTER(SfwGoalArgs), C.c_int32, vp, vp, vp, C.POINTER(SfwBest)]
         L.sfw_ensemble_blend.argtypes = [vp, vp, C.c_int32, vp, C.POINTER(SfwBlendStat), vp, vp]
+        L.sfw_sequences_control_cost.argtypes = [vp, C.c_double, vp]
+        L.sfw_grid_blend_control.argtypes = [vp, vp, C.c_int32, C.c_double, vp, C.POINTER(SfwBlendStat), vp, vp]
+        L.sfw_mppi_run.argtypes = [vp, C.POINTER(SfwRobotState), C.POINTER(SfwPerturb), C.c_int32, C.c_int32, vp,
+                                   C.POINTER(SfwGoalArgs), C.POINTER(SfwMppi), C.POINTER(SfwBlendStat), vp, C.POINTER(SfwBest)]
         _lib = L
     return _lib
 
@@ -580,11 +586,13 @@ class HipScorer:
         return [best[k].as_dict() for k in range(K)], costs
 
     # -- softmin blend ---------------------------------------------------------
-    def blend(self, lambdas, bias=None, want_weights=False):
+    def blend(self, lambdas, bias=None, want_weights=False, gamma=None):
         """sfw_grid_blend over the last launch (grid, list or sequences): the softmin weights exp(-(J - J_min) / lambda) of
         L temperatures, reduced on the device.  bias: one value per sample added to its cost (None: none).  Returns
         (stats: L dicts with lambda, j_min, eta, sum_w2, ess, n_valid, index_min; u[L, K, 3]: the weighted mean of the
-        (vx, vy, vtheta) knots; weights[L, T] or None).  Read-only for the launch."""
+        (vx, vy, vtheta) knots; weights[L, T] or None).  Read-only for the launch.
+        gamma (a perturbed stage only): sfw_grid_blend_control — gamma times the control cost of every sample's perturbation
+        (control_cost) joins the bias on the device."""
         lam = np.ascontiguousarray(np.asarray(lambdas, dtype=np.float64).reshape(-1))
         L = len(lam)
         if L < 1 or L > SFW_BLEND_MAX_L:
@@ -602,9 +610,40 @@ class HipScorer:
         stats = (SfwBlendStat * L)()
         u = np.zeros((L, K, 3), dtype=np.float64)
         w = np.zeros((L, T), dtype=np.float64) if want_weights else None
-        self._check(lib().sfw_grid_blend(self._h, lam.ctypes.data, L, b.ctypes.data if b is not None and T else None, stats,
-                                         u.ctypes.data, w.ctypes.data if w is not None and T else None), "sfw_grid_blend")
+        bp, wp = b.ctypes.data if b is not None and T else None, w.ctypes.data if w is not None and T else None
+        if gamma is None:
+            self._check(lib().sfw_grid_blend(self._h, lam.ctypes.data, L, bp, stats, u.ctypes.data, wp), "sfw_grid_blend")
+        else:
+            self._check(lib().sfw_grid_blend_control(self._h, lam.ctypes.data, L, float(gamma), bp, stats, u.ctypes.data, wp),
+                        "sfw_grid_blend_control")
         return [stats[l].as_dict() for l in range(L)], u, w
+
+    # -- MPPI on the device: the control cost, chained iterations ----------------
+    def control_cost(self, gamma):
+        """sfw_sequences_control_cost of the staged perturbed sequences: gamma * c_t for every sample, c_t = sum over knots and
+        channels of (nominal / sigma) * z (mppi.control_cost restates it).  Before or after the launch."""
+        n = self._grid[0] if self._grid is not None else 0
+        out = np.zeros(max(n, 1), dtype=np.float64)
+        self._check(lib().sfw_sequences_control_cost(self._h, float(gamma), out.ctypes.data), "sfw_sequences_control_cost")
+        return out[:n]
+
+    def mppi_run(self, robot_state, n, seed, nominal, sigma, lo, hi, knot_steps, goal_args, iterations, lam, gamma, flags=0):
+        """sfw_mppi_run: `iterations` times perturb (seed + i) -> score -> control cost -> blend at temperature lam -> new
+        nominal, chained on the device behind one wait.  Returns (stats: one dict per iteration; plans[I, K, 3]: the nominal
+        plan after every iteration; best of the last iteration).  The scorer is left as after the last iteration's
+        score_perturbed."""
+        p, nom, ks = self._perturb(seed, nominal, sigma, lo, hi, knot_steps, flags)
+        rs, ga = SfwRobotState(*robot_state), SfwGoalArgs(*goal_args)
+        K, I = nom.shape[0], int(iterations)
+        m = SfwMppi(I, 0, float(lam), float(gamma))
+        room = min(max(I, 1), SFW_MPPI_MAX_ITER)  # (a refused iteration count writes nothing)
+        stats = (SfwBlendStat * room)()
+        plans = np.zeros((room, K, 3), dtype=np.float64)
+        best = SfwBest()
+        self._check(lib().sfw_mppi_run(self._h, C.byref(rs), C.byref(p), n, K, ks.ctypes.data if len(ks) else None, C.byref(ga),
+                                       C.byref(m), stats, plans.ctypes.data, C.byref(best)), "sfw_mppi_run")
+        self._mark_staged((n, 1), knots=K)
+        return [stats[i].as_dict() for i in range(I)], plans, best.as_dict()
 
 
 def plan_row_blocks(linvels, angvels, robot_state, goal_args, sim_time, num_steps, n_agents, n_ranks):
