@@ -969,6 +969,42 @@ int sfw_ensemble_score_perturbed(sfw_ensemble e, const sfw_robot_state *rs, cons
  * rule of sfw_ensemble_aggregate.  Member 0's own sfw_grid_blend is not disturbed: the ensemble has buffers of its own. */
 int sfw_ensemble_blend(sfw_ensemble e, const double *lambda, int32_t L, const double *bias, sfw_blend_stat *stat_out,
                        double *u_out, double *weights_out);
+/* sfw_ensemble_blend with the control cost: J_t = cost_t + b_t, where b_t = gamma * c_t (bias == NULL) or (gamma * c_t) +
+ * bias_t, and c_t is the "Control cost" of member 0's perturbed stage (every member staged the same sfw_perturb).  Nothing
+ * else differs — the definition, the outputs, the summation tree and the state rule are sfw_ensemble_blend's: what
+ * sfw_grid_blend_control is to sfw_grid_blend.  The bias vector never leaves the device, and lives in a buffer of the
+ * ensemble's: member 0's own sfw_grid_blend_control is not disturbed, nor the other way round.  gamma == 0 is bit for bit
+ * sfw_ensemble_blend with the same `bias`.  SFW_ERR_STATE: sfw_ensemble_blend's rule, and when the last score was not a
+ * perturbed one (sfw_ensemble_score_perturbed, sfw_ensemble_mppi_run).  SFW_ERR_INVALID_ARG (before any device call; a
+ * refused call changes nothing): what sfw_ensemble_blend refuses, and a gamma that is not finite. */
+int sfw_ensemble_blend_control(sfw_ensemble e, const double *lambda, int32_t L, double gamma, const double *bias,
+                               sfw_blend_stat *stat_out, double *u_out, double *weights_out);
+/* sfw_mppi_run under M crowd hypotheses: I = m->iterations iterations of perturb -> score all members -> aggregate -> control
+ * cost -> blend -> new nominal plan, enqueued back to back on the ensemble's stream behind ONE wait.  It is defined as this
+ * loop of the calls above and equals it BIT FOR BIT in every output:
+ *   nom_0 = p->nominal
+ *   for i = 0 .. I-1:
+ *       pt = *p;  pt.seed = p->seed + i (mod 2^64);  pt.nominal = nom_i
+ *       sfw_ensemble_score_perturbed(e, rs, &pt, n, K, knot_step, args, mode, probs, costs_i, rejected_i, &best_i)
+ *       sfw_ensemble_blend_control(e, &m->lambda, 1, m->gamma, NULL, &stat_out[i], u_i, NULL)
+ *       nom_(i+1) = stat_out[i].n_valid > 0 ? u_i : nom_i
+ *       plans_out[i] = nom_(i+1)                                      (K x 3 doubles: [k][vx, vy, vtheta])
+ *   costs_out = costs_(I-1);  rejected_out = rejected_(I-1);  *best_out = best_(I-1)        (n, n, one: each nullable)
+ * Iteration 0 stages the members as sfw_ensemble_score_perturbed does.  From there nothing goes through the host: ONE kernel
+ * (sfw_perturb_members_kernel) draws each knot once around the plan in device memory and stores it into every member's rows,
+ * the members' kernels and the aggregation follow, and the blend's last kernel leaves the next plan where the next draw
+ * reads it.  Afterwards the ensemble and every member are exactly as after iteration I-1 of that loop: sfw_ensemble_aggregate,
+ * sfw_ensemble_blend(_control), a member's costs view, terms, points, sfw_sequences_knots / _normals and sfw_grid_crowd act on
+ * that iteration, and every member remembers nom_(I-1) and seed + I - 1 as what it was drawn from.
+ * Refusals, in this order (all SFW_ERR_INVALID_ARG, before any member is staged, so the previous score stays usable): mode and
+ * probabilities; m NULL, iterations outside [1, SFW_MPPI_MAX_ITER], reserved != 0, a lambda that is not finite or not > 0, a
+ * gamma that is not finite; a NULL stat_out or plans_out; everything sfw_ensemble_score_perturbed refuses.  Then SFW_ERR_STATE
+ * as for every ensemble score.  Any later failure leaves nothing scored, and every member with nothing staged or launched. */
+int sfw_ensemble_mppi_run(sfw_ensemble e, const sfw_robot_state *rs, const sfw_perturb *p, int32_t n, int32_t K,
+                          const int32_t *knot_step, const sfw_goal_args *args, int32_t mode, const double *probs,
+                          const sfw_mppi *m, sfw_blend_stat *stat_out /* I */, double *plans_out /* I x K x 3 */,
+                          double *costs_out /* n, nullable */, int32_t *rejected_out /* n, nullable */,
+                          sfw_best *best_out /* nullable */);
 /* Host wall-clock of the last calls, microseconds: which = 0 staging of the members (the score calls only), 1 the enqueue of
  * the launch and the aggregation, 2 the wait and the copies out. */
 int sfw_ensemble_last_us(sfw_ensemble e, int32_t which, double *us_out);

@@ -232,6 +232,8 @@ EXPORTED_SYMBOLS = (
     "sfw_sequences_control_cost",
     "sfw_grid_blend_control",
     "sfw_mppi_run",
+    "sfw_ensemble_blend_control",
+    "sfw_ensemble_mppi_run",
 )
 # per-term costs (sfw_set_terms_capture / sfw_grid_rescore / sfw_grid_terms)
 SFW_TERM_VEL, SFW_TERM_DISTANCE, SFW_TERM_ANGLE, SFW_TERM_COSTMAP, SFW_TERM_SOCIAL = 0, 1, 2, 3, 4

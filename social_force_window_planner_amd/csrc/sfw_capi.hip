@@ -1930,18 +1930,19 @@ int blend_run(sfw_handle h, const blend_area &a, const double *d_costs, int64_t 
 }
 
 // The bias vector gamma * c_t (+ bias[t], nullable: T host doubles, uploaded to the blend's bias buffer first) of the staged
-// perturbed stage into h->ctrl_bias, on h's stream.  plan (nullable): the nominal rows in device memory (sfw_mppi_run).
-int control_cost_enqueue(sfw_handle h, double gamma, const double *bias, const double *plan) {
+// perturbed stage into `out`, on h's stream.  plan (nullable): the nominal rows in device memory (sfw_mppi_run).  out / add: the
+// handle's ctrl_bias / blend_bias, or an sfw_ensemble's own (member 0's belong to that member's calls).
+int control_cost_enqueue(sfw_handle h, double gamma, const double *bias, const double *plan, dev_buf<double> &out, dev_buf<double> &add) {
   const int64_t n = h->st.nv;
-  SFW_HIP(h, h->ctrl_bias.reserve(static_cast<size_t>(n)));
+  SFW_HIP(h, out.reserve(static_cast<size_t>(n)));
   const double *d_add = nullptr;
   if (bias) {
-    SFW_HIP(h, h->blend_bias.reserve(static_cast<size_t>(n)));
-    SFW_HIP(h, hipMemcpyAsync(h->blend_bias.p, bias, sizeof(double) * static_cast<size_t>(n), hipMemcpyHostToDevice, h->stream));
-    d_add = h->blend_bias.p;
+    SFW_HIP(h, add.reserve(static_cast<size_t>(n)));
+    SFW_HIP(h, hipMemcpyAsync(add.p, bias, sizeof(double) * static_cast<size_t>(n), hipMemcpyHostToDevice, h->stream));
+    d_add = add.p;
   }
   SFW_HIP(h, sfw_launch_control_cost(h->st.pert, plan, h->st.nk, n, h->st.index_base, h->st.normals_kept ? h->normals.p : nullptr, gamma,
-                                     d_add, h->ctrl_bias.p, h->stream));
+                                     d_add, out.p, h->stream));
   return SFW_OK;
 }
 const char *control_state_refusal(sfw_handle h) {
@@ -1979,7 +1980,7 @@ int mppi_chain(sfw_handle h, const sfw_perturb *p, int K, const sfw_mppi *m, sfw
     if (int e = launch_common(h)) return e;
     const double *d_bias = nullptr;
     if (m->gamma != 0.0) {  // (as sfw_grid_blend_control: gamma == 0 is the plain blend)
-      if (int e = control_cost_enqueue(h, m->gamma, nullptr, plan)) return e;
+      if (int e = control_cost_enqueue(h, m->gamma, nullptr, plan, h->ctrl_bias, h->blend_bias)) return e;
       d_bias = h->ctrl_bias.p;
     }
     if (int e = blend_enqueue(h, area, h->costs.p, n, K, h->st.d_linvels, h->st.d_vy, h->st.d_angvels, 1, true, &m->lambda, 1, d_bias,
@@ -2805,7 +2806,7 @@ int sfw_sequences_control_cost(sfw_handle h, double gamma, double *bias_out) {
   const size_t bytes = sizeof(double) * static_cast<size_t>(h->st.nv);
   if (bytes > h->pin_knots.cap) SFW_HIP(h, hipStreamSynchronize(h->stream));  // (growing the area frees the old one)
   SFW_HIP(h, h->pin_knots.reserve(bytes));
-  if (int e = control_cost_enqueue(h, gamma, nullptr, nullptr)) return e;
+  if (int e = control_cost_enqueue(h, gamma, nullptr, nullptr, h->ctrl_bias, h->blend_bias)) return e;
   SFW_HIP(h, hipMemcpyAsync(h->pin_knots.p, h->ctrl_bias.p, bytes, hipMemcpyDeviceToHost, h->stream));
   SFW_HIP(h, wait_stream(h));
   stream_is_idle(h);
@@ -2828,7 +2829,7 @@ int sfw_grid_blend_control(sfw_handle h, const double *lambda, int32_t L, double
   // gamma == 0: sfw_grid_blend itself (a bias of gamma * c_t = +-0.0 would turn a cost of -0.0 into +0.0)
   const double *d_bias = nullptr;
   if (gamma != 0.0) {
-    if (int e = control_cost_enqueue(h, gamma, bias, nullptr)) return e;
+    if (int e = control_cost_enqueue(h, gamma, bias, nullptr, h->ctrl_bias, h->blend_bias)) return e;
     d_bias = h->ctrl_bias.p;
     bias = nullptr;
   }
@@ -3929,6 +3930,13 @@ struct sfw_ensemble_s {
   dev_buf<sfw_blend_min> blend_mins;
   dev_buf<double> blend_partials, blend_bias, blend_weights;
   pinned_buf pin_blend;
+  // sfw_ensemble_blend_control: the bias vector gamma * c_t (+ bias_t) on the device (member 0's ctrl_bias belongs to its
+  // sfw_grid_blend_control).  sfw_ensemble_mppi_run: the nominal plan on the device, moved on by every iteration's update
+  // kernel; the members' knot rows as sfw_perturb_members_kernel reads them (M sfw_perturb_dst); pin_mppi = one blend slot per
+  // iteration | the caller's nominal | that table (the sources of the two copies that start the chain)
+  dev_buf<double> ctrl_bias, mppi_plan;
+  dev_buf<sfw_perturb_dst> pert_dst;
+  pinned_buf pin_mppi;
 };
 
 namespace {
@@ -3953,8 +3961,10 @@ int ensemble_check_mode(sfw_ensemble e, int32_t mode, const double *probs, const
 }
 
 // The aggregation behind the members' launch on the batch's stream: member table upload, stage 1 (+ stage 2), and for a grid
-// too large for the mirror nothing more (ensemble_finish copies it out after the wait).
-int ensemble_enqueue(sfw_ensemble e, int32_t mode, const double *probs) {
+// too large for the mirror nothing more (ensemble_finish copies it out after the wait).  reuse_tab: the member table on the
+// device is the last aggregation's and would be the same bytes (sfw_ensemble_mppi_run, iterations > 0: same members, same
+// probabilities) — no reserve of the pinned table, which waits for the last upload, and no upload.
+int ensemble_enqueue(sfw_ensemble e, int32_t mode, const double *probs, bool reuse_tab = false) {
   const int32_t M = static_cast<int32_t>(e->b->h.size());
   sfw_handle h0 = e->b->h[0];
   const int64_t T = static_cast<int64_t>(h0->st.nv) * h0->st.nw;
@@ -3970,17 +3980,19 @@ int ensemble_enqueue(sfw_ensemble e, int32_t mode, const double *probs) {
       e->partials.reserve(static_cast<size_t>(sfw_argmin_partials(T))) != hipSuccess)
     return efail(e, SFW_ERR_HIP, "ensemble: output allocation failed");
   const size_t tab_bytes = 2 * sizeof(double) * static_cast<size_t>(M);
-  if (e->pin_tab.reserve(tab_bytes) != hipSuccess || e->tab.reserve(tab_bytes) != hipSuccess)
-    return efail(e, SFW_ERR_HIP, "ensemble: member table allocation failed");
-  const double **ptrs = reinterpret_cast<const double **>(e->pin_tab.p);
-  double *const p = reinterpret_cast<double *>(e->pin_tab.p + sizeof(double) * static_cast<size_t>(M));
-  for (int32_t m = 0; m < M; ++m) {
-    ptrs[m] = e->b->h[static_cast<size_t>(m)]->terms.p;
-    p[m] = probs ? probs[m] : 1.0 / M;
+  if (!reuse_tab) {
+    if (e->pin_tab.reserve(tab_bytes) != hipSuccess || e->tab.reserve(tab_bytes) != hipSuccess)
+      return efail(e, SFW_ERR_HIP, "ensemble: member table allocation failed");
+    const double **ptrs = reinterpret_cast<const double **>(e->pin_tab.p);
+    double *const p = reinterpret_cast<double *>(e->pin_tab.p + sizeof(double) * static_cast<size_t>(M));
+    for (int32_t m = 0; m < M; ++m) {
+      ptrs[m] = e->b->h[static_cast<size_t>(m)]->terms.p;
+      p[m] = probs ? probs[m] : 1.0 / M;
+    }
+    if (hipMemcpyAsync(e->tab.p, e->pin_tab.p, tab_bytes, hipMemcpyHostToDevice, e->b->stream) != hipSuccess ||
+        e->pin_tab.mark(e->b->stream) != hipSuccess)
+      return efail(e, SFW_ERR_HIP, "ensemble: member table copy failed");
   }
-  if (hipMemcpyAsync(e->tab.p, e->pin_tab.p, tab_bytes, hipMemcpyHostToDevice, e->b->stream) != hipSuccess ||
-      e->pin_tab.mark(e->b->stream) != hipSuccess)
-    return efail(e, SFW_ERR_HIP, "ensemble: member table copy failed");
   const sfw_weights w{e->params.vel_weight, e->params.distance_weight, e->params.angle_weight, e->params.costmap_weight,
                       e->params.social_weight};
   char *const out = e->mirrored ? e->pin_out.p + kEnsRecBytes : e->d_out.p;
@@ -4064,6 +4076,117 @@ int ensemble_launch_and_finish(sfw_ensemble e, int32_t mode, const double *probs
   e->scored = true;
   return SFW_OK;
 }
+
+// sfw_ensemble_blend (gamma null) and sfw_ensemble_blend_control over the last aggregation's cost vector: ONE text.  The control
+// cost is that of member 0's perturbed stage (every member staged the same sfw_perturb), into the ensemble's own bias buffer.
+int ensemble_blend(sfw_ensemble e, const char *what, const double *lambda, int32_t L, const double *gamma, const double *bias,
+                   sfw_blend_stat *stat_out, double *u_out, double *weights_out) {
+  if (!e) return SFW_ERR_INVALID_ARG;
+  if (const char *why = blend_refusal(lambda, L, stat_out, u_out)) return efail(e, SFW_ERR_INVALID_ARG, std::string(what) + ": " + why);
+  if (gamma && !std::isfinite(*gamma)) return efail(e, SFW_ERR_INVALID_ARG, std::string(what) + ": gamma is not finite");
+  if (int rc = ensemble_check_scored(e, what)) return rc;
+  sfw_handle h0 = e->b->h[0];
+  if (gamma)
+    if (const char *why = control_state_refusal(h0))
+      return efail(e, SFW_ERR_STATE, std::string(what) + ": the last score was not a perturbed one: " + why);
+  if (bias && !all_finite(bias, static_cast<size_t>(e->T))) return efail(e, SFW_ERR_INVALID_ARG, std::string(what) + ": non-finite bias");
+  if (hipSetDevice(e->device) != hipSuccess) return efail(e, SFW_ERR_HIP, std::string(what) + ": hipSetDevice failed");
+  if (!e->cost_dev) {  // a grid's aggregation left the vector in the pinned mirror only: the blend's kernels read a device copy
+    if (!e->mirrored) return efail(e, SFW_ERR_STATE, std::string(what) + ": the last aggregation left no cost vector");
+    if (e->d_cost.reserve(static_cast<size_t>(e->T)) != hipSuccess ||
+        hipMemcpyAsync(e->d_cost.p, e->pin_out.p + kEnsRecBytes, sizeof(double) * static_cast<size_t>(e->T), hipMemcpyHostToDevice,
+                       e->b->stream) != hipSuccess)
+      return efail(e, SFW_ERR_HIP, std::string(what) + ": cost vector upload failed");
+    e->cost_dev = e->d_cost.p;  // (the blend waits for the stream before it returns: the mirror is free again by then)
+  }
+  const blend_area area{e->blend_mins, e->blend_partials, e->blend_bias, e->blend_weights, e->pin_blend};
+  // gamma == 0: the plain blend (as sfw_grid_blend_control)
+  const double *d_bias = nullptr;
+  if (gamma && *gamma != 0.0) {
+    if (int rc = control_cost_enqueue(h0, *gamma, bias, nullptr, e->ctrl_bias, e->blend_bias)) return emember_fail(e, 0, rc, what);
+    d_bias = e->ctrl_bias.p;
+    bias = nullptr;
+  }
+  if (int rc = blend_run(h0, area, e->cost_dev, e->T, h0->st.list ? h0->st.nk : 1, h0->st.d_linvels, h0->st.d_vy, h0->st.d_angvels,
+                         h0->st.nw, h0->st.list, lambda, L, bias, stat_out, u_out, weights_out, d_bias))
+    return emember_fail(e, 0, rc, what);
+  return SFW_OK;
+}
+
+// sfw_ensemble_mppi_run behind its stage of iteration 0: everything enqueued on the batch's stream, one wait, the outputs.  A
+// failure is the caller's to clean up.  The members are lists, so batch_launch builds no member table (each takes its own
+// path); the aggregation's table is uploaded by iteration 0 and read again from the device by the others.
+int ensemble_mppi_chain(sfw_ensemble e, const sfw_perturb *p, int K, int32_t mode, const double *probs, const sfw_mppi *m,
+                        sfw_blend_stat *stat_out, double *plans_out, double *costs_out, int32_t *rejected_out, sfw_best *best_out) {
+  const char *const what = "ensemble_mppi_run";
+  const size_t M = e->b->h.size();
+  const int I = m->iterations;
+  sfw_handle h0 = e->b->h[0];
+  const int64_t n = h0->st.nv;
+  const size_t slot = (blend_slot_bytes(1, K) + 15) & ~size_t(15), plan_bytes = sizeof(double) * 3 * static_cast<size_t>(K);
+  const size_t plan_at = I * slot, dst_at = (plan_at + plan_bytes + 15) & ~size_t(15), dst_bytes = sizeof(sfw_perturb_dst) * M;
+  // every buffer the chain writes is in place before its first kernel is enqueued: nothing in flight is ever freed
+  if (dst_at + dst_bytes > e->pin_mppi.cap && hipStreamSynchronize(e->b->stream) != hipSuccess)
+    return efail(e, SFW_ERR_HIP, std::string(what) + ": hipStreamSynchronize failed");
+  if (e->pin_mppi.reserve(dst_at + dst_bytes) != hipSuccess || e->mppi_plan.reserve(3 * static_cast<size_t>(SFW_SEQ_MAX_KNOTS)) != hipSuccess ||
+      e->pert_dst.reserve(M) != hipSuccess || e->d_cost.reserve(static_cast<size_t>(n)) != hipSuccess ||
+      (m->gamma != 0.0 && e->ctrl_bias.reserve(static_cast<size_t>(n)) != hipSuccess) ||
+      e->blend_mins.reserve(static_cast<size_t>(sfw_blend_min_blocks(n))) != hipSuccess ||
+      e->blend_partials.reserve(static_cast<size_t>(sfw_blend_blocks(n)) * static_cast<size_t>(sfw_blend_channels(1, K))) != hipSuccess)
+    return efail(e, SFW_ERR_HIP, std::string(what) + ": allocation failed");
+  const blend_area area{e->blend_mins, e->blend_partials, e->blend_bias, e->blend_weights, e->pin_blend};
+  char *const pin = e->pin_mppi.p;
+  std::memcpy(pin + plan_at, p->nominal, plan_bytes);
+  sfw_perturb_dst *const dst = reinterpret_cast<sfw_perturb_dst *>(pin + dst_at);
+  for (size_t k = 0; k < M; ++k) {
+    const sfw_handle h = e->b->h[k];
+    dst[k] = sfw_perturb_dst{const_cast<double *>(h->st.d_linvels), const_cast<double *>(h->st.d_vy), const_cast<double *>(h->st.d_angvels),
+                             h->st.normals_kept ? h->normals.p : nullptr};
+  }
+  if (hipMemcpyAsync(e->mppi_plan.p, pin + plan_at, plan_bytes, hipMemcpyHostToDevice, e->b->stream) != hipSuccess ||
+      hipMemcpyAsync(e->pert_dst.p, dst, dst_bytes, hipMemcpyHostToDevice, e->b->stream) != hipSuccess)
+    return efail(e, SFW_ERR_HIP, std::string(what) + ": plan or member table copy failed");
+  double *const plan = e->mppi_plan.p;
+  auto t0 = std::chrono::steady_clock::now();
+  for (int i = 0; i < I; ++i) {
+    if (i > 0) {  // the stage of iteration i: its seed, and every member's knots drawn once around the plan the last update left
+      const uint64_t seed = p->seed + static_cast<uint64_t>(i);
+      for (sfw_handle h : e->b->h) {
+        h->st.pert.key0 = static_cast<uint32_t>(seed & 0xffffffffu);
+        h->st.pert.key1 = static_cast<uint32_t>(seed >> 32);
+      }
+      if (const hipError_t he = sfw_launch_perturb_members(h0->st.pert, plan, n, K, 0, e->pert_dst.p, static_cast<int>(M), e->b->stream);
+          he != hipSuccess)
+        return efail(e, SFW_ERR_HIP, std::string(what) + ": sfw_perturb_members_kernel: " + hipGetErrorString(he));
+    }
+    if (int rc = batch_launch(e->b)) return efail(e, rc, std::string(what) + ": " + e->b->err);
+    for (size_t k = 0; k < M; ++k)
+      if (!e->b->h[k]->last.terms) return efail(e, SFW_ERR_STATE, std::string(what) + ": member " + std::to_string(k) + " did not capture terms");
+    if (int rc = ensemble_enqueue(e, mode, probs, i > 0)) return rc;
+    const double *d_bias = nullptr;
+    if (m->gamma != 0.0) {  // (as sfw_ensemble_blend_control: gamma == 0 is the plain blend)
+      if (int rc = control_cost_enqueue(h0, m->gamma, nullptr, plan, e->ctrl_bias, e->blend_bias)) return emember_fail(e, 0, rc, what);
+      d_bias = e->ctrl_bias.p;
+    }
+    if (int rc = blend_enqueue(h0, area, e->cost_dev, n, K, h0->st.d_linvels, h0->st.d_vy, h0->st.d_angvels, 1, true, &m->lambda, 1,
+                               d_bias, nullptr, pin + i * slot, plan))
+      return emember_fail(e, 0, rc, what);
+  }
+  if (e->pin_mppi.mark(e->b->stream) != hipSuccess) return efail(e, SFW_ERR_HIP, std::string(what) + ": hipEventRecord failed");
+  e->us[1] = us_since(t0);
+  t0 = std::chrono::steady_clock::now();
+  if (int rc = batch_fetch(e->b, nullptr)) return efail(e, rc, std::string(what) + ": " + e->b->err);  // THE wait, all members
+  e->pin_mppi.pending = false;
+  if (int rc = ensemble_finish(e, costs_out, rejected_out, best_out)) return rc;
+  for (int i = 0; i < I; ++i) blend_finish(pin + i * slot, &m->lambda, 1, K, stat_out + i, plans_out + static_cast<size_t>(i) * 3 * K);
+  // the stage every member holds is iteration I - 1's: drawn around nom_(I-1)
+  if (I > 1)
+    for (sfw_handle h : e->b->h) std::memcpy(h->st.pert.nominal, plans_out + static_cast<size_t>(I - 2) * 3 * K, plan_bytes);
+  e->us[2] = us_since(t0);
+  for (size_t k = 0; k < M; ++k) e->seq[k] = e->b->h[k]->launch_seq;
+  e->scored = true;
+  return SFW_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -4105,6 +4228,10 @@ int sfw_ensemble_destroy(sfw_ensemble e) {
   e->blend_bias.release();
   e->blend_weights.release();
   e->pin_blend.release();
+  e->ctrl_bias.release();
+  e->mppi_plan.release();
+  e->pert_dst.release();
+  e->pin_mppi.release();
   delete e;
   return SFW_OK;
 }
@@ -4213,25 +4340,44 @@ int sfw_ensemble_score_perturbed(sfw_ensemble e, const sfw_robot_state *rs, cons
 
 int sfw_ensemble_blend(sfw_ensemble e, const double *lambda, int32_t L, const double *bias, sfw_blend_stat *stat_out, double *u_out,
                        double *weights_out) {
+  return ensemble_blend(e, "ensemble_blend", lambda, L, nullptr, bias, stat_out, u_out, weights_out);
+}
+
+int sfw_ensemble_blend_control(sfw_ensemble e, const double *lambda, int32_t L, double gamma, const double *bias,
+                               sfw_blend_stat *stat_out, double *u_out, double *weights_out) {
+  return ensemble_blend(e, "ensemble_blend_control", lambda, L, &gamma, bias, stat_out, u_out, weights_out);
+}
+
+int sfw_ensemble_mppi_run(sfw_ensemble e, const sfw_robot_state *rs, const sfw_perturb *p, int32_t n, int32_t K, const int32_t *knot_step,
+                          const sfw_goal_args *args, int32_t mode, const double *probs, const sfw_mppi *m, sfw_blend_stat *stat_out,
+                          double *plans_out, double *costs_out, int32_t *rejected_out, sfw_best *best_out) {
   if (!e) return SFW_ERR_INVALID_ARG;
-  if (const char *why = blend_refusal(lambda, L, stat_out, u_out)) return efail(e, SFW_ERR_INVALID_ARG, std::string("ensemble_blend: ") + why);
-  if (int rc = ensemble_check_scored(e, "ensemble_blend")) return rc;
-  if (bias && !all_finite(bias, static_cast<size_t>(e->T))) return efail(e, SFW_ERR_INVALID_ARG, "ensemble_blend: non-finite bias");
-  if (hipSetDevice(e->device) != hipSuccess) return efail(e, SFW_ERR_HIP, "ensemble_blend: hipSetDevice failed");
-  sfw_handle h0 = e->b->h[0];
-  if (!e->cost_dev) {  // a grid's aggregation left the vector in the pinned mirror only: the blend's kernels read a device copy
-    if (!e->mirrored) return efail(e, SFW_ERR_STATE, "ensemble_blend: the last aggregation left no cost vector");
-    if (e->d_cost.reserve(static_cast<size_t>(e->T)) != hipSuccess ||
-        hipMemcpyAsync(e->d_cost.p, e->pin_out.p + kEnsRecBytes, sizeof(double) * static_cast<size_t>(e->T), hipMemcpyHostToDevice,
-                       e->b->stream) != hipSuccess)
-      return efail(e, SFW_ERR_HIP, "ensemble_blend: cost vector upload failed");
-    e->cost_dev = e->d_cost.p;  // (the blend waits for the stream before it returns: the mirror is free again by then)
+  const char *const what = "ensemble_mppi_run";
+  if (int rc = ensemble_check_mode(e, mode, probs, what)) return rc;
+  if (!m || m->iterations < 1 || m->iterations > SFW_MPPI_MAX_ITER || m->reserved != 0)
+    return efail(e, SFW_ERR_INVALID_ARG, std::string(what) + ": m is NULL, iterations outside 1..SFW_MPPI_MAX_ITER, or reserved != 0");
+  if (!std::isfinite(m->lambda) || !(m->lambda > 0.0) || !std::isfinite(m->gamma))
+    return efail(e, SFW_ERR_INVALID_ARG, std::string(what) + ": lambda is not finite or not > 0, or gamma is not finite");
+  if (!stat_out || !plans_out) return efail(e, SFW_ERR_INVALID_ARG, std::string(what) + ": stat_out or plans_out is NULL");
+  const char *why = perturb_refusal(rs, p, n, K, knot_step, args, 0);
+  if (!why) why = list_stage_refusal(rs, nullptr, nullptr, nullptr, n, static_cast<size_t>(K), args, true);
+  if (why) return efail(e, SFW_ERR_INVALID_ARG, std::string(what) + ": " + why);
+  if (int rc = ensemble_check_members(e, what)) return rc;
+  e->scored = false;
+  if (hipSetDevice(e->device) != hipSuccess) return efail(e, SFW_ERR_HIP, std::string(what) + ": hipSetDevice failed");
+  const auto t0 = std::chrono::steady_clock::now();
+  int rc = SFW_OK;
+  // iteration 0's stage: sfw_ensemble_score_perturbed's
+  for (size_t k = 0; k < e->b->h.size() && rc == SFW_OK; ++k)
+    if ((rc = sfw_sequences_perturb_stage(e->b->h[k], rs, p, n, K, knot_step, args, 0)) != SFW_OK)
+      (void)emember_fail(e, static_cast<int32_t>(k), rc, "ensemble_mppi_run: stage");
+  e->us[0] = us_since(t0);
+  if (rc == SFW_OK) rc = ensemble_mppi_chain(e, p, K, mode, probs, m, stat_out, plans_out, costs_out, rejected_out, best_out);
+  if (rc != SFW_OK) {  // nothing scored, and no member left staged or launched
+    if (e->pin_mppi.done) (void)e->pin_mppi.mark(e->b->stream);  // (kernels of the chain may still be writing there)
+    for (sfw_handle h : e->b->h) drop_stage(h);
   }
-  const blend_area area{e->blend_mins, e->blend_partials, e->blend_bias, e->blend_weights, e->pin_blend};
-  if (int rc = blend_run(h0, area, e->cost_dev, e->T, h0->st.list ? h0->st.nk : 1, h0->st.d_linvels, h0->st.d_vy, h0->st.d_angvels,
-                         h0->st.nw, h0->st.list, lambda, L, bias, stat_out, u_out, weights_out))
-    return emember_fail(e, 0, rc, "ensemble_blend");
-  return SFW_OK;
+  return rc;
 }
 
 int sfw_ensemble_aggregate(sfw_ensemble e, int32_t mode, const double *probs, double *costs_out, int32_t *rejected_out,

@@ -387,6 +387,13 @@ static_assert(sizeof(sfw_perturb_head) == offsetof(sfw_perturb_dev, nominal), "s
 // The same draw around `plan` (K x 3 doubles in device memory; a.nominal is not read): sfw_perturb_plan_kernel
 hipError_t sfw_launch_perturb_plan(const sfw_perturb_dev &a, const double *plan, int64_t n, int K, int64_t index_base, double *vx,
                                    double *vy, double *vtheta, double *z_out, hipStream_t stream);
+// ... into the knot rows of M handles that stage the same sfw_perturb (sfw_ensemble_mppi_run), each value drawn once:
+// sfw_perturb_members_kernel.  dst: M records in DEVICE memory; vy / z are null in every record or in none.
+struct sfw_perturb_dst {
+  double *vx, *vy, *vtheta, *z;
+};
+hipError_t sfw_launch_perturb_members(const sfw_perturb_dev &a, const double *plan, int64_t n, int K, int64_t index_base,
+                                      const sfw_perturb_dst *dst, int M, hipStream_t stream);
 // sfw_sequences_control_cost: bias[t] = gamma * c_t (+ bias_add[t], nullable) of the perturbed stage `a` describes, n doubles
 // on the device.  plan (nullable): the nominal rows in device memory instead of a.nominal; z_kept (nullable): the stage's kept
 // normals, else they are drawn again.

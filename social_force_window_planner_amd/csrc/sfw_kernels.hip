@@ -3082,6 +3082,11 @@ __device__ __forceinline__ uniform_doubles nominal_of_first_arg() {
   return (uniform_doubles)((const __attribute__((address_space(4))) char *)__builtin_amdgcn_kernarg_segment_ptr() +
                            offsetof(sfw_perturb_dev, nominal));
 }
+// A drawn value's knot: the affine map around the nominal value, then the clamp box.  ONE text for every perturb kernel.
+__device__ __forceinline__ double perturb_knot(double nominal, double sigma, double z, double lo, double hi) {
+  const double step = sigma * z;
+  return fmin(fmax(nominal + step, lo), hi);
+}
 // One thread's work of a perturb kernel: sample t, knot blockIdx.y, the three channels.  ARGS: sfw_perturb_dev or its head.
 template <typename ARGS>
 __device__ __forceinline__ void perturb_sample(const ARGS &a, const uniform_doubles nominal, int64_t n, int64_t index_base, double *vx,
@@ -3097,10 +3102,7 @@ __device__ __forceinline__ void perturb_sample(const ARGS &a, const uniform_doub
     const double z = perturb_normal(a.key0, a.key1, a.keep_nominal, g, k, c);
     const int64_t at = static_cast<int64_t>(k) * n + t;
     if (z_out) z_out[(static_cast<int64_t>(k) * 3 + c) * n + t] = z;
-    if (row[c]) {
-      const double step = a.sigma[c] * z;
-      row[c][at] = fmin(fmax(nominal[k * 3 + c] + step, a.lo[c]), a.hi[c]);
-    }
+    if (row[c]) row[c][at] = perturb_knot(nominal[k * 3 + c], a.sigma[c], z, a.lo[c], a.hi[c]);
   }
 }
 // vy == null: a stage without a vy row (SFW_PERTURB_NO_VY); z_out == null: the normals are not kept
@@ -3114,6 +3116,33 @@ __global__ void __launch_bounds__(PERTURB_C)
 sfw_perturb_plan_kernel(sfw_perturb_head a, const double *plan, int64_t n, int64_t index_base, double *vx, double *vy, double *vtheta,
                         double *z_out) {
   perturb_sample(a, uniform_of(plan), n, index_base, vx, vy, vtheta, z_out);
+}
+// sfw_ensemble_mppi_run, iterations > 0: the M members of an ensemble hold the SAME rollouts, so each value is drawn once and
+// stored into every member's knot rows (and kept normals).  dst: M records in device memory, read wave-uniformly (s_load) as
+// sfw_ens_list_first reads its member table; vy / z are null in every member or in none (one sfw_perturb for all).  Same
+// thread layout and the same coalesced stores as sfw_perturb_plan_kernel, M times.  No LDS, no atomics.
+__global__ void __launch_bounds__(PERTURB_C)
+sfw_perturb_members_kernel(sfw_perturb_head a, const double *plan, int64_t n, int64_t index_base, const sfw_perturb_dst *dst, int M) {
+  typedef const __attribute__((address_space(4))) sfw_perturb_dst *dst_ptr;
+  const dst_ptr dp = (dst_ptr)(const __attribute__((address_space(1))) sfw_perturb_dst *)dst;
+  const uniform_doubles nominal = uniform_of(plan);
+  const int64_t t = static_cast<int64_t>(blockIdx.x) * PERTURB_C + threadIdx.x;
+  if (t >= n) return;
+  const int k = blockIdx.y;
+  const uint64_t g = static_cast<uint64_t>(index_base + t);
+  const bool has_vy = dp[0].vy != nullptr, keep_z = dp[0].z != nullptr;
+  const int64_t at = static_cast<int64_t>(k) * n + t;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    if (c == 1 && !has_vy && !keep_z) continue;
+    const double z = perturb_normal(a.key0, a.key1, a.keep_nominal, g, k, c);
+    const double v = perturb_knot(nominal[k * 3 + c], a.sigma[c], z, a.lo[c], a.hi[c]);
+    for (int m = 0; m < M; ++m) {
+      double *const row = c == 0 ? dp[m].vx : c == 1 ? dp[m].vy : dp[m].vtheta;
+      if (keep_z) dp[m].z[(static_cast<int64_t>(k) * 3 + c) * n + t] = z;
+      if (c != 1 || has_vy) row[at] = v;
+    }
+  }
 }
 
 // The control-cost term of a perturbed stage (sfw_sequences_control_cost, sfw_hip.h "Control cost"): c_t = sum over k, then
@@ -3893,6 +3922,20 @@ hipError_t sfw_launch_perturb_plan(const sfw_perturb_dev &a, const double *plan,
   }
   hipLaunchKernelGGL(sfw_perturb_plan_kernel, dim3(static_cast<unsigned>(blocks), static_cast<unsigned>(K)), dim3(PERTURB_C), 0, stream,
                      head, plan, n, index_base, vx, vy, vtheta, z_out);
+  return hipGetLastError();
+}
+hipError_t sfw_launch_perturb_members(const sfw_perturb_dev &a, const double *plan, int64_t n, int K, int64_t index_base,
+                                      const sfw_perturb_dst *dst, int M, hipStream_t stream) {
+  const int64_t blocks = (n + PERTURB_C - 1) / PERTURB_C;
+  if (n < 1 || K < 1 || K > SFW_SEQ_MAX_KNOTS || index_base < 0 || blocks > INT_MAX || !plan || !dst || M < 1) return hipErrorInvalidValue;
+  sfw_perturb_head head{a.key0, a.key1, a.keep_nominal, 0, {}, {}, {}};
+  for (int c = 0; c < 3; ++c) {
+    head.sigma[c] = a.sigma[c];
+    head.lo[c] = a.lo[c];
+    head.hi[c] = a.hi[c];
+  }
+  hipLaunchKernelGGL(sfw_perturb_members_kernel, dim3(static_cast<unsigned>(blocks), static_cast<unsigned>(K)), dim3(PERTURB_C), 0, stream,
+                     head, plan, n, index_base, dst, M);
   return hipGetLastError();
 }
 hipError_t sfw_launch_control_cost(const sfw_perturb_dev &a, const double *plan, int K, int64_t n, int64_t index_base,

@@ -186,6 +186,10 @@ def lib():
         L.sfw_grid_blend_control.argtypes = [vp, vp, C.c_int32, C.c_double, vp, C.POINTER(SfwBlendStat), vp, vp]
         L.sfw_mppi_run.argtypes = [vp, C.POINTER(SfwRobotState), C.POINTER(SfwPerturb), C.c_int32, C.c_int32, vp,
                                    C.POINTER(SfwGoalArgs), C.POINTER(SfwMppi), C.POINTER(SfwBlendStat), vp, C.POINTER(SfwBest)]
+        L.sfw_ensemble_blend_control.argtypes = [vp, vp, C.c_int32, C.c_double, vp, C.POINTER(SfwBlendStat), vp, vp]
+        L.sfw_ensemble_mppi_run.argtypes = [vp, C.POINTER(SfwRobotState), C.POINTER(SfwPerturb), C.c_int32, C.c_int32, vp,
+                                            C.POINTER(SfwGoalArgs), C.c_int32, vp, C.POINTER(SfwMppi), C.POINTER(SfwBlendStat), vp,
+                                            vp, vp, C.POINTER(SfwBest)]
         _lib = L
     return _lib
 
@@ -1081,9 +1085,11 @@ class EnsembleScorer:
                     "sfw_ensemble_aggregate")
         return costs, rejected, best.as_dict()
 
-    def blend(self, lambdas, bias=None, want_weights=False):
+    def blend(self, lambdas, bias=None, want_weights=False, gamma=None):
         """sfw_ensemble_blend: HipScorer.blend over the ENSEMBLE cost vector of the last aggregation and member 0's knots —
-        (stats, u[L, K, 3], weights[L, n] or None)."""
+        (stats, u[L, K, 3], weights[L, n] or None).
+        gamma (after score_perturbed or mppi_run only): sfw_ensemble_blend_control — gamma times the control cost of every
+        sample's perturbation joins the bias on the device."""
         lam = np.ascontiguousarray(np.asarray(lambdas, dtype=np.float64).reshape(-1))
         L = len(lam)
         if L < 1 or L > SFW_BLEND_MAX_L:
@@ -1100,9 +1106,37 @@ class EnsembleScorer:
         stats = (SfwBlendStat * L)()
         u = np.zeros((L, K, 3), dtype=np.float64)
         w = np.zeros((L, T), dtype=np.float64) if want_weights else None
-        self._check(lib().sfw_ensemble_blend(self._e, lam.ctypes.data, L, b.ctypes.data if b is not None and T else None, stats,
-                                             u.ctypes.data, w.ctypes.data if w is not None and T else None), "sfw_ensemble_blend")
+        bp, wp = b.ctypes.data if b is not None and T else None, w.ctypes.data if w is not None and T else None
+        if gamma is None:
+            self._check(lib().sfw_ensemble_blend(self._e, lam.ctypes.data, L, bp, stats, u.ctypes.data, wp), "sfw_ensemble_blend")
+        else:
+            self._check(lib().sfw_ensemble_blend_control(self._e, lam.ctypes.data, L, float(gamma), bp, stats, u.ctypes.data, wp),
+                        "sfw_ensemble_blend_control")
         return [stats[l].as_dict() for l in range(L)], u, w
+
+    def mppi_run(self, robot_state, n, seed, nominal, sigma, lo, hi, knot_steps, goal_args, iterations, lam, gamma, flags=0,
+                 mode="mean", probs=None, want_costs=False):
+        """sfw_ensemble_mppi_run: HipScorer.mppi_run under every hypothesis — `iterations` times perturb (seed + i) -> score all
+        members -> aggregate -> control cost -> blend at temperature lam -> new nominal, chained on the device behind one wait.
+        Returns (stats: one dict per iteration; plans[I, K, 3]; best of the last iteration), and with want_costs also the last
+        iteration's costs[n] and rejected[n].  The ensemble is left as after the last iteration's score_perturbed."""
+        pt, nom, ks = HipScorer._perturb(seed, nominal, sigma, lo, hi, knot_steps, flags)
+        rs, ga = SfwRobotState(*robot_state), SfwGoalArgs(*goal_args)
+        p = self._checked_probs(probs, "mppi_run")
+        K, I = nom.shape[0], int(iterations)
+        m = SfwMppi(I, 0, float(lam), float(gamma))
+        room = min(max(I, 1), SFW_MPPI_MAX_ITER)  # (a refused iteration count writes nothing)
+        stats = (SfwBlendStat * room)()
+        plans = np.zeros((room, K, 3), dtype=np.float64)
+        costs, rejected, best = self._outputs((max(n, 0), 1))
+        out = want_costs and n > 0
+        self._check(lib().sfw_ensemble_mppi_run(self._e, C.byref(rs), C.byref(pt), n, K, ks.ctypes.data if len(ks) else None,
+                                                C.byref(ga), self._mode(mode), p.ctypes.data if p is not None else None, C.byref(m),
+                                                stats, plans.ctypes.data, costs.ctypes.data if out else None,
+                                                rejected.ctypes.data if out else None, C.byref(best)), "sfw_ensemble_mppi_run")
+        self._mark_scored((n, 1), knots=K)
+        res = ([stats[i].as_dict() for i in range(I)], plans, best.as_dict())
+        return res + (costs, rejected) if want_costs else res
 
     def knots(self, first, count):
         """The knots of samples [first, first + count) of the last sequence score as (K, 3, count): member 0's (every member
