@@ -2,7 +2,10 @@
 // gfx950 vector ALU: no special-case branches, hardware rcp/rsq seeds refined by
 // one Newton step, short Horner polynomials.  Accuracy targets: double ~5e-14
 // relative (asin 7 / exp 9; the parity tests hold the whole path to 1e-9), float ~1e-7.
-// Coefficients: tools/gen_poly.py.
+// Coefficients: kAtanPf is tools/gen_poly.py's (`legacy`); the generator of the kAsinQ / kExp2P sets is not in the tree.
+// `tools/gen_poly.py check` reproduces the error figure beside every table from the literals (mpmath), and
+// tests/test_device_math_tables.py holds the tables to them; tests/test_device_math_gpu.py holds the functions below, on the
+// device, to the figures in these comments (measured values: profiles/r18_device_math.txt).
 #ifndef SFW_MATH_H_
 #define SFW_MATH_H_
 
@@ -10,8 +13,8 @@
 
 namespace sfwm {
 
-// Degrees of the two f64 polynomials of the pair term (tuning knobs, csrc/Makefile EXTRA; tools/gen_poly.py prints the
-// coefficient sets and their errors).  Every VALU instruction of the pair loop costs one 4-cycle issue slot, so a degree
+// Degrees of the two f64 polynomials of the pair term (tuning knobs, csrc/Makefile EXTRA; `tools/gen_poly.py check` prints
+// the errors of the coefficient sets).  Every VALU instruction of the pair loop costs one 4-cycle issue slot, so a degree
 // is an issue slot per evaluation.  asin 7 / exp 9 (round 5) put the pair term at ~5e-14 relative; with exp 8 (rounds 3-4,
 // ~1e-12, 1.6 % less of K2) four random scenes in 6000 — chaotic 0.25 s-Euler crowds — deviated by more than 50 x the oracle's
 // own conditioning, with degree 9 none (profiles/r04_sweep_degrees.txt, r05_parity_sweep.txt).  The parity tests hold the whole
@@ -31,7 +34,7 @@ __device__ constexpr double kAsinQ[9] = {
 __device__ constexpr double kAsinQ[8] = {
     9.99999999999873768e-01, 1.66666666776879580e-01, 7.49999842884431500e-02, 4.46437065808175729e-02,
     3.03595339518422935e-02, 2.26899347940125971e-02, 1.49057938849694732e-02, 2.32986453124961607e-02};
-#elif SFW_ASIN_DEG == 6  // max abs err 1.6e-12
+#elif SFW_ASIN_DEG == 6  // max abs err 1.65e-12
 __device__ constexpr double kAsinQ[7] = {
     1.00000000000385847e+00, 1.66666664088492733e-01, 7.50002798152002437e-02, 4.46315408500555302e-02,
     3.05977872550623718e-02, 2.02964541344591819e-02, 2.68224190000059641e-02};
@@ -58,7 +61,8 @@ __device__ constexpr double kExp2P[8] = {
 #else
 #error "SFW_EXP_DEG must be 7, 8 or 9"
 #endif
-// float 2*atan(t) = t * P(t*t); max abs err 1.4e-8 + float rounding
+// float 2*atan(t) = t * P(t*t), t in [0, tan(pi/8)]; max abs err 1.4e-8 as written, 2.9e-8 as float, + the rounding of the
+// evaluation (the leading literal lies closer to 2.0f than to the float below it: the compiled polynomial is 3.7e-8 t higher)
 __device__ constexpr float kAtanPf[5] = {1.999999963e+00f, -6.666557114e-01f, 3.994815087e-01f, -2.769682950e-01f, 1.595208338e-01f};
 
 // ---- double ---------------------------------------------------------------
@@ -145,8 +149,10 @@ __device__ __forceinline__ void fp_mode_for_omod() {
   asm volatile("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 6, 2), 0\n\ts_setreg_imm32_b32 hwreg(HW_REG_MODE, 9, 1), 0" ::: "memory");
 #endif
 }
-// v_rsq_f64 / v_rcp_f64 deliver ~23 good bits; one Newton step gives ~46.
-// x must be > 0 and finite (callers clamp with fmax).
+// v_rsq_f64 / v_rcp_f64 deliver ~23 good bits; one Newton step gives ~46.  Measured on gfx950 against mpmath over
+// x = 10^U(-300, 300) (tests/test_device_math_gpu.py, profiles/r18_device_math.txt): worst relative error after the step
+// 3.9e-15 for rs and sq, 2.1e-15 for rcp_nr — seeds good to ~2^-24.2, inside what 23 bits imply (2.2e-14 / 1.5e-14).
+// x must be > 0 and at most 2^1022 (callers clamp with fmax): above that y * y is denormal, is flushed, and the step is void.
 __device__ __forceinline__ void rsqrt_sqrt(double x, double &rs, double &sq) {
   const double y = __builtin_amdgcn_rsq(x);
 #if SFW_OMOD
@@ -196,7 +202,8 @@ __device__ __forceinline__ double exp2_scaled(const poly_consts &pc, double u, d
 // (the register form sits exactly at its 80-VGPR budget) nor the constant bus (a literal next to the vcc mask does not
 // assemble on gfx9); the asm keeps the compiler from materialising it in a register across the rollout all the same, and
 // the compare writes vcc for the select right behind it (through an SGPR pair and s_mov the two sat on the dependency chain
-// of a lone wave: a control cycle's pair loop ran 8-12 % longer).
+// of a lone wave: a control cycle's pair loop ran 8-12 % longer).  A denormal cw (|cw| < 2.2e-308) closes the gate like a
+// zero: the compare runs with FP64 denormals flushed (measured, tests/test_device_math_gpu.py; NaN and every normal cw open it).
 __device__ __forceinline__ int gate_exponent(int k, double cw) {
   int r;
   asm("v_cmp_neq_f64 vcc, 0, %2\n\tv_cndmask_b32_e32 %0, -4.0, %1, vcc" : "=v"(r) : "v"(k), "v"(cw) : "vcc");
@@ -226,6 +233,9 @@ __device__ __forceinline__ void exp2_fast2_gated(const poly_consts &pc, double x
 //     <= 0, the octant fold maps it to -e exactly when y > |x| (sign of d); f = (that) - pi/4 is <= 0 again, the
 //     half-plane fold maps it to -f exactly when x < 0 (sign of nx); theta = f + pi/2.  (Rounding can leave e or f a few
 //     1e-17 on the wrong side of 0: the transfer then moves the angle by that much.)
+// The polynomial's error is largest at the ends of its interval, which are the fold angles: y = 0, x > 0 gives +5.37e-14 at
+// degree 7 (+2.2e-15 at degree 8), not 0, and every fold is approached from below by that much less and from above by that
+// much more — the result stays in [0, pi] and never decreases across a fold (tests/test_device_math_gpu.py).
 // 19 issue slots at degree 7, against 29 for the half-angle form t = min / (max + hyp) with its v_rcp_f64 (4 slots) +
 // Newton step and two compare/select folds.
 __device__ __forceinline__ double angle_abs(const poly_consts &pc, double y, double nx, double rh, double /*hyp*/) {
