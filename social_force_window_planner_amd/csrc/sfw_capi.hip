@@ -119,6 +119,35 @@ struct agent_set {
   std::vector<std::pair<int32_t, int32_t>> rest_pairs;
 };
 
+// The buffers of a softmin blend, one set per owner (a handle's sfw_grid_blend; an sfw_ensemble's sfw_ensemble_blend, which
+// runs on member 0's stream but must not touch what belongs to that member's own calls): first-pass records, per-block partial
+// sums, the bias and weight vectors on the device; pin receives the minimum record | eta[L] | sum_w2[L] | u[L][K][3] from the
+// kernels
+struct blend_buffers {
+  dev_buf<sfw_blend_min> mins;
+  dev_buf<double> partials, bias, weights;
+  pinned_buf pin;
+  void release() {
+    mins.release();
+    partials.release();
+    bias.release();
+    weights.release();
+    pin.release();
+  }
+};
+// ... and of the control cost and the MPPI chain: the bias vector gamma * c_t (+ bias_t) on the device; the nominal plan on the
+// device (SFW_SEQ_MAX_KNOTS x 3 doubles, moved on by every iteration's update kernel); pin_mppi = one blend slot per iteration |
+// the caller's nominal (the source of the copy that starts the chain) [| an ensemble's member table: ensemble_mppi_chain]
+struct mppi_buffers {
+  dev_buf<double> ctrl_bias, mppi_plan;
+  pinned_buf pin_mppi;
+  void release() {
+    ctrl_bias.release();
+    mppi_plan.release();
+    pin_mppi.release();
+  }
+};
+
 }  // namespace
 
 // The handle's state, grouped by who owns it:
@@ -306,20 +335,12 @@ struct sfw_planner_s {
   dev_buf<sfw_sel> rescore_partials;
   dev_buf<double> rescore_costs;
   pinned_buf pin_rescore;          // K records (written by the kernels) | K weight vectors (copied from)
-  // sfw_grid_blend: first-pass records, per-block partial sums, the bias and weight vectors on the device; pin_blend receives
-  // the minimum record | eta[L] | sum_w2[L] | u[L][K][3] from the kernels
-  dev_buf<sfw_blend_min> blend_mins;
-  dev_buf<double> blend_partials, blend_bias, blend_weights;
-  pinned_buf pin_blend;
+  blend_buffers blend;  // sfw_grid_blend / sfw_grid_blend_control
+  mppi_buffers mppi;    // sfw_sequences_control_cost / sfw_grid_blend_control (ctrl_bias), sfw_mppi_run
   // sfw_sequences_perturb_stage: the normals of a stage with SFW_PERTURB_KEEP_NORMALS; pin_knots receives the winner's first knot
   // (sel_to_best) and the ranges sfw_sequences_knots / _normals read back
   dev_buf<double> normals;
   pinned_buf pin_knots;
-  // sfw_sequences_control_cost / sfw_grid_blend_control: the bias vector gamma * c_t on the device.  sfw_mppi_run: the nominal
-  // plan on the device (SFW_SEQ_MAX_KNOTS x 3 doubles, moved on by every iteration's update kernel) and pin_mppi = one blend
-  // slot per iteration | the caller's nominal (the source of the copy that starts the chain)
-  dev_buf<double> ctrl_bias, mppi_plan;
-  pinned_buf pin_mppi;
   // sfw_score_one_crowd / sfw_grid_crowd: cost | n_points | coll_step | state [S][A][4] | work [S][A] | has_goal [S][A],
   // contiguous -> one D2H into pin_crowd; the pair table of the kernel with run-time plane capacity (sfw_crowd_kernel)
   dev_buf<char> crowd_out;
@@ -377,7 +398,7 @@ bool all_finite(const double *v, size_t n) {
 // and waking up costs 10-20 us — of a 100 us control cycle or a 600 us grid; the blocking call polls the stream instead
 // (one core busy for the duration of the launch, as a caller asking hipDeviceScheduleSpin would have it) for up to spin_us,
 // then blocks.
-hipError_t wait_stream(sfw_handle h) {
+hipError_t poll_stream(sfw_handle h) {
   if (h->cfg.spin_us > 0) {
     const auto t0 = std::chrono::steady_clock::now();
     bool polled = false;
@@ -401,6 +422,11 @@ hipError_t wait_stream(sfw_handle h) {
 }
 // ... after which no upload enqueued on it is still reading its pinned staging area
 void stream_is_idle(sfw_handle h) { h->pin_map.pending = h->pin_arena.pending = h->pin_cls.pending = false; }
+hipError_t wait_stream(sfw_handle h) {
+  const hipError_t e = poll_stream(h);
+  if (e == hipSuccess) stream_is_idle(h);
+  return e;
+}
 
 // the register-form K2 addresses a unit inside a step row of the position / velocity table by a 32-bit byte offset: a row of
 // `chunk` positions and at most chunk + 2 velocities (a one-column grid) must stay below 4 GB
@@ -1094,6 +1120,20 @@ int64_t plan_tables_host(sfw_handle h, int *err) {
   h->st.plan_epoch = h->live.params_epoch;
   return chunk;
 }
+// The arena a stage left in pinned memory only (st.arena_pending) is fetched by the blocks of the kernel that carries L ...
+void arena_by_kernel(sfw_handle h, sfw_launch &L) {
+  if (!h->st.arena_pending) return;
+  L.arena_host = h->pin_arena.p + h->st.arena_from;
+  L.arena_dev = h->arena.p + h->st.arena_from;
+  L.arena_bytes = static_cast<uint32_t>(h->st.arena_bytes);
+}
+// ... and once that kernel is enqueued, the pinned copy is guarded like one a copy reads
+hipError_t arena_fetched(sfw_handle h) {
+  if (!h->st.arena_pending) return hipSuccess;
+  h->st.arena_pending = false;
+  return h->pin_arena.mark(h->stream);
+}
+
 // Device half: the K1->K2 tables and the class-record buffers; with may_start_poses the pose rollout of a single-chunk grid
 // is enqueued here, by the STAGE (the robot's poses depend on the sample vectors alone).
 int plan_tables_device(sfw_handle h, int64_t chunk, bool may_start_poses) {
@@ -1126,10 +1166,8 @@ int plan_tables_device(sfw_handle h, int64_t chunk, bool may_start_poses) {
         L.terms = h->terms.p;
         L.terms_T = T;
       }
-      if (h->st.arena_pending) {  // no copy was enqueued: this kernel fetches the arena, and reads its sample vectors at their host addresses
-        L.arena_host = h->pin_arena.p + h->st.arena_from;
-        L.arena_dev = h->arena.p + h->st.arena_from;
-        L.arena_bytes = static_cast<uint32_t>(h->st.arena_bytes);
+      arena_by_kernel(h, L);
+      if (h->st.arena_pending) {  // no copy was enqueued: this kernel reads its sample vectors at their host addresses
         L.linvels = reinterpret_cast<const double *>(h->pin_arena.p + (reinterpret_cast<const char *>(h->st.d_linvels) - h->arena.p));
         L.angvels = reinterpret_cast<const double *>(h->pin_arena.p + (reinterpret_cast<const char *>(h->st.d_angvels) - h->arena.p));
         if (h->st.d_vy) L.vy_samps = reinterpret_cast<const double *>(h->pin_arena.p + (reinterpret_cast<const char *>(h->st.d_vy) - h->arena.p));
@@ -1137,10 +1175,7 @@ int plan_tables_device(sfw_handle h, int64_t chunk, bool may_start_poses) {
           L.knot_step = reinterpret_cast<const int32_t *>(h->pin_arena.p + (reinterpret_cast<const char *>(h->st.d_knot_step) - h->arena.p));
       }
       SFW_HIP(h, sfw_launch_rollout_poses(L, h->stream));
-      if (h->st.arena_pending) {
-        h->st.arena_pending = false;
-        SFW_HIP(h, h->pin_arena.mark(h->stream));
-      }
+      SFW_HIP(h, arena_fetched(h));
       h->st.early_poses = true;
     }
   }
@@ -1234,43 +1269,72 @@ struct perturb_source {
   bool vy, keep_normals, zero_admitted;
 };
 
+// What a stage is asked to put on the device: one of the four kinds of stage_common, made by the functions below
+struct stage_request {
+  enum kind_t { GRID, LIST, SEQUENCES, PERTURBED } kind;
+  const double *lin, *vy_list, *ang;  // null when the device draws them (PERTURBED); vy_list nullable: all 0.0
+  int32_t nv, nw, nk;                 // nk rows of nv values (lin, vy_list) and of nw (a grid) or nv (a list) values (ang), knot-major
+  const int32_t *knot_step;           // the nk steps at which a knot takes over (checked by the caller: sequences_refusal)
+  const perturb_source *dev;
+  double vy_samp;
+  int skip_zero;
+  int64_t index_base;
+  const char *name() const {  // in messages
+    return kind == PERTURBED ? "sequences_perturb_stage" : kind == SEQUENCES ? "sequences_stage" : kind == LIST ? "samples_stage" : "grid_stage";
+  }
+  bool is_list() const { return kind != GRID; }
+  bool drawn() const { return kind == PERTURBED; }  // the device draws the sample vectors: lin == ang == null
+  size_t kn() const { return static_cast<size_t>(nk); }
+  size_t n_ang() const { return static_cast<size_t>(is_list() ? nv : nw); }
+};
+// sfw_grid_stage: nv linear x nw angular targets, the (0, 0) sample skipped
+stage_request grid_request(const double *lin, int32_t nv, const double *ang, int32_t nw, int64_t index_base) {
+  return {stage_request::GRID, lin, nullptr, ang, nv, nw, 1, nullptr, nullptr, 0.0, 1, index_base};
+}
+// sfw_score_one / sfw_score_one_crowd: a grid of 1 x 1 with its vy, never skipped
+stage_request one_request(const double *vx, double vy, const double *vtheta) {
+  return {stage_request::GRID, vx, nullptr, vtheta, 1, 1, 1, nullptr, nullptr, vy, 0, 0};
+}
+// sfw_samples_stage: a grid of n rows by one column to everything that counts samples; never the (0, 0) skip
+stage_request list_request(const double *vx, const double *vy, const double *vtheta, int32_t n, int64_t index_base) {
+  return {stage_request::LIST, vx, vy, vtheta, n, 1, 1, nullptr, nullptr, 0.0, 0, index_base};
+}
+// sfw_sequences_stage: that list with K rows of n values behind its vectors
+stage_request sequences_request(const double *vx, const double *vy, const double *vtheta, int32_t n, int32_t K,
+                                const int32_t *knot_step, int64_t index_base) {
+  return {stage_request::SEQUENCES, vx, vy, vtheta, n, 1, K, knot_step, nullptr, 0.0, 0, index_base};
+}
+// sfw_sequences_perturb_stage: sequences whose rows the device draws from dev (null: a request to read the argument rules by)
+stage_request perturbed_request(const perturb_source *dev, int32_t n, int32_t K, const int32_t *knot_step, int64_t index_base) {
+  return {stage_request::PERTURBED, nullptr, nullptr, nullptr, n, 1, K, knot_step, dev, 0.0, 0, index_base};
+}
+
 // stage_common's argument rules as texts of their own (null: accepted), in two parts because the costmap's state check stands
-// between them: an ensemble's score calls read the same ones before ANY member is staged.  drawn: the device draws the sample
-// vectors (lin == ang == null); n_ang: values per row of ang; kn: rows of the sample vectors.
-const char *stage_null_refusal(const sfw_robot_state *rs, const double *lin, int32_t nv, const double *ang, int32_t nw,
-                               const sfw_goal_args *args, bool drawn) {
-  if (!rs || (!drawn && (!lin || !ang)) || !args || nv <= 0 || nw <= 0) return "null pointer or non-positive sample count";
+// between them: an ensemble's score calls read the same ones before ANY member is staged.
+const char *stage_null_refusal(const sfw_robot_state *rs, const sfw_goal_args *args, const stage_request &q) {
+  if (!rs || (!q.drawn() && (!q.lin || !q.ang)) || !args || q.nv <= 0 || q.nw <= 0) return "null pointer or non-positive sample count";
   return nullptr;
 }
 // A NaN would come back as a NaN cost (the header promises sentinels, never NaN) and, in a sample vector, break the
 // ordering the shared-prefix planner sorts by: O(nv + nw) checks
-const char *stage_finite_refusal(const sfw_robot_state *rs, const double *lin, int32_t nv, const double *ang, size_t n_ang,
-                                 const sfw_goal_args *args, double vy_samp, const double *vy_list, size_t kn, bool drawn) {
-  if (!all_finite(&rs->x, 6) || !all_finite(&args->acc_x, 5) || !std::isfinite(vy_samp))
+const char *stage_finite_refusal(const sfw_robot_state *rs, const sfw_goal_args *args, const stage_request &q) {
+  if (!all_finite(&rs->x, 6) || !all_finite(&args->acc_x, 5) || !std::isfinite(q.vy_samp))
     return "non-finite robot state, goal argument or sample velocity";
-  if (!drawn && (!all_finite(lin, kn * static_cast<size_t>(nv)) || !all_finite(ang, kn * n_ang) ||
-                 (vy_list && !all_finite(vy_list, kn * static_cast<size_t>(nv)))))
+  const size_t rows = q.kn() * static_cast<size_t>(q.nv);
+  if (!q.drawn() && (!all_finite(q.lin, rows) || !all_finite(q.ang, q.kn() * q.n_ang()) || (q.vy_list && !all_finite(q.vy_list, rows))))
     return "non-finite sample velocity";
   return nullptr;
 }
 
-// list: sfw_samples_stage — lin / ang are vx / vtheta of nv samples (nw == 1), vy_list their vy (nullable: all 0.0)
-// knot_step (list only, nullable): sfw_sequences_stage — lin / ang / vy_list hold nk rows of nv values, knot-major, and
-// knot_step the nk steps at which a knot takes over (checked by the caller: knot_step[0] == 0, strictly ascending)
-int stage_common(sfw_handle h, const sfw_robot_state *rs, const double *lin, int32_t nv, const double *ang,
-                 int32_t nw, const sfw_goal_args *args, double vy_samp, int skip_zero, int64_t index_base,
-                 bool grid = false, bool list = false, const double *vy_list = nullptr, int32_t nk = 1,
-                 const int32_t *knot_step = nullptr, const perturb_source *dev = nullptr) {
+int stage_common(sfw_handle h, const sfw_robot_state *rs, const sfw_goal_args *args, const stage_request &q) {
   if (!h) return SFW_ERR_INVALID_ARG;
-  const std::string what = dev ? "sequences_perturb_stage" : knot_step ? "sequences_stage" : list ? "samples_stage" : "grid_stage";
-  const size_t kn = knot_step ? static_cast<size_t>(nk) : size_t(1);  // rows of the sample vectors
+  const std::string what = q.name();
+  const auto [kind, lin, vy_list, ang, nv, nw, nk, knot_step, dev, vy_samp, skip_zero, index_base] = q;
+  const size_t kn = q.kn(), n_ang = q.n_ang();
   const bool has_vy = dev ? dev->vy : vy_list != nullptr;
-  if (const char *why = stage_null_refusal(rs, lin, nv, ang, nw, args, dev != nullptr))
-    return fail(h, SFW_ERR_INVALID_ARG, what + ": " + why);
-  const size_t n_ang = list ? static_cast<size_t>(nv) : static_cast<size_t>(nw);
+  if (const char *why = stage_null_refusal(rs, args, q)) return fail(h, SFW_ERR_INVALID_ARG, what + ": " + why);
   if (!h->world.have_costmap) return fail(h, SFW_ERR_STATE, what + ": no costmap set (sfw_set_costmap)");
-  if (const char *why = stage_finite_refusal(rs, lin, nv, ang, n_ang, args, vy_samp, vy_list, kn, dev != nullptr))
-    return fail(h, SFW_ERR_INVALID_ARG, what + ": " + why);
+  if (const char *why = stage_finite_refusal(rs, args, q)) return fail(h, SFW_ERR_INVALID_ARG, what + ": " + why);
   drop_stage(h);  // (valid again at the end of this function, and only there)
   host_phases ph("stage:");
   SFW_HIP(h, hipSetDevice(h->device));
@@ -1297,7 +1361,7 @@ int stage_common(sfw_handle h, const sfw_robot_state *rs, const double *lin, int
     h->st.lin.assign(lin, lin + kn * nv);
     h->st.ang.assign(ang, ang + kn * n_ang);
   }
-  h->st.list = list;
+  h->st.list = q.is_list();
   if (vy_list) h->st.vy.assign(vy_list, vy_list + kn * nv);
   else h->st.vy.clear();
   h->st.nk = static_cast<int>(kn);
@@ -1384,7 +1448,7 @@ int stage_common(sfw_handle h, const sfw_robot_state *rs, const double *lin, int
         // would read its sample vectors there.
         if (o_lin > from) SFW_HIP(h, hipMemcpyAsync(h->arena.p + from, pb + from, o_lin - from, hipMemcpyHostToDevice, h->stream));
         if (total > o_knot) SFW_HIP(h, hipMemcpyAsync(h->arena.p + o_knot, pb + o_knot, total - o_knot, hipMemcpyHostToDevice, h->stream));
-      } else if (grid && h->cfg.arena_direct_on && (small || early) && (total - from) % 16 == 0 && from % 16 == 0) {
+      } else if (h->cfg.arena_direct_on && (small || early) && (total - from) % 16 == 0 && from % 16 == 0) {
         h->st.arena_pending = true;
         h->st.arena_from = from;
         h->st.arena_bytes = total - from;
@@ -1443,7 +1507,7 @@ int stage_common(sfw_handle h, const sfw_robot_state *rs, const double *lin, int
     h->st.normals_kept = dev->keep_normals;
     ph.mark("perturb");
   }
-  if (int e = plan_tables_device(h, chunk, grid)) return e;
+  if (int e = plan_tables_device(h, chunk, true)) return e;
   if (T > 1024)
     if (int e = flush_arena(h)) return e;  // (no pose rollout was enqueued after all: the copy it would have stood in for)
   ph.mark("tables+K1a");
@@ -1603,19 +1667,12 @@ bool cycle_launch_of(sfw_handle h, const launch_prep &lp, sfw_launch &L) {
   L.terms = lp.terms;
   L.terms_T = lp.T;
   if (!sfw_cycle_applies(L)) return false;
-  if (h->st.arena_pending) {  // the kernel's blocks fetch the arena from pinned memory themselves: no copy at all this cycle
-    L.arena_host = h->pin_arena.p + h->st.arena_from;
-    L.arena_dev = h->arena.p + h->st.arena_from;
-    L.arena_bytes = static_cast<uint32_t>(h->st.arena_bytes);
-  }
+  arena_by_kernel(h, L);  // no copy at all this cycle
   return true;
 }
 // Step 2, once the kernel that carries L is enqueued: the handle's state after its launch
 int cycle_commit(sfw_handle h, bool timing) {
-  if (h->st.arena_pending) {
-    h->st.arena_pending = false;
-    SFW_HIP(h, h->pin_arena.mark(h->stream));
-  }
+  SFW_HIP(h, arena_fetched(h));
   if (timing) {
     SFW_HIP(h, hipEventRecord(h->ev[2], h->stream));
     SFW_HIP(h, hipEventRecord(h->ev[3], h->stream));
@@ -1755,7 +1812,6 @@ int knots_from_device(sfw_handle h, int64_t first, int64_t count, const double *
     rows[c] = reinterpret_cast<const double *>(dst);
   }
   SFW_HIP(h, wait_stream(h));
-  stream_is_idle(h);
   return SFW_OK;
 }
 
@@ -1811,10 +1867,7 @@ const char *perturb_refusal(const sfw_robot_state *rs, const sfw_perturb *p, int
                             const sfw_goal_args *args, int64_t index_base) {
   if (!rs || !p || !p->nominal || !knot_step || !args) return "rs, p, p->nominal, knot_step or args is NULL";
   if (n < 1) return "n < 1";
-  if (K < 1 || K > SFW_SEQ_MAX_KNOTS) return "K outside 1..SFW_SEQ_MAX_KNOTS";
-  if (knot_step[0] != 0) return "knot_step[0] must be 0";
-  for (int32_t k = 1; k < K; ++k)
-    if (knot_step[k] <= knot_step[k - 1]) return "knot_step must be strictly ascending";
+  if (const char *why = sequences_refusal(K, knot_step)) return why;
   if (index_base < 0) return "index_base < 0";
   constexpr int32_t known = SFW_PERTURB_KEEP_NOMINAL | SFW_PERTURB_NO_VY | SFW_PERTURB_KEEP_NORMALS;
   if ((p->flags & ~known) != 0 || p->reserved != 0) return "unknown flag bits, or reserved != 0";
@@ -1831,11 +1884,10 @@ const char *perturb_refusal(const sfw_robot_state *rs, const sfw_perturb *p, int
   }
   return nullptr;
 }
-// ... and stage_common's own (stage_null_refusal, stage_finite_refusal) for a list of n samples with kn knot rows
-const char *list_stage_refusal(const sfw_robot_state *rs, const double *lin, const double *vy_list, const double *ang, int32_t n,
-                               size_t kn, const sfw_goal_args *args, bool drawn) {
-  if (const char *why = stage_null_refusal(rs, lin, n, ang, 1, args, drawn)) return why;
-  return stage_finite_refusal(rs, lin, n, ang, static_cast<size_t>(n), args, 0.0, vy_list, kn, drawn);
+// ... and stage_common's own (stage_null_refusal, stage_finite_refusal) for the list a request describes
+const char *list_stage_refusal(const sfw_robot_state *rs, const sfw_goal_args *args, const stage_request &q) {
+  if (const char *why = stage_null_refusal(rs, args, q)) return why;
+  return stage_finite_refusal(rs, args, q);
 }
 const char *blend_refusal(const double *lambda, int32_t L, const sfw_blend_stat *stat_out, const double *u_out) {
   if (!lambda || !stat_out || !u_out) return "lambda, stat_out or u_out is NULL";
@@ -1845,24 +1897,20 @@ const char *blend_refusal(const double *lambda, int32_t L, const sfw_blend_stat 
   return nullptr;
 }
 
-// The buffers of a softmin blend (the handle's own; an sfw_ensemble's) and the blend itself over a device cost vector of T
-// samples with the knot rows at lin / vy / ang: ONE text for sfw_grid_blend and sfw_ensemble_blend, on h's stream.  Arguments
-// and state are the caller's to check.
-struct blend_area {
-  dev_buf<sfw_blend_min> &mins;
-  dev_buf<double> &partials, &bias, &weights;
-  pinned_buf &pin;
-};
+// The softmin blend over a device cost vector of T samples, on h's stream and into the buffers `a` (h's own; an sfw_ensemble's):
+// ONE text for sfw_grid_blend and sfw_ensemble_blend.  The knot rows are those of h's stage: st.nk rows (1: a grid, a plain list)
+// at st.d_linvels / d_vy / d_angvels.  Arguments and state are the caller's to check.
+//
 // What a blend leaves in pinned memory (a "slot"): the minimum record | eta[L] | sum_w2[L] | u[L][K][3]
 constexpr size_t kBlendHead = (sizeof(sfw_blend_min) + 15) & ~size_t(15);
 size_t blend_slot_bytes(int L, int K) { return kBlendHead + sizeof(double) * static_cast<size_t>(sfw_blend_channels(L, K)); }
 
 // The blend in two parts.  blend_enqueue: the kernels (and the copies of weights_out) on h's stream, no wait — d_bias
-// (nullable) is ON THE DEVICE and `slot` is pinned memory of blend_slot_bytes(L, K) that stays put until the stream has been
+// (nullable) is ON THE DEVICE and `slot` is pinned memory of blend_slot_bytes(L, st.nk) that stays put until the stream has been
 // waited for.  plan (sfw_mppi_run, L == 1): see sfw_launch_blend.  blend_finish: the outputs from a slot the stream is done with.
-int blend_enqueue(sfw_handle h, const blend_area &a, const double *d_costs, int64_t T, int K, const double *d_lin, const double *d_vy,
-                  const double *d_ang, int nw, bool list, const double *lambda, int32_t L, const double *d_bias, double *weights_out,
-                  char *slot, double *plan = nullptr) {
+int blend_enqueue(sfw_handle h, blend_buffers &a, const double *d_costs, int64_t T, const double *lambda, int32_t L, const double *d_bias,
+                  double *weights_out, char *slot, double *plan = nullptr) {
+  const int K = h->st.nk;
   const int64_t n_ch = sfw_blend_channels(L, K), blocks = sfw_blend_blocks(T);
   SFW_HIP(h, a.mins.reserve(static_cast<size_t>(sfw_blend_min_blocks(T))));
   SFW_HIP(h, a.partials.reserve(static_cast<size_t>(blocks) * static_cast<size_t>(n_ch)));
@@ -1876,7 +1924,7 @@ int blend_enqueue(sfw_handle h, const blend_area &a, const double *d_costs, int6
   for (int32_t l = 0; l < L; ++l) lam.v[l] = lambda[l];
   sfw_blend_min *const min_host = reinterpret_cast<sfw_blend_min *>(slot);
   double *const out_host = reinterpret_cast<double *>(slot + kBlendHead);
-  SFW_HIP(h, sfw_launch_blend(d_costs, d_bias, T, lam, L, K, d_lin, d_vy, d_ang, nw, list, a.mins.p, a.partials.p,
+  SFW_HIP(h, sfw_launch_blend(d_costs, d_bias, T, lam, L, K, h->st.d_linvels, h->st.d_vy, h->st.d_angvels, h->st.nw, h->st.list, a.mins.p, a.partials.p,
                               weights_out && !sliced ? a.weights.p : nullptr, min_host, out_host, h->stream, plan));
   if (weights_out && !sliced)
     SFW_HIP(h, hipMemcpyAsync(weights_out, a.weights.p, sizeof(double) * static_cast<size_t>(L) * static_cast<size_t>(T),
@@ -1908,9 +1956,9 @@ void blend_finish(const char *slot, const double *lambda, int32_t L, int K, sfw_
 }
 // The blocking blend: the area's pinned slot, the enqueue, one wait, the finish.  bias (nullable, host) goes up first; d_bias
 // (nullable) is a bias vector the device holds already, read instead.
-int blend_run(sfw_handle h, const blend_area &a, const double *d_costs, int64_t T, int K, const double *d_lin, const double *d_vy,
-              const double *d_ang, int nw, bool list, const double *lambda, int32_t L, const double *bias, sfw_blend_stat *stat_out,
-              double *u_out, double *weights_out, const double *d_bias = nullptr) {
+int blend_run(sfw_handle h, blend_buffers &a, const double *d_costs, int64_t T, const double *lambda, int32_t L, const double *bias,
+              sfw_blend_stat *stat_out, double *u_out, double *weights_out, const double *d_bias) {
+  const int K = h->st.nk;
   const size_t out_bytes = blend_slot_bytes(L, K);
   // (growing the pinned area frees the old one: nothing in the stream may still be writing there)
   if (out_bytes > a.pin.cap) SFW_HIP(h, hipStreamSynchronize(h->stream));
@@ -1920,19 +1968,19 @@ int blend_run(sfw_handle h, const blend_area &a, const double *d_costs, int64_t 
     SFW_HIP(h, hipMemcpyAsync(a.bias.p, bias, sizeof(double) * static_cast<size_t>(T), hipMemcpyHostToDevice, h->stream));
     d_bias = a.bias.p;
   }
-  if (int e = blend_enqueue(h, a, d_costs, T, K, d_lin, d_vy, d_ang, nw, list, lambda, L, d_bias, weights_out, a.pin.p)) return e;
+  if (int e = blend_enqueue(h, a, d_costs, T, lambda, L, d_bias, weights_out, a.pin.p)) return e;
   SFW_HIP(h, a.pin.mark(h->stream));
   SFW_HIP(h, wait_stream(h));
   a.pin.pending = false;
-  stream_is_idle(h);
   blend_finish(a.pin.p, lambda, L, K, stat_out, u_out);
   return SFW_OK;
 }
 
 // The bias vector gamma * c_t (+ bias[t], nullable: T host doubles, uploaded to the blend's bias buffer first) of the staged
-// perturbed stage into `out`, on h's stream.  plan (nullable): the nominal rows in device memory (sfw_mppi_run).  out / add: the
-// handle's ctrl_bias / blend_bias, or an sfw_ensemble's own (member 0's belong to that member's calls).
-int control_cost_enqueue(sfw_handle h, double gamma, const double *bias, const double *plan, dev_buf<double> &out, dev_buf<double> &add) {
+// perturbed stage into mb.ctrl_bias, on h's stream.  plan (nullable): the nominal rows in device memory (sfw_mppi_run).  mb / bb:
+// the handle's buffers, or an sfw_ensemble's own (member 0's belong to that member's calls).
+int control_cost_enqueue(sfw_handle h, double gamma, const double *bias, const double *plan, mppi_buffers &mb, blend_buffers &bb) {
+  dev_buf<double> &out = mb.ctrl_bias, &add = bb.bias;
   const int64_t n = h->st.nv;
   SFW_HIP(h, out.reserve(static_cast<size_t>(n)));
   const double *d_add = nullptr;
@@ -1950,53 +1998,164 @@ const char *control_state_refusal(sfw_handle h) {
 }
 
 
-// sfw_mppi_run behind its stage of iteration 0: everything enqueued, one wait, the outputs.  A failure is the caller's to clean up.
-int mppi_chain(sfw_handle h, const sfw_perturb *p, int K, const sfw_mppi *m, sfw_blend_stat *stat_out, double *plans_out,
-               sfw_best *best_out) {
-  const int I = m->iterations;
-  const int64_t n = h->st.nv;
-  const size_t slot = (blend_slot_bytes(1, K) + 15) & ~size_t(15), plan_bytes = sizeof(double) * 3 * static_cast<size_t>(K);
+// sfw_grid_blend (gamma null) and sfw_grid_blend_control over the last launch's cost vector: ONE text, the shape of
+// ensemble_blend.  The control cost goes into the handle's ctrl_bias, on top of `bias` when there is one.
+int grid_blend(sfw_handle h, const char *what, const double *lambda, int32_t L, const double *gamma, const double *bias,
+               sfw_blend_stat *stat_out, double *u_out, double *weights_out) {
+  if (!h) return SFW_ERR_INVALID_ARG;
+  if (const char *why = blend_refusal(lambda, L, stat_out, u_out)) return fail(h, SFW_ERR_INVALID_ARG, std::string(what) + ": " + why);
+  if (gamma && !std::isfinite(*gamma)) return fail(h, SFW_ERR_INVALID_ARG, std::string(what) + ": gamma is not finite");
+  if (gamma)
+    if (const char *why = control_state_refusal(h)) return fail(h, SFW_ERR_STATE, std::string(what) + ": " + why);
+  if (!h->last.launched) return fail(h, SFW_ERR_STATE, std::string(what) + ": no launch, or a stage or sfw_score_one came in since");
+  const int64_t T = static_cast<int64_t>(h->st.nv) * h->st.nw;
+  if (bias && !all_finite(bias, static_cast<size_t>(T))) return fail(h, SFW_ERR_INVALID_ARG, std::string(what) + ": non-finite bias");
   SFW_HIP(h, hipSetDevice(h->device));
-  // every buffer the chain writes is in place before its first kernel is enqueued: nothing in flight is ever freed
-  if (I * slot + plan_bytes > h->pin_mppi.cap) SFW_HIP(h, hipStreamSynchronize(h->stream));
-  SFW_HIP(h, h->pin_mppi.reserve(I * slot + plan_bytes));
-  SFW_HIP(h, h->mppi_plan.reserve(3 * static_cast<size_t>(SFW_SEQ_MAX_KNOTS)));
-  if (m->gamma != 0.0) SFW_HIP(h, h->ctrl_bias.reserve(static_cast<size_t>(n)));
-  SFW_HIP(h, h->blend_mins.reserve(static_cast<size_t>(sfw_blend_min_blocks(n))));
-  SFW_HIP(h, h->blend_partials.reserve(static_cast<size_t>(sfw_blend_blocks(n)) * static_cast<size_t>(sfw_blend_channels(1, K))));
-  const blend_area area{h->blend_mins, h->blend_partials, h->blend_bias, h->blend_weights, h->pin_blend};
-  char *const pin = h->pin_mppi.p;
-  std::memcpy(pin + I * slot, p->nominal, plan_bytes);
-  SFW_HIP(h, hipMemcpyAsync(h->mppi_plan.p, pin + I * slot, plan_bytes, hipMemcpyHostToDevice, h->stream));
-  double *const plan = h->mppi_plan.p;
+  // gamma == 0: sfw_grid_blend itself (a bias of gamma * c_t = +-0.0 would turn a cost of -0.0 into +0.0)
+  const double *d_bias = nullptr;
+  if (gamma && *gamma != 0.0) {
+    if (int e = control_cost_enqueue(h, *gamma, bias, nullptr, h->mppi, h->blend)) return e;
+    d_bias = h->mppi.ctrl_bias.p;
+    bias = nullptr;
+  }
+  return blend_run(h, h->blend, h->costs.p, T, lambda, L, bias, stat_out, u_out, weights_out, d_bias);
+}
+
+// The sfw_mppi argument rules of sfw_mppi_run and sfw_ensemble_mppi_run (m null: the first one's to report; each call words its
+// null pointers itself)
+const char *const kMppiIterations = "iterations outside 1..SFW_MPPI_MAX_ITER, or reserved != 0";
+const char *mppi_refusal(const sfw_mppi *m) {
+  if (!m || m->iterations < 1 || m->iterations > SFW_MPPI_MAX_ITER || m->reserved != 0) return kMppiIterations;
+  if (!std::isfinite(m->lambda) || !(m->lambda > 0.0) || !std::isfinite(m->gamma))
+    return "lambda is not finite or not > 0, or gamma is not finite";
+  return nullptr;
+}
+
+void perturb_seed(sfw_perturb_dev &d, uint64_t seed) {
+  d.key0 = static_cast<uint32_t>(seed & 0xffffffffu);
+  d.key1 = static_cast<uint32_t>(seed >> 32);
+}
+
+// The pinned area of a chain of I iterations with K knots: one blend slot per iteration | the caller's nominal | `extra` bytes
+// (16-aligned: an ensemble's member table)
+struct mppi_slots {
+  size_t slot, plan_bytes, plan_at, extra_at, bytes;
+  mppi_slots(int I, int K, size_t extra)
+      : slot((blend_slot_bytes(1, K) + 15) & ~size_t(15)), plan_bytes(sizeof(double) * 3 * static_cast<size_t>(K)), plan_at(I * slot),
+        extra_at((plan_at + plan_bytes + 15) & ~size_t(15)), bytes(extra ? extra_at + extra : plan_at + plan_bytes) {}
+};
+// Every buffer a chain over n samples writes is in place before its first kernel is enqueued: nothing in flight is ever freed.
+// (A pinned area that has to grow frees the old one: the caller waits for its stream first.)
+hipError_t mppi_reserve(mppi_buffers &mb, blend_buffers &bb, const mppi_slots &s, int K, int64_t n, bool control) {
+  hipError_t e = mb.pin_mppi.reserve(s.bytes);
+  if (e == hipSuccess) e = mb.mppi_plan.reserve(3 * static_cast<size_t>(SFW_SEQ_MAX_KNOTS));
+  if (e == hipSuccess && control) e = mb.ctrl_bias.reserve(static_cast<size_t>(n));
+  if (e == hipSuccess) e = bb.mins.reserve(static_cast<size_t>(sfw_blend_min_blocks(n)));
+  if (e == hipSuccess) e = bb.partials.reserve(static_cast<size_t>(sfw_blend_blocks(n)) * static_cast<size_t>(sfw_blend_channels(1, K)));
+  return e;
+}
+// After THE wait: every iteration's statistics and plan from its slot; and the stage each of the nh handles holds is iteration
+// I - 1's, drawn around nom_(I-1)
+void mppi_finish(const mppi_slots &s, const char *pin, const sfw_mppi *m, int K, sfw_blend_stat *stat_out, double *plans_out,
+                 const sfw_handle *hs, size_t nh) {
+  const int I = m->iterations;
+  for (int i = 0; i < I; ++i) blend_finish(pin + i * s.slot, &m->lambda, 1, K, stat_out + i, plans_out + static_cast<size_t>(i) * 3 * K);
+  if (I > 1)
+    for (size_t k = 0; k < nh; ++k) std::memcpy(hs[k]->st.pert.nominal, plans_out + static_cast<size_t>(I - 2) * 3 * K, s.plan_bytes);
+}
+
+// sfw_mppi_run behind its stage of iteration 0: everything enqueued, one wait, the outputs.  A failure is the caller's to clean up.
+int mppi_chain(sfw_handle h, const sfw_perturb *p, const sfw_mppi *m, sfw_blend_stat *stat_out, double *plans_out, sfw_best *best_out) {
+  const int I = m->iterations, K = h->st.nk;
+  const int64_t n = h->st.nv;
+  const mppi_slots s(I, K, 0);
+  SFW_HIP(h, hipSetDevice(h->device));
+  if (s.bytes > h->mppi.pin_mppi.cap) SFW_HIP(h, hipStreamSynchronize(h->stream));
+  SFW_HIP(h, mppi_reserve(h->mppi, h->blend, s, K, n, m->gamma != 0.0));
+  char *const pin = h->mppi.pin_mppi.p;
+  std::memcpy(pin + s.plan_at, p->nominal, s.plan_bytes);
+  SFW_HIP(h, hipMemcpyAsync(h->mppi.mppi_plan.p, pin + s.plan_at, s.plan_bytes, hipMemcpyHostToDevice, h->stream));
+  double *const plan = h->mppi.mppi_plan.p;
   for (int i = 0; i < I; ++i) {
     if (i > 0) {  // the stage of iteration i: its seed, and the knots drawn around the plan the last update left
-      const uint64_t seed = p->seed + static_cast<uint64_t>(i);
-      h->st.pert.key0 = static_cast<uint32_t>(seed & 0xffffffffu);
-      h->st.pert.key1 = static_cast<uint32_t>(seed >> 32);
+      perturb_seed(h->st.pert, p->seed + static_cast<uint64_t>(i));
       SFW_HIP(h, sfw_launch_perturb_plan(h->st.pert, plan, n, K, 0, const_cast<double *>(h->st.d_linvels), const_cast<double *>(h->st.d_vy),
                                          const_cast<double *>(h->st.d_angvels), h->st.normals_kept ? h->normals.p : nullptr, h->stream));
     }
     if (int e = launch_common(h)) return e;
     const double *d_bias = nullptr;
     if (m->gamma != 0.0) {  // (as sfw_grid_blend_control: gamma == 0 is the plain blend)
-      if (int e = control_cost_enqueue(h, m->gamma, nullptr, plan, h->ctrl_bias, h->blend_bias)) return e;
-      d_bias = h->ctrl_bias.p;
+      if (int e = control_cost_enqueue(h, m->gamma, nullptr, plan, h->mppi, h->blend)) return e;
+      d_bias = h->mppi.ctrl_bias.p;
     }
-    if (int e = blend_enqueue(h, area, h->costs.p, n, K, h->st.d_linvels, h->st.d_vy, h->st.d_angvels, 1, true, &m->lambda, 1, d_bias,
-                              nullptr, pin + i * slot, plan))
-      return e;
+    if (int e = blend_enqueue(h, h->blend, h->costs.p, n, &m->lambda, 1, d_bias, nullptr, pin + i * s.slot, plan)) return e;
   }
-  SFW_HIP(h, h->pin_mppi.mark(h->stream));
+  SFW_HIP(h, h->mppi.pin_mppi.mark(h->stream));
   sfw_best best;
   if (int e = sfw_grid_fetch(h, nullptr, &best, nullptr)) return e;  // THE wait (and the winner's first knot behind it)
-  h->pin_mppi.pending = false;
-  for (int i = 0; i < I; ++i) blend_finish(pin + i * slot, &m->lambda, 1, K, stat_out + i, plans_out + static_cast<size_t>(i) * 3 * K);
-  // the stage the handle holds is iteration I - 1's: drawn around nom_(I-1)
-  if (I > 1) std::memcpy(h->st.pert.nominal, plans_out + static_cast<size_t>(I - 2) * 3 * K, plan_bytes);
+  h->mppi.pin_mppi.pending = false;
+  mppi_finish(s, pin, m, K, stat_out, plans_out, &h, 1);
   if (best_out) *best_out = best;
   return SFW_OK;
 }
+
+// The blocking score behind its stage, whose status is `staged`: launch + fetch
+int score_staged(sfw_handle h, int staged, double *costs_out, sfw_best *best_out) {
+  if (staged) return staged;
+  if (int e = sfw_grid_launch(h)) return e;
+  return sfw_grid_fetch(h, costs_out, best_out, nullptr);
+}
+
+// The launch record of samples [first, first + count) run once more, alone, into the scratch outputs (the launch's own results
+// stay intact).  The kernels index per-sample outputs by the global sample index: the pointers are biased by -first.
+void fill_scratch_launch(sfw_handle h, sfw_launch &L, int64_t first, int64_t count) {
+  fill_launch(h, L, first, count, count);
+  L.status = h->pts_status.p - first;
+  L.base_cost = h->pts_base.p - first;
+  L.ptab = h->pts_ptab.p;
+  L.cs_tab = h->pts_cs.p;
+}
+
+// The one-sample stage of sfw_score_one / sfw_score_one_crowd.  The agent set is checked before the stage (a refused call leaves
+// the staged grid alone); past the checks the call consumes its stage, whatever the outcome (no grid to launch or dump)
+int stage_one(sfw_handle h, const sfw_robot_state *rs, const sfw_goal_args *args, double vx, double vy, double vtheta) {
+  const agent_set &ag = h->world.agents;
+  if (int e = check_lds(h, ag.A, ag.O, ag.NG, ag.n_grp_mem, 1)) return e;
+  return stage_common(h, rs, args, one_request(&vx, vy, &vtheta));
+}
+struct consume_stage {
+  sfw_handle h;
+  ~consume_stage() { h->st.valid = false; }
+};
+
+// sfw_score_one's outputs, wherever its kernels write them: cost (8) | n_points (4) | coll_step (4) | points (24 S)
+constexpr size_t kOneHead = 16;
+void score_one_outputs_at(sfw_launch &L, char *base) {
+  L.costs = reinterpret_cast<double *>(base);
+  L.n_points = reinterpret_cast<int32_t *>(base + 8);
+  L.coll_step = reinterpret_cast<int32_t *>(base + 12);
+  L.points = reinterpret_cast<double *>(base + kOneHead);
+}
+// ... and from a host copy of them to the caller
+int32_t one_head_unpack(const char *src, double *cost_out) {  // -> the point (step) count
+  int32_t n = 0, coll = -1;
+  if (cost_out) std::memcpy(cost_out, src, sizeof(double));
+  std::memcpy(&n, src + 8, sizeof(n));
+  std::memcpy(&coll, src + 12, sizeof(coll));
+  if (coll >= 0 && coll + 1 < n) n = coll + 1;  // rejected by contact at step `coll`: poses (steps) 0..coll were added (integrated)
+  return n;
+}
+void score_one_unpack(const char *src, double *cost_out, double *points_xyth, int32_t points_cap, int32_t *n_points) {
+  const int32_t n = one_head_unpack(src, cost_out);
+  if (n_points) *n_points = n;
+  if (points_xyth && points_cap > 0 && n > 0) {
+    const int m = n < points_cap ? n : points_cap;
+    std::memcpy(points_xyth, src + kOneHead, sizeof(double) * 3 * static_cast<size_t>(m));
+  }
+}
+
+// Samples [first, first + count) with count >= 1 inside [0, n)
+bool sample_range_ok(int64_t first, int64_t count, int64_t n) { return first >= 0 && count >= 1 && first < n && count <= n - first; }
 }  // namespace
 
 extern "C" {
@@ -2140,14 +2299,8 @@ int destroy_handle(sfw_handle h) {
   h->rescore_partials.release();
   h->rescore_costs.release();
   h->pin_rescore.release();
-  h->blend_mins.release();
-  h->blend_partials.release();
-  h->blend_bias.release();
-  h->blend_weights.release();
-  h->pin_blend.release();
-  h->ctrl_bias.release();
-  h->mppi_plan.release();
-  h->pin_mppi.release();
+  h->blend.release();
+  h->mppi.release();
   h->normals.release();
   h->pin_knots.release();
   h->points.release();
@@ -2342,13 +2495,12 @@ int sfw_set_agents(sfw_handle h, const sfw_agent *agents, int32_t A, const doubl
 
 int sfw_grid_stage(sfw_handle h, const sfw_robot_state *rs, const double *linvels, int32_t nv,
                    const double *angvels, int32_t nw, const sfw_goal_args *args, int64_t index_base) {
-  return stage_common(h, rs, linvels, nv, angvels, nw, args, 0.0, 1, index_base, true);
+  return stage_common(h, rs, args, grid_request(linvels, nv, angvels, nw, index_base));
 }
 
 int sfw_samples_stage(sfw_handle h, const sfw_robot_state *rs, const double *vx, const double *vy, const double *vtheta,
                       int32_t n, const sfw_goal_args *args, int64_t index_base) {
-  // a grid of n rows by one column to everything that counts samples; never the (0,0) skip
-  return stage_common(h, rs, vx, n, vtheta, 1, args, 0.0, 0, index_base, true, true, vy);
+  return stage_common(h, rs, args, list_request(vx, vy, vtheta, n, index_base));
 }
 
 int sfw_sequences_stage(sfw_handle h, const sfw_robot_state *rs, const double *vx, const double *vy, const double *vtheta,
@@ -2356,8 +2508,7 @@ int sfw_sequences_stage(sfw_handle h, const sfw_robot_state *rs, const double *v
   if (!h) return SFW_ERR_INVALID_ARG;
   // (refused before anything is touched: the staged grid, list or sequences stay launchable)
   if (const char *why = sequences_refusal(K, knot_step)) return fail(h, SFW_ERR_INVALID_ARG, std::string("sequences_stage: ") + why);
-  // a list of n samples to everything that counts samples; K rows of n values behind its vectors
-  return stage_common(h, rs, vx, n, vtheta, 1, args, 0.0, 0, index_base, true, true, vy, K, knot_step);
+  return stage_common(h, rs, args, sequences_request(vx, vy, vtheta, n, K, knot_step, index_base));
 }
 
 int sfw_grid_launch(sfw_handle h) { return launch_common(h); }
@@ -2379,7 +2530,6 @@ int sfw_grid_fetch(sfw_handle h, double *costs_out, sfw_best *best_out, sfw_best
   if (h->last.mirrored) {  // the launch's selection kernels wrote both to pin_mirror: nothing to copy, only to wait for
     const size_t all_bytes = sizeof(double) * static_cast<size_t>(T);
     SFW_HIP(h, wait_stream(h));
-    stream_is_idle(h);
     h->last.fetched = true;
     if (costs_out) std::memcpy(costs_out, h->pin_mirror.p, all_bytes);
     std::memcpy(&s, h->pin_mirror.p + all_bytes, sizeof(s));
@@ -2389,7 +2539,6 @@ int sfw_grid_fetch(sfw_handle h, double *costs_out, sfw_best *best_out, sfw_best
     const char *src = reinterpret_cast<const char *>(h->st.d_sel) - cost_bytes;
     SFW_HIP(h, hipMemcpyAsync(h->pin_out.p, src, cost_bytes + sizeof(sfw_sel), hipMemcpyDeviceToHost, h->stream));
     SFW_HIP(h, wait_stream(h));
-    stream_is_idle(h);
     h->last.fetched = true;
     if (costs_out) std::memcpy(costs_out, h->pin_out.p, cost_bytes);
     std::memcpy(&s, h->pin_out.p + cost_bytes, sizeof(s));
@@ -2405,24 +2554,18 @@ const double *sfw_grid_costs_view(sfw_handle h) {
 int sfw_score_grid(sfw_handle h, const sfw_robot_state *rs, const double *linvels, int32_t nv,
                    const double *angvels, int32_t nw, const sfw_goal_args *args, double *costs_out,
                    sfw_best *best_out) {
-  if (int e = sfw_grid_stage(h, rs, linvels, nv, angvels, nw, args, 0)) return e;
-  if (int e = sfw_grid_launch(h)) return e;
-  return sfw_grid_fetch(h, costs_out, best_out, nullptr);
+  return score_staged(h, sfw_grid_stage(h, rs, linvels, nv, angvels, nw, args, 0), costs_out, best_out);
 }
 
 int sfw_score_samples(sfw_handle h, const sfw_robot_state *rs, const double *vx, const double *vy, const double *vtheta,
                       int32_t n, const sfw_goal_args *args, double *costs_out, sfw_best *best_out) {
-  if (int e = sfw_samples_stage(h, rs, vx, vy, vtheta, n, args, 0)) return e;
-  if (int e = sfw_grid_launch(h)) return e;
-  return sfw_grid_fetch(h, costs_out, best_out, nullptr);
+  return score_staged(h, sfw_samples_stage(h, rs, vx, vy, vtheta, n, args, 0), costs_out, best_out);
 }
 
 int sfw_score_sequences(sfw_handle h, const sfw_robot_state *rs, const double *vx, const double *vy, const double *vtheta,
                         int32_t n, int32_t K, const int32_t *knot_step, const sfw_goal_args *args, double *costs_out,
                         sfw_best *best_out) {
-  if (int e = sfw_sequences_stage(h, rs, vx, vy, vtheta, n, K, knot_step, args, 0)) return e;
-  if (int e = sfw_grid_launch(h)) return e;
-  return sfw_grid_fetch(h, costs_out, best_out, nullptr);
+  return score_staged(h, sfw_sequences_stage(h, rs, vx, vy, vtheta, n, K, knot_step, args, 0), costs_out, best_out);
 }
 
 int sfw_sequences_perturb_stage(sfw_handle h, const sfw_robot_state *rs, const sfw_perturb *p, int32_t n, int32_t K,
@@ -2433,8 +2576,7 @@ int sfw_sequences_perturb_stage(sfw_handle h, const sfw_robot_state *rs, const s
     return fail(h, SFW_ERR_INVALID_ARG, std::string("sequences_perturb_stage: ") + why);
   const bool no_vy = (p->flags & SFW_PERTURB_NO_VY) != 0;
   perturb_source src{};
-  src.args.key0 = static_cast<uint32_t>(p->seed & 0xffffffffu);
-  src.args.key1 = static_cast<uint32_t>(p->seed >> 32);
+  perturb_seed(src.args, p->seed);
   src.args.keep_nominal = (p->flags & SFW_PERTURB_KEEP_NOMINAL) ? 1 : 0;
   for (int c = 0; c < 3; ++c) {
     src.args.sigma[c] = p->sigma[c];
@@ -2445,21 +2587,19 @@ int sfw_sequences_perturb_stage(sfw_handle h, const sfw_robot_state *rs, const s
   src.vy = !no_vy;
   src.keep_normals = (p->flags & SFW_PERTURB_KEEP_NORMALS) != 0;
   src.zero_admitted = p->lo[0] <= 0.0 && 0.0 <= p->hi[0] && (no_vy || (p->lo[1] <= 0.0 && 0.0 <= p->hi[1]));
-  return stage_common(h, rs, nullptr, n, nullptr, 1, args, 0.0, 0, index_base, true, true, nullptr, K, knot_step, &src);
+  return stage_common(h, rs, args, perturbed_request(&src, n, K, knot_step, index_base));
 }
 
 int sfw_score_perturbed(sfw_handle h, const sfw_robot_state *rs, const sfw_perturb *p, int32_t n, int32_t K,
                         const int32_t *knot_step, const sfw_goal_args *args, double *costs_out, sfw_best *best_out) {
-  if (int e = sfw_sequences_perturb_stage(h, rs, p, n, K, knot_step, args, 0)) return e;
-  if (int e = sfw_grid_launch(h)) return e;
-  return sfw_grid_fetch(h, costs_out, best_out, nullptr);
+  return score_staged(h, sfw_sequences_perturb_stage(h, rs, p, n, K, knot_step, args, 0), costs_out, best_out);
 }
 
 int sfw_sequences_knots(sfw_handle h, int64_t first, int64_t count, double *vx_out, double *vy_out, double *vtheta_out) {
   if (!h) return SFW_ERR_INVALID_ARG;
   if (!h->st.valid || !h->st.list) return fail(h, SFW_ERR_STATE, "sequences_knots: no list or sequences are staged");
   const int64_t n = h->st.nv;
-  if (first < 0 || count < 1 || first >= n || count > n - first) return fail(h, SFW_ERR_INVALID_ARG, "sequences_knots: range outside [0, n)");
+  if (!sample_range_ok(first, count, n)) return fail(h, SFW_ERR_INVALID_ARG, "sequences_knots: range outside [0, n)");
   if (!vx_out || !vtheta_out) return fail(h, SFW_ERR_INVALID_ARG, "sequences_knots: vx_out or vtheta_out is NULL");
   const size_t K = static_cast<size_t>(h->st.nk), cnt = static_cast<size_t>(count);
   double *const out[3] = {vx_out, vy_out, vtheta_out};
@@ -2490,7 +2630,7 @@ int sfw_sequences_normals(sfw_handle h, int64_t first, int64_t count, double *z_
   if (!h->st.valid || !h->st.perturbed || !h->st.normals_kept)
     return fail(h, SFW_ERR_STATE, "sequences_normals: no perturbed stage with SFW_PERTURB_KEEP_NORMALS is staged");
   const int64_t n = h->st.nv;
-  if (first < 0 || count < 1 || first >= n || count > n - first) return fail(h, SFW_ERR_INVALID_ARG, "sequences_normals: range outside [0, n)");
+  if (!sample_range_ok(first, count, n)) return fail(h, SFW_ERR_INVALID_ARG, "sequences_normals: range outside [0, n)");
   if (!z_out) return fail(h, SFW_ERR_INVALID_ARG, "sequences_normals: z_out is NULL");
   const size_t rows = 3 * static_cast<size_t>(h->st.nk), row = sizeof(double) * static_cast<size_t>(count);
   SFW_HIP(h, hipSetDevice(h->device));
@@ -2499,7 +2639,6 @@ int sfw_sequences_normals(sfw_handle h, int64_t first, int64_t count, double *z_
   SFW_HIP(h, hipMemcpy2DAsync(h->pin_knots.p, row, h->normals.p + first, sizeof(double) * static_cast<size_t>(n), row, rows,
                               hipMemcpyDeviceToHost, h->stream));
   SFW_HIP(h, wait_stream(h));
-  stream_is_idle(h);
   std::memcpy(z_out, h->pin_knots.p, rows * row);
   return SFW_OK;
 }
@@ -2509,89 +2648,46 @@ int sfw_score_one(sfw_handle h, const sfw_robot_state *rs, double vx_samp, doubl
                   int32_t *n_points) {
   if (!h) return SFW_ERR_INVALID_ARG;
   if (!cost_out) return fail(h, SFW_ERR_INVALID_ARG, "score_one: cost_out is NULL");
-  const agent_set &ag = h->world.agents;  // (checked before the stage: a refused call leaves the staged grid alone)
-  if (int e = check_lds(h, ag.A, ag.O, ag.NG, ag.n_grp_mem, 1)) return e;
-  if (int e = stage_common(h, rs, &vx_samp, 1, &vtheta_samp, 1, args, vy_samp, 0, 0, true)) return e;
-  // past the checks the call consumes its one-sample stage, whatever the outcome (no grid to launch or dump)
-  struct consume_stage {
-    sfw_handle h;
-    ~consume_stage() { h->st.valid = false; }
-  } consumed{h};
+  if (int e = stage_one(h, rs, args, vx_samp, vy_samp, vtheta_samp)) return e;
+  consume_stage consumed{h};
   const int S = num_steps_of(h->live.params);
+  // cost (8) | n_points (4) | coll_step (4) | points (24 S), contiguous
+  const size_t head = kOneHead, pts_bytes = sizeof(double) * 3 * static_cast<size_t>(S);
+  sfw_launch L;
+  fill_launch(h, L, 0, 1, 1);
+  // With points wanted a costmap-rejected sample is integrated too: a pedestrian contact at an earlier step ends the
+  // reference's Trajectory there (ref :613-627 returns before the later illegal pose is ever reached)
+  L.force_alive = (points_xyth && points_cap > 0) || n_points ? 1 : 0;
   {
     // The latency path (called on every approach / rotate cycle, ref :204-206, :299-301) as ONE launch and no copy: the
     // one-launch kernel with its outputs — cost, point count, contact step, Trajectory points — in pinned host memory, the
     // stage's arena fetched by the kernel (stage_common left it pending), no selection.
-    const size_t head = 16, pts_bytes = sizeof(double) * 3 * static_cast<size_t>(S);
-    sfw_launch L;
-    fill_launch(h, L, 0, 1, 1);
-    L.sel_out = nullptr;
-    L.cycle_counter = nullptr;
-    const bool want_pts = (points_xyth && points_cap > 0) || n_points;
-    L.force_alive = want_pts ? 1 : 0;
-    if (sfw_cycle_applies(L)) {
+    sfw_launch C = L;
+    C.sel_out = nullptr;
+    C.cycle_counter = nullptr;
+    if (sfw_cycle_applies(C)) {
       if (head + pts_bytes > h->pin_one.cap) SFW_HIP(h, hipStreamSynchronize(h->stream));  // (growing it frees the old area)
       SFW_HIP(h, h->pin_one.reserve(head + pts_bytes));
-      L.costs = reinterpret_cast<double *>(h->pin_one.p);
-      L.n_points = reinterpret_cast<int32_t *>(h->pin_one.p + 8);
-      L.coll_step = reinterpret_cast<int32_t *>(h->pin_one.p + 12);
-      L.points = reinterpret_cast<double *>(h->pin_one.p + head);
-      if (h->st.arena_pending) {
-        L.arena_host = h->pin_arena.p + h->st.arena_from;
-        L.arena_dev = h->arena.p + h->st.arena_from;
-        L.arena_bytes = static_cast<uint32_t>(h->st.arena_bytes);
-      }
-      SFW_HIP(h, h->live.params.precision == SFW_PRECISION_F64_STRICT ? sfw_launch_cycle_strict(L, h->stream) : sfw_launch_cycle(L, h->stream));
-      if (h->st.arena_pending) {
-        h->st.arena_pending = false;
-        SFW_HIP(h, h->pin_arena.mark(h->stream));
-      }
+      score_one_outputs_at(C, h->pin_one.p);
+      arena_by_kernel(h, C);
+      SFW_HIP(h, launch_cycle_of(C, h->stream));
+      SFW_HIP(h, arena_fetched(h));
       SFW_HIP(h, wait_stream(h));
-      stream_is_idle(h);
-      int32_t n = 0, coll = -1;
-      std::memcpy(cost_out, h->pin_one.p, sizeof(double));
-      std::memcpy(&n, h->pin_one.p + 8, sizeof(n));
-      std::memcpy(&coll, h->pin_one.p + 12, sizeof(coll));
-      if (coll >= 0 && coll + 1 < n) n = coll + 1;  // rejected by contact at step `coll`: poses 0..coll were added
-      if (n_points) *n_points = n;
-      if (points_xyth && points_cap > 0 && n > 0) {
-        const int m = n < points_cap ? n : points_cap;
-        std::memcpy(points_xyth, h->pin_one.p + head, sizeof(double) * 3 * static_cast<size_t>(m));
-      }
+      score_one_unpack(h->pin_one.p, cost_out, points_xyth, points_cap, n_points);
       return SFW_OK;
     }
     if (int e = flush_arena(h)) return e;  // the three-kernel path below reads the device copy
   }
-  // cost (8) | n_points (4) | coll_step (4) | points (24 S): contiguous on the device, so the latency path
-  // (called on every approach / rotate cycle, ref :204-206, :299-301) pays one pinned D2H, like sfw_grid_fetch
-  const size_t head = 16, pts_bytes = sizeof(double) * 3 * static_cast<size_t>(S);
+  // ... else on the device, so that the call pays one pinned D2H, like sfw_grid_fetch
   SFW_HIP(h, h->one_out.reserve(head + pts_bytes));
-  sfw_launch L;
-  fill_launch(h, L, 0, 1, 1);
-  L.costs = reinterpret_cast<double *>(h->one_out.p);
-  L.n_points = reinterpret_cast<int32_t *>(h->one_out.p + 8);
-  L.coll_step = reinterpret_cast<int32_t *>(h->one_out.p + 12);
-  L.points = reinterpret_cast<double *>(h->one_out.p + head);
-  const bool want_pts = (points_xyth && points_cap > 0) || n_points;
-  // With points wanted a costmap-rejected sample is integrated too: a pedestrian contact at an earlier step ends the
-  // reference's Trajectory there (ref :613-627 returns before the later illegal pose is ever reached)
-  L.force_alive = want_pts ? 1 : 0;
+  score_one_outputs_at(L, h->one_out.p);
   SFW_HIP(h, sfw_launch_rollout(L, h->stream));
   SFW_HIP(h, launch_social_of(L, h->stream));
   const size_t fetch = head + ((points_xyth && points_cap > 0) ? pts_bytes : 0);
   SFW_HIP(h, h->pin_out.reserve(fetch));
   SFW_HIP(h, hipMemcpyAsync(h->pin_out.p, h->one_out.p, fetch, hipMemcpyDeviceToHost, h->stream));
   SFW_HIP(h, hipStreamSynchronize(h->stream));
-  int32_t n = 0, coll = -1;
-  std::memcpy(cost_out, h->pin_out.p, sizeof(double));
-  std::memcpy(&n, h->pin_out.p + 8, sizeof(n));
-  std::memcpy(&coll, h->pin_out.p + 12, sizeof(coll));
-  if (coll >= 0 && coll + 1 < n) n = coll + 1;  // rejected by contact at step `coll`: poses 0..coll were added
-  if (n_points) *n_points = n;
-  if (points_xyth && points_cap > 0 && n > 0) {
-    const int m = n < points_cap ? n : points_cap;
-    std::memcpy(points_xyth, h->pin_out.p + head, sizeof(double) * 3 * static_cast<size_t>(m));
-  }
+  score_one_unpack(h->pin_out.p, cost_out, points_xyth, points_cap, n_points);
   return SFW_OK;
 }
 
@@ -2779,7 +2875,6 @@ int sfw_grid_rescore(sfw_handle h, const sfw_weights *w, int32_t K, sfw_best *be
   SFW_HIP(h, h->pin_rescore.mark(h->stream));
   SFW_HIP(h, wait_stream(h));
   h->pin_rescore.pending = false;
-  stream_is_idle(h);
   for (int32_t k = 0; k < K; ++k)
     if (int e = sel_to_best(h, sel_host[k], best_out + k, nullptr)) return e;
   return SFW_OK;
@@ -2787,15 +2882,7 @@ int sfw_grid_rescore(sfw_handle h, const sfw_weights *w, int32_t K, sfw_best *be
 
 int sfw_grid_blend(sfw_handle h, const double *lambda, int32_t L, const double *bias, sfw_blend_stat *stat_out, double *u_out,
                    double *weights_out) {
-  if (!h) return SFW_ERR_INVALID_ARG;
-  if (const char *why = blend_refusal(lambda, L, stat_out, u_out)) return fail(h, SFW_ERR_INVALID_ARG, std::string("grid_blend: ") + why);
-  if (!h->last.launched) return fail(h, SFW_ERR_STATE, "grid_blend: no launch, or a stage or sfw_score_one came in since");
-  const int64_t T = static_cast<int64_t>(h->st.nv) * h->st.nw;
-  if (bias && !all_finite(bias, static_cast<size_t>(T))) return fail(h, SFW_ERR_INVALID_ARG, "grid_blend: non-finite bias");
-  SFW_HIP(h, hipSetDevice(h->device));
-  const blend_area area{h->blend_mins, h->blend_partials, h->blend_bias, h->blend_weights, h->pin_blend};
-  return blend_run(h, area, h->costs.p, T, h->st.list ? h->st.nk : 1, h->st.d_linvels, h->st.d_vy, h->st.d_angvels, h->st.nw,
-                   h->st.list, lambda, L, bias, stat_out, u_out, weights_out);
+  return grid_blend(h, "grid_blend", lambda, L, nullptr, bias, stat_out, u_out, weights_out);
 }
 
 int sfw_sequences_control_cost(sfw_handle h, double gamma, double *bias_out) {
@@ -2806,35 +2893,16 @@ int sfw_sequences_control_cost(sfw_handle h, double gamma, double *bias_out) {
   const size_t bytes = sizeof(double) * static_cast<size_t>(h->st.nv);
   if (bytes > h->pin_knots.cap) SFW_HIP(h, hipStreamSynchronize(h->stream));  // (growing the area frees the old one)
   SFW_HIP(h, h->pin_knots.reserve(bytes));
-  if (int e = control_cost_enqueue(h, gamma, nullptr, nullptr, h->ctrl_bias, h->blend_bias)) return e;
-  SFW_HIP(h, hipMemcpyAsync(h->pin_knots.p, h->ctrl_bias.p, bytes, hipMemcpyDeviceToHost, h->stream));
+  if (int e = control_cost_enqueue(h, gamma, nullptr, nullptr, h->mppi, h->blend)) return e;
+  SFW_HIP(h, hipMemcpyAsync(h->pin_knots.p, h->mppi.ctrl_bias.p, bytes, hipMemcpyDeviceToHost, h->stream));
   SFW_HIP(h, wait_stream(h));
-  stream_is_idle(h);
   std::memcpy(bias_out, h->pin_knots.p, bytes);
   return SFW_OK;
 }
 
 int sfw_grid_blend_control(sfw_handle h, const double *lambda, int32_t L, double gamma, const double *bias, sfw_blend_stat *stat_out,
                            double *u_out, double *weights_out) {
-  if (!h) return SFW_ERR_INVALID_ARG;
-  if (const char *why = blend_refusal(lambda, L, stat_out, u_out))
-    return fail(h, SFW_ERR_INVALID_ARG, std::string("grid_blend_control: ") + why);
-  if (!std::isfinite(gamma)) return fail(h, SFW_ERR_INVALID_ARG, "grid_blend_control: gamma is not finite");
-  if (const char *why = control_state_refusal(h)) return fail(h, SFW_ERR_STATE, std::string("grid_blend_control: ") + why);
-  if (!h->last.launched) return fail(h, SFW_ERR_STATE, "grid_blend_control: no launch, or a stage or sfw_score_one came in since");
-  const int64_t T = h->st.nv;
-  if (bias && !all_finite(bias, static_cast<size_t>(T))) return fail(h, SFW_ERR_INVALID_ARG, "grid_blend_control: non-finite bias");
-  SFW_HIP(h, hipSetDevice(h->device));
-  const blend_area area{h->blend_mins, h->blend_partials, h->blend_bias, h->blend_weights, h->pin_blend};
-  // gamma == 0: sfw_grid_blend itself (a bias of gamma * c_t = +-0.0 would turn a cost of -0.0 into +0.0)
-  const double *d_bias = nullptr;
-  if (gamma != 0.0) {
-    if (int e = control_cost_enqueue(h, gamma, bias, nullptr, h->ctrl_bias, h->blend_bias)) return e;
-    d_bias = h->ctrl_bias.p;
-    bias = nullptr;
-  }
-  return blend_run(h, area, h->costs.p, T, h->st.nk, h->st.d_linvels, h->st.d_vy, h->st.d_angvels, 1, true, lambda, L, bias, stat_out,
-                   u_out, weights_out, d_bias);
+  return grid_blend(h, "grid_blend_control", lambda, L, &gamma, bias, stat_out, u_out, weights_out);
 }
 
 int sfw_mppi_run(sfw_handle h, const sfw_robot_state *rs, const sfw_perturb *p, int32_t n, int32_t K, const int32_t *knot_step,
@@ -2842,14 +2910,11 @@ int sfw_mppi_run(sfw_handle h, const sfw_robot_state *rs, const sfw_perturb *p, 
   if (!h) return SFW_ERR_INVALID_ARG;
   // (refused before anything is touched: the staged grid, list or sequences stay launchable)
   if (!m || !stat_out || !plans_out) return fail(h, SFW_ERR_INVALID_ARG, "mppi_run: m, stat_out or plans_out is NULL");
-  if (m->iterations < 1 || m->iterations > SFW_MPPI_MAX_ITER || m->reserved != 0)
-    return fail(h, SFW_ERR_INVALID_ARG, "mppi_run: iterations outside 1..SFW_MPPI_MAX_ITER, or reserved != 0");
-  if (!std::isfinite(m->lambda) || !(m->lambda > 0.0) || !std::isfinite(m->gamma))
-    return fail(h, SFW_ERR_INVALID_ARG, "mppi_run: lambda is not finite or not > 0, or gamma is not finite");
+  if (const char *why = mppi_refusal(m)) return fail(h, SFW_ERR_INVALID_ARG, std::string("mppi_run: ") + why);
   if (const char *why = perturb_refusal(rs, p, n, K, knot_step, args, 0)) return fail(h, SFW_ERR_INVALID_ARG, std::string("mppi_run: ") + why);
   if (int e = sfw_sequences_perturb_stage(h, rs, p, n, K, knot_step, args, 0)) return e;
-  if (int e = mppi_chain(h, p, K, m, stat_out, plans_out, best_out)) {
-    if (h->pin_mppi.done) (void)h->pin_mppi.mark(h->stream);  // (kernels of the chain may still be writing there)
+  if (int e = mppi_chain(h, p, m, stat_out, plans_out, best_out)) {
+    if (h->mppi.pin_mppi.done) (void)h->mppi.pin_mppi.mark(h->stream);  // (kernels of the chain may still be writing there)
     const std::string why = h->err;
     drop_stage(h);
     h->err = why;
@@ -2864,7 +2929,9 @@ int sfw_grid_terms(sfw_handle h, int64_t first, int64_t count, double *terms_out
     return fail(h, SFW_ERR_STATE, "grid_terms: the last launch did not capture terms (sfw_set_terms_capture), or a stage or "
                                   "sfw_score_one came in since");
   const int64_t T = static_cast<int64_t>(h->st.nv) * h->st.nw;
-  if (count < 0 || first < 0 || first > T || count > T - first) return fail(h, SFW_ERR_INVALID_ARG, "grid_terms: range out of the grid");
+  // (an empty range may also sit at the end of the grid)
+  if (count == 0 ? first < 0 || first > T : !sample_range_ok(first, count, T))
+    return fail(h, SFW_ERR_INVALID_ARG, "grid_terms: range out of the grid");
   if (count > 0 && !terms_out) return fail(h, SFW_ERR_INVALID_ARG, "grid_terms: terms_out is NULL");
   if (count == 0) return SFW_OK;
   SFW_HIP(h, hipSetDevice(h->device));
@@ -2899,7 +2966,7 @@ int sfw_grid_points_batch(sfw_handle h, int64_t first, int64_t count, double *po
   if (!h) return SFW_ERR_INVALID_ARG;
   if (!h->st.valid) return fail(h, SFW_ERR_STATE, "grid_points before grid_stage");
   const int64_t T = static_cast<int64_t>(h->st.nv) * h->st.nw;
-  if (first < 0 || count <= 0 || first + count > T || !points_xyth || !n_points)
+  if (!sample_range_ok(first, count, T) || !points_xyth || !n_points)
     return fail(h, SFW_ERR_INVALID_ARG, "grid_points: bad range or buffer");
   SFW_HIP(h, hipSetDevice(h->device));
   if (int e = flush_arena(h)) return e;  // (a dump between stage and launch: the re-run below reads the device copy of the arena)
@@ -2911,7 +2978,6 @@ int sfw_grid_points_batch(sfw_handle h, int64_t first, int64_t count, double *po
     const size_t pts_bytes = sizeof(double) * 3 * static_cast<size_t>(S) * static_cast<size_t>(T);
     if (!h->last.fetched) {
       SFW_HIP(h, wait_stream(h));
-      stream_is_idle(h);
     }
     const int32_t *np = reinterpret_cast<const int32_t *>(h->pin_cap.p + pts_bytes), *coll = np + T;
     std::memcpy(points_xyth, h->pin_cap.p + sizeof(double) * 3 * static_cast<size_t>(S) * static_cast<size_t>(first), sizeof(double) * 3 * S * n);
@@ -2936,13 +3002,9 @@ int sfw_grid_points_batch(sfw_handle h, int64_t first, int64_t count, double *po
   if (e == hipSuccess) e = h->pts_fcode.reserve(static_cast<size_t>(S) * n);
   if (e == hipSuccess) {
     sfw_launch L;
-    fill_launch(h, L, first, count, count);
-    L.status = h->pts_status.p - first;
-    L.base_cost = h->pts_base.p - first;
+    fill_scratch_launch(h, L, first, count);
     L.costs = h->pts_costs.p - first;
     L.coll_step = nullptr;  // keep the launch's contact steps
-    L.ptab = h->pts_ptab.p;
-    L.cs_tab = h->pts_cs.p;
     L.fcode = h->pts_fcode.p;
     L.points = h->points.p;
     L.n_points = h->n_points.p;
@@ -2970,13 +3032,9 @@ int sfw_grid_points_batch(sfw_handle h, int64_t first, int64_t count, double *po
     if (int rc = check_lds(h, h->st.A, h->st.O, h->st.NG, h->st.n_grp_mem, count)) return rc;
     SFW_HIP(h, h->pts_coll.reserve(n));
     sfw_launch L;
-    fill_launch(h, L, first, count, count);
-    L.status = h->pts_status.p - first;
-    L.base_cost = h->pts_base.p - first;
+    fill_scratch_launch(h, L, first, count);
     L.costs = h->pts_costs.p - first;
     L.coll_step = h->pts_coll.p - first;
-    L.ptab = h->pts_ptab.p;
-    L.cs_tab = h->pts_cs.p;
     L.force_alive = 1;
     SFW_HIP(h, hipMemsetAsync(h->pts_coll.p, 0xff, sizeof(int32_t) * n, h->stream));  // -1: no contact
     SFW_HIP(h, launch_social_of(L, h->stream));
@@ -3040,15 +3098,10 @@ int crowd_run(sfw_handle h, int64_t t, double *cost_out, double *state_xyvv, dou
   }
   char *const out = h->crowd_out.p;
   sfw_launch L;
-  fill_launch(h, L, t, 1, 1);
-  // (the kernels index per-sample outputs by the global sample index: the pointers are biased by -t)
-  L.status = h->pts_status.p - t;
-  L.base_cost = h->pts_base.p - t;
+  fill_scratch_launch(h, L, t, 1);
   L.costs = reinterpret_cast<double *>(out) - t;
   L.coll_step = reinterpret_cast<int32_t *>(out + 12) - t;
   L.n_points = reinterpret_cast<int32_t *>(out + 8);
-  L.ptab = h->pts_ptab.p;
-  L.cs_tab = h->pts_cs.p;
   L.fcode = h->pts_fcode.p;
   L.pair_tab = h->crowd_pair_tab.p;
   L.force_alive = 1;
@@ -3063,12 +3116,8 @@ int crowd_run(sfw_handle h, int64_t t, double *cost_out, double *state_xyvv, dou
   SFW_HIP(h, hipMemcpyAsync(h->pin_crowd.p, out, total, hipMemcpyDeviceToHost, h->stream));
   SFW_HIP(h, hipStreamSynchronize(h->stream));
   const char *const pin = h->pin_crowd.p;
-  int32_t n = 0, coll = -1;
-  if (cost_out) std::memcpy(cost_out, pin, sizeof(double));
-  std::memcpy(&n, pin + 8, sizeof(n));
-  std::memcpy(&coll, pin + 12, sizeof(coll));
-  if (coll >= 0 && coll + 1 < n) n = coll + 1;  // rejected by contact at step `coll`: steps 0..coll were integrated
-  if (A <= 0) n = 0;                            // nobody to predict
+  int32_t n = one_head_unpack(pin, cost_out);
+  if (A <= 0) n = 0;  // nobody to predict
   *n_steps = n;
   const size_t m = static_cast<size_t>(n < steps_cap ? n : steps_cap) * static_cast<size_t>(A > 0 ? A : 0);
   if (m > 0) {
@@ -3088,15 +3137,9 @@ int sfw_score_one_crowd(sfw_handle h, const sfw_robot_state *rs, double vx_samp,
   if (!h) return SFW_ERR_INVALID_ARG;
   if (!cost_out || !state_xyvv || !n_steps || steps_cap < 1)
     return fail(h, SFW_ERR_INVALID_ARG, "score_one_crowd: cost_out, state_xyvv or n_steps is NULL, or steps_cap < 1");
-  const agent_set &ag = h->world.agents;  // (checked before the stage: a refused call leaves the staged grid alone)
-  if (agents != ag.A) return fail(h, SFW_ERR_INVALID_ARG, "score_one_crowd: agents is not the agent count of sfw_set_agents");
-  if (int e = check_lds(h, ag.A, ag.O, ag.NG, ag.n_grp_mem, 1)) return e;
-  if (int e = stage_common(h, rs, &vx_samp, 1, &vtheta_samp, 1, args, vy_samp, 0, 0, true)) return e;
-  // past the checks the call consumes its one-sample stage, whatever the outcome (as sfw_score_one)
-  struct consume_stage {
-    sfw_handle h;
-    ~consume_stage() { h->st.valid = false; }
-  } consumed{h};
+  if (agents != h->world.agents.A) return fail(h, SFW_ERR_INVALID_ARG, "score_one_crowd: agents is not the agent count of sfw_set_agents");
+  if (int e = stage_one(h, rs, args, vx_samp, vy_samp, vtheta_samp)) return e;
+  consume_stage consumed{h};
   return crowd_run(h, 0, cost_out, state_xyvv, work, has_goal, steps_cap, n_steps);
 }
 
@@ -3927,16 +3970,12 @@ struct sfw_ensemble_s {
   // and the blend's own buffers (member 0's belong to its sfw_grid_blend)
   dev_buf<double> d_cost;
   const double *cost_dev = nullptr;
-  dev_buf<sfw_blend_min> blend_mins;
-  dev_buf<double> blend_partials, blend_bias, blend_weights;
-  pinned_buf pin_blend;
-  // sfw_ensemble_blend_control: the bias vector gamma * c_t (+ bias_t) on the device (member 0's ctrl_bias belongs to its
-  // sfw_grid_blend_control).  sfw_ensemble_mppi_run: the nominal plan on the device, moved on by every iteration's update
-  // kernel; the members' knot rows as sfw_perturb_members_kernel reads them (M sfw_perturb_dst); pin_mppi = one blend slot per
-  // iteration | the caller's nominal | that table (the sources of the two copies that start the chain)
-  dev_buf<double> ctrl_bias, mppi_plan;
+  blend_buffers blend;
+  // sfw_ensemble_blend_control: the control cost's bias vector (member 0's ctrl_bias belongs to its sfw_grid_blend_control).
+  // sfw_ensemble_mppi_run: the chain's buffers, and the members' knot rows as sfw_perturb_members_kernel reads them (M
+  // sfw_perturb_dst: the table behind the nominal in pin_mppi is the source of its copy)
+  mppi_buffers mppi;
   dev_buf<sfw_perturb_dst> pert_dst;
-  pinned_buf pin_mppi;
 };
 
 namespace {
@@ -3948,6 +3987,13 @@ int efail(sfw_ensemble e, int code, const std::string &msg) {
 }
 int emember_fail(sfw_ensemble e, int32_t m, int code, const char *what) {
   return efail(e, code, std::string(what) + " (member " + std::to_string(m) + "): " + e->b->h[static_cast<size_t>(m)]->err);
+}
+// f(member) for every member in order, until one fails: that member's failure under `what`
+template <typename F>
+int ensemble_each(sfw_ensemble e, const char *what, F f) {
+  for (size_t m = 0; m < e->b->h.size(); ++m)
+    if (int rc = f(e->b->h[m])) return emember_fail(e, static_cast<int32_t>(m), rc, what);
+  return SFW_OK;
 }
 // mode and probabilities: no device call
 int ensemble_check_mode(sfw_ensemble e, int32_t mode, const double *probs, const char *what) {
@@ -4058,11 +4104,28 @@ int ensemble_check_scored(sfw_ensemble e, const char *what) {
   return SFW_OK;
 }
 
-// Every member is staged: one batch launch, the aggregation behind it, one wait (the shape of sfw_ensemble_score_grid)
-int ensemble_launch_and_finish(sfw_ensemble e, int32_t mode, const double *probs, double *costs_out, int32_t *rejected_out,
-                               sfw_best *best_out, const std::string &what) {
+// How every ensemble score begins: the mode, the stage's argument rules (`why`: null, or what they refuse — read before ANY member
+// is staged, so that a refused call leaves the previous score as it was), the members' state; then nothing is scored any more
+int ensemble_score_begin(sfw_ensemble e, const char *what, int32_t mode, const double *probs, const std::string &why) {
+  if (!e) return SFW_ERR_INVALID_ARG;
+  if (int rc = ensemble_check_mode(e, mode, probs, what)) return rc;
+  if (!why.empty()) return efail(e, SFW_ERR_INVALID_ARG, std::string(what) + ": " + why);
+  if (int rc = ensemble_check_members(e, what)) return rc;
+  e->scored = false;
+  if (hipSetDevice(e->device) != hipSuccess) return efail(e, SFW_ERR_HIP, std::string(what) + ": hipSetDevice failed");
+  return SFW_OK;
+}
+// A whole ensemble score (the shape of sfw_ensemble_score_grid): that beginning, the timed loop that stages every member, one batch
+// launch, the aggregation behind it, one wait
+template <typename Stage>
+int ensemble_score(sfw_ensemble e, const std::string &what, int32_t mode, const double *probs, const char *why, Stage stage,
+                   double *costs_out, int32_t *rejected_out, sfw_best *best_out) {
+  if (int rc = ensemble_score_begin(e, what.c_str(), mode, probs, why ? why : "")) return rc;
   const size_t M = e->b->h.size();
   auto t0 = std::chrono::steady_clock::now();
+  if (int rc = ensemble_each(e, (what + ": stage").c_str(), stage)) return rc;
+  e->us[0] = us_since(t0);
+  t0 = std::chrono::steady_clock::now();
   if (int rc = batch_launch(e->b)) return efail(e, rc, what + ": " + e->b->err);
   for (size_t m = 0; m < M; ++m)
     if (!e->b->h[m]->last.terms) return efail(e, SFW_ERR_STATE, what + ": member " + std::to_string(m) + " did not capture terms");
@@ -4099,16 +4162,14 @@ int ensemble_blend(sfw_ensemble e, const char *what, const double *lambda, int32
       return efail(e, SFW_ERR_HIP, std::string(what) + ": cost vector upload failed");
     e->cost_dev = e->d_cost.p;  // (the blend waits for the stream before it returns: the mirror is free again by then)
   }
-  const blend_area area{e->blend_mins, e->blend_partials, e->blend_bias, e->blend_weights, e->pin_blend};
   // gamma == 0: the plain blend (as sfw_grid_blend_control)
   const double *d_bias = nullptr;
   if (gamma && *gamma != 0.0) {
-    if (int rc = control_cost_enqueue(h0, *gamma, bias, nullptr, e->ctrl_bias, e->blend_bias)) return emember_fail(e, 0, rc, what);
-    d_bias = e->ctrl_bias.p;
+    if (int rc = control_cost_enqueue(h0, *gamma, bias, nullptr, e->mppi, e->blend)) return emember_fail(e, 0, rc, what);
+    d_bias = e->mppi.ctrl_bias.p;
     bias = nullptr;
   }
-  if (int rc = blend_run(h0, area, e->cost_dev, e->T, h0->st.list ? h0->st.nk : 1, h0->st.d_linvels, h0->st.d_vy, h0->st.d_angvels,
-                         h0->st.nw, h0->st.list, lambda, L, bias, stat_out, u_out, weights_out, d_bias))
+  if (int rc = blend_run(h0, e->blend, e->cost_dev, e->T, lambda, L, bias, stat_out, u_out, weights_out, d_bias))
     return emember_fail(e, 0, rc, what);
   return SFW_OK;
 }
@@ -4116,45 +4177,36 @@ int ensemble_blend(sfw_ensemble e, const char *what, const double *lambda, int32
 // sfw_ensemble_mppi_run behind its stage of iteration 0: everything enqueued on the batch's stream, one wait, the outputs.  A
 // failure is the caller's to clean up.  The members are lists, so batch_launch builds no member table (each takes its own
 // path); the aggregation's table is uploaded by iteration 0 and read again from the device by the others.
-int ensemble_mppi_chain(sfw_ensemble e, const sfw_perturb *p, int K, int32_t mode, const double *probs, const sfw_mppi *m,
+int ensemble_mppi_chain(sfw_ensemble e, const sfw_perturb *p, int32_t mode, const double *probs, const sfw_mppi *m,
                         sfw_blend_stat *stat_out, double *plans_out, double *costs_out, int32_t *rejected_out, sfw_best *best_out) {
   const char *const what = "ensemble_mppi_run";
   const size_t M = e->b->h.size();
-  const int I = m->iterations;
   sfw_handle h0 = e->b->h[0];
+  const int I = m->iterations, K = h0->st.nk;
   const int64_t n = h0->st.nv;
-  const size_t slot = (blend_slot_bytes(1, K) + 15) & ~size_t(15), plan_bytes = sizeof(double) * 3 * static_cast<size_t>(K);
-  const size_t plan_at = I * slot, dst_at = (plan_at + plan_bytes + 15) & ~size_t(15), dst_bytes = sizeof(sfw_perturb_dst) * M;
-  // every buffer the chain writes is in place before its first kernel is enqueued: nothing in flight is ever freed
-  if (dst_at + dst_bytes > e->pin_mppi.cap && hipStreamSynchronize(e->b->stream) != hipSuccess)
+  const size_t dst_bytes = sizeof(sfw_perturb_dst) * M;
+  const mppi_slots s(I, K, dst_bytes);
+  if (s.bytes > e->mppi.pin_mppi.cap && hipStreamSynchronize(e->b->stream) != hipSuccess)
     return efail(e, SFW_ERR_HIP, std::string(what) + ": hipStreamSynchronize failed");
-  if (e->pin_mppi.reserve(dst_at + dst_bytes) != hipSuccess || e->mppi_plan.reserve(3 * static_cast<size_t>(SFW_SEQ_MAX_KNOTS)) != hipSuccess ||
-      e->pert_dst.reserve(M) != hipSuccess || e->d_cost.reserve(static_cast<size_t>(n)) != hipSuccess ||
-      (m->gamma != 0.0 && e->ctrl_bias.reserve(static_cast<size_t>(n)) != hipSuccess) ||
-      e->blend_mins.reserve(static_cast<size_t>(sfw_blend_min_blocks(n))) != hipSuccess ||
-      e->blend_partials.reserve(static_cast<size_t>(sfw_blend_blocks(n)) * static_cast<size_t>(sfw_blend_channels(1, K))) != hipSuccess)
+  if (mppi_reserve(e->mppi, e->blend, s, K, n, m->gamma != 0.0) != hipSuccess || e->pert_dst.reserve(M) != hipSuccess ||
+      e->d_cost.reserve(static_cast<size_t>(n)) != hipSuccess)
     return efail(e, SFW_ERR_HIP, std::string(what) + ": allocation failed");
-  const blend_area area{e->blend_mins, e->blend_partials, e->blend_bias, e->blend_weights, e->pin_blend};
-  char *const pin = e->pin_mppi.p;
-  std::memcpy(pin + plan_at, p->nominal, plan_bytes);
-  sfw_perturb_dst *const dst = reinterpret_cast<sfw_perturb_dst *>(pin + dst_at);
+  char *const pin = e->mppi.pin_mppi.p;
+  std::memcpy(pin + s.plan_at, p->nominal, s.plan_bytes);
+  sfw_perturb_dst *const dst = reinterpret_cast<sfw_perturb_dst *>(pin + s.extra_at);
   for (size_t k = 0; k < M; ++k) {
     const sfw_handle h = e->b->h[k];
     dst[k] = sfw_perturb_dst{const_cast<double *>(h->st.d_linvels), const_cast<double *>(h->st.d_vy), const_cast<double *>(h->st.d_angvels),
                              h->st.normals_kept ? h->normals.p : nullptr};
   }
-  if (hipMemcpyAsync(e->mppi_plan.p, pin + plan_at, plan_bytes, hipMemcpyHostToDevice, e->b->stream) != hipSuccess ||
+  if (hipMemcpyAsync(e->mppi.mppi_plan.p, pin + s.plan_at, s.plan_bytes, hipMemcpyHostToDevice, e->b->stream) != hipSuccess ||
       hipMemcpyAsync(e->pert_dst.p, dst, dst_bytes, hipMemcpyHostToDevice, e->b->stream) != hipSuccess)
     return efail(e, SFW_ERR_HIP, std::string(what) + ": plan or member table copy failed");
-  double *const plan = e->mppi_plan.p;
+  double *const plan = e->mppi.mppi_plan.p;
   auto t0 = std::chrono::steady_clock::now();
   for (int i = 0; i < I; ++i) {
     if (i > 0) {  // the stage of iteration i: its seed, and every member's knots drawn once around the plan the last update left
-      const uint64_t seed = p->seed + static_cast<uint64_t>(i);
-      for (sfw_handle h : e->b->h) {
-        h->st.pert.key0 = static_cast<uint32_t>(seed & 0xffffffffu);
-        h->st.pert.key1 = static_cast<uint32_t>(seed >> 32);
-      }
+      for (sfw_handle h : e->b->h) perturb_seed(h->st.pert, p->seed + static_cast<uint64_t>(i));
       if (const hipError_t he = sfw_launch_perturb_members(h0->st.pert, plan, n, K, 0, e->pert_dst.p, static_cast<int>(M), e->b->stream);
           he != hipSuccess)
         return efail(e, SFW_ERR_HIP, std::string(what) + ": sfw_perturb_members_kernel: " + hipGetErrorString(he));
@@ -4165,23 +4217,19 @@ int ensemble_mppi_chain(sfw_ensemble e, const sfw_perturb *p, int K, int32_t mod
     if (int rc = ensemble_enqueue(e, mode, probs, i > 0)) return rc;
     const double *d_bias = nullptr;
     if (m->gamma != 0.0) {  // (as sfw_ensemble_blend_control: gamma == 0 is the plain blend)
-      if (int rc = control_cost_enqueue(h0, m->gamma, nullptr, plan, e->ctrl_bias, e->blend_bias)) return emember_fail(e, 0, rc, what);
-      d_bias = e->ctrl_bias.p;
+      if (int rc = control_cost_enqueue(h0, m->gamma, nullptr, plan, e->mppi, e->blend)) return emember_fail(e, 0, rc, what);
+      d_bias = e->mppi.ctrl_bias.p;
     }
-    if (int rc = blend_enqueue(h0, area, e->cost_dev, n, K, h0->st.d_linvels, h0->st.d_vy, h0->st.d_angvels, 1, true, &m->lambda, 1,
-                               d_bias, nullptr, pin + i * slot, plan))
+    if (int rc = blend_enqueue(h0, e->blend, e->cost_dev, n, &m->lambda, 1, d_bias, nullptr, pin + i * s.slot, plan))
       return emember_fail(e, 0, rc, what);
   }
-  if (e->pin_mppi.mark(e->b->stream) != hipSuccess) return efail(e, SFW_ERR_HIP, std::string(what) + ": hipEventRecord failed");
+  if (e->mppi.pin_mppi.mark(e->b->stream) != hipSuccess) return efail(e, SFW_ERR_HIP, std::string(what) + ": hipEventRecord failed");
   e->us[1] = us_since(t0);
   t0 = std::chrono::steady_clock::now();
   if (int rc = batch_fetch(e->b, nullptr)) return efail(e, rc, std::string(what) + ": " + e->b->err);  // THE wait, all members
-  e->pin_mppi.pending = false;
+  e->mppi.pin_mppi.pending = false;
   if (int rc = ensemble_finish(e, costs_out, rejected_out, best_out)) return rc;
-  for (int i = 0; i < I; ++i) blend_finish(pin + i * slot, &m->lambda, 1, K, stat_out + i, plans_out + static_cast<size_t>(i) * 3 * K);
-  // the stage every member holds is iteration I - 1's: drawn around nom_(I-1)
-  if (I > 1)
-    for (sfw_handle h : e->b->h) std::memcpy(h->st.pert.nominal, plans_out + static_cast<size_t>(I - 2) * 3 * K, plan_bytes);
+  mppi_finish(s, pin, m, K, stat_out, plans_out, e->b->h.data(), M);
   e->us[2] = us_since(t0);
   for (size_t k = 0; k < M; ++k) e->seq[k] = e->b->h[k]->launch_seq;
   e->scored = true;
@@ -4223,15 +4271,9 @@ int sfw_ensemble_destroy(sfw_ensemble e) {
   e->d_out.release();
   e->partials.release();
   e->d_cost.release();
-  e->blend_mins.release();
-  e->blend_partials.release();
-  e->blend_bias.release();
-  e->blend_weights.release();
-  e->pin_blend.release();
-  e->ctrl_bias.release();
-  e->mppi_plan.release();
+  e->blend.release();
+  e->mppi.release();
   e->pert_dst.release();
-  e->pin_mppi.release();
   delete e;
   return SFW_OK;
 }
@@ -4245,8 +4287,7 @@ sfw_handle sfw_ensemble_member(sfw_ensemble e, int32_t m) { return e ? sfw_batch
 int sfw_ensemble_set_params(sfw_ensemble e, const sfw_params *params) {
   if (!e) return SFW_ERR_INVALID_ARG;
   if (int rc = check_params(nullptr, params)) return efail(e, rc, "ensemble_set_params: invalid parameters");
-  for (size_t m = 0; m < e->b->h.size(); ++m)
-    if (int rc = sfw_set_params(e->b->h[m], params)) return emember_fail(e, static_cast<int32_t>(m), rc, "ensemble_set_params");
+  if (int rc = ensemble_each(e, "ensemble_set_params", [&](sfw_handle h) { return sfw_set_params(h, params); })) return rc;
   e->params = *params;
   return SFW_OK;
 }
@@ -4254,17 +4295,13 @@ int sfw_ensemble_set_params(sfw_ensemble e, const sfw_params *params) {
 int sfw_ensemble_set_costmap(sfw_ensemble e, const uint8_t *cells, uint32_t size_x, uint32_t size_y, double origin_x,
                              double origin_y, double resolution) {
   if (!e) return SFW_ERR_INVALID_ARG;
-  for (size_t m = 0; m < e->b->h.size(); ++m)
-    if (int rc = sfw_set_costmap(e->b->h[m], cells, size_x, size_y, origin_x, origin_y, resolution))
-      return emember_fail(e, static_cast<int32_t>(m), rc, "ensemble_set_costmap");
-  return SFW_OK;
+  return ensemble_each(e, "ensemble_set_costmap",
+                       [&](sfw_handle h) { return sfw_set_costmap(h, cells, size_x, size_y, origin_x, origin_y, resolution); });
 }
 
 int sfw_ensemble_set_footprint(sfw_ensemble e, const double *xy, int32_t K) {
   if (!e) return SFW_ERR_INVALID_ARG;
-  for (size_t m = 0; m < e->b->h.size(); ++m)
-    if (int rc = sfw_set_footprint(e->b->h[m], xy, K)) return emember_fail(e, static_cast<int32_t>(m), rc, "ensemble_set_footprint");
-  return SFW_OK;
+  return ensemble_each(e, "ensemble_set_footprint", [&](sfw_handle h) { return sfw_set_footprint(h, xy, K); });
 }
 
 int sfw_ensemble_set_hypothesis(sfw_ensemble e, int32_t m, const sfw_agent *agents, int32_t A, const double *obstacles_xy,
@@ -4280,62 +4317,32 @@ int sfw_ensemble_set_hypothesis(sfw_ensemble e, int32_t m, const sfw_agent *agen
 int sfw_ensemble_score_grid(sfw_ensemble e, const sfw_robot_state *rs, const double *linvels, int32_t nv, const double *angvels,
                             int32_t nw, const sfw_goal_args *args, int32_t mode, const double *probs, double *costs_out,
                             int32_t *rejected_out, sfw_best *best_out) {
-  if (!e) return SFW_ERR_INVALID_ARG;
-  if (int rc = ensemble_check_mode(e, mode, probs, "ensemble_score_grid")) return rc;
-  if (!rs || !args || !linvels || !angvels || nv <= 0 || nw <= 0)
-    return efail(e, SFW_ERR_INVALID_ARG, "ensemble_score_grid: null robot state, goal arguments or sample vectors");
-  const char *const what = "ensemble_score_grid";
-  if (int rc = ensemble_check_members(e, what)) return rc;
-  e->scored = false;
-  if (hipSetDevice(e->device) != hipSuccess) return efail(e, SFW_ERR_HIP, "ensemble_score_grid: hipSetDevice failed");
-  const auto t0 = std::chrono::steady_clock::now();
-  for (size_t m = 0; m < e->b->h.size(); ++m)
-    if (int rc = sfw_grid_stage(e->b->h[m], rs, linvels, nv, angvels, nw, args, 0))
-      return emember_fail(e, static_cast<int32_t>(m), rc, "ensemble_score_grid: stage");
-  e->us[0] = us_since(t0);
-  return ensemble_launch_and_finish(e, mode, probs, costs_out, rejected_out, best_out, what);
+  const char *const why =
+      !rs || !args || !linvels || !angvels || nv <= 0 || nw <= 0 ? "null robot state, goal arguments or sample vectors" : nullptr;
+  return ensemble_score(
+      e, "ensemble_score_grid", mode, probs, why, [&](sfw_handle h) { return sfw_grid_stage(h, rs, linvels, nv, angvels, nw, args, 0); },
+      costs_out, rejected_out, best_out);
 }
 
 int sfw_ensemble_score_sequences(sfw_ensemble e, const sfw_robot_state *rs, const double *vx, const double *vy, const double *vtheta,
                                  int32_t n, int32_t K, const int32_t *knot_step, const sfw_goal_args *args, int32_t mode,
                                  const double *probs, double *costs_out, int32_t *rejected_out, sfw_best *best_out) {
-  if (!e) return SFW_ERR_INVALID_ARG;
-  const char *const what = "ensemble_score_sequences";
-  if (int rc = ensemble_check_mode(e, mode, probs, what)) return rc;
-  // (the stage's argument rules, before any member is staged: a refused call leaves the previous score as it was)
   const char *why = sequences_refusal(K, knot_step);
-  if (!why) why = list_stage_refusal(rs, vx, vy, vtheta, n, static_cast<size_t>(K), args, false);
-  if (why) return efail(e, SFW_ERR_INVALID_ARG, std::string(what) + ": " + why);
-  if (int rc = ensemble_check_members(e, what)) return rc;
-  e->scored = false;
-  if (hipSetDevice(e->device) != hipSuccess) return efail(e, SFW_ERR_HIP, std::string(what) + ": hipSetDevice failed");
-  const auto t0 = std::chrono::steady_clock::now();
-  for (size_t m = 0; m < e->b->h.size(); ++m)
-    if (int rc = sfw_sequences_stage(e->b->h[m], rs, vx, vy, vtheta, n, K, knot_step, args, 0))
-      return emember_fail(e, static_cast<int32_t>(m), rc, "ensemble_score_sequences: stage");
-  e->us[0] = us_since(t0);
-  return ensemble_launch_and_finish(e, mode, probs, costs_out, rejected_out, best_out, what);
+  if (!why) why = list_stage_refusal(rs, args, sequences_request(vx, vy, vtheta, n, K, knot_step, 0));
+  return ensemble_score(
+      e, "ensemble_score_sequences", mode, probs, why,
+      [&](sfw_handle h) { return sfw_sequences_stage(h, rs, vx, vy, vtheta, n, K, knot_step, args, 0); }, costs_out, rejected_out, best_out);
 }
 
 int sfw_ensemble_score_perturbed(sfw_ensemble e, const sfw_robot_state *rs, const sfw_perturb *p, int32_t n, int32_t K,
                                  const int32_t *knot_step, const sfw_goal_args *args, int32_t mode, const double *probs,
                                  double *costs_out, int32_t *rejected_out, sfw_best *best_out) {
-  if (!e) return SFW_ERR_INVALID_ARG;
-  const char *const what = "ensemble_score_perturbed";
-  if (int rc = ensemble_check_mode(e, mode, probs, what)) return rc;
   const char *why = perturb_refusal(rs, p, n, K, knot_step, args, 0);
-  if (!why) why = list_stage_refusal(rs, nullptr, nullptr, nullptr, n, static_cast<size_t>(K), args, true);
-  if (why) return efail(e, SFW_ERR_INVALID_ARG, std::string(what) + ": " + why);
-  if (int rc = ensemble_check_members(e, what)) return rc;
-  e->scored = false;
-  if (hipSetDevice(e->device) != hipSuccess) return efail(e, SFW_ERR_HIP, std::string(what) + ": hipSetDevice failed");
-  const auto t0 = std::chrono::steady_clock::now();
+  if (!why) why = list_stage_refusal(rs, args, perturbed_request(nullptr, n, K, knot_step, 0));
   // (every member draws the knots itself: a function of (seed, index, knot, channel) alone, so bitwise the same M times)
-  for (size_t m = 0; m < e->b->h.size(); ++m)
-    if (int rc = sfw_sequences_perturb_stage(e->b->h[m], rs, p, n, K, knot_step, args, 0))
-      return emember_fail(e, static_cast<int32_t>(m), rc, "ensemble_score_perturbed: stage");
-  e->us[0] = us_since(t0);
-  return ensemble_launch_and_finish(e, mode, probs, costs_out, rejected_out, best_out, what);
+  return ensemble_score(
+      e, "ensemble_score_perturbed", mode, probs, why,
+      [&](sfw_handle h) { return sfw_sequences_perturb_stage(h, rs, p, n, K, knot_step, args, 0); }, costs_out, rejected_out, best_out);
 }
 
 int sfw_ensemble_blend(sfw_ensemble e, const double *lambda, int32_t L, const double *bias, sfw_blend_stat *stat_out, double *u_out,
@@ -4351,30 +4358,20 @@ int sfw_ensemble_blend_control(sfw_ensemble e, const double *lambda, int32_t L, 
 int sfw_ensemble_mppi_run(sfw_ensemble e, const sfw_robot_state *rs, const sfw_perturb *p, int32_t n, int32_t K, const int32_t *knot_step,
                           const sfw_goal_args *args, int32_t mode, const double *probs, const sfw_mppi *m, sfw_blend_stat *stat_out,
                           double *plans_out, double *costs_out, int32_t *rejected_out, sfw_best *best_out) {
-  if (!e) return SFW_ERR_INVALID_ARG;
-  const char *const what = "ensemble_mppi_run";
-  if (int rc = ensemble_check_mode(e, mode, probs, what)) return rc;
-  if (!m || m->iterations < 1 || m->iterations > SFW_MPPI_MAX_ITER || m->reserved != 0)
-    return efail(e, SFW_ERR_INVALID_ARG, std::string(what) + ": m is NULL, iterations outside 1..SFW_MPPI_MAX_ITER, or reserved != 0");
-  if (!std::isfinite(m->lambda) || !(m->lambda > 0.0) || !std::isfinite(m->gamma))
-    return efail(e, SFW_ERR_INVALID_ARG, std::string(what) + ": lambda is not finite or not > 0, or gamma is not finite");
-  if (!stat_out || !plans_out) return efail(e, SFW_ERR_INVALID_ARG, std::string(what) + ": stat_out or plans_out is NULL");
-  const char *why = perturb_refusal(rs, p, n, K, knot_step, args, 0);
-  if (!why) why = list_stage_refusal(rs, nullptr, nullptr, nullptr, n, static_cast<size_t>(K), args, true);
-  if (why) return efail(e, SFW_ERR_INVALID_ARG, std::string(what) + ": " + why);
-  if (int rc = ensemble_check_members(e, what)) return rc;
-  e->scored = false;
-  if (hipSetDevice(e->device) != hipSuccess) return efail(e, SFW_ERR_HIP, std::string(what) + ": hipSetDevice failed");
+  std::string why;
+  if (const char *w = mppi_refusal(m)) why = std::string(w == kMppiIterations ? "m is NULL, " : "") + w;
+  else if (!stat_out || !plans_out) why = "stat_out or plans_out is NULL";
+  else if (const char *w = perturb_refusal(rs, p, n, K, knot_step, args, 0)) why = w;
+  else if (const char *w = list_stage_refusal(rs, args, perturbed_request(nullptr, n, K, knot_step, 0))) why = w;
+  if (int rc = ensemble_score_begin(e, "ensemble_mppi_run", mode, probs, why)) return rc;
   const auto t0 = std::chrono::steady_clock::now();
-  int rc = SFW_OK;
   // iteration 0's stage: sfw_ensemble_score_perturbed's
-  for (size_t k = 0; k < e->b->h.size() && rc == SFW_OK; ++k)
-    if ((rc = sfw_sequences_perturb_stage(e->b->h[k], rs, p, n, K, knot_step, args, 0)) != SFW_OK)
-      (void)emember_fail(e, static_cast<int32_t>(k), rc, "ensemble_mppi_run: stage");
+  int rc = ensemble_each(e, "ensemble_mppi_run: stage",
+                         [&](sfw_handle h) { return sfw_sequences_perturb_stage(h, rs, p, n, K, knot_step, args, 0); });
   e->us[0] = us_since(t0);
-  if (rc == SFW_OK) rc = ensemble_mppi_chain(e, p, K, mode, probs, m, stat_out, plans_out, costs_out, rejected_out, best_out);
+  if (rc == SFW_OK) rc = ensemble_mppi_chain(e, p, mode, probs, m, stat_out, plans_out, costs_out, rejected_out, best_out);
   if (rc != SFW_OK) {  // nothing scored, and no member left staged or launched
-    if (e->pin_mppi.done) (void)e->pin_mppi.mark(e->b->stream);  // (kernels of the chain may still be writing there)
+    if (e->mppi.pin_mppi.done) (void)e->mppi.pin_mppi.mark(e->b->stream);  // (kernels of the chain may still be writing there)
     for (sfw_handle h : e->b->h) drop_stage(h);
   }
   return rc;

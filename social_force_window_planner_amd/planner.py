@@ -52,8 +52,8 @@ class SfwError(RuntimeError):
 def build(force=False):
     """Compile the HIP library in-tree for gfx950 (hipcc cross-compiles on CPU)."""
     csrc = os.path.join(_HERE, "csrc")
-    srcs = [os.path.join(csrc, f) for f in ("sfw_capi.hip", "sfw_kernels.hip", "sfw_kernels_strict.hip", "sfw_device.h", "sfw_math.h")]
-    srcs.append(os.path.join(_HERE, "..", "include", "sfw_hip.h"))
+    # (everything the Makefile compiles or includes, and the Makefile itself)
+    srcs = [os.path.join(csrc, f) for f in os.listdir(csrc)] + [os.path.join(_HERE, "..", "include", "sfw_hip.h")]
     stale = (not os.path.exists(LIB_PATH)) or any(
         os.path.getmtime(LIB_PATH) < os.path.getmtime(s) for s in srcs)
     if force or stale:
@@ -203,9 +203,73 @@ def _f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
 
 
-class HipScorer:
+class _Owner:
+    """What the owners of a library object share.  A subclass names the attribute that holds its object (_attr) and the
+    library's calls that destroy it and read its last error; members (views of handles the object owns) are closed first."""
+    _members = ()
+
+    def close(self):
+        if getattr(self, self._attr, None):
+            for m in self._members:
+                m.close()
+            getattr(lib(), self._destroy)(getattr(self, self._attr))
+            setattr(self, self._attr, C.c_void_p())
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc, what):
+        if rc != SFW_OK:
+            raise SfwError(rc, what, (getattr(lib(), self._last_error)(getattr(self, self._attr)) or b"").decode())
+
+
+def _blend(check, fn, fn_control, handle, T, K, lambdas, bias, want_weights, gamma):
+    """One blend call marshalled (HipScorer.blend, EnsembleScorer.blend): fn without gamma, fn_control with it, over T samples
+    of K knots.  Returns (stats, u[L, K, 3], weights[L, T] or None)."""
+    lam = np.ascontiguousarray(np.asarray(lambdas, dtype=np.float64).reshape(-1))
+    L = len(lam)
+    if L < 1 or L > SFW_BLEND_MAX_L:
+        raise ValueError(f"blend: need 1 .. {SFW_BLEND_MAX_L} lambdas, got {L}")
+    if not np.all(np.isfinite(lam)) or not np.all(lam > 0.0):
+        raise ValueError("blend: every lambda must be finite and > 0")
+    b = None
+    if bias is not None:
+        b = np.ascontiguousarray(np.asarray(bias, dtype=np.float64).reshape(-1))
+        if len(b) != T:
+            raise ValueError(f"blend: bias must hold one value per sample ({T}), got {len(b)}")
+    stats = (SfwBlendStat * L)()
+    u = np.zeros((L, K, 3), dtype=np.float64)
+    w = np.zeros((L, T), dtype=np.float64) if want_weights else None
+    bp, wp = b.ctypes.data if b is not None and T else None, w.ctypes.data if w is not None and T else None
+    if gamma is None:
+        check(fn(handle, lam.ctypes.data, L, bp, stats, u.ctypes.data, wp), fn.__name__)
+    else:
+        check(fn_control(handle, lam.ctypes.data, L, float(gamma), bp, stats, u.ctypes.data, wp), fn_control.__name__)
+    return [stats[l].as_dict() for l in range(L)], u, w
+
+
+def _mppi_args(robot_state, n, seed, nominal, sigma, lo, hi, knot_steps, goal_args, iterations, lam, gamma, flags):
+    """What both mppi_runs hand the library: (the arguments up to goal_args, those from the sfw_mppi on, K, I, stats, plans,
+    and what has to stay alive for the duration of the call)."""
+    p, nom, ks = HipScorer._perturb(seed, nominal, sigma, lo, hi, knot_steps, flags)
+    rs, ga = SfwRobotState(*robot_state), SfwGoalArgs(*goal_args)
+    K, I = nom.shape[0], int(iterations)
+    m = SfwMppi(I, 0, float(lam), float(gamma))
+    room = min(max(I, 1), SFW_MPPI_MAX_ITER)  # (a refused iteration count writes nothing)
+    stats = (SfwBlendStat * room)()
+    plans = np.zeros((room, K, 3), dtype=np.float64)
+    head = (C.byref(rs), C.byref(p), n, K, ks.ctypes.data if len(ks) else None, C.byref(ga))
+    return head, (C.byref(m), stats, plans.ctypes.data), K, I, stats, plans, (p, nom, ks, rs, ga, m)
+
+
+class HipScorer(_Owner):
     """The (v,w) grid scorer on one MI355X.  Method-for-method the same surface
     as the CPU checker's scorer class under oracle/ (which this package never imports)."""
+
+    _attr, _destroy, _last_error = "_h", "sfw_destroy", "sfw_last_error"
 
     def __init__(self, params: SfwParams | None = None, device: int = 0):
         self.params = params if params is not None else default_params()
@@ -240,19 +304,7 @@ class HipScorer:
         if getattr(self, "_owner", None) is not None:
             self._h = C.c_void_p()
             return
-        if getattr(self, "_h", None):
-            lib().sfw_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc, what):
-        if rc != SFW_OK:
-            raise SfwError(rc, what, (lib().sfw_last_error(self._h) or b"").decode())
+        super().close()
 
     # -- world state -------------------------------------------------------
     def set_params(self, params):
@@ -597,30 +649,11 @@ class HipScorer:
         (vx, vy, vtheta) knots; weights[L, T] or None).  Read-only for the launch.
         gamma (a perturbed stage only): sfw_grid_blend_control — gamma times the control cost of every sample's perturbation
         (control_cost) joins the bias on the device."""
-        lam = np.ascontiguousarray(np.asarray(lambdas, dtype=np.float64).reshape(-1))
-        L = len(lam)
-        if L < 1 or L > SFW_BLEND_MAX_L:
-            raise ValueError(f"blend: need 1 .. {SFW_BLEND_MAX_L} lambdas, got {L}")
-        if not np.all(np.isfinite(lam)) or not np.all(lam > 0.0):
-            raise ValueError("blend: every lambda must be finite and > 0")
         # (no grid staged through this object, e.g. since sfw_score_one: the library answers SFW_ERR_STATE)
         nv, nw = self._grid if self._grid is not None else (0, 0)
-        T, K = nv * nw, getattr(self, "_n_knots", 1) if self._grid is not None else 64  # (SFW_SEQ_MAX_KNOTS: room for any stage)
-        b = None
-        if bias is not None:
-            b = np.ascontiguousarray(np.asarray(bias, dtype=np.float64).reshape(-1))
-            if len(b) != T:
-                raise ValueError(f"blend: bias must hold one value per sample ({T}), got {len(b)}")
-        stats = (SfwBlendStat * L)()
-        u = np.zeros((L, K, 3), dtype=np.float64)
-        w = np.zeros((L, T), dtype=np.float64) if want_weights else None
-        bp, wp = b.ctypes.data if b is not None and T else None, w.ctypes.data if w is not None and T else None
-        if gamma is None:
-            self._check(lib().sfw_grid_blend(self._h, lam.ctypes.data, L, bp, stats, u.ctypes.data, wp), "sfw_grid_blend")
-        else:
-            self._check(lib().sfw_grid_blend_control(self._h, lam.ctypes.data, L, float(gamma), bp, stats, u.ctypes.data, wp),
-                        "sfw_grid_blend_control")
-        return [stats[l].as_dict() for l in range(L)], u, w
+        K = getattr(self, "_n_knots", 1) if self._grid is not None else 64  # (SFW_SEQ_MAX_KNOTS: room for any stage)
+        return _blend(self._check, lib().sfw_grid_blend, lib().sfw_grid_blend_control, self._h, nv * nw, K, lambdas, bias,
+                      want_weights, gamma)
 
     # -- MPPI on the device: the control cost, chained iterations ----------------
     def control_cost(self, gamma):
@@ -636,16 +669,10 @@ class HipScorer:
         nominal, chained on the device behind one wait.  Returns (stats: one dict per iteration; plans[I, K, 3]: the nominal
         plan after every iteration; best of the last iteration).  The scorer is left as after the last iteration's
         score_perturbed."""
-        p, nom, ks = self._perturb(seed, nominal, sigma, lo, hi, knot_steps, flags)
-        rs, ga = SfwRobotState(*robot_state), SfwGoalArgs(*goal_args)
-        K, I = nom.shape[0], int(iterations)
-        m = SfwMppi(I, 0, float(lam), float(gamma))
-        room = min(max(I, 1), SFW_MPPI_MAX_ITER)  # (a refused iteration count writes nothing)
-        stats = (SfwBlendStat * room)()
-        plans = np.zeros((room, K, 3), dtype=np.float64)
+        head, tail, K, I, stats, plans, _alive = _mppi_args(robot_state, n, seed, nominal, sigma, lo, hi, knot_steps, goal_args,
+                                                            iterations, lam, gamma, flags)
         best = SfwBest()
-        self._check(lib().sfw_mppi_run(self._h, C.byref(rs), C.byref(p), n, K, ks.ctypes.data if len(ks) else None, C.byref(ga),
-                                       C.byref(m), stats, plans.ctypes.data, C.byref(best)), "sfw_mppi_run")
+        self._check(lib().sfw_mppi_run(self._h, *head, *tail, C.byref(best)), "sfw_mppi_run")
         self._mark_staged((n, 1), knots=K)
         return [stats[i].as_dict() for i in range(I)], plans, best.as_dict()
 
@@ -745,10 +772,12 @@ class PreparedGrid:
         return None, self.best.as_dict(), self.key.as_tuple()
 
 
-class MultiScorer:
+class MultiScorer(_Owner):
     """sfw_multi_*: one process driving one handle per listed device (rows of the grid split over them, one
     RCCL all-reduce(min) of the [R,5] key table).  exchange = SFW_MULTI_HOST_REDUCE lets a device be listed
     more than once (tests on a one-GPU box)."""
+
+    _attr, _destroy, _last_error = "_m", "sfw_multi_destroy", "sfw_multi_last_error"
 
     def __init__(self, params=None, devices=(0,), exchange=0):
         self.params = params if params is not None else default_params()
@@ -758,21 +787,6 @@ class MultiScorer:
         if rc != SFW_OK:
             raise SfwError(rc, "sfw_multi_create", (lib().sfw_multi_last_error(None) or b"").decode())
         self.n_ranks = lib().sfw_multi_ranks(self._m)
-
-    def close(self):
-        if getattr(self, "_m", None):
-            lib().sfw_multi_destroy(self._m)
-            self._m = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc, what):
-        if rc != SFW_OK:
-            raise SfwError(rc, what, (lib().sfw_multi_last_error(self._m) or b"").decode())
 
     def load_scene(self, scene):
         cells = np.ascontiguousarray(scene.cells, dtype=np.uint8)
@@ -838,10 +852,12 @@ class MultiScorer:
         return pts[: min(n.value, points_cap)].copy()
 
 
-class BatchScorer:
+class BatchScorer(_Owner):
     """B planners on one MI355X whose control cycles are scored together (sfw_batch_*): one launch of the batched cycle
     kernel per kernel variant for the members that qualify, the others on their usual path on the same stream.  Each
     member's results are bit-identical to scoring it alone."""
+
+    _attr, _destroy, _last_error = "_b", "sfw_batch_destroy", "sfw_batch_last_error"
 
     def __init__(self, params: SfwParams | None = None, device: int = 0, B: int = 1):
         self.params = params if params is not None else default_params()
@@ -853,23 +869,6 @@ class BatchScorer:
             raise SfwError(rc, "sfw_batch_create")
         self.B = B
         self._members = [HipScorer._member_view(lib().sfw_batch_member(self._b, i), self.params, self) for i in range(B)]
-
-    def close(self):
-        if getattr(self, "_b", None):
-            for m in self._members:
-                m.close()
-            lib().sfw_batch_destroy(self._b)
-            self._b = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc, what):
-        if rc != SFW_OK:
-            raise SfwError(rc, what, (lib().sfw_batch_last_error(self._b) or b"").decode())
 
     def member(self, i):
         """Member i as a HipScorer that does not own its handle (world state, staging, single-member scoring, points)."""
@@ -923,11 +922,13 @@ class BatchScorer:
 _ENSEMBLE_MODES = {"mean": SFW_ENSEMBLE_MEAN, "max": SFW_ENSEMBLE_MAX}
 
 
-class EnsembleScorer:
+class EnsembleScorer(_Owner):
     """One robot's grid under M crowd hypotheses (sfw_ensemble_*): every hypothesis is scored as a standalone handle would
     score it, in one batch launch, and the per-sample social work is aggregated on the device — "mean" (probability-weighted
     sum, probs default 1/M each) or "max" (worst case).  A sample any hypothesis rejects is rejected; `rejected` counts the
     hypotheses that reject each sample."""
+
+    _attr, _destroy, _last_error = "_e", "sfw_ensemble_destroy", "sfw_ensemble_last_error"
 
     def __init__(self, params: SfwParams | None = None, device: int = 0, M: int = 1):
         self.params = params if params is not None else default_params()
@@ -940,23 +941,6 @@ class EnsembleScorer:
         self.M = M
         self._grid = None
         self._members = [HipScorer._member_view(lib().sfw_ensemble_member(self._e, m), self.params, self) for m in range(M)]
-
-    def close(self):
-        if getattr(self, "_e", None):
-            for m in self._members:
-                m.close()
-            lib().sfw_ensemble_destroy(self._e)
-            self._e = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc, what):
-        if rc != SFW_OK:
-            raise SfwError(rc, what, (lib().sfw_ensemble_last_error(self._e) or b"").decode())
 
     def member(self, m):
         """Hypothesis m's handle as a HipScorer that does not own it (its costs, captured terms, points)."""
@@ -1090,29 +1074,9 @@ class EnsembleScorer:
         (stats, u[L, K, 3], weights[L, n] or None).
         gamma (after score_perturbed or mppi_run only): sfw_ensemble_blend_control — gamma times the control cost of every
         sample's perturbation joins the bias on the device."""
-        lam = np.ascontiguousarray(np.asarray(lambdas, dtype=np.float64).reshape(-1))
-        L = len(lam)
-        if L < 1 or L > SFW_BLEND_MAX_L:
-            raise ValueError(f"blend: need 1 .. {SFW_BLEND_MAX_L} lambdas, got {L}")
-        if not np.all(np.isfinite(lam)) or not np.all(lam > 0.0):
-            raise ValueError("blend: every lambda must be finite and > 0")
         nv, nw = self._grid if self._grid is not None else (0, 0)  # (nothing scored: the library answers SFW_ERR_STATE)
-        T, K = nv * nw, getattr(self, "_n_knots", 1)
-        b = None
-        if bias is not None:
-            b = np.ascontiguousarray(np.asarray(bias, dtype=np.float64).reshape(-1))
-            if len(b) != T:
-                raise ValueError(f"blend: bias must hold one value per sample ({T}), got {len(b)}")
-        stats = (SfwBlendStat * L)()
-        u = np.zeros((L, K, 3), dtype=np.float64)
-        w = np.zeros((L, T), dtype=np.float64) if want_weights else None
-        bp, wp = b.ctypes.data if b is not None and T else None, w.ctypes.data if w is not None and T else None
-        if gamma is None:
-            self._check(lib().sfw_ensemble_blend(self._e, lam.ctypes.data, L, bp, stats, u.ctypes.data, wp), "sfw_ensemble_blend")
-        else:
-            self._check(lib().sfw_ensemble_blend_control(self._e, lam.ctypes.data, L, float(gamma), bp, stats, u.ctypes.data, wp),
-                        "sfw_ensemble_blend_control")
-        return [stats[l].as_dict() for l in range(L)], u, w
+        return _blend(self._check, lib().sfw_ensemble_blend, lib().sfw_ensemble_blend_control, self._e, nv * nw,
+                      getattr(self, "_n_knots", 1), lambdas, bias, want_weights, gamma)
 
     def mppi_run(self, robot_state, n, seed, nominal, sigma, lo, hi, knot_steps, goal_args, iterations, lam, gamma, flags=0,
                  mode="mean", probs=None, want_costs=False):
@@ -1120,20 +1084,14 @@ class EnsembleScorer:
         members -> aggregate -> control cost -> blend at temperature lam -> new nominal, chained on the device behind one wait.
         Returns (stats: one dict per iteration; plans[I, K, 3]; best of the last iteration), and with want_costs also the last
         iteration's costs[n] and rejected[n].  The ensemble is left as after the last iteration's score_perturbed."""
-        pt, nom, ks = HipScorer._perturb(seed, nominal, sigma, lo, hi, knot_steps, flags)
-        rs, ga = SfwRobotState(*robot_state), SfwGoalArgs(*goal_args)
+        head, tail, K, I, stats, plans, _alive = _mppi_args(robot_state, n, seed, nominal, sigma, lo, hi, knot_steps, goal_args,
+                                                            iterations, lam, gamma, flags)
         p = self._checked_probs(probs, "mppi_run")
-        K, I = nom.shape[0], int(iterations)
-        m = SfwMppi(I, 0, float(lam), float(gamma))
-        room = min(max(I, 1), SFW_MPPI_MAX_ITER)  # (a refused iteration count writes nothing)
-        stats = (SfwBlendStat * room)()
-        plans = np.zeros((room, K, 3), dtype=np.float64)
         costs, rejected, best = self._outputs((max(n, 0), 1))
         out = want_costs and n > 0
-        self._check(lib().sfw_ensemble_mppi_run(self._e, C.byref(rs), C.byref(pt), n, K, ks.ctypes.data if len(ks) else None,
-                                                C.byref(ga), self._mode(mode), p.ctypes.data if p is not None else None, C.byref(m),
-                                                stats, plans.ctypes.data, costs.ctypes.data if out else None,
-                                                rejected.ctypes.data if out else None, C.byref(best)), "sfw_ensemble_mppi_run")
+        self._check(lib().sfw_ensemble_mppi_run(self._e, *head, self._mode(mode), p.ctypes.data if p is not None else None, *tail,
+                                                costs.ctypes.data if out else None, rejected.ctypes.data if out else None,
+                                                C.byref(best)), "sfw_ensemble_mppi_run")
         self._mark_scored((n, 1), knots=K)
         res = ([stats[i].as_dict() for i in range(I)], plans, best.as_dict())
         return res + (costs, rejected) if want_costs else res

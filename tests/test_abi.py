@@ -9,14 +9,9 @@ import pytest
 from social_force_window_planner_amd import planner
 from social_force_window_planner_amd._abi import (EXPORTED_SYMBOLS, SFW_ERR_INVALID_ARG, SFW_ERR_NO_DEVICE, SFW_OK,
                                                    SfwParams, default_params)
+from sfw_test_util import _gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _gpu():
-    import torch
-
-    return torch.cuda.is_available()
 
 
 def test_header_symbols_all_exported():

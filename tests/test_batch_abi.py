@@ -11,16 +11,11 @@ import pytest
 from social_force_window_planner_amd import planner
 from social_force_window_planner_amd._abi import (EXPORTED_SYMBOLS, SFW_BATCH_MAX, SFW_ERR_INVALID_ARG, SFW_ERR_NO_DEVICE,
                                                    SFW_OK, SfwBatchDesc, default_params)
+from sfw_test_util import _gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BATCH_SYMBOLS = ("sfw_batch_create", "sfw_batch_destroy", "sfw_batch_last_error", "sfw_batch_size", "sfw_batch_member",
                  "sfw_batch_launch", "sfw_batch_fetch", "sfw_batch_score_grid", "sfw_batch_describe", "sfw_batch_last_us")
-
-
-def _gpu():
-    import torch
-
-    return torch.cuda.is_available()
 
 
 def test_batch_symbols_declared_and_exported():

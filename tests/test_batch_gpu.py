@@ -9,16 +9,13 @@ import pytest
 from social_force_window_planner_amd import synthetic as syn
 from social_force_window_planner_amd._abi import (SFW_ERR_STATE, SFW_OK, SFW_PRECISION_F32, SFW_PRECISION_F64,
                                                    SFW_PRECISION_F64_STRICT, default_params)
+from sfw_test_util import _same
 
 pytestmark = pytest.mark.gpu
 
 # (people, laser points, nv, nw, steps, groups)
 MIX = [(5, 0, 5, 9, 40, False), (0, 16, 3, 7, 6, False), (20, 60, 5, 9, 40, True), (1, 0, 32, 32, 6, False),
        (50, 240, 5, 9, 1, False), (62, 0, 3, 7, 40, False), (8, 16, 5, 9, 6, True)]
-
-
-def _same(a, b):
-    return np.array_equal(np.asarray(a, dtype=np.float64).view(np.uint64), np.asarray(b, dtype=np.float64).view(np.uint64))
 
 
 @dataclasses.dataclass

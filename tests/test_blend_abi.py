@@ -18,15 +18,12 @@ import pytest
 from social_force_window_planner_amd import blend, planner
 from social_force_window_planner_amd._abi import (EXPORTED_SYMBOLS, SFW_BLEND_MAX_L, SFW_COST_INVALID, SFW_COST_SKIPPED,
                                                    SFW_ERR_INVALID_ARG, SfwBlendStat)
+from sfw_test_util import _header
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 U = 2.0 ** -53
 SIZES = [1, 63, 64, 65, blend.C - 1, blend.C, blend.C + 1, 2 * blend.C + 3, 40000]
 LAMBDAS = [0.05, 1.0, 30.0]
-
-
-def _header():
-    return open(os.path.join(ROOT, "include", "sfw_hip.h")).read()
 
 
 def _gamma(m):

@@ -18,7 +18,8 @@ import pytest
 from social_force_window_planner_amd import blend
 from social_force_window_planner_amd import synthetic as syn
 from social_force_window_planner_amd._abi import (SFW_COST_INVALID, SFW_COST_SKIPPED, SFW_ERR_INVALID_ARG, SFW_ERR_STATE,
-                                                   SFW_PRECISION_F64, SfwBlendStat, default_params)
+                                                   SfwBlendStat)
+from sfw_test_util import _bits, _commands, _knot_steps, _params, _same, _scorer, _workload
 
 pytestmark = pytest.mark.gpu
 
@@ -33,10 +34,6 @@ SCENE_KEYS = [(5, 12, 0), (20, 14, 16), "lethal"]
 
 
 # ---- the scenes and helpers of tests/test_sequences_gpu.py -------------------------------------------------------------------------
-def _workload(n_people, seed, n_obstacles, **kw):
-    return syn.Workload("t", 1, 1, n_people, 200, 1.0, sim_granularity=GRAN, seed=seed, n_obstacles=n_obstacles, n_discs=0, **kw)
-
-
 @functools.lru_cache(maxsize=None)
 def _scene(key):
     """(cached and never written to)"""
@@ -52,38 +49,7 @@ def _scene(key):
     return syn.make_scene(_workload(*key))
 
 
-def _params(precision=SFW_PRECISION_F64, **kw):
-    return default_params(sim_time=1.0, sim_granularity=GRAN, precision=precision, **kw)
-
-
-def _scorer(hip_mod, scene, **kw):
-    g = hip_mod.HipScorer(_params(**kw))
-    g.load_scene(scene)
-    return g
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def _same(a, b):
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    return a.shape == b.shape and np.array_equal(_bits(a), _bits(b))
-
-
-def _commands(n, seed, K=1, holonomic=True):
-    """(K, n) arrays of random commands inside the robot's limits"""
-    rng = np.random.default_rng(seed)
-    vx, vth = rng.uniform(0.0, 0.7, (K, n)), rng.uniform(-0.5, 0.5, (K, n))
-    vy = rng.uniform(-0.3, 0.3, (K, n)) if holonomic else None
-    return vx, vy, vth
-
-
 # ---- stages -------------------------------------------------------------------------------------------------------------------------
-def _knot_steps(K):
-    return tuple(range(K)) if K > 3 else (0, 7, 19)[:K]
-
-
 def _knots(vx, vy, vth):
     """(K, n) arrays -> the mirror's (K, 3, n)"""
     return np.stack([vx, np.zeros_like(vx) if vy is None else vy, vth], axis=1)

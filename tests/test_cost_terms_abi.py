@@ -13,14 +13,11 @@ from social_force_window_planner_amd import planner
 from social_force_window_planner_amd._abi import (EXPORTED_SYMBOLS, SFW_ERR_INVALID_ARG, SFW_N_TERMS, SFW_RESCORE_MAX_K,
                                                    SFW_TERM_ANGLE, SFW_TERM_COSTMAP, SFW_TERM_DISTANCE, SFW_TERM_SOCIAL,
                                                    SFW_TERM_VEL, SfwBest, SfwWeights)
+from sfw_test_util import _header
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "social_force_window_planner_amd", "csrc")
 TERM_SYMBOLS = ("sfw_set_terms_capture", "sfw_grid_rescore", "sfw_grid_terms")
-
-
-def _header():
-    return open(os.path.join(ROOT, "include", "sfw_hip.h")).read()
 
 
 def test_term_symbols_declared_and_exported():

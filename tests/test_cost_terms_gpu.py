@@ -13,14 +13,11 @@ from social_force_window_planner_amd import synthetic as syn
 from social_force_window_planner_amd._abi import (SFW_COST_SKIPPED, SFW_ERR_INVALID_ARG, SFW_ERR_STATE, SFW_K2_AUTO,
                                                    SFW_K2_FLAT, SFW_K2_REGISTER, SFW_PRECISION_F32, SFW_PRECISION_F64,
                                                    SFW_PRECISION_F64_STRICT, SfwAgent, default_params)
+from sfw_test_util import _same
 
 pytestmark = pytest.mark.gpu
 
 WEIGHT_FIELDS = ("vel_weight", "distance_weight", "angle_weight", "costmap_weight", "social_weight")
-
-
-def _same(a, b):
-    return np.array_equal(np.asarray(a, dtype=np.float64).view(np.uint64), np.asarray(b, dtype=np.float64).view(np.uint64))
 
 
 def _params(w, precision=SFW_PRECISION_F64, weights=None):

@@ -10,13 +10,10 @@ import pytest
 
 from social_force_window_planner_amd import planner
 from social_force_window_planner_amd._abi import EXPORTED_SYMBOLS, SFW_ERR_INVALID_ARG, SfwGoalArgs, SfwRobotState
+from sfw_test_util import _header
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CROWD_SYMBOLS = ("sfw_score_one_crowd", "sfw_grid_crowd")
-
-
-def _header():
-    return open(os.path.join(ROOT, "include", "sfw_hip.h")).read()
 
 
 def test_crowd_symbols_declared_and_exported():

@@ -13,14 +13,14 @@ What is held to what:
 Every scene is one wave of S = 32 steps with dt = 2^-5 exactly."""
 import ctypes as C
 import dataclasses
-import functools
 
 import numpy as np
 import pytest
 
 from social_force_window_planner_amd import synthetic as syn
 from social_force_window_planner_amd._abi import (SFW_COST_SKIPPED, SFW_ERR_INVALID_ARG, SFW_ERR_STATE, SFW_PRECISION_F32,
-                                                   SFW_PRECISION_F64, SFW_PRECISION_F64_STRICT, SfwAgent, default_params)
+                                                   SFW_PRECISION_F64, SFW_PRECISION_F64_STRICT, SfwAgent)
+from sfw_test_util import _group_scene as _scene, _new_velocity, _params, _same, _scorer, _workload
 
 pytestmark = pytest.mark.gpu
 
@@ -38,31 +38,6 @@ PLAIN_KEYS = [k for k in SCENE_KEYS if k != "group" and k[2] == 0]  # no laser p
 SAMPLES = [(0.5, 0.2), (0.1, -0.4), (0.7, 0.0)]
 SOCIAL_ONLY = dict(vel_weight=0.0, distance_weight=0.0, angle_weight=0.0, costmap_weight=0.0, social_weight=1.0)
 HOLO_GA = (1.0, 0.7, 1.0, 2.0, 0.5)
-
-
-def _workload(n_people, seed, n_obstacles, **kw):
-    return syn.Workload("t", 1, 1, n_people, 200, 1.0, sim_granularity=GRAN, seed=seed, n_obstacles=n_obstacles, n_discs=0, **kw)
-
-
-@functools.lru_cache(maxsize=None)
-def _scene(key):
-    """(cached and never written to)"""
-    if key == "group":
-        scene = syn.make_scene(_workload(8, 18, 0))
-        for i, q in ((1, 0), (2, 0), (3, 0), (5, 1), (6, 1)):
-            scene.agents[i].group_id = q
-        return scene
-    return syn.make_scene(_workload(*key))
-
-
-def _params(precision=SFW_PRECISION_F64, sim_time=1.0, **kw):
-    return default_params(sim_time=sim_time, sim_granularity=GRAN, precision=precision, **kw)
-
-
-def _scorer(hip_mod, scene, precision=SFW_PRECISION_F64, **kw):
-    g = hip_mod.HipScorer(_params(precision, **kw))
-    g.load_scene(scene)
-    return g
 
 
 def _oracle(oracle_mod, scene, agents=None, sim_time=1.0, **kw):
@@ -85,15 +60,6 @@ def _kept(oracle_mod, key):
         o.close()
     assert len(_KEPT[key]) >= 2, (key, _KEPT[key])
     return _KEPT[key]
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def _same(a, b):
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    return a.shape == b.shape and np.array_equal(_bits(a), _bits(b))
 
 
 def _same_crowd(a, b):
@@ -266,13 +232,6 @@ def test_work_sums_to_the_social_term(oracle_mod, hip_mod, key, precision):
 
 
 # ---- 3. continuation through the oracle -------------------------------------------------------------------------------------
-def _new_velocity(vg, vi, a_max, dt):
-    """computeNewVelocity (ref sfw_planner.hpp:457-463)"""
-    if vg - vi >= 0:
-        return min(vg, vi + a_max * dt)
-    return max(vg, vi - a_max * dt)
-
-
 def _agents_from_row(scene, state_row, has_goal_row):
     A = len(scene.agents)
     out = (SfwAgent * A)()

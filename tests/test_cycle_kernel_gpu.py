@@ -8,17 +8,10 @@ import numpy as np
 import pytest
 
 from social_force_window_planner_amd import synthetic as syn
-from social_force_window_planner_amd._abi import (SFW_PRECISION_F32, SFW_PRECISION_F64_STRICT, default_params)
+from social_force_window_planner_amd._abi import (SFW_PRECISION_F32, SFW_PRECISION_F64_STRICT)
+from sfw_test_util import _same, _workload_params as _params
 
 pytestmark = pytest.mark.gpu
-
-
-def _same(a, b):
-    return np.array_equal(np.asarray(a, dtype=np.float64).view(np.uint64), np.asarray(b, dtype=np.float64).view(np.uint64))
-
-
-def _params(w, **kw):
-    return default_params(sim_time=w.sim_time, sim_granularity=w.sim_granularity, **kw)
 
 
 def _run(hip_mod, monkeypatch, scene, params, fused, capture=False, calls=1, goal_args=None, robot_state=None):

@@ -16,22 +16,13 @@ from social_force_window_planner_amd import synthetic as syn
 from social_force_window_planner_amd._abi import (EXPORTED_SYMBOLS, SFW_ENSEMBLE_MAX, SFW_ENSEMBLE_MAX_M, SFW_ENSEMBLE_MEAN,
                                                    SFW_ERR_INVALID_ARG, SFW_ERR_NO_DEVICE, SFW_OK, SfwBest, default_params)
 from social_force_window_planner_amd.hypotheses import naive_goal_hypotheses
+from sfw_test_util import _gpu, _header
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "social_force_window_planner_amd", "csrc")
 ENSEMBLE_SYMBOLS = ("sfw_ensemble_create", "sfw_ensemble_destroy", "sfw_ensemble_last_error", "sfw_ensemble_size",
                     "sfw_ensemble_member", "sfw_ensemble_set_params", "sfw_ensemble_set_costmap", "sfw_ensemble_set_footprint",
                     "sfw_ensemble_set_hypothesis", "sfw_ensemble_score_grid", "sfw_ensemble_aggregate", "sfw_ensemble_last_us")
-
-
-def _header():
-    return open(os.path.join(ROOT, "include", "sfw_hip.h")).read()
-
-
-def _gpu():
-    import torch
-
-    return torch.cuda.is_available()
 
 
 def test_ensemble_symbols_declared_and_exported():

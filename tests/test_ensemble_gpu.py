@@ -14,8 +14,9 @@ import pytest
 from social_force_window_planner_amd import synthetic as syn
 from social_force_window_planner_amd._abi import (SFW_COST_INVALID, SFW_COST_SKIPPED, SFW_ERR_INVALID_ARG, SFW_ERR_STATE,
                                                    SFW_PRECISION_F32, SFW_PRECISION_F64, SFW_PRECISION_F64_STRICT, SfwAgent,
-                                                   SfwBest, default_params)
+                                                   SfwBest)
 from social_force_window_planner_amd.hypotheses import naive_goal_hypotheses
+from sfw_test_util import _same, _scene_params as _params
 
 pytestmark = pytest.mark.gpu
 
@@ -28,15 +29,6 @@ def _scene(name):
     if name == "ref5x9":
         return syn.make_scene("ref5x9")
     return syn.make_scene(dataclasses.replace(syn.WORKLOADS["cfg2"], nv=48, nw=48, n_people=8))
-
-
-def _params(scene, precision=SFW_PRECISION_F64, **kw):
-    w = scene.workload
-    return default_params(sim_time=w.sim_time, sim_granularity=w.sim_granularity, precision=precision, **kw)
-
-
-def _same(a, b):
-    return np.array_equal(np.asarray(a, dtype=np.float64).view(np.uint64), np.asarray(b, dtype=np.float64).view(np.uint64))
 
 
 def _grid_args(scene):

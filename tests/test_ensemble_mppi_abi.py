@@ -12,13 +12,10 @@ import pytest
 from social_force_window_planner_amd import planner
 from social_force_window_planner_amd._abi import (EXPORTED_SYMBOLS, SFW_ERR_INVALID_ARG, SfwBest, SfwBlendStat, SfwGoalArgs, SfwMppi,
                                                    SfwPerturb, SfwRobotState)
+from sfw_test_util import _header
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ("sfw_ensemble_blend_control", "sfw_ensemble_mppi_run")
-
-
-def _header():
-    return open(os.path.join(ROOT, "include", "sfw_hip.h")).read()
 
 
 def test_symbols_declared_and_exported():

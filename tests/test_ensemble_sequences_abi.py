@@ -11,15 +11,12 @@ import pytest
 
 from social_force_window_planner_amd import planner
 from social_force_window_planner_amd._abi import EXPORTED_SYMBOLS, SFW_ERR_INVALID_ARG, SfwBest, SfwBlendStat
+from sfw_test_util import _header
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "social_force_window_planner_amd", "csrc")
 NEW_SYMBOLS = ("sfw_ensemble_score_sequences", "sfw_ensemble_score_perturbed", "sfw_ensemble_blend")
 LIST_KERNEL = "sfw_ens_list_first"
-
-
-def _header():
-    return open(os.path.join(ROOT, "include", "sfw_hip.h")).read()
 
 
 def test_symbols_declared_exported_and_listed():

@@ -25,9 +25,10 @@ from social_force_window_planner_amd import synthetic as syn
 from social_force_window_planner_amd._abi import (SFW_COST_INVALID, SFW_COST_SKIPPED, SFW_ERR_INVALID_ARG, SFW_ERR_STATE, SFW_OK,
                                                    SFW_PERTURB_KEEP_NOMINAL, SFW_PERTURB_KEEP_NORMALS, SFW_PERTURB_NO_VY,
                                                    SFW_PRECISION_F32, SFW_PRECISION_F64, SFW_PRECISION_F64_STRICT, SfwAgent,
-                                                   SfwBest, SfwBlendStat, SfwGoalArgs, SfwRobotState, default_params)
+                                                   SfwBest, SfwBlendStat, SfwGoalArgs, SfwRobotState)
 from social_force_window_planner_amd.hypotheses import naive_goal_hypotheses
 from test_blend_gpu import ULP4  # the bound that file holds the device exp to
+from sfw_test_util import _bits, _np_best, _same, _scene_params as _params
 
 pytestmark = pytest.mark.gpu
 
@@ -49,11 +50,6 @@ def _scene(name):
     if name == "ref5x9":
         return syn.make_scene("ref5x9")
     return syn.make_scene(dataclasses.replace(syn.WORKLOADS["cfg2"], nv=48, nw=48, n_people=8))
-
-
-def _params(scene, precision=SFW_PRECISION_F64, **kw):
-    w = scene.workload
-    return default_params(sim_time=w.sim_time, sim_granularity=w.sim_granularity, precision=precision, **kw)
 
 
 def _with_person(agents, x, y, vx, vy):
@@ -124,15 +120,6 @@ def _standalone(hip_mod, scene, agents, obstacles, params=None):
     return g
 
 
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def _same(a, b):
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    return a.shape == b.shape and np.array_equal(_bits(a), _bits(b))
-
-
 # ---- commands --------------------------------------------------------------------------------------------------------------------
 def _commands(n, seed, K=1, holonomic=True):
     """(K, n) arrays of random commands (tests/test_sequences_gpu.py's generator over this file's box).  Every second sample
@@ -188,22 +175,6 @@ def _hold_mix(rejected, M, n, what="", copies=False):
     assert valid + partial + by_all == n
     if n > 1:
         assert valid > 0 and by_all > 0 and (partial > 0 or copies), (valid, partial, by_all)
-
-
-def _np_best(costs, vx, vy, vth):
-    """The list rule over a cost vector and the FIRST knots: cost up, vx down, |vtheta| up, index down, the 10000.0 cap clause."""
-    best = {"index": -1, "cost": -1.0, "vx": 0.0, "vy": 0.0, "vtheta": 0.0, "n_valid": int(np.sum(costs >= 0))}
-    key = None
-    for t, c in enumerate(costs):
-        if not c >= 0:
-            continue
-        if not (c < 10000.0 or (c == 10000.0 and (vx[t] > 0 or (vx[t] == 0 and vth[t] == 0)))):
-            continue
-        k = (c, -vx[t], abs(vth[t]), -t)
-        if key is None or k < key:
-            key = k
-            best.update(index=t, cost=float(c), vx=float(vx[t]), vy=float(vy[t]) if vy is not None else 0.0, vtheta=float(vth[t]))
-    return best
 
 
 # ---- the blend's checks, as tests/test_blend_gpu.py has them --------------------------------------------------------------------------

@@ -8,16 +8,9 @@ import pytest
 
 from social_force_window_planner_amd import synthetic as syn
 from social_force_window_planner_amd._abi import default_params
+from sfw_test_util import _same, _workload_params as _params
 
 pytestmark = pytest.mark.gpu
-
-
-def _same(a, b):
-    return np.array_equal(np.asarray(a, dtype=np.float64).view(np.uint64), np.asarray(b, dtype=np.float64).view(np.uint64))
-
-
-def _params(w):
-    return default_params(sim_time=w.sim_time, sim_granularity=w.sim_granularity)
 
 
 @pytest.mark.parametrize("name,nv,nw", [("ref5x9", 5, 9), ("cfg2", 40, 36), ("cfg2", 96, 96)])

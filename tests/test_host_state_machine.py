@@ -12,18 +12,13 @@ from social_force_window_planner_amd import host, synthetic as syn
 from social_force_window_planner_amd._abi import (BRANCH_APPROACH, BRANCH_GOAL_REACHED, BRANCH_GRID,
                                                    BRANCH_GRID_FAILED, BRANCH_NOT_RUNNING, BRANCH_ROTATE_BLOCKED,
                                                    BRANCH_ROTATE_IN_PLACE, default_ctrl_params)
+from sfw_test_util import _gpu
 
 
 @pytest.fixture(scope="module")
 def host_built():
     host.build()
     return host
-
-
-def _gpu():
-    import torch
-
-    return torch.cuda.is_available()
 
 
 def _pair(oracle_mod, host_built, scene, **ckw):

@@ -13,17 +13,10 @@ import pytest
 
 from social_force_window_planner_amd import mppi, planner
 from social_force_window_planner_amd._abi import EXPORTED_SYMBOLS, SFW_ERR_INVALID_ARG, SFW_MPPI_MAX_ITER, SfwMppi
+from sfw_test_util import _bits, _header
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ("sfw_sequences_control_cost", "sfw_grid_blend_control", "sfw_mppi_run")
-
-
-def _header():
-    return open(os.path.join(ROOT, "include", "sfw_hip.h")).read()
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
 
 
 def test_symbols_declared_and_exported():

@@ -16,7 +16,8 @@ from social_force_window_planner_amd import mppi
 from social_force_window_planner_amd import synthetic as syn
 from social_force_window_planner_amd._abi import (SFW_COST_INVALID, SFW_ERR_INVALID_ARG, SFW_ERR_STATE, SFW_PERTURB_KEEP_NOMINAL,
                                                    SFW_PERTURB_KEEP_NORMALS, SFW_PERTURB_NO_VY, SfwBest, SfwBlendStat, SfwMppi,
-                                                   SfwPerturb, default_params)
+                                                   SfwPerturb)
+from sfw_test_util import _bits, _knot_steps, _nominal, _params, _same, _scorer, _workload
 
 pytestmark = pytest.mark.gpu
 
@@ -30,10 +31,6 @@ WIDE = ((0.0, -0.3, -0.5), (0.7, 0.3, 0.5))  # the robot's limits
 
 
 # ---- the scenes and helpers of tests/test_perturb_gpu.py ----------------------------------------------------------------------------
-def _workload(n_people, seed, n_obstacles, **kw):
-    return syn.Workload("t", 1, 1, n_people, 200, 1.0, sim_granularity=GRAN, seed=seed, n_obstacles=n_obstacles, n_discs=0, **kw)
-
-
 @functools.lru_cache(maxsize=None)
 def _scene(key):
     """(cached and never written to)"""
@@ -57,39 +54,8 @@ def _scene(key):
     return syn.make_scene(_workload(*key))
 
 
-def _params(**kw):
-    return default_params(sim_time=1.0, sim_granularity=GRAN, **kw)
-
-
-def _scorer(hip_mod, scene, **kw):
-    g = hip_mod.HipScorer(_params(**kw))
-    g.load_scene(scene)
-    return g
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def _same(a, b):
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    return a.shape == b.shape and np.array_equal(_bits(a), _bits(b))
-
-
 def _stat_bits(stats):
     return [sorted((k, _bits(float(v)).item()) for k, v in d.items()) for d in stats]
-
-
-def _knot_steps(K):
-    return tuple(range(K)) if K > 3 else (0, 7, 19)[:K]
-
-
-def _nominal(K, no_vy=False):
-    k = np.arange(K, dtype=np.float64)
-    nom = np.stack([0.35 + 0.05 * np.cos(k), 0.02 * np.sin(k), -0.05 + 0.1 * np.sin(0.7 * k)], axis=1)
-    if no_vy:
-        nom[:, 1] = 0.0
-    return nom
 
 
 def _stage(g, scene, n, K, seed, flags=0, sigma=SIGMA, index_base=0):

@@ -17,6 +17,7 @@ import pytest
 
 from social_force_window_planner_amd import synthetic as syn
 from social_force_window_planner_amd._abi import SfwAgent, default_params
+from sfw_test_util import _new_velocity
 
 # SURVEY.md Appendix B (generated from the reference's line_iterator.hpp)
 APPENDIX_B = {
@@ -98,10 +99,6 @@ def test_trajectory_container_real_reference(oracle_mod):
 
 
 # ---------------------------------------------------------------------------
-def _new_velocity(vg, vi, a, dt):  # reference sfw_planner.hpp:457-463
-    return min(vg, vi + a * dt) if (vg - vi) >= 0 else max(vg, vi - a * dt)
-
-
 def _closed_form_cost(p, rs, vs, ws, ga):
     """Independent Python restatement of scoreTrajectory for the pedestrian-free,
     empty-map, K<3 case (reference src/sfw_planner.cpp:519-527, :581-588, :643-667)."""

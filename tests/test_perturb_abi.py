@@ -18,17 +18,10 @@ import pytest
 from social_force_window_planner_amd import perturb, planner
 from social_force_window_planner_amd._abi import (EXPORTED_SYMBOLS, SFW_ERR_INVALID_ARG, SFW_PERTURB_KEEP_NOMINAL,
                                                    SFW_PERTURB_KEEP_NORMALS, SFW_PERTURB_NO_VY, SFW_SEQ_MAX_KNOTS, SfwPerturb)
+from sfw_test_util import _bits, _header
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ("sfw_sequences_perturb_stage", "sfw_score_perturbed", "sfw_sequences_knots", "sfw_sequences_normals")
-
-
-def _header():
-    return open(os.path.join(ROOT, "include", "sfw_hip.h")).read()
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
 
 
 def test_symbols_declared_and_exported():

@@ -19,7 +19,8 @@ import pytest
 from social_force_window_planner_amd import perturb
 from social_force_window_planner_amd import synthetic as syn
 from social_force_window_planner_amd._abi import (SFW_COST_INVALID, SFW_ERR_INVALID_ARG, SFW_ERR_STATE, SFW_PERTURB_KEEP_NOMINAL,
-                                                   SFW_PERTURB_KEEP_NORMALS, SFW_PERTURB_NO_VY, SfwAgent, SfwPerturb, default_params)
+                                                   SFW_PERTURB_KEEP_NORMALS, SFW_PERTURB_NO_VY, SfwAgent, SfwPerturb)
+from sfw_test_util import _bits, _knot_steps, _nominal, _params, _same, _scorer, _workload
 
 pytestmark = pytest.mark.gpu
 
@@ -35,10 +36,6 @@ HALF = ((0.27, -0.04, -0.2), (0.5, 0.07, 0.15))    # cuts about half the draws a
 
 
 # ---- the scenes and helpers of tests/test_blend_gpu.py -----------------------------------------------------------------------------
-def _workload(n_people, seed, n_obstacles, **kw):
-    return syn.Workload("t", 1, 1, n_people, 200, 1.0, sim_granularity=GRAN, seed=seed, n_obstacles=n_obstacles, n_discs=0, **kw)
-
-
 @functools.lru_cache(maxsize=None)
 def _scene(key):
     """(cached and never written to)"""
@@ -57,37 +54,6 @@ def _scene(key):
         p.x, p.y, p.vx, p.vy, p.has_goal, p.desired_velocity = 1.2, 0.4, 0.0, 0.0, 0, 0.0
         return dataclasses.replace(base, agents=agents)
     return syn.make_scene(_workload(*key))
-
-
-def _params(**kw):
-    return default_params(sim_time=1.0, sim_granularity=GRAN, **kw)
-
-
-def _scorer(hip_mod, scene, **kw):
-    g = hip_mod.HipScorer(_params(**kw))
-    g.load_scene(scene)
-    return g
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def _same(a, b):
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    return a.shape == b.shape and np.array_equal(_bits(a), _bits(b))
-
-
-def _knot_steps(K):
-    return tuple(range(K)) if K > 3 else (0, 7, 19)[:K]
-
-
-def _nominal(K, no_vy=False):
-    k = np.arange(K, dtype=np.float64)
-    nom = np.stack([0.35 + 0.05 * np.cos(k), 0.02 * np.sin(k), -0.05 + 0.1 * np.sin(0.7 * k)], axis=1)
-    if no_vy:
-        nom[:, 1] = 0.0
-    return nom
 
 
 def _stage(g, scene, n, K, seed, flags=0, box=WIDE, sigma=SIGMA, index_base=0, nominal=None):

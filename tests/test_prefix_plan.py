@@ -8,6 +8,7 @@ import pytest
 
 from social_force_window_planner_amd import planner
 from social_force_window_planner_amd import synthetic as syn
+from sfw_test_util import _new_velocity
 
 
 def _lib():
@@ -28,12 +29,6 @@ def _plan(lin, ang, vx0, vth0, acc_x, acc_th, sim_time, S, A, cap=64):
                                        sim_time, S, A, ends.ctypes.data, classes.ctypes.data, cap, C.byref(n))
     assert rc == 0
     return [int(v) for v in ends[:n.value]], [int(v) for v in classes[:n.value]]
-
-
-def _new_velocity(vg, vi, a_max, dt):  # reference sfw_planner.hpp:457-463
-    if (vg - vi) >= 0:
-        return min(vg, vi + a_max * dt)
-    return max(vg, vi - a_max * dt)
 
 
 def _n_classes(targets, v0, a_max, dt, p):

@@ -10,6 +10,7 @@ import pytest
 
 from social_force_window_planner_amd import synthetic as syn
 from social_force_window_planner_amd._abi import SFW_PRECISION_F32, default_params
+from sfw_test_util import _workload_params as _params
 
 pytestmark = pytest.mark.gpu
 
@@ -38,10 +39,6 @@ def _score(hip_mod, scene, params, prefix, budget_mb=None, goal_args=None, want_
 
 def _same(a, b):
     return np.array_equal(np.asarray(a).view(np.uint64), np.asarray(b).view(np.uint64))
-
-
-def _params(w, **kw):
-    return default_params(sim_time=w.sim_time, sim_granularity=w.sim_granularity, **kw)
 
 
 @pytest.mark.parametrize("name,nv,nw,people", [("cfg2", 64, 64, 20), ("target", 64, 64, 50), ("cfg5", 16, 32, 100),

@@ -11,13 +11,10 @@ import pytest
 from social_force_window_planner_amd import planner
 from social_force_window_planner_amd._abi import (EXPORTED_SYMBOLS, SFW_ERR_INVALID_ARG, SfwBest, SfwGoalArgs,
                                                    SfwRobotState)
+from sfw_test_util import _header
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIST_SYMBOLS = ("sfw_samples_stage", "sfw_score_samples")
-
-
-def _header():
-    return open(os.path.join(ROOT, "include", "sfw_hip.h")).read()
 
 
 def test_list_symbols_declared_and_exported():

@@ -14,16 +14,13 @@ from social_force_window_planner_amd import synthetic as syn
 from social_force_window_planner_amd._abi import (SFW_COST_INVALID, SFW_COST_SKIPPED, SFW_ERR_INVALID_ARG, SFW_ERR_STATE,
                                                    SFW_K2_AUTO, SFW_K2_FLAT, SFW_ORG_REGISTER_2, SFW_PRECISION_F32,
                                                    SFW_PRECISION_F64, SFW_PRECISION_F64_STRICT, default_params)
+from sfw_test_util import _np_best, _same
 
 pytestmark = pytest.mark.gpu
 
 RTOL_F64 = 1e-9  # the project's parity tolerance (tests/test_parity_gpu.py)
 HOLO_GA = (1.0, 0.7, 1.0, 2.0, 0.5)
 S = 40  # every workload here: sim_time 1.0 at 0.025
-
-
-def _same(a, b):
-    return np.array_equal(np.asarray(a, dtype=np.float64).view(np.uint64), np.asarray(b, dtype=np.float64).view(np.uint64))
 
 
 def _scorer(hip_mod, scene, precision=SFW_PRECISION_F64, form=SFW_K2_AUTO):
@@ -39,22 +36,6 @@ def _products(scene):
     vx = np.repeat(scene.linvels, len(scene.angvels))
     vth = np.tile(scene.angvels, len(scene.linvels))
     return vx, vth
-
-
-def _np_best(costs, vx, vy, vth):
-    """The reference's selection (ref :394-414, sel_consider / sel_less) restated over a cost vector."""
-    best = {"index": -1, "cost": -1.0, "vx": 0.0, "vy": 0.0, "vtheta": 0.0, "n_valid": int(np.sum(costs >= 0))}
-    key = None
-    for t, c in enumerate(costs):
-        if not c >= 0:
-            continue
-        if not (c < 10000.0 or (c == 10000.0 and (vx[t] > 0 or (vx[t] == 0 and vth[t] == 0)))):
-            continue
-        k = (c, -vx[t], abs(vth[t]), -t)
-        if key is None or k < key:
-            key = k
-            best.update(index=t, cost=float(c), vx=float(vx[t]), vy=float(vy[t]) if vy is not None else 0.0, vtheta=float(vth[t]))
-    return best
 
 
 def _grid_as_list_reference(hip_mod, scene, precision=SFW_PRECISION_F64):

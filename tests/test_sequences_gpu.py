@@ -16,15 +16,14 @@ What is held to what (the contract points of include/sfw_hip.h):
 sim_time 0.375 + 0.625), the synthetic scenes of tests/test_crowd_gpu.py."""
 import ctypes as C
 import dataclasses
-import functools
 
 import numpy as np
 import pytest
 
 from social_force_window_planner_amd import synthetic as syn
 from social_force_window_planner_amd._abi import (SFW_COST_INVALID, SFW_COST_SKIPPED, SFW_ERR_INVALID_ARG, SFW_ERR_STATE,
-                                                   SFW_PRECISION_F32, SFW_PRECISION_F64, SFW_PRECISION_F64_STRICT, SfwAgent,
-                                                   default_params)
+                                                   SFW_PRECISION_F32, SFW_PRECISION_F64, SFW_PRECISION_F64_STRICT, SfwAgent)
+from sfw_test_util import _bits, _commands, _group_scene as _scene, _new_velocity, _np_best, _params, _same, _scorer, _workload
 
 pytestmark = pytest.mark.gpu
 
@@ -46,31 +45,6 @@ HOLO_GA = (1.0, 0.7, 1.0, 2.0, 0.5)
 
 
 # ---- the scenes and helpers of tests/test_crowd_gpu.py ----------------------------------------------------------------------------
-def _workload(n_people, seed, n_obstacles, **kw):
-    return syn.Workload("t", 1, 1, n_people, 200, 1.0, sim_granularity=GRAN, seed=seed, n_obstacles=n_obstacles, n_discs=0, **kw)
-
-
-@functools.lru_cache(maxsize=None)
-def _scene(key):
-    """(cached and never written to)"""
-    if key == "group":
-        scene = syn.make_scene(_workload(8, 18, 0))
-        for i, q in ((1, 0), (2, 0), (3, 0), (5, 1), (6, 1)):
-            scene.agents[i].group_id = q
-        return scene
-    return syn.make_scene(_workload(*key))
-
-
-def _params(precision=SFW_PRECISION_F64, sim_time=1.0, **kw):
-    return default_params(sim_time=sim_time, sim_granularity=GRAN, precision=precision, **kw)
-
-
-def _scorer(hip_mod, scene, precision=SFW_PRECISION_F64, **kw):
-    g = hip_mod.HipScorer(_params(precision, **kw))
-    g.load_scene(scene)
-    return g
-
-
 def _oracle(oracle_mod, scene, agents=None, sim_time=1.0, **kw):
     o = oracle_mod.OracleScorer(_params(sim_time=sim_time, **kw))
     o.set_costmap(scene.cells, scene.origin_x, scene.origin_y, scene.resolution)
@@ -79,25 +53,9 @@ def _oracle(oracle_mod, scene, agents=None, sim_time=1.0, **kw):
     return o
 
 
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def _same(a, b):
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    return a.shape == b.shape and np.array_equal(_bits(a), _bits(b))
-
-
 def _same_crowd(a, b):
     return (_same(a["cost"], b["cost"]) and a["n_steps"] == b["n_steps"] and _same(a["state"], b["state"]) and
             _same(a["work"], b["work"]) and np.array_equal(a["has_goal"], b["has_goal"]))
-
-
-def _new_velocity(vg, vi, a_max, dt):
-    """computeNewVelocity (ref sfw_planner.hpp:457-463)"""
-    if vg - vi >= 0:
-        return min(vg, vi + a_max * dt)
-    return max(vg, vi - a_max * dt)
 
 
 def _agents_from_row(scene, state_row, has_goal_row):
@@ -118,35 +76,11 @@ def _copy_agents(scene):
 
 
 # ---- sequences -------------------------------------------------------------------------------------------------------------------
-def _commands(n, seed, K=1, holonomic=True):
-    """(K, n) arrays of random commands inside the robot's limits"""
-    rng = np.random.default_rng(seed)
-    vx, vth = rng.uniform(0.0, 0.7, (K, n)), rng.uniform(-0.5, 0.5, (K, n))
-    vy = rng.uniform(-0.3, 0.3, (K, n)) if holonomic else None
-    return vx, vy, vth
-
-
 def _two_knots(pairs):
     """(2, n) vx and vtheta of the two-knot sequences (c1 until KNOT, c2 after)"""
     vx = np.array([[c1[0] for c1, _ in pairs], [c2[0] for _, c2 in pairs]])
     vth = np.array([[c1[1] for c1, _ in pairs], [c2[1] for _, c2 in pairs]])
     return vx, vth
-
-
-def _np_best(costs, vx, vy, vth):
-    """The reference's selection (ref :394-414) restated over a cost vector and the FIRST knots."""
-    best = {"index": -1, "cost": -1.0, "vx": 0.0, "vy": 0.0, "vtheta": 0.0, "n_valid": int(np.sum(costs >= 0))}
-    key = None
-    for t, c in enumerate(costs):
-        if not c >= 0:
-            continue
-        if not (c < 10000.0 or (c == 10000.0 and (vx[t] > 0 or (vx[t] == 0 and vth[t] == 0)))):
-            continue
-        k = (c, -vx[t], abs(vth[t]), -t)
-        if key is None or k < key:
-            key = k
-            best.update(index=t, cost=float(c), vx=float(vx[t]), vy=float(vy[t]) if vy is not None else 0.0, vtheta=float(vth[t]))
-    return best
 
 
 def _no_skip_no_nan(costs):
