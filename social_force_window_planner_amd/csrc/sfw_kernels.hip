@@ -1060,21 +1060,17 @@ __device__ __forceinline__ double2 obs_point(obs_lds_ptr obs, int o) { return do
 // so that the independent chains are interleaved.  The loads run up to two points past the range — into the next segment, or
 // into the padding behind the last point (64 bytes in global memory, sfw_set_agents; two points in the LDS copy, lds_layout):
 // loaded, never evaluated, and no index to clamp.
-// Points in global memory (a GPU-FILLING launch): scalar counter, scalar base address + the lane's fixed byte offset
-// (global_load saddr form), loads written as asm into two register sets that the unrolled body alternates without copying —
-// the waits are explicit, the compiler does not count an asm load.
+// Points in global memory (a GPU-FILLING launch, the crowd capture): scalar counter, scalar base address + the lane's fixed byte
+// offset (the saddr form of global_load), two register sets that the unrolled body alternates.  The loads are plain loads
+// through a global-address-space pointer: the compiler counts them and places the waits.  (Rounds 4-19 issued them as asm
+// statements and waited by hand.  The compiler takes an asm's output as ready where the statement ends, so nothing kept the
+// register allocator from putting a copy of a point between its load and its wait; it did, in the second run of a scan whose
+// length is no multiple of the segment length — in every float instantiation and in several double ones — and
+// SFW_PRECISION_F32 summed registers the load had not written yet: tests/test_force_terms_gpu.py.)
 typedef double obs_d2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ obs_d2 obs_load_ahead(const double2 *base, uint32_t lane_bytes) {
-  obs_d2 q;
-  // (s_nop 4: the base may have just come back from an SGPR spill lane — v_readlane — and a VMEM instruction reading such an
-  // SGPR needs 5 wait states, which the hazard recogniser does not insert into an asm block: load_pair_entries)
-  asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %1, %2" : "=v"(q) : "v"(lane_bytes), "s"(base) : "memory");
-  return q;
-}
-// the oldest of the point loads has arrived (YOUNGER: point loads issued after it; loads return in order, and whatever
-// else is in flight — the next step's robot record — is older than both)
-template <int YOUNGER> __device__ __forceinline__ void obs_load_wait(obs_d2 &q) {
-  asm volatile("s_waitcnt vmcnt(%1)" : "+v"(q) : "n"(YOUNGER));
+  const __attribute__((address_space(1))) char *const p = (const __attribute__((address_space(1))) char *)(const char *)base;
+  return *(const __attribute__((address_space(1))) obs_d2 *)(p + lane_bytes);
 }
 // (LDS copy of the points — an under-filled launch —: the same two loops with the compiler's own loads)
 template <typename R, int NJ>
@@ -1125,14 +1121,11 @@ __device__ __forceinline__ void obstacle_segment_multi_uniform(const sfm_consts<
     int i = 0;
 #pragma unroll 1
     for (; i + 2 <= n; i += 2) {
-      obs_d2 qb = obs_load_ahead(base + i + 1, lane_bytes);
-      obs_load_wait<1>(qa);
+      const obs_d2 qb = obs_load_ahead(base + i + 1, lane_bytes);
       terms(qa);
       qa = obs_load_ahead(base + i + 2, lane_bytes);
-      obs_load_wait<1>(qb);
       terms(qb);
     }
-    obs_load_wait<0>(qa);  // (also when it is not evaluated: no load of this loop is left in flight)
     if (i < n) terms(qa);
   };
   const int first = partial > 0 ? partial : Lseg;  // points every non-empty segment has

@@ -5,6 +5,9 @@ cross-compiles gfx950).  The occupancy the launch plan counts on is a property o
   scratch (VERDICT r2 "next round" 3; the round-2 build kept 80 bytes per lane there, reloaded one after the other in every
   per-agent pass);
 * the flat form of the north-star crowd (f64, 64-double planes) fits five waves per SIMD (at most 96 VGPRs) without scratch.
+  The kernels WITH the laser-point pass keep the five waves and 96 VGPRs but spill one pair and a word — 12 bytes per lane,
+  24 with 64-double planes — since their loop over points in global memory uses the compiler's loads (round 20: the asm-issued
+  loads it had could be read before they had landed, and were in SFW_PRECISION_F32: tests/test_force_terms_gpu.py).
 """
 import os
 import re
@@ -57,7 +60,8 @@ def test_flat_form_five_waves_without_scratch(resources):
     for cap in (64, 104, 128, 208, 256):
         for obs in (0, 1):
             k = _kernel(resources, f"sfw_social_kernel_flatIdLb0ELi{cap}ELb{obs}E")
-            assert k["vgpr"] <= 96 and k["scratch"] == 0 and k["occupancy"] >= 5, (cap, obs, k)
+            scratch = 0 if obs == 0 else 24 if cap == 64 else 12  # (module docstring)
+            assert k["vgpr"] <= 96 and k["scratch"] <= scratch and k["occupancy"] >= 5, (cap, obs, k)
 
 
 def test_mixed_launch_kernel_holds_six_waves_per_simd(resources):
@@ -111,12 +115,12 @@ def test_pair_loop_instruction_counts(isa_loops):
 
 def test_laser_point_loop_instruction_counts(isa_loops):
     """25 VALU instructions per (agent, point) (24 until round 4: the exponential's degree 9), one of them v_rsq_f64.  The flat form's task loops with wave-uniform trip counts
-    carry no other vector instruction (global-memory loops: 2 points x 1..4 agents per iteration, 2 loads) or three per
-    iteration (LDS copy); the register form's scalar loop: 4 points per s_load_dwordx16."""
+    carry one other vector instruction per iteration (global-memory loops: 2 points x 1..4 agents per iteration, 2 loads — none
+    while the loads were asm statements, which the compiler could not order against their waits) or three (LDS copy); the register form's scalar loop: 4 points per s_load_dwordx16."""
     obs = isa_loops["flat_obs"]
     for nj in (1, 2, 3, 4):
         g = [l for l in obs if l["trans"] == 2 * nj and l["vmem"] == 2 and l["ds"] == 0 and l["f64"] == 50 * nj]
-        assert g and all(l["valu"] == 50 * nj for l in g), (nj, obs)
+        assert g and all(l["valu"] <= 50 * nj + 1 for l in g), (nj, obs)
         lds = [l for l in obs if l["trans"] == 2 * nj and l["vmem"] == 0 and l["ds"] == 2 and l["f64"] == 50 * nj]
         assert lds and all(l["valu"] <= 50 * nj + 3 for l in lds), (nj, obs)
     reg = [l for l in isa_loops["reg"] if l["trans"] == 4 and l["ds"] == 0 and l["vmem"] == 0]
@@ -125,8 +129,7 @@ def test_laser_point_loop_instruction_counts(isa_loops):
 
 def test_inline_asm_idioms_hold_in_the_whole_isa(isa_loops):
     """What the compiler cannot check about the kernels' inline asm (tools/isa_asm_hazards.py, whole functions — preheaders and
-    exits, not just loop bodies): no instruction touches the destination of an asm-issued load (obs_load_ahead,
-    load_pair_entries) between the load and the s_waitcnt that covers it, and every kernel with an output-modifier fma
+    exits, not just loop bodies): no instruction touches the destination of an asm-issued load (load_pair_entries) between the load and the s_waitcnt that covers it, and every kernel with an output-modifier fma
     (`v_fma_f64 ... div:2`, sfw_math.h) switches the MODE register in front of the first one."""
     rc, out = isa_loops["hazards"]
     assert rc == 0, out[-3000:]
