@@ -192,7 +192,18 @@ const char *sfw_last_error(sfw_handle h);
  * scores the old state.
  * cells: row-major, y outer, cells[my*size_x+mx] == Costmap2D::getCost(mx,my) (the reference reads nav2's live
  * costmap, sfw_planner.hpp:362).  A snapshot whose cells and geometry equal the last one's is recognised (a memcmp)
- * and not sent again: hand the live map over every cycle. */
+ * and not sent again: hand the live map over every cycle.
+ * SFW_ERR_INVALID_ARG: a NULL map, a zero size, a resolution that is not > 0, an origin or resolution that is not finite
+ * (a NaN origin would pass every "below the origin" rejection), or a map beyond what the cell arithmetic is good for:
+ *   - SFW_MAX_MAP_AXIS_CELLS per axis.  The kernels form a cell index as trunc((w - origin) * (1 / resolution)) and take
+ *     the IEEE division the reference executes only when the product lies within 1e-9 of an integer.  Product and
+ *     quotient differ by at most 3 * 2^-53 of the quotient (the reciprocal's rounding, the product's, the division's),
+ *     so up to a quotient of 1e-9 / (3 * 2^-53) ~ 3.0e6 the two truncations agree whenever the division is not taken;
+ *     2^21 cells (and the one cell beyond the border that decides "off the map") stay inside that with a third to spare.
+ *   - SFW_MAX_MAP_CELLS in all: the Bresenham walk forms my * size_x + mx in a 32-bit int.
+ * 4096 x 4096 cells are far inside both. */
+#define SFW_MAX_MAP_AXIS_CELLS 2097152u  /* 2^21 */
+#define SFW_MAX_MAP_CELLS 2147483647ull  /* 2^31 - 1 */
 int sfw_set_costmap(sfw_handle h, const uint8_t *cells, uint32_t size_x,
                     uint32_t size_y, double origin_x, double origin_y,
                     double resolution);

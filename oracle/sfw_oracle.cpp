@@ -103,8 +103,12 @@ struct World {
   // truncate, then bound check.
   bool worldToMap(double wx, double wy, unsigned &mx, unsigned &my) const {
     if (wx < origin_x || wy < origin_y) return false;
-    mx = static_cast<unsigned>((wx - origin_x) / resolution);
-    my = static_cast<unsigned>((wy - origin_y) / resolution);
+    // (a quotient that does not fit an unsigned has no defined cast — x86 yields 0, "on the map", for 1e300 — and is
+    // off the map here, as on the device, whose conversion saturates: tests/costmap_reference.py)
+    const double qx = (wx - origin_x) / resolution, qy = (wy - origin_y) / resolution;
+    if (!(qx < 4294967296.0) || !(qy < 4294967296.0)) return false;
+    mx = static_cast<unsigned>(qx);
+    my = static_cast<unsigned>(qy);
     return mx < size_x && my < size_y;
   }
   uint8_t getCost(unsigned mx, unsigned my) const {

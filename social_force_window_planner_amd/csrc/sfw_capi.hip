@@ -2366,6 +2366,12 @@ int sfw_set_costmap(sfw_handle h, const uint8_t *cells, uint32_t size_x, uint32_
   if (!h) return SFW_ERR_INVALID_ARG;
   if (!cells || size_x == 0 || size_y == 0 || !(resolution > 0))
     return fail(h, SFW_ERR_INVALID_ARG, "set_costmap: null cells, zero size or non-positive resolution");
+  // A NaN origin passes every `wx < origin` rejection and lands every pose in cell (0, 0); an infinite resolution or origin
+  // does the like.  The two size limits are what the kernels' cell arithmetic is good for (sfw_hip.h; sfw_kernels.hip cell_index).
+  if (!std::isfinite(origin_x) || !std::isfinite(origin_y) || !std::isfinite(resolution))
+    return fail(h, SFW_ERR_INVALID_ARG, "set_costmap: origin or resolution is not finite");
+  if (size_x > SFW_MAX_MAP_AXIS_CELLS || size_y > SFW_MAX_MAP_AXIS_CELLS || static_cast<uint64_t>(size_x) * size_y > SFW_MAX_MAP_CELLS)
+    return fail(h, SFW_ERR_INVALID_ARG, "set_costmap: more than SFW_MAX_MAP_AXIS_CELLS cells on an axis or SFW_MAX_MAP_CELLS in all");
   SFW_HIP(h, hipSetDevice(h->device));
   const size_t n = static_cast<size_t>(size_x) * size_y;
   // The snapshot is taken here (the caller's buffer may change on return) and reaches the device with the NEXT stage — like

@@ -58,6 +58,13 @@ constexpr int WAVE = 64;
 // ~14-instruction division 34 times per pose: a * (1/res) is within a few ulp of the quotient, so the
 // truncations can only differ when the product lies within 1e-9 of an integer — then, and only then,
 // the lane takes the exact division (grid-aligned coordinates; rare, and still exact).
+// "A few ulp": inv_res = fl(1 / res), the product and the IEEE quotient round once each, so product and quotient lie
+// within 3 * 2^-53 Q of each other at a quotient Q, and an integer between them (the only way the truncations differ) is
+// that close to the product.  3 * 2^-53 Q < 1e-9 holds up to Q ~ 3.0e6; sfw_set_costmap refuses a map of more than
+// SFW_MAX_MAP_AXIS_CELLS = 2^21 cells on an axis (sfw_hip.h), and a coordinate whose quotient is beyond size + 1 is off
+// the map whichever way it truncates.  (line_max below forms y * size_x + x in int: SFW_MAX_MAP_CELLS = 2^31 - 1 in all.)
+// tests/test_costmap_edges_gpu.py puts coordinates on cell edges; tests/test_costmap_reference.py shows that the
+// unguarded product does differ there.
 __device__ __forceinline__ unsigned cell_index(double a, double res, double inv_res) {
   const double q = a * inv_res;
   const double m = __builtin_trunc(q);

@@ -239,3 +239,31 @@ def test_unsupported_agent_sets(hip_mod):
     g.load_scene(scene)
     c, b = g.score_grid(scene.robot_state, scene.linvels, scene.angvels, scene.goal_args)
     assert (c >= 0).any()
+
+
+def test_set_costmap_refuses_non_finite_geometry_and_oversized_maps(hip_mod):
+    """A NaN origin would pass every `wx < origin` rejection and put every pose in cell (0, 0); the size limits are what the
+    kernels' cell arithmetic is good for (sfw_hip.h SFW_MAX_MAP_AXIS_CELLS / SFW_MAX_MAP_CELLS).  A refused call leaves the map
+    that was there in place."""
+    L = hip_mod.lib()
+    scene = syn.make_scene("ref5x9")
+    g = hip_mod.HipScorer(default_params())
+    g.load_scene(scene)
+    before, _ = g.score_grid(scene.robot_state, scene.linvels, scene.angvels, scene.goal_args)
+    cells = np.zeros((4, 4), dtype=np.uint8)
+    nan, inf = float("nan"), float("inf")
+    for ox, oy, res in ((nan, 0.0, 0.05), (0.0, nan, 0.05), (inf, 0.0, 0.05), (0.0, -inf, 0.05), (0.0, 0.0, inf), (0.0, 0.0, nan),
+                        (0.0, 0.0, -0.05)):
+        assert L.sfw_set_costmap(g._h, cells.ctypes.data, 4, 4, ox, oy, res) == SFW_ERR_INVALID_ARG, (ox, oy, res)
+        assert b"set_costmap" in L.sfw_last_error(g._h)
+    # (the sizes are judged before a byte of the map is read)
+    for sx, sy in (((1 << 21) + 1, 1), (1, (1 << 21) + 1), (1 << 16, 1 << 15), (1 << 21, 1 << 21), (0xFFFFFFFF, 0xFFFFFFFF)):
+        assert L.sfw_set_costmap(g._h, cells.ctypes.data, sx, sy, 0.0, 0.0, 0.05) == SFW_ERR_INVALID_ARG, (sx, sy)
+    after, _ = g.score_grid(scene.robot_state, scene.linvels, scene.angvels, scene.goal_args)
+    assert np.array_equal(before, after)
+    strip = np.zeros((1, 1 << 21), dtype=np.uint8)  # the longest axis there is
+    g.set_costmap(strip, -1.0, -0.5, 1.0)
+    g.set_costmap(np.zeros((4096, 4096), dtype=np.uint8), -102.4, -102.4, 0.05)  # BASELINE config 5's map
+    g.set_costmap(strip.reshape(-1, 1), -0.5, -1.0, 1.0)
+    costs, _ = g.score_grid(scene.robot_state, scene.linvels, scene.angvels, scene.goal_args)
+    assert (costs >= 0).sum() > 0

@@ -177,3 +177,19 @@ def test_naive_goal_hypotheses_rotation():
             if d == 0.0:
                 assert _bits(a.vx) == _bits(b.vx) and _bits(a.vy) == _bits(b.vy)
             assert b.goal_x == b.x + t * b.vx and b.goal_y == b.y + t * b.vy
+
+
+@pytest.mark.gpu
+def test_ensemble_set_costmap_refuses_non_finite_geometry_and_oversized_maps():
+    """sfw_ensemble_set_costmap applies sfw_set_costmap's checks (sfw_hip.h) and names the failure"""
+    L = planner.lib()
+    e = planner.EnsembleScorer(default_params(), 0, 3)
+    cells = np.zeros((4, 4), dtype=np.uint8)
+    nan, inf = float("nan"), float("inf")
+    for ox, oy, res in ((nan, 0.0, 0.05), (0.0, inf, 0.05), (0.0, 0.0, inf), (0.0, 0.0, nan)):
+        assert L.sfw_ensemble_set_costmap(e._e, cells.ctypes.data, 4, 4, ox, oy, res) == SFW_ERR_INVALID_ARG, (ox, oy, res)
+        assert b"set_costmap" in L.sfw_ensemble_last_error(e._e)
+    for sx, sy in (((1 << 21) + 1, 1), (1 << 16, 1 << 15)):
+        assert L.sfw_ensemble_set_costmap(e._e, cells.ctypes.data, sx, sy, 0.0, 0.0, 0.05) == SFW_ERR_INVALID_ARG, (sx, sy)
+    e.set_costmap(cells, 0.0, 0.0, 0.05)
+    e.close()
