@@ -906,7 +906,8 @@ int sfw_batch_last_us(sfw_batch b, int32_t which, double *us_out);
  *   - the (0,0) sample is SFW_COST_SKIPPED in every member: ensemble cost SFW_COST_SKIPPED, rejected[t] = 0;
  *   - rejected[t] = members whose cost is SFW_COST_INVALID; rejected[t] > 0: ensemble cost SFW_COST_INVALID (contact in any
  *     hypothesis rejects the command).  Costmap rejection does not depend on the agents: rejected[t] == M covers it, and
- *     0 < rejected[t] < M always means pedestrian contact in some crowds (a chance constraint reads `rejected`);
+ *     0 < rejected[t] < M always means pedestrian contact in some crowds (a chance constraint is sfw_risk.contact_mass,
+ *     "Risk" below);
  *   - otherwise the social work W_m is aggregated: SFW_ENSEMBLE_MEAN: acc = 0.0; acc = acc + p[m] * W_m for m = 0..M-1 in
  *     that order, each product and sum rounded on its own (p: caller-given, finite, >= 0, need not sum to 1; NULL: 1.0 / M
  *     each); SFW_ENSEMBLE_MAX: the largest W_m (worst case).  The cost is the scoring kernels' own combination of member 0's
@@ -1016,6 +1017,49 @@ int sfw_ensemble_mppi_run(sfw_ensemble e, const sfw_robot_state *rs, const sfw_p
                           const sfw_mppi *m, sfw_blend_stat *stat_out /* I */, double *plans_out /* I x K x 3 */,
                           double *costs_out /* n, nullable */, int32_t *rejected_out /* n, nullable */,
                           sfw_best *best_out /* nullable */);
+/* ---- Risk: a tail expectation (CVaR) of the social work and a bound on the contact mass ----
+ * Sticky state of the ensemble, off by default.  While it is off every call does exactly what is written above.  While it is
+ * set, EVERY aggregation reads it — the three score calls, sfw_ensemble_aggregate and every iteration of
+ * sfw_ensemble_mppi_run — and `mode` keeps its two values.  sfw_ensemble_set_risk makes no device call and does not
+ * invalidate the last score: sfw_ensemble_aggregate after it re-aggregates under the new setting (a risk sweep over one scored
+ * grid costs a launch and a wait per setting, no rollout).  r == NULL turns it off.  A refused call keeps the previous setting.
+ *
+ * Once per aggregation, on the host: p[m] the caller's probability, or 1.0 / M when probs is NULL;
+ * P = ((0.0 + p[0]) + p[1]) + ... in member order; thr = contact_mass * P (one product).
+ * Per sample t, with d_m member m's distance term and W_m its social work; all arithmetic in double, every product, sum and
+ * quotient rounded on its own (no contraction), loops in member order unless stated:
+ *   1. any member SFW_COST_SKIPPED: cost SFW_COST_SKIPPED, rejected[t] = 0 (grids only; unchanged);
+ *   2. rejected[t] = members with d_m == SFW_COST_INVALID (unchanged);
+ *   3. R = the sum of p[m] over the rejecting members, Pa = the sum over the accepting members, both from +0.0;
+ *   4. the cost is SFW_COST_INVALID when rejected[t] == M; or contact_mass == 0 and rejected[t] > 0 (the rule above, bit for
+ *      bit); or contact_mass > 0 and R > thr; or Pa == 0;
+ *   5. otherwise the aggregate A is
+ *        SFW_ENSEMBLE_MAX:  the largest W_m over the ACCEPTING members (tail_mass is not read);
+ *        SFW_ENSEMBLE_MEAN: tau = tail_mass * Pa; rem = tau; acc = +0.0; the accepting members are visited by W_m descending,
+ *          the lower member index first among equal W_m; for each: take = min(p[m], rem); acc = acc + take * W_m;
+ *          rem = rem - take; finally A = acc / tau.  (Once rem == 0 every later member adds +0.0: stopping there changes no
+ *          bit, and the kernel stops there.)
+ *   6. the cost is the scoring kernels' own combination of the pedestrian-free terms of the LOWEST-INDEXED ACCEPTING member and
+ *      A.
+ * Selection, n_valid, the blend and the MPPI chain read this cost vector as they read the plain one.  Consequences:
+ *   - M = 1, p = {1}, tail_mass = 1, contact_mass = 0 is the member's cost bit for bit;
+ *   - tail_mass = 1 is the NORMALISED mean (divided by Pa): it equals the plain SFW_ENSEMBLE_MEAN only to rounding, and only
+ *     when the probabilities sum to 1;
+ *   - a tail_mass no larger than the worst member's share is SFW_ENSEMBLE_MAX to within two roundings ((tau * W) / tau);
+ *   - under contact_mass > 0 a sample may be valid although member 0 rejects it: its cost then comes from another member's
+ *     terms, and `rejected[t]` still counts the rejecting members.
+ * SFW_ERR_INVALID_ARG: e NULL (setter and getter; the getter also for out NULL); a tail_mass that is not finite or outside
+ * (0, 1]; a contact_mass that is not finite or outside [0, 1); reserved != 0.  While a risk is set every aggregating call
+ * refuses P == 0 (all probabilities zero) with SFW_ERR_INVALID_ARG, where it checks the mode and the probabilities: before any
+ * member is staged, so the previous score stays usable. */
+typedef struct sfw_risk {
+  double tail_mass;    /* finite, 0 < tail_mass <= 1: share of the (accepted) probability mass, worst social work first */
+  double contact_mass; /* finite, 0 <= contact_mass < 1: share of the probability mass that may end in contact         */
+  int64_t reserved;    /* 0 */
+} sfw_risk;
+int sfw_ensemble_set_risk(sfw_ensemble e, const sfw_risk *r); /* NULL: off (the default) */
+/* *out: the setting (tail_mass 1, contact_mass 0 while off); *active_out (nullable): 1 while a risk is set, else 0. */
+int sfw_ensemble_get_risk(sfw_ensemble e, sfw_risk *out, int32_t *active_out);
 /* Host wall-clock of the last calls, microseconds: which = 0 staging of the members (the score calls only), 1 the enqueue of
  * the launch and the aggregation, 2 the wait and the copies out. */
 int sfw_ensemble_last_us(sfw_ensemble e, int32_t which, double *us_out);

@@ -234,6 +234,8 @@ EXPORTED_SYMBOLS = (
     "sfw_mppi_run",
     "sfw_ensemble_blend_control",
     "sfw_ensemble_mppi_run",
+    "sfw_ensemble_set_risk",
+    "sfw_ensemble_get_risk",
 )
 # per-term costs (sfw_set_terms_capture / sfw_grid_rescore / sfw_grid_terms)
 SFW_TERM_VEL, SFW_TERM_DISTANCE, SFW_TERM_ANGLE, SFW_TERM_COSTMAP, SFW_TERM_SOCIAL = 0, 1, 2, 3, 4
@@ -290,6 +292,13 @@ class SfwMppi(C.Structure):
 # one grid under several crowd hypotheses (sfw_ensemble_*)
 SFW_ENSEMBLE_MAX_M = 64
 SFW_ENSEMBLE_MEAN, SFW_ENSEMBLE_MAX = 0, 1
+
+
+class SfwRisk(C.Structure):
+    """sfw_risk (include/sfw_hip.h): the tail mass of the social work's CVaR and the bound on the contact mass."""
+
+    _fields_ = [("tail_mass", C.c_double), ("contact_mass", C.c_double), ("reserved", C.c_int64)]
+
 
 SFW_MULTI_RCCL, SFW_MULTI_HOST_REDUCE = 0, 1
 SFW_BATCH_MAX = 256

@@ -3982,6 +3982,9 @@ struct sfw_ensemble_s {
   // sfw_perturb_dst: the table behind the nominal in pin_mppi is the source of its copy)
   mppi_buffers mppi;
   dev_buf<sfw_perturb_dst> pert_dst;
+  // sfw_ensemble_set_risk: read by every aggregation while risk_on (ensemble_check_mode, ensemble_enqueue)
+  sfw_risk risk{1.0, 0.0, 0};
+  bool risk_on = false;
 };
 
 namespace {
@@ -4001,6 +4004,12 @@ int ensemble_each(sfw_ensemble e, const char *what, F f) {
     if (int rc = f(e->b->h[m])) return emember_fail(e, static_cast<int32_t>(m), rc, what);
   return SFW_OK;
 }
+// P of the risk's definition: ((0.0 + p[0]) + p[1]) + ... in member order, p[m] = 1.0 / M without probabilities
+double ensemble_mass(int32_t M, const double *probs) {
+  double P = 0.0;
+  for (int32_t m = 0; m < M; ++m) P = P + (probs ? probs[m] : 1.0 / M);
+  return P;
+}
 // mode and probabilities: no device call
 int ensemble_check_mode(sfw_ensemble e, int32_t mode, const double *probs, const char *what) {
   if (mode != SFW_ENSEMBLE_MEAN && mode != SFW_ENSEMBLE_MAX)
@@ -4009,6 +4018,8 @@ int ensemble_check_mode(sfw_ensemble e, int32_t mode, const double *probs, const
     for (size_t m = 0; m < e->hyp_set.size(); ++m)
       if (!std::isfinite(probs[m]) || !(probs[m] >= 0.0))
         return efail(e, SFW_ERR_INVALID_ARG, std::string(what) + ": probability " + std::to_string(m) + " is not finite and >= 0");
+  if (e->risk_on && ensemble_mass(static_cast<int32_t>(e->hyp_set.size()), probs) == 0.0)
+    return efail(e, SFW_ERR_INVALID_ARG, std::string(what) + ": every probability is zero under a risk (sfw_ensemble_set_risk)");
   return SFW_OK;
 }
 
@@ -4050,15 +4061,24 @@ int ensemble_enqueue(sfw_ensemble e, int32_t mode, const double *probs, bool reu
   char *const out = e->mirrored ? e->pin_out.p + kEnsRecBytes : e->d_out.p;
   const double *const *const d_terms = reinterpret_cast<const double *const *>(e->tab.p);
   const double *const d_probs = reinterpret_cast<const double *>(e->tab.p + sizeof(double) * static_cast<size_t>(M));
+  const double thr = e->risk_on ? e->risk.contact_mass * ensemble_mass(M, probs) : 0.0;  // (the risk's contact threshold: one product)
   const hipError_t he =
-      list ? sfw_launch_ensemble_list(d_terms, d_probs, M, T, mode, w, h0->st.d_linvels, h0->st.d_angvels, reinterpret_cast<double *>(out),
+      e->risk_on
+          ? sfw_launch_ensemble_risk(d_terms, d_probs, M, T, mode, w, e->risk.tail_mass, e->risk.contact_mass, thr, list,
+                                     h0->st.d_linvels, h0->st.d_angvels, h0->st.nw, reinterpret_cast<double *>(out),
+                                     list && e->mirrored ? e->d_cost.p : nullptr, reinterpret_cast<int32_t *>(out + cost_bytes),
+                                     e->partials.p, reinterpret_cast<sfw_sel *>(e->pin_out.p), e->b->stream)
+      : list ? sfw_launch_ensemble_list(d_terms, d_probs, M, T, mode, w, h0->st.d_linvels, h0->st.d_angvels, reinterpret_cast<double *>(out),
                                       e->mirrored ? e->d_cost.p : nullptr, reinterpret_cast<int32_t *>(out + cost_bytes),
                                       e->partials.p, reinterpret_cast<sfw_sel *>(e->pin_out.p), e->b->stream)
            : sfw_launch_ensemble(d_terms, d_probs, M, T, mode, w, h0->st.d_linvels, h0->st.d_angvels, h0->st.nw,
                                  reinterpret_cast<double *>(out), reinterpret_cast<int32_t *>(out + cost_bytes), e->partials.p,
                                  reinterpret_cast<sfw_sel *>(e->pin_out.p), e->b->stream);
   if (he != hipSuccess)
-    return efail(e, SFW_ERR_HIP, std::string(list ? "ensemble: sfw_ens_list_first / sfw_ensemble_stage2: " : "ensemble: sfw_ensemble_stage1/2: ") +
+    return efail(e, SFW_ERR_HIP, std::string(e->risk_on ? (list ? "ensemble: sfw_ens_risk_list / sfw_ensemble_stage2: "
+                                                                : "ensemble: sfw_ens_risk_grid / sfw_ensemble_stage2: ")
+                                             : list   ? "ensemble: sfw_ens_list_first / sfw_ensemble_stage2: "
+                                                      : "ensemble: sfw_ensemble_stage1/2: ") +
                                      hipGetErrorString(he));
   e->cost_dev = !e->mirrored ? reinterpret_cast<const double *>(e->d_out.p) : list ? e->d_cost.p : nullptr;
   return SFW_OK;
@@ -4401,6 +4421,30 @@ int sfw_ensemble_aggregate(sfw_ensemble e, int32_t mode, const double *probs, do
   for (sfw_handle h : e->b->h) stream_is_idle(h);
   if (int rc = ensemble_finish(e, costs_out, rejected_out, best_out)) return rc;
   e->us[2] = us_since(t0);
+  return SFW_OK;
+}
+
+int sfw_ensemble_set_risk(sfw_ensemble e, const sfw_risk *r) {
+  if (!e) return SFW_ERR_INVALID_ARG;
+  if (!r) {
+    e->risk = sfw_risk{1.0, 0.0, 0};
+    e->risk_on = false;
+    return SFW_OK;
+  }
+  if (!std::isfinite(r->tail_mass) || !(r->tail_mass > 0.0 && r->tail_mass <= 1.0))
+    return efail(e, SFW_ERR_INVALID_ARG, "ensemble_set_risk: tail_mass must be finite, > 0 and <= 1");
+  if (!std::isfinite(r->contact_mass) || !(r->contact_mass >= 0.0 && r->contact_mass < 1.0))
+    return efail(e, SFW_ERR_INVALID_ARG, "ensemble_set_risk: contact_mass must be finite, >= 0 and < 1");
+  if (r->reserved != 0) return efail(e, SFW_ERR_INVALID_ARG, "ensemble_set_risk: reserved must be 0");
+  e->risk = *r;
+  e->risk_on = true;
+  return SFW_OK;
+}
+
+int sfw_ensemble_get_risk(sfw_ensemble e, sfw_risk *out, int32_t *active_out) {
+  if (!e || !out) return SFW_ERR_INVALID_ARG;
+  *out = e->risk;
+  if (active_out) *active_out = e->risk_on ? 1 : 0;
   return SFW_OK;
 }
 

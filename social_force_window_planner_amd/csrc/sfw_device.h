@@ -340,6 +340,12 @@ hipError_t sfw_launch_ensemble(const double *const *terms, const double *probs, 
 hipError_t sfw_launch_ensemble_list(const double *const *terms, const double *probs, int M, int64_t T, int mode,
                                     const sfw_weights &w, const double *linvels, const double *angvels, double *costs,
                                     double *costs_dev, int32_t *rejected, sfw_sel *partials, sfw_sel *sel_host, hipStream_t stream);
+// ... under a risk (sfw_ensemble_set_risk): the grid's first stage (list false: nw, no costs_dev) or the list's, then the same
+// second stage.  thr = contact_mass * P, the host's product.
+hipError_t sfw_launch_ensemble_risk(const double *const *terms, const double *probs, int M, int64_t T, int mode,
+                                    const sfw_weights &w, double tail_mass, double contact_mass, double thr, bool list,
+                                    const double *linvels, const double *angvels, int32_t nw, double *costs, double *costs_dev,
+                                    int32_t *rejected, sfw_sel *partials, sfw_sel *sel_host, hipStream_t stream);
 // sfw_grid_blend: the cost vector (+ bias, nullable) of a launch over T samples -> softmin weights for L temperatures, their
 // sums and the weighted mean of the K knot rows (list: linvels / vy (nullable) / angvels hold K rows of T values, knot-major;
 // else a grid of T / nw x nw samples, K == 1).  Three launches: `mins` (sfw_blend_min_blocks(T) records), `partials`

@@ -2847,6 +2847,108 @@ sfw_ens_list_first(const double *const *terms, const double *probs, int M, int64
     if (sel_host) *sel_host = best;  // (single-block launch: the partial is the result)
   }
 }
+
+// The first stage under a risk (sfw_ensemble_set_risk; the definition is the header's, in its operation order): a bound on the
+// probability mass that may end in contact in place of "any member rejects", and under MEAN the conditional tail expectation
+// of the social work over the accepting members in place of the weighted sum.  One text for the grid and the list
+// (sfw_ens_risk_grid / sfw_ens_risk_list).  Pass 1 reads every member's distance term and social work once and leaves the
+// accepting members as a 64-bit mask (M <= SFW_ENSEMBLE_MAX_M), R, Pa and MAX's aggregate.  The ordered walk is a selection
+// walk: each pass re-reads the social work of the members not yet visited (coalesced over t, resident in L2), takes the
+// largest — the lower index among equals — with its probability, and the walk ends once the tail mass is used up (every
+// later member would add +0.0).  The masks are registers and the member index is wave-uniform: no private array, no scratch.
+// The cost is formed from the terms of the lowest-indexed accepting member, whose table entry is the one per-lane load.
+template <bool LIST>
+__device__ __forceinline__ void sfw_ens_risk_first(const double *const *terms, const double *probs, int M, int64_t T, int mode,
+                                                   const sfw_weights &w, double tail_mass, double contact_mass, double thr,
+                                                   const double *linvels, const double *angvels, int nw, double *costs,
+                                                   double *costs_dev, int32_t *rejected, sfw_sel *partials, sfw_sel *sel_host) {
+#pragma clang fp contract(off)
+  typedef const double *member_terms;
+  typedef const __attribute__((address_space(4))) member_terms *terms_ptr;
+  typedef const __attribute__((address_space(4))) double *probs_ptr;
+  const terms_ptr tp = (terms_ptr)terms;
+  const probs_ptr pp = (probs_ptr)probs;
+  sfw_sel best = sel_empty();
+  for (int64_t t = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; t < T;
+       t += static_cast<int64_t>(gridDim.x) * blockDim.x) {
+    int32_t rej = 0;
+    bool skipped = false;
+    uint64_t accept = 0;
+    double R = 0.0, Pa = 0.0, wmax = 0.0;
+    for (int m = 0; m < M; ++m) {
+      const double *const tm = tp[m];
+      const double d = tm[SFW_TERM_DISTANCE * T + t], sw = tm[SFW_TERM_SOCIAL * T + t];
+      const double p = pp[m];
+      const bool rejects = d == SFW_COST_INVALID;
+      if (!LIST) skipped = skipped || d == SFW_COST_SKIPPED;
+      rej += rejects ? 1 : 0;
+      R = rejects ? R + p : R;
+      Pa = rejects ? Pa : Pa + p;
+      wmax = (!rejects && (accept == 0 || sw > wmax)) ? sw : wmax;
+      accept |= rejects ? uint64_t(0) : uint64_t(1) << m;
+    }
+    double c;
+    if (skipped) {
+      c = SFW_COST_SKIPPED;
+      rej = 0;
+    } else if (rej == M || (contact_mass == 0.0 ? rej > 0 : R > thr) || Pa == 0.0) {
+      c = SFW_COST_INVALID;
+    } else {
+      double A = wmax;
+      if (mode == SFW_ENSEMBLE_MEAN) {
+        const double tau = tail_mass * Pa;
+        double rem = tau, acc = 0.0;
+        uint64_t left = accept;
+        while (left != 0 && rem != 0.0) {
+          double bw = 0.0, bp = 0.0;
+          int bm = -1;
+          for (int m = 0; m < M; ++m) {
+            if (!((left >> m) & 1)) continue;
+            const double sw = tp[m][SFW_TERM_SOCIAL * T + t];
+            if (bm < 0 || sw > bw) {
+              bw = sw;
+              bp = pp[m];
+              bm = m;
+            }
+          }
+          left &= ~(uint64_t(1) << bm);
+          const double take = bp < rem ? bp : rem;
+          acc = acc + take * bw;
+          rem = rem - take;
+        }
+        A = acc / tau;
+      }
+      const double *const t0 = terms[__builtin_ctzll(accept)];
+      const double vel = t0[SFW_TERM_VEL * T + t], d0 = t0[SFW_TERM_DISTANCE * T + t], ang = t0[SFW_TERM_ANGLE * T + t];
+      const double cm = t0[SFW_TERM_COSTMAP * T + t];
+      c = sfw_cost_add_social(sfw_cost_add_costmap(sfw_cost_base(w.vel, vel, w.distance, d0, w.angle, ang), w.costmap, cm),
+                              w.social, A);
+    }
+    costs[t] = c;
+    if (LIST && costs_dev) costs_dev[t] = c;
+    rejected[t] = rej;
+    sel_consider<LIST>(best, c, linvels, angvels, nw, t, 0);
+  }
+  best = block_reduce(best);
+  if (threadIdx.x == 0) {
+    partials[blockIdx.x] = best;
+    if (sel_host) *sel_host = best;  // (single-block launch: the partial is the result)
+  }
+}
+__global__ void __launch_bounds__(ARGMIN_BLOCK)
+sfw_ens_risk_grid(const double *const *terms, const double *probs, int M, int64_t T, int mode, sfw_weights w, double tail_mass,
+                  double contact_mass, double thr, const double *linvels, const double *angvels, int nw, double *costs,
+                  int32_t *rejected, sfw_sel *partials, sfw_sel *sel_host) {
+  sfw_ens_risk_first<false>(terms, probs, M, T, mode, w, tail_mass, contact_mass, thr, linvels, angvels, nw, costs, nullptr, rejected,
+                            partials, sel_host);
+}
+__global__ void __launch_bounds__(ARGMIN_BLOCK)
+sfw_ens_risk_list(const double *const *terms, const double *probs, int M, int64_t T, int mode, sfw_weights w, double tail_mass,
+                  double contact_mass, double thr, const double *linvels, const double *angvels, double *costs, double *costs_dev,
+                  int32_t *rejected, sfw_sel *partials, sfw_sel *sel_host) {
+  sfw_ens_risk_first<true>(terms, probs, M, T, mode, w, tail_mass, contact_mass, thr, linvels, angvels, 1, costs, costs_dev, rejected,
+                           partials, sel_host);
+}
 #endif  // SFW_STRICT_BUILD
 
 #ifndef SFW_STRICT_BUILD  // (costs are doubles in every precision mode: the blend's kernels exist once)
@@ -3851,6 +3953,24 @@ hipError_t sfw_launch_ensemble_list(const double *const *terms, const double *pr
   hipLaunchKernelGGL(sfw_ens_list_first, dim3(static_cast<unsigned>(blocks)), dim3(ARGMIN_BLOCK), 0, stream, terms, probs, M, T,
                      mode, w, linvels, angvels, costs, costs_dev, rejected, partials,
                      blocks == 1 ? sel_host : static_cast<sfw_sel *>(nullptr));
+  if (blocks > 1)
+    hipLaunchKernelGGL(sfw_ensemble_stage2, dim3(1), dim3(ARGMIN_BLOCK), 0, stream, static_cast<const sfw_sel *>(partials), blocks,
+                       sel_host);
+  return hipGetLastError();
+}
+hipError_t sfw_launch_ensemble_risk(const double *const *terms, const double *probs, int M, int64_t T, int mode,
+                                    const sfw_weights &w, double tail_mass, double contact_mass, double thr, bool list,
+                                    const double *linvels, const double *angvels, int32_t nw, double *costs, double *costs_dev,
+                                    int32_t *rejected, sfw_sel *partials, sfw_sel *sel_host, hipStream_t stream) {
+  if (M < 1 || M > SFW_ENSEMBLE_MAX_M || T < 1) return hipErrorInvalidValue;  // (the accepting members are a 64-bit mask)
+  const int blocks = static_cast<int>(sfw_argmin_partials(T));
+  sfw_sel *const rec = blocks == 1 ? sel_host : static_cast<sfw_sel *>(nullptr);
+  if (list)
+    hipLaunchKernelGGL(sfw_ens_risk_list, dim3(static_cast<unsigned>(blocks)), dim3(ARGMIN_BLOCK), 0, stream, terms, probs, M, T, mode,
+                       w, tail_mass, contact_mass, thr, linvels, angvels, costs, costs_dev, rejected, partials, rec);
+  else
+    hipLaunchKernelGGL(sfw_ens_risk_grid, dim3(static_cast<unsigned>(blocks)), dim3(ARGMIN_BLOCK), 0, stream, terms, probs, M, T, mode,
+                       w, tail_mass, contact_mass, thr, linvels, angvels, nw, costs, rejected, partials, rec);
   if (blocks > 1)
     hipLaunchKernelGGL(sfw_ensemble_stage2, dim3(1), dim3(ARGMIN_BLOCK), 0, stream, static_cast<const sfw_sel *>(partials), blocks,
                        sel_host);

@@ -29,6 +29,7 @@ from ._abi import (
     SFW_MPPI_MAX_ITER,
     SfwParams,
     SfwPerturb,
+    SfwRisk,
     SfwRobotState,
     SfwPlanInfo,
     SfwWeights,
@@ -190,6 +191,8 @@ def lib():
         L.sfw_ensemble_mppi_run.argtypes = [vp, C.POINTER(SfwRobotState), C.POINTER(SfwPerturb), C.c_int32, C.c_int32, vp,
                                             C.POINTER(SfwGoalArgs), C.c_int32, vp, C.POINTER(SfwMppi), C.POINTER(SfwBlendStat), vp,
                                             vp, vp, C.POINTER(SfwBest)]
+        L.sfw_ensemble_set_risk.argtypes = [vp, C.POINTER(SfwRisk)]
+        L.sfw_ensemble_get_risk.argtypes = [vp, C.POINTER(SfwRisk), C.POINTER(C.c_int32)]
         _lib = L
     return _lib
 
@@ -1095,6 +1098,25 @@ class EnsembleScorer(_Owner):
         self._mark_scored((n, 1), knots=K)
         res = ([stats[i].as_dict() for i in range(I)], plans, best.as_dict())
         return res + (costs, rejected) if want_costs else res
+
+    # -- risk ---------------------------------------------------------------
+    def set_risk(self, tail_mass=1.0, contact_mass=0.0):
+        """sfw_ensemble_set_risk: from here on every aggregation (the score calls, aggregate, mppi_run) takes "mean" as the
+        tail expectation of the social work over the worst `tail_mass` of the accepted probability mass, and rejects a sample
+        only when more than `contact_mass` of the probability mass ends in contact.  The last score stays: aggregate()
+        re-aggregates it under the new setting."""
+        r = SfwRisk(float(tail_mass), float(contact_mass), 0)
+        self._check(lib().sfw_ensemble_set_risk(self._e, C.byref(r)), "sfw_ensemble_set_risk")
+
+    def clear_risk(self):
+        """Back to the plain aggregation (sfw_ensemble_set_risk with NULL)."""
+        self._check(lib().sfw_ensemble_set_risk(self._e, None), "sfw_ensemble_set_risk")
+
+    def risk(self):
+        """The setting as {"tail_mass", "contact_mass"}, or None while no risk is set."""
+        r, on = SfwRisk(), C.c_int32()
+        self._check(lib().sfw_ensemble_get_risk(self._e, C.byref(r), C.byref(on)), "sfw_ensemble_get_risk")
+        return {"tail_mass": r.tail_mass, "contact_mass": r.contact_mass} if on.value else None
 
     def knots(self, first, count):
         """The knots of samples [first, first + count) of the last sequence score as (K, 3, count): member 0's (every member
