@@ -182,7 +182,27 @@ int sfw_abi_version(void);
  * visible — there is no CPU fallback in this library. */
 int sfw_create(const sfw_params *params, int device, sfw_handle *out);
 int sfw_destroy(sfw_handle h);
-/* The reference re-reads its parameters on every cycle (:125). */
+/* The reference re-reads its parameters on every cycle (:125).
+ * Every call that takes parameters — sfw_create, sfw_set_params, sfw_batch_create, sfw_ensemble_create,
+ * sfw_ensemble_set_params — answers SFW_ERR_INVALID_ARG, and leaves the handle's parameters as they were, for
+ *   - a sim_time or sim_granularity that is not finite, a sim_granularity that is not > 0, a sim_time < 0;
+ *   - a step count beyond SFW_MAX_STEPS.  The count is int(sim_time / sim_granularity + 0.5), at least 1 (:519-525); it
+ *     is an `int` in every kernel and sizes every table, and a quotient that does not fit an int has no defined
+ *     conversion.  What indexes by the count S: the step counters themselves, which run in strides of 8 (S + 8 must
+ *     fit); S * K over the footprint's vertices and 3 * S over a pose's components, formed in int; (sample * S + step) * 3,
+ *     step * row and chunk * S, formed in 64 bits; and (chunk * S) / 256 blocks of the footprint launch in 32 bits, a
+ *     chunk being at least 1024 samples when the stage has as many.  2^20 steps keep every one of the int products
+ *     below 2^31 with a factor of 2^10 to spare (1024 footprint vertices) and the block count below 2^32 up to chunks
+ *     of 2^20 samples; at the reference's 0.025 s per step they are a horizon of seven hours.  Memory for that many
+ *     steps is another matter: a stage that cannot have its tables answers SFW_ERR_HIP;
+ *   - max_vel_x that is 0 or not finite: the velocity term is |max_vel_x - vx| / max_vel_x (:654), 0/0 or x/0 there — a
+ *     cost that is neither a cost nor a sentinel.  A NEGATIVE max_vel_x is the caller's business: the reference divides
+ *     by it unguarded and so does this library (the term is then <= 0).
+ * The accelerations of sfw_goal_args must be finite (every stage checks that) and are otherwise the caller's business
+ * as well: the reference's computeNewVelocity (:457-463) has a value for a zero and for a negative limit (0: the
+ * velocity never changes; negative: min(target, v - |a| dt) runs away from a target above it), and the kernels compute
+ * exactly that (tests/test_rollout_gpu.py holds both). */
+#define SFW_MAX_STEPS 1048576 /* 2^20 */
 int sfw_set_params(sfw_handle h, const sfw_params *params);
 const char *sfw_last_error(sfw_handle h);
 

@@ -356,6 +356,11 @@ static double social_work(const sfw_params &p, const std::vector<Agent> &ag) {
   return wr + wp;
 }
 
+// what sfw_create / sfw_set_params refuse about the step count (sfw_hip.h SFW_MAX_STEPS): no defined conversion beyond it
+static inline bool steps_ok(const sfw_params &p) {
+  return std::isfinite(p.sim_time) && std::isfinite(p.sim_granularity) && p.sim_granularity > 0 && p.sim_time >= 0 &&
+         p.sim_time / p.sim_granularity + 0.5 < double(SFW_MAX_STEPS) + 1.0;
+}
 static inline int num_steps_of(const sfw_params &p) {
   int n = int(p.sim_time / p.sim_granularity + 0.5);  // ref :519
   return n == 0 ? 1 : n;                               // ref :523-525
@@ -581,7 +586,7 @@ using sfwo::World;
 extern "C" {
 
 int sfwo_create(const sfw_params *p, void **out) {
-  if (!p || !out) return SFW_ERR_INVALID_ARG;
+  if (!p || !out || !sfwo::steps_ok(*p)) return SFW_ERR_INVALID_ARG;
   World *w = new World();
   w->p = *p;
   *out = w;
@@ -589,7 +594,7 @@ int sfwo_create(const sfw_params *p, void **out) {
 }
 int sfwo_destroy(void *h) { delete static_cast<World *>(h); return SFW_OK; }
 int sfwo_set_params(void *h, const sfw_params *p) {
-  if (!h || !p) return SFW_ERR_INVALID_ARG;
+  if (!h || !p || !sfwo::steps_ok(*p)) return SFW_ERR_INVALID_ARG;
   static_cast<World *>(h)->p = *p;
   return SFW_OK;
 }
@@ -726,7 +731,8 @@ int sfwo_group_force(const sfw_params *p, const sfw_agent *a, int32_t A, int32_t
   return SFW_OK;
 }
 float sfwo_normalize_angle(float v, float mn, float mx) { return sfwo::normalize_angle_f(v, mn, mx); }
-int sfwo_num_steps(const sfw_params *p) { return sfwo::num_steps_of(*p); }
+// (SFW_ERR_INVALID_ARG, a negative number, for what sfw_set_params refuses)
+int sfwo_num_steps(const sfw_params *p) { return p && sfwo::steps_ok(*p) ? sfwo::num_steps_of(*p) : SFW_ERR_INVALID_ARG; }
 int sfwo_max_threads(void) {
 #ifdef _OPENMP
   return omp_get_max_threads();

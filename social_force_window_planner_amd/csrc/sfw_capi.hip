@@ -432,6 +432,7 @@ hipError_t wait_stream(sfw_handle h) {
 // `chunk` positions and at most chunk + 2 velocities (a one-column grid) must stay below 4 GB
 constexpr int64_t kRowLimit = static_cast<int64_t>((uint64_t(1) << 32) / (2 * sizeof(sfw_unit))) - 2;
 
+// (of params check_params has admitted: the quotient is finite and below SFW_MAX_STEPS + 1, so the conversion is defined)
 int num_steps_of(const sfw_params &p) {
   int n = static_cast<int>(p.sim_time / p.sim_granularity + 0.5);  // ref :519
   return n == 0 ? 1 : n;                                           // ref :523-525
@@ -441,6 +442,14 @@ int check_params(sfw_handle h, const sfw_params *p) {
   if (!p) return fail(h, SFW_ERR_INVALID_ARG, "params is NULL");
   if (!(p->sim_granularity > 0) || !(p->sim_time >= 0))
     return fail(h, SFW_ERR_INVALID_ARG, "sim_time/sim_granularity out of range");
+  // The step count sizes every table and is an `int` everywhere: a quotient that does not fit has no defined conversion
+  // (sfw_hip.h SFW_MAX_STEPS).  The compare is written so that an infinite or NaN quotient fails it.
+  if (!std::isfinite(p->sim_time) || !std::isfinite(p->sim_granularity) ||
+      !(p->sim_time / p->sim_granularity + 0.5 < static_cast<double>(SFW_MAX_STEPS) + 1.0))
+    return fail(h, SFW_ERR_INVALID_ARG, "sim_time/sim_granularity not finite, or more than SFW_MAX_STEPS steps");
+  // the velocity term divides by max_vel_x (ref :654): 0 gives 0/0 or x/0, a cost that is neither a cost nor a sentinel
+  if (!std::isfinite(p->max_vel_x) || p->max_vel_x == 0.0)
+    return fail(h, SFW_ERR_INVALID_ARG, "max_vel_x must be finite and not 0");
   if (p->precision != SFW_PRECISION_F64 && p->precision != SFW_PRECISION_F32 && p->precision != SFW_PRECISION_F64_STRICT)
     return fail(h, SFW_ERR_INVALID_ARG, "unknown precision");
   if (!(p->sfm_gamma > 0) || !(p->sfm_relaxation_time > 0) || !(p->sfm_force_sigma_obstacle > 0))
