@@ -340,10 +340,13 @@ const double *sfw_grid_costs_view(sfw_handle h);
  * a grid's rows (a sample with vx == 0 and vy == 0).
  *
  * A member of a sfw_batch may be staged with a list: its results after
- * sfw_batch_launch / _fetch are bit-identical to its own launch; it does not
- * join the batched kernel (sfw_batch_desc.own_path_members counts it).
- * sfw_batch_score_grid and sfw_multi_* take grids only; an ensemble scores
- * a list as sequences of one knot (sfw_ensemble_score_sequences, K == 1).
+ * sfw_batch_launch / _fetch are bit-identical to its own launch.  By default
+ * it does not join the batched kernel (sfw_batch_desc.own_path_members counts
+ * it); with sfw_batch_set_list_fusion(b, 1) a list whose launch is the
+ * one-kernel cycle (one_launch) joins the batched launch of the lists
+ * (one_launch_members).  sfw_batch_score_samples scores one list per member;
+ * sfw_multi_* take grids only; an ensemble scores a list as sequences of one
+ * knot (sfw_ensemble_score_sequences, K == 1).
  */
 int sfw_samples_stage(sfw_handle h, const sfw_robot_state *rs, const double *vx, const double *vy,
                       const double *vtheta, int32_t n, const sfw_goal_args *args, int64_t index_base);
@@ -412,10 +415,14 @@ int sfw_score_samples(sfw_handle h, const sfw_robot_state *rs, const double *vx,
  * move at a later knot is at rest at the handed-over pose only: reproduced,
  * flag 0.
  *
- * A member of a sfw_batch may be staged with sequences: it takes its own
- * path (sfw_batch_desc.own_path_members), bit-identical to its own launch.
- * sfw_batch_score_grid and sfw_multi_* keep taking grids only; an ensemble
- * scores sequences through sfw_ensemble_score_sequences / _score_perturbed.
+ * A member of a sfw_batch may be staged with sequences: by default it takes
+ * its own path (sfw_batch_desc.own_path_members); with
+ * sfw_batch_set_list_fusion(b, 1) sequences whose launch is the one-kernel
+ * cycle join the batched launch of the sequences (K == 1: of the lists).
+ * Either way bit-identical to its own launch.  sfw_batch_score_sequences /
+ * _score_perturbed score one set of sequences per member; sfw_multi_* keep
+ * taking grids only; an ensemble scores sequences through
+ * sfw_ensemble_score_sequences / _score_perturbed.
  */
 #define SFW_SEQ_MAX_KNOTS 64
 int sfw_sequences_stage(sfw_handle h, const sfw_robot_state *rs, const double *vx, const double *vy,
@@ -885,7 +892,14 @@ int sfw_multi_grid_points(sfw_multi_handle m, int64_t index, double *points_xyth
  * laser points: a homogeneous fleet is one launch), the others through their usual kernels behind it on the same stream.
  * Every member's results (costs, sentinels, selection, captured Trajectory points, contact steps) are bit-identical to
  * its own launch, and after sfw_batch_fetch sfw_grid_costs_view / sfw_grid_fetch / sfw_grid_points(_batch) of a member
- * behave as after that member's own launch.  Member timing (sfw_set_timing) is not recorded in a batch launch. */
+ * behave as after that member's own launch.  Member timing (sfw_set_timing) is not recorded in a batch launch.
+ * A member staged with a sample list, sequences or perturbed rollouts takes its own path by default.  Under the sticky switch
+ * sfw_batch_set_list_fusion (off when the batch is created) such a member joins the batched launch too, when its own launch
+ * would be the one-kernel cycle: the kernel variant is then stage kind (grid / list / sequences of more than one knot) x
+ * precision x groups x laser points — a fleet of MPPI controllers with n <= 1024 rollouts each is ONE launch — and the member
+ * counts under one_launch_members.  A member that does not qualify (more than 1024 samples, more steps than the small-rollout
+ * limit, a crowd beyond the 64-double planes, SFW_CYCLE_FUSED=0, a chunked stage) keeps its own path.  A perturbed member's
+ * draw is enqueued by its stage on the batch's stream, ahead of the launch.  Results are bit-identical either way. */
 #define SFW_BATCH_MAX 256
 typedef struct sfw_batch_s *sfw_batch;
 /* 1 <= B <= SFW_BATCH_MAX; SFW_ERR_NO_DEVICE without a GPU, as sfw_create. */
@@ -904,6 +918,22 @@ int sfw_batch_fetch(sfw_batch b, sfw_best *best_out);
  * nothing. */
 int sfw_batch_score_grid(sfw_batch b, const sfw_robot_state *rs, const double *linvels, int32_t nv,
                          const double *angvels, int32_t nw, const sfw_goal_args *args, sfw_best *best_out);
+/* The sticky switch described above.  enabled != 0: on.  SFW_ERR_INVALID_ARG: b (or enabled_out) NULL. */
+int sfw_batch_set_list_fusion(sfw_batch b, int32_t enabled);
+int sfw_batch_get_list_fusion(sfw_batch b, int32_t *enabled_out);
+/* The list forms of sfw_batch_score_grid: member i is staged with rs[i], args[i] and its OWN samples by the single stage's
+ * function (sfw_samples_stage, sfw_sequences_stage, sfw_sequences_perturb_stage; index_base 0), then launch and fetch.  The
+ * arrays are member-major: member i's knot k of sample t lies at [(i * K + k) * n + t] (K == 1 for samples); vy is nullable;
+ * knot_step[K] is common; p holds B perturbations.  The argument rules are the single stage's, read for ALL members before any
+ * member is staged: a call refused for its arguments (SFW_ERR_INVALID_ARG) changes nothing — the previous launch is still
+ * fetchable —, and a failing stage launches nothing.  They honour sfw_batch_set_list_fusion; they do not turn it on. */
+int sfw_batch_score_samples(sfw_batch b, const sfw_robot_state *rs, const double *vx, const double *vy, const double *vtheta,
+                            int32_t n, const sfw_goal_args *args, sfw_best *best_out);
+int sfw_batch_score_sequences(sfw_batch b, const sfw_robot_state *rs, const double *vx, const double *vy,
+                              const double *vtheta, int32_t n, int32_t K, const int32_t *knot_step,
+                              const sfw_goal_args *args, sfw_best *best_out);
+int sfw_batch_score_perturbed(sfw_batch b, const sfw_robot_state *rs, const sfw_perturb *p /* [B] */, int32_t n, int32_t K,
+                              const int32_t *knot_step, const sfw_goal_args *args, sfw_best *best_out);
 /* What the last launch did: members that went through a batched launch, members on their own path, batched launches,
  * blocks over all batched launches and the largest dynamic LDS of a block among them (bytes). */
 typedef struct sfw_batch_desc {
@@ -1080,6 +1110,15 @@ typedef struct sfw_risk {
 int sfw_ensemble_set_risk(sfw_ensemble e, const sfw_risk *r); /* NULL: off (the default) */
 /* *out: the setting (tail_mass 1, contact_mass 0 while off); *active_out (nullable): 1 while a risk is set, else 0. */
 int sfw_ensemble_get_risk(sfw_ensemble e, sfw_risk *out, int32_t *active_out);
+/* sfw_batch_set_list_fusion of the ensemble's private batch (off by default): with it on, sfw_ensemble_score_sequences,
+ * _score_perturbed and every iteration of sfw_ensemble_mppi_run score the M members in one batched launch (per kernel variant)
+ * instead of M launches; the chain uploads the member table in iteration 0 and launches again from the device copy while an
+ * iteration's records are the bytes last uploaded.  Bit-identical results either way. */
+int sfw_ensemble_set_list_fusion(sfw_ensemble e, int32_t enabled);
+int sfw_ensemble_get_list_fusion(sfw_ensemble e, int32_t *enabled_out);
+/* sfw_batch_describe of the private batch's last launch (SFW_ERR_STATE before any); *table_uploads_out (nullable): member-table
+ * uploads of the last sfw_ensemble_mppi_run's launches (0 without list fusion). */
+int sfw_ensemble_batch_desc(sfw_ensemble e, sfw_batch_desc *out, int64_t *table_uploads_out);
 /* Host wall-clock of the last calls, microseconds: which = 0 staging of the members (the score calls only), 1 the enqueue of
  * the launch and the aggregation, 2 the wait and the copies out. */
 int sfw_ensemble_last_us(sfw_ensemble e, int32_t which, double *us_out);

@@ -200,6 +200,14 @@ EXPORTED_SYMBOLS = (
     "sfw_batch_score_grid",
     "sfw_batch_describe",
     "sfw_batch_last_us",
+    "sfw_batch_set_list_fusion",
+    "sfw_batch_get_list_fusion",
+    "sfw_batch_score_samples",
+    "sfw_batch_score_sequences",
+    "sfw_batch_score_perturbed",
+    "sfw_ensemble_set_list_fusion",
+    "sfw_ensemble_get_list_fusion",
+    "sfw_ensemble_batch_desc",
     "sfw_set_terms_capture",
     "sfw_grid_rescore",
     "sfw_grid_terms",

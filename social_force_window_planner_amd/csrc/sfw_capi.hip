@@ -3713,6 +3713,12 @@ struct sfw_batch_s {
   sfw_batch_desc desc{};
   double us[3] = {0.0, 0.0, 0.0};
   bool launched = false;
+  // sfw_batch_set_list_fusion: list / sequence / perturbed members that qualify join the member table (off: their own path)
+  bool list_fusion = false;
+  // the member table as last uploaded (host copy), and how many uploads there have been: a launch that may re-use the device
+  // copy (batch_enqueue reuse_table) compares what it has built with it
+  std::vector<char> table_host, table_sent;
+  int64_t table_uploads = 0;
 };
 
 namespace {
@@ -3728,8 +3734,10 @@ double us_since(std::chrono::steady_clock::time_point t0) {
 }
 
 // every member staged (batch_launch has checked): one launch per kernel variant for the members that qualify for the
-// one-kernel control cycle, the others' kernels behind them on the same stream
-int batch_enqueue(sfw_batch b) {
+// one-kernel control cycle, the others' kernels behind them on the same stream.  reuse_table (sfw_ensemble_mppi_run, iterations
+// > 0): when the table built here is byte for byte the one the device holds, neither the pinned copy — whose reserve waits for
+// the last upload's event — nor the upload is redone; when it is not, it is uploaded as always.
+int batch_enqueue(sfw_batch b, bool reuse_table = false) {
   const int32_t B = static_cast<int32_t>(b->h.size());
   if (hipSetDevice(b->device) != hipSuccess) return bfail(b, SFW_ERR_HIP, "batch_launch: hipSetDevice failed");
   std::vector<launch_prep> lp(static_cast<size_t>(B));
@@ -3739,7 +3747,9 @@ int batch_enqueue(sfw_batch b) {
   for (int32_t i = 0; i < B; ++i) {
     const size_t m = static_cast<size_t>(i);
     if (int e = launch_prepare(b->h[m], false, lp[m])) return bmember_fail(b, i, e, "batch_launch");
-    if (b->h[m]->st.list) continue;  // a sample list (sfw_samples_stage) takes its own path: no list form of the batched kernel
+    // a sample list (sfw_samples_stage, sequences, perturbed rollouts) takes its own path unless the batch fuses lists
+    // (sfw_batch_set_list_fusion): then it joins the table under the variant of its kind
+    if (b->h[m]->st.list && !b->list_fusion) continue;
     if (cycle_launch_of(b->h[m], lp[m], L[m])) {
       variant[m] = sfw_cycle_batch_variant(L[m]);
       ++n_cycle;
@@ -3751,7 +3761,7 @@ int batch_enqueue(sfw_batch b) {
   d.own_path_members = B - n_cycle;
   if (n_cycle > 0) {
     // table: per variant (= per launch) first[n + 1], then the records of all launches, in variant order
-    constexpr int kVariants = 9;
+    constexpr int kVariants = SFW_BATCH_VARIANTS;
     int32_t count[kVariants] = {};
     for (int v : variant)
       if (v >= 0) ++count[v];
@@ -3764,9 +3774,9 @@ int batch_enqueue(sfw_batch b) {
       }
     head = (head + 15) & ~size_t(15);
     const size_t bytes = head + sizeof(sfw_batch_rec) * static_cast<size_t>(n_cycle);
-    if (b->pin_table.reserve(bytes) != hipSuccess || b->table.reserve(bytes) != hipSuccess)
-      return bfail(b, SFW_ERR_HIP, "batch_launch: member table allocation failed");
-    char *const pt = b->pin_table.p;
+    // (built in plain host memory first: whether it must be uploaded is known only once it stands)
+    b->table_host.assign(bytes, 0);
+    char *const pt = b->table_host.data();
     size_t rec_at[kVariants] = {};
     for (int v = 0, r = 0; v < kVariants; ++v)
       if (count[v] > 0) {
@@ -3788,13 +3798,22 @@ int batch_enqueue(sfw_batch b) {
     }
     for (int v = 0; v < kVariants; ++v)
       if (count[v] > 0) reinterpret_cast<uint32_t *>(pt + first_at[v])[count[v]] = blocks[v];
-    if (hipMemcpyAsync(b->table.p, pt, bytes, hipMemcpyHostToDevice, b->stream) != hipSuccess || b->pin_table.mark(b->stream) != hipSuccess)
-      return bfail(b, SFW_ERR_HIP, "batch_launch: member table copy failed");
+    if (!(reuse_table && b->table.p && b->table_sent == b->table_host)) {
+      b->table_sent.clear();  // (nothing is known of the device copy until the upload below is enqueued)
+      if (b->pin_table.reserve(bytes) != hipSuccess || b->table.reserve(bytes) != hipSuccess)
+        return bfail(b, SFW_ERR_HIP, "batch_launch: member table allocation failed");
+      std::memcpy(b->pin_table.p, pt, bytes);
+      if (hipMemcpyAsync(b->table.p, b->pin_table.p, bytes, hipMemcpyHostToDevice, b->stream) != hipSuccess ||
+          b->pin_table.mark(b->stream) != hipSuccess)
+        return bfail(b, SFW_ERR_HIP, "batch_launch: member table copy failed");
+      b->table_sent.swap(b->table_host);
+      ++b->table_uploads;
+    }
     for (int v = 0; v < kVariants; ++v) {
       if (count[v] == 0) continue;
       const uint32_t *const d_first = reinterpret_cast<const uint32_t *>(b->table.p + first_at[v]);
       const sfw_batch_rec *const d_recs = reinterpret_cast<const sfw_batch_rec *>(b->table.p + rec_at[v]);
-      const hipError_t e = v / 3 == 2 ? sfw_launch_cycle_batch_strict(v, d_first, d_recs, count[v], blocks[v], lds[v], b->stream)
+      const hipError_t e = v % 9 / 3 == 2 ? sfw_launch_cycle_batch_strict(v, d_first, d_recs, count[v], blocks[v], lds[v], b->stream)
                                       : sfw_launch_cycle_batch(v, d_first, d_recs, count[v], blocks[v], lds[v], b->stream);
       if (e != hipSuccess) return bfail(b, SFW_ERR_HIP, std::string("batch_launch: sfw_batch_cycle_kernel: ") + hipGetErrorString(e));
       ++d.batch_launches;
@@ -3825,12 +3844,12 @@ int batch_enqueue(sfw_batch b) {
   return SFW_OK;
 }
 
-int batch_launch(sfw_batch b) {
+int batch_launch(sfw_batch b, bool reuse_table = false) {
   // every member staged, or nothing is enqueued
   for (size_t i = 0; i < b->h.size(); ++i)
     if (!b->h[i]->st.valid)
       return bfail(b, SFW_ERR_STATE, "batch_launch: member " + std::to_string(i) + " has no staged grid (sfw_grid_stage; sfw_score_one consumes it)");
-  const int rc = batch_enqueue(b);
+  const int rc = batch_enqueue(b, reuse_table);
   if (rc != SFW_OK)
     for (sfw_handle h : b->h) drop_launch(h);  // all or none: the members committed before the failure included
   return rc;
@@ -3858,6 +3877,22 @@ int batch_fetch(sfw_batch b, sfw_best *best_out) {
     }
   }
   return SFW_OK;
+}
+
+// The three list forms of sfw_batch_score_grid: every member's arguments are read against the single stage's rules before ANY
+// member is staged (a refused call changes nothing), then stage (the member's own stage function, index_base 0), launch, fetch.
+// `refusal(i)`: null, or why member i's arguments are refused; `stage(i)`: the member's stage call.
+template <typename Refusal, typename Stage>
+int batch_score_lists(sfw_batch b, const char *what, const char *common, Refusal refusal, Stage stage, sfw_best *best_out) {
+  if (common) return bfail(b, SFW_ERR_INVALID_ARG, std::string(what) + ": " + common);
+  for (size_t i = 0; i < b->h.size(); ++i)
+    if (const char *why = refusal(i)) return bfail(b, SFW_ERR_INVALID_ARG, std::string(what) + " (member " + std::to_string(i) + "): " + why);
+  const auto t0 = std::chrono::steady_clock::now();
+  for (size_t i = 0; i < b->h.size(); ++i)
+    if (int e = stage(i)) return bmember_fail(b, static_cast<int32_t>(i), e, (std::string(what) + ": stage").c_str());
+  b->us[0] = us_since(t0);
+  if (int e = sfw_batch_launch(b)) return e;
+  return sfw_batch_fetch(b, best_out);
 }
 }  // namespace
 
@@ -3944,6 +3979,61 @@ int sfw_batch_score_grid(sfw_batch b, const sfw_robot_state *rs, const double *l
   return sfw_batch_fetch(b, best_out);
 }
 
+int sfw_batch_set_list_fusion(sfw_batch b, int32_t enabled) {
+  if (!b) return SFW_ERR_INVALID_ARG;
+  b->list_fusion = enabled != 0;
+  return SFW_OK;
+}
+
+int sfw_batch_get_list_fusion(sfw_batch b, int32_t *enabled_out) {
+  if (!b || !enabled_out) return SFW_ERR_INVALID_ARG;
+  *enabled_out = b->list_fusion ? 1 : 0;
+  return SFW_OK;
+}
+
+int sfw_batch_score_samples(sfw_batch b, const sfw_robot_state *rs, const double *vx, const double *vy, const double *vtheta, int32_t n,
+                            const sfw_goal_args *args, sfw_best *best_out) {
+  if (!b) return SFW_ERR_INVALID_ARG;
+  const char *const common = !rs || !args || !vx || !vtheta ? "null robot states, goal arguments or sample vectors" : n < 1 ? "n < 1" : nullptr;
+  const size_t row = n > 0 ? static_cast<size_t>(n) : 0;
+  const auto vy_of = [&](size_t i) { return vy ? vy + i * row : nullptr; };
+  return batch_score_lists(
+      b, "batch_score_samples", common,
+      [&](size_t i) { return list_stage_refusal(rs + i, args + i, list_request(vx + i * row, vy_of(i), vtheta + i * row, n, 0)); },
+      [&](size_t i) { return sfw_samples_stage(b->h[i], rs + i, vx + i * row, vy_of(i), vtheta + i * row, n, args + i, 0); }, best_out);
+}
+
+int sfw_batch_score_sequences(sfw_batch b, const sfw_robot_state *rs, const double *vx, const double *vy, const double *vtheta, int32_t n,
+                              int32_t K, const int32_t *knot_step, const sfw_goal_args *args, sfw_best *best_out) {
+  if (!b) return SFW_ERR_INVALID_ARG;
+  const char *common = !rs || !args || !vx || !vtheta ? "null robot states, goal arguments or sample vectors" : n < 1 ? "n < 1" : nullptr;
+  if (!common) common = sequences_refusal(K, knot_step);
+  const size_t rows = common ? 0 : static_cast<size_t>(K) * static_cast<size_t>(n);
+  const auto vy_of = [&](size_t i) { return vy ? vy + i * rows : nullptr; };
+  return batch_score_lists(
+      b, "batch_score_sequences", common,
+      [&](size_t i) {
+        return list_stage_refusal(rs + i, args + i, sequences_request(vx + i * rows, vy_of(i), vtheta + i * rows, n, K, knot_step, 0));
+      },
+      [&](size_t i) {
+        return sfw_sequences_stage(b->h[i], rs + i, vx + i * rows, vy_of(i), vtheta + i * rows, n, K, knot_step, args + i, 0);
+      },
+      best_out);
+}
+
+int sfw_batch_score_perturbed(sfw_batch b, const sfw_robot_state *rs, const sfw_perturb *p, int32_t n, int32_t K,
+                              const int32_t *knot_step, const sfw_goal_args *args, sfw_best *best_out) {
+  if (!b) return SFW_ERR_INVALID_ARG;
+  const char *const common = !rs || !args || !p ? "null robot states, goal arguments or perturbations" : nullptr;
+  return batch_score_lists(
+      b, "batch_score_perturbed", common,
+      [&](size_t i) {
+        if (const char *why = perturb_refusal(rs + i, p + i, n, K, knot_step, args + i, 0)) return why;
+        return list_stage_refusal(rs + i, args + i, perturbed_request(nullptr, n, K, knot_step, 0));
+      },
+      [&](size_t i) { return sfw_sequences_perturb_stage(b->h[i], rs + i, p + i, n, K, knot_step, args + i, 0); }, best_out);
+}
+
 int sfw_batch_describe(sfw_batch b, sfw_batch_desc *out) {
   if (!b || !out) return SFW_ERR_INVALID_ARG;
   if (!b->launched) return bfail(b, SFW_ERR_STATE, "batch_describe before batch_launch");
@@ -3994,6 +4084,7 @@ struct sfw_ensemble_s {
   // sfw_ensemble_set_risk: read by every aggregation while risk_on (ensemble_check_mode, ensemble_enqueue)
   sfw_risk risk{1.0, 0.0, 0};
   bool risk_on = false;
+  int64_t chain_uploads = 0;  // member-table uploads of the last sfw_ensemble_mppi_run's batched launches (sfw_ensemble_batch_desc)
 };
 
 namespace {
@@ -4210,8 +4301,10 @@ int ensemble_blend(sfw_ensemble e, const char *what, const double *lambda, int32
 }
 
 // sfw_ensemble_mppi_run behind its stage of iteration 0: everything enqueued on the batch's stream, one wait, the outputs.  A
-// failure is the caller's to clean up.  The members are lists, so batch_launch builds no member table (each takes its own
-// path); the aggregation's table is uploaded by iteration 0 and read again from the device by the others.
+// failure is the caller's to clean up.  The members are lists: without list fusion batch_launch builds no member table (each
+// takes its own path); with it (sfw_ensemble_set_list_fusion) every iteration is one batched launch, whose member table an
+// iteration > 0 reads again from the device when its records are the bytes last uploaded (batch_enqueue reuse_table).  The
+// aggregation's table is uploaded by iteration 0 and read again from the device by the others.
 int ensemble_mppi_chain(sfw_ensemble e, const sfw_perturb *p, int32_t mode, const double *probs, const sfw_mppi *m,
                         sfw_blend_stat *stat_out, double *plans_out, double *costs_out, int32_t *rejected_out, sfw_best *best_out) {
   const char *const what = "ensemble_mppi_run";
@@ -4239,6 +4332,7 @@ int ensemble_mppi_chain(sfw_ensemble e, const sfw_perturb *p, int32_t mode, cons
     return efail(e, SFW_ERR_HIP, std::string(what) + ": plan or member table copy failed");
   double *const plan = e->mppi.mppi_plan.p;
   auto t0 = std::chrono::steady_clock::now();
+  const int64_t uploads0 = e->b->table_uploads;
   for (int i = 0; i < I; ++i) {
     if (i > 0) {  // the stage of iteration i: its seed, and every member's knots drawn once around the plan the last update left
       for (sfw_handle h : e->b->h) perturb_seed(h->st.pert, p->seed + static_cast<uint64_t>(i));
@@ -4246,7 +4340,7 @@ int ensemble_mppi_chain(sfw_ensemble e, const sfw_perturb *p, int32_t mode, cons
           he != hipSuccess)
         return efail(e, SFW_ERR_HIP, std::string(what) + ": sfw_perturb_members_kernel: " + hipGetErrorString(he));
     }
-    if (int rc = batch_launch(e->b)) return efail(e, rc, std::string(what) + ": " + e->b->err);
+    if (int rc = batch_launch(e->b, i > 0)) return efail(e, rc, std::string(what) + ": " + e->b->err);
     for (size_t k = 0; k < M; ++k)
       if (!e->b->h[k]->last.terms) return efail(e, SFW_ERR_STATE, std::string(what) + ": member " + std::to_string(k) + " did not capture terms");
     if (int rc = ensemble_enqueue(e, mode, probs, i > 0)) return rc;
@@ -4259,6 +4353,7 @@ int ensemble_mppi_chain(sfw_ensemble e, const sfw_perturb *p, int32_t mode, cons
       return emember_fail(e, 0, rc, what);
   }
   if (e->mppi.pin_mppi.mark(e->b->stream) != hipSuccess) return efail(e, SFW_ERR_HIP, std::string(what) + ": hipEventRecord failed");
+  e->chain_uploads = e->b->table_uploads - uploads0;
   e->us[1] = us_since(t0);
   t0 = std::chrono::steady_clock::now();
   if (int rc = batch_fetch(e->b, nullptr)) return efail(e, rc, std::string(what) + ": " + e->b->err);  // THE wait, all members
@@ -4454,6 +4549,24 @@ int sfw_ensemble_get_risk(sfw_ensemble e, sfw_risk *out, int32_t *active_out) {
   if (!e || !out) return SFW_ERR_INVALID_ARG;
   *out = e->risk;
   if (active_out) *active_out = e->risk_on ? 1 : 0;
+  return SFW_OK;
+}
+
+int sfw_ensemble_set_list_fusion(sfw_ensemble e, int32_t enabled) {
+  if (!e) return SFW_ERR_INVALID_ARG;
+  return sfw_batch_set_list_fusion(e->b, enabled);
+}
+
+int sfw_ensemble_get_list_fusion(sfw_ensemble e, int32_t *enabled_out) {
+  if (!e) return SFW_ERR_INVALID_ARG;
+  return sfw_batch_get_list_fusion(e->b, enabled_out);
+}
+
+int sfw_ensemble_batch_desc(sfw_ensemble e, sfw_batch_desc *out, int64_t *table_uploads_out) {
+  if (!e || !out) return SFW_ERR_INVALID_ARG;
+  if (!e->b->launched) return efail(e, SFW_ERR_STATE, "ensemble_batch_desc: nothing launched");
+  *out = e->b->desc;
+  if (table_uploads_out) *table_uploads_out = e->chain_uploads;
   return SFW_OK;
 }
 

@@ -285,7 +285,10 @@ hipError_t sfw_launch_cycle(const sfw_launch &L, hipStream_t stream);
 // Many handles' control cycles in ONE launch (sfw_batch_*, sfw_kernels.hip sfw_batch_cycle_kernel).  The device table is
 // first[B + 1] (uint32: member m owns blocks [first[m], first[m + 1]), one per sample) followed, at sfw_batch_recs_offset(B),
 // by B records; the host fills it in pinned memory and copies it in one piece.  Members of one launch share the kernel
-// instantiation: sfw_cycle_batch_variant (precision, groups, laser points) is the grouping key.
+// instantiation: sfw_cycle_batch_variant is the grouping key, 9 * kind + 3 * precision + (groups / laser points / neither), with
+// kind 0 a grid (sfw_batch_cycle_kernel: the values 0..8 grids have always had), 1 a sample list (sfw_batch_cycle_list_kernel),
+// 2 sequences of more than one knot (sfw_batch_cycle_seq_kernel).
+#define SFW_BATCH_VARIANTS 27
 struct sfw_batch_rec {
   sfw_launch L;      // the member's launch as sfw_launch_cycle would launch it (sfw_cycle_batch_record)
   int32_t k2_bytes;  // its block's LDS layout: K2 wave's area | k1s_lds | cycle_result

@@ -3416,7 +3416,12 @@ __device__ __forceinline__ void cycle_block(const sfw_launch &L, const late_laun
       const double base = res->base;
       const bool legal = res->legal != 0;
       const int d = social ? res->dead : 0;
-      if (legal && L.A > 0) {  // (no agent vector at all: scan_finish has written the cost)
+      // (a batched list's block reads the agent count and, below, its block count again from the member's record where they
+      // are used: carried from the block's start in scalar registers, the two values are spilled to VGPR lanes, and that one
+      // VGPR costs the f32 kernel a wave of occupancy against sfw_cycle_list_kernel; the same values, the same statements)
+      int n_agents = L.A;
+      if constexpr (BATCH && LIST) n_agents = late_args_of<true>(Lb)->A;
+      if (legal && n_agents > 0) {  // (no agent vector at all: scan_finish has written the cost)
         if (d == 0) {
           const double sw = social ? res->social_work : 0.0;
           L.costs[t] = sfw_cost_add_social(base, L.p.social_weight, sw);  // finish_wave / sfw_no_social_kernel
@@ -3438,7 +3443,9 @@ __device__ __forceinline__ void cycle_block(const sfw_launch &L, const late_laun
   unsigned prev = 0;
   if (lane == 0) prev = atomicAdd(L.cycle_counter, 1u);
   prev = __shfl(prev, 0, WAVE);
-  if (prev != (BATCH ? nblk : gridDim.x) - 1) return;
+  unsigned n_blocks = BATCH ? nblk : gridDim.x;
+  if constexpr (BATCH && LIST) n_blocks = static_cast<unsigned>(late_args_of<true>(Lb)->chunk_count);  // (= nblk: one block per sample)
+  if (prev != n_blocks - 1) return;
   __threadfence();
   sfw_sel best = sel_empty();
   for (int64_t i = lane; i < L.chunk_count; i += WAVE) {
@@ -3487,6 +3494,45 @@ __global__ void __launch_bounds__(CYCLE_BLOCK) sfw_batch_cycle_kernel(const uint
   const rec_ptr r = (rec_ptr)recs + lo;
   const late_launch Lb = (late_launch)&r->L;
   cycle_block<R, GROUPS, OBS, true, false>(*(const sfw_launch *)Lb, Lb, r->k2_bytes, b - f[lo], f[lo + 1] - f[lo]);
+}
+// ... whose members are sample lists (sfw_samples_stage) or command sequences (sfw_sequences_stage, _perturb_stage): the same
+// search, then the block of sfw_cycle_list_kernel / sfw_cycle_seq_kernel over the member's record.  Everything the list's block
+// reads beyond the grid's — the sample's three values, the knot rows, knot_step[], n_knots, knot_stride — it reads through L,
+// which here is the record: member-local sample `bid`, the member's own counter and selection.  Kernels of their own names,
+// not template parameters of sfw_batch_cycle_kernel: a batch of grids launches the kernel it always has.
+template <typename R, bool GROUPS, bool OBS>
+__global__ void __launch_bounds__(CYCLE_BLOCK) sfw_batch_cycle_list_kernel(const uint32_t *const first, const sfw_batch_rec *const recs,
+                                                                          const int B) {
+  typedef const __attribute__((address_space(4))) uint32_t *first_ptr;
+  typedef const __attribute__((address_space(4))) sfw_batch_rec *rec_ptr;
+  const first_ptr f = (first_ptr)first;
+  const unsigned b = blockIdx.x;
+  int lo = 0, hi = B;  // first[lo] <= b < first[hi]
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (f[mid] <= b) lo = mid;
+    else hi = mid;
+  }
+  const rec_ptr r = (rec_ptr)recs + lo;
+  const late_launch Lb = (late_launch)&r->L;
+  cycle_block<R, GROUPS, OBS, true, true>(*(const sfw_launch *)Lb, Lb, r->k2_bytes, b - f[lo], f[lo + 1] - f[lo]);
+}
+template <typename R, bool GROUPS, bool OBS>
+__global__ void __launch_bounds__(CYCLE_BLOCK) sfw_batch_cycle_seq_kernel(const uint32_t *const first, const sfw_batch_rec *const recs,
+                                                                         const int B) {
+  typedef const __attribute__((address_space(4))) uint32_t *first_ptr;
+  typedef const __attribute__((address_space(4))) sfw_batch_rec *rec_ptr;
+  const first_ptr f = (first_ptr)first;
+  const unsigned b = blockIdx.x;
+  int lo = 0, hi = B;  // first[lo] <= b < first[hi]
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (f[mid] <= b) lo = mid;
+    else hi = mid;
+  }
+  const rec_ptr r = (rec_ptr)recs + lo;
+  const late_launch Lb = (late_launch)&r->L;
+  cycle_block<R, GROUPS, OBS, true, true, true>(*(const sfw_launch *)Lb, Lb, r->k2_bytes, b - f[lo], f[lo + 1] - f[lo]);
 }
 
 }  // namespace
@@ -4129,12 +4175,14 @@ hipError_t sfw_launch_cycle(const sfw_launch &L, hipStream_t stream) {
   return launch_cycle_typed<double>(L, stream);
 }
 // ---- many handles' control cycles in one launch (sfw_batch_*) --------------------------------------------------------
-// The key members of one batched launch share: precision (the build and the force type) x the kernel variant the single
-// launcher picks (groups / laser points / neither)
+// The key members of one batched launch share: the stage kind (grid / list / sequences: the block's sample lookup) x precision
+// (the build and the force type) x the kernel variant the single launcher picks (groups / laser points / neither).  Kind 0 keeps
+// the numbering grids have always had (0..8); a sequence stage of one knot is a list, as in launch_cycle_typed.
 int sfw_cycle_batch_variant(const sfw_launch &L) {
   const int v = L.NG > 0 ? 2 : L.O > 0 ? 1 : 0;
   const int prec = L.p.precision == SFW_PRECISION_F64_STRICT ? 2 : L.p.precision == SFW_PRECISION_F32 ? 1 : 0;
-  return 3 * prec + v;
+  const int kind = L.n_knots > 1 ? 2 : L.list ? 1 : 0;
+  return 9 * kind + 3 * prec + v;
 }
 void sfw_cycle_batch_record(const sfw_launch &L, sfw_batch_rec *rec) {
   // what launch_cycle_typed would launch: the same obs_lds decision, the same layout
@@ -4150,9 +4198,21 @@ void sfw_cycle_batch_record(const sfw_launch &L, sfw_batch_rec *rec) {
   rec->lds_bytes = static_cast<int32_t>(k2 + k1_bytes + ((sizeof(cycle_result) + 15) & ~size_t(15)));
 }
 template <typename R>
-static hipError_t launch_cycle_batch_typed(int v, const uint32_t *d_first, const sfw_batch_rec *d_recs, int B, unsigned blocks,
+static hipError_t launch_cycle_batch_typed(int kind, int v, const uint32_t *d_first, const sfw_batch_rec *d_recs, int B, unsigned blocks,
                                            size_t lds, hipStream_t stream) {
   const dim3 grid(blocks), block(CYCLE_BLOCK);
+  if (kind == 2) {
+    if (v == 2) hipLaunchKernelGGL((sfw_batch_cycle_seq_kernel<R, true, true>), grid, block, lds, stream, d_first, d_recs, B);
+    else if (v == 1) hipLaunchKernelGGL((sfw_batch_cycle_seq_kernel<R, false, true>), grid, block, lds, stream, d_first, d_recs, B);
+    else hipLaunchKernelGGL((sfw_batch_cycle_seq_kernel<R, false, false>), grid, block, lds, stream, d_first, d_recs, B);
+    return hipGetLastError();
+  }
+  if (kind == 1) {
+    if (v == 2) hipLaunchKernelGGL((sfw_batch_cycle_list_kernel<R, true, true>), grid, block, lds, stream, d_first, d_recs, B);
+    else if (v == 1) hipLaunchKernelGGL((sfw_batch_cycle_list_kernel<R, false, true>), grid, block, lds, stream, d_first, d_recs, B);
+    else hipLaunchKernelGGL((sfw_batch_cycle_list_kernel<R, false, false>), grid, block, lds, stream, d_first, d_recs, B);
+    return hipGetLastError();
+  }
   if (v == 2) hipLaunchKernelGGL((sfw_batch_cycle_kernel<R, true, true>), grid, block, lds, stream, d_first, d_recs, B);
   else if (v == 1) hipLaunchKernelGGL((sfw_batch_cycle_kernel<R, false, true>), grid, block, lds, stream, d_first, d_recs, B);
   else hipLaunchKernelGGL((sfw_batch_cycle_kernel<R, false, false>), grid, block, lds, stream, d_first, d_recs, B);
@@ -4160,9 +4220,11 @@ static hipError_t launch_cycle_batch_typed(int v, const uint32_t *d_first, const
 }
 hipError_t sfw_launch_cycle_batch(int variant, const uint32_t *d_first, const sfw_batch_rec *d_recs, int B, unsigned blocks,
                                   size_t lds, hipStream_t stream) {
-  if (B < 1 || blocks < 1 || variant < 0 || variant >= 9) return hipErrorInvalidValue;
+  if (B < 1 || blocks < 1 || variant < 0 || variant >= SFW_BATCH_VARIANTS) return hipErrorInvalidValue;
+  const int kind = variant / 9, prec = variant % 9 / 3, v = variant % 3;
 #ifndef SFW_STRICT_BUILD
-  if (variant / 3 == 1) return launch_cycle_batch_typed<float>(variant % 3, d_first, d_recs, B, blocks, lds, stream);
+  if (prec == 1) return launch_cycle_batch_typed<float>(kind, v, d_first, d_recs, B, blocks, lds, stream);
 #endif
-  return launch_cycle_batch_typed<double>(variant % 3, d_first, d_recs, B, blocks, lds, stream);
+  (void)prec;
+  return launch_cycle_batch_typed<double>(kind, v, d_first, d_recs, B, blocks, lds, stream);
 }

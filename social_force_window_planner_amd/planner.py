@@ -193,6 +193,14 @@ def lib():
                                             vp, vp, C.POINTER(SfwBest)]
         L.sfw_ensemble_set_risk.argtypes = [vp, C.POINTER(SfwRisk)]
         L.sfw_ensemble_get_risk.argtypes = [vp, C.POINTER(SfwRisk), C.POINTER(C.c_int32)]
+        L.sfw_batch_set_list_fusion.argtypes = [vp, C.c_int32]
+        L.sfw_batch_get_list_fusion.argtypes = [vp, C.POINTER(C.c_int32)]
+        L.sfw_batch_score_samples.argtypes = [vp, vp, vp, vp, vp, C.c_int32, vp, vp]
+        L.sfw_batch_score_sequences.argtypes = [vp, vp, vp, vp, vp, C.c_int32, C.c_int32, vp, vp, vp]
+        L.sfw_batch_score_perturbed.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, vp, vp, vp]
+        L.sfw_ensemble_set_list_fusion.argtypes = [vp, C.c_int32]
+        L.sfw_ensemble_get_list_fusion.argtypes = [vp, C.POINTER(C.c_int32)]
+        L.sfw_ensemble_batch_desc.argtypes = [vp, C.POINTER(SfwBatchDesc), C.POINTER(C.c_int64)]
         _lib = L
     return _lib
 
@@ -907,6 +915,81 @@ class BatchScorer(_Owner):
             m._mark_staged((len(lin), len(ang)))
         return [(self._costs(i), best[i].as_dict()) for i in range(self.B)]
 
+    # -- lists, sequences and perturbed rollouts (sfw_batch_set_list_fusion, sfw_batch_score_samples / _sequences / _perturbed)
+    def set_list_fusion(self, enabled=True):
+        """The sticky switch (off at creation): members staged with a list, sequences or perturbed rollouts whose own launch
+        would be the one-kernel cycle join the batched launch instead of taking their own path.  Same bits either way."""
+        self._check(lib().sfw_batch_set_list_fusion(self._b, 1 if enabled else 0), "sfw_batch_set_list_fusion")
+
+    def list_fusion(self):
+        v = C.c_int32()
+        self._check(lib().sfw_batch_get_list_fusion(self._b, C.byref(v)), "sfw_batch_get_list_fusion")
+        return v.value
+
+    def stage_samples(self, i, robot_state, vx, vtheta, goal_args, vy=None):
+        self._members[i].stage_samples(robot_state, vx, vtheta, goal_args, vy=vy)
+
+    def stage_sequences(self, i, robot_state, vx, vtheta, knot_steps, goal_args, vy=None):
+        self._members[i].stage_sequences(robot_state, vx, vtheta, knot_steps, goal_args, vy=vy)
+
+    def stage_perturbed(self, i, robot_state, n, seed, nominal, sigma, lo, hi, knot_steps, goal_args, flags=0):
+        self._members[i].stage_perturbed(robot_state, n, seed, nominal, sigma, lo, hi, knot_steps, goal_args, flags=flags)
+
+    def _fleet(self, robot_states, goal_args_list):
+        if len(robot_states) != self.B or len(goal_args_list) != self.B:
+            raise ValueError(f"batch score: {len(robot_states)} robot states and {len(goal_args_list)} goal arguments for {self.B} members")
+        return ((SfwRobotState * self.B)(*[SfwRobotState(*r) for r in robot_states]),
+                (SfwGoalArgs * self.B)(*[SfwGoalArgs(*g) for g in goal_args_list]), (SfwBest * self.B)())
+
+    def _scored_lists(self, best, n, knots):
+        for m in self._members:
+            m._mark_staged((n, 1), knots=knots)
+        return [(self._costs(i), best[i].as_dict()) for i in range(self.B)]
+
+    def score_samples(self, robot_states, vx, vtheta, goal_args_list, vy=None):
+        """sfw_batch_score_samples: member i scores its own list vx[i], vy[i], vtheta[i] ((B, n) arrays; vy=None: all 0) from
+        robot_states[i] with goal_args_list[i].  A list of (costs, best), member order."""
+        vx, vth = np.ascontiguousarray(_f64(vx)), np.ascontiguousarray(_f64(vtheta))
+        vyv = None if vy is None else np.ascontiguousarray(_f64(vy))
+        if vx.ndim != 2 or vx.shape[0] != self.B or vth.shape != vx.shape or (vyv is not None and vyv.shape != vx.shape):
+            raise ValueError("batch score_samples: vx, vy and vtheta must be (B, n) arrays")
+        rs, ga, best = self._fleet(robot_states, goal_args_list)
+        n = vx.shape[1]
+        self._check(lib().sfw_batch_score_samples(self._b, rs, vx.ctypes.data if vx.size else None,
+                                                  vyv.ctypes.data if vyv is not None and vyv.size else None,
+                                                  vth.ctypes.data if vth.size else None, n, ga, best), "sfw_batch_score_samples")
+        return self._scored_lists(best, n, 1)
+
+    def score_sequences(self, robot_states, vx, vtheta, knot_steps, goal_args_list, vy=None):
+        """sfw_batch_score_sequences: member i scores its own sequences vx[i] ... ((B, K, n) arrays) under the common
+        knot_steps.  A list of (costs, best), member order."""
+        vx, vth = np.ascontiguousarray(_f64(vx)), np.ascontiguousarray(_f64(vtheta))
+        vyv = None if vy is None else np.ascontiguousarray(_f64(vy))
+        ks = np.ascontiguousarray(np.asarray(knot_steps, dtype=np.int32).reshape(-1))
+        if vx.ndim != 3 or vx.shape[0] != self.B or vth.shape != vx.shape or (vyv is not None and vyv.shape != vx.shape):
+            raise ValueError("batch score_sequences: vx, vy and vtheta must be (B, K, n) arrays")
+        rs, ga, best = self._fleet(robot_states, goal_args_list)
+        K, n = vx.shape[1], vx.shape[2]
+        self._check(lib().sfw_batch_score_sequences(self._b, rs, vx.ctypes.data if vx.size else None,
+                                                    vyv.ctypes.data if vyv is not None and vyv.size else None,
+                                                    vth.ctypes.data if vth.size else None, n, K,
+                                                    ks.ctypes.data if len(ks) else None, ga, best), "sfw_batch_score_sequences")
+        return self._scored_lists(best, n, K)
+
+    def score_perturbed(self, robot_states, n, perturbs, knot_steps, goal_args_list):
+        """sfw_batch_score_perturbed: member i scores n rollouts the device draws from perturbs[i], a dict of
+        HipScorer.stage_perturbed's arguments (seed, nominal, sigma, lo, hi and optionally flags).  A list of (costs, best)."""
+        if len(perturbs) != self.B:
+            raise ValueError(f"batch score_perturbed: {len(perturbs)} perturbations for {self.B} members")
+        made = [HipScorer._perturb(q["seed"], q["nominal"], q["sigma"], q["lo"], q["hi"], knot_steps, q.get("flags", 0)) for q in perturbs]
+        pt = (SfwPerturb * self.B)(*[m[0] for m in made])
+        ks = made[0][2]
+        K = made[0][1].shape[0]
+        rs, ga, best = self._fleet(robot_states, goal_args_list)
+        self._check(lib().sfw_batch_score_perturbed(self._b, rs, pt, n, K, ks.ctypes.data if len(ks) else None, ga, best),
+                    "sfw_batch_score_perturbed")
+        return self._scored_lists(best, n, K)
+
     def describe(self):
         d = SfwBatchDesc()
         self._check(lib().sfw_batch_describe(self._b, C.byref(d)), "sfw_batch_describe")
@@ -1122,6 +1205,26 @@ class EnsembleScorer(_Owner):
         """The knots of samples [first, first + count) of the last sequence score as (K, 3, count): member 0's (every member
         holds the same)."""
         return self._members[0].knots(first, count)
+
+    # -- list fusion ----------------------------------------------------------
+    def set_list_fusion(self, enabled=True):
+        """sfw_ensemble_set_list_fusion (off at creation): score_sequences, score_perturbed and every iteration of mppi_run
+        score the M members in one batched launch instead of M.  Same bits either way."""
+        self._check(lib().sfw_ensemble_set_list_fusion(self._e, 1 if enabled else 0), "sfw_ensemble_set_list_fusion")
+
+    def list_fusion(self):
+        v = C.c_int32()
+        self._check(lib().sfw_ensemble_get_list_fusion(self._e, C.byref(v)), "sfw_ensemble_get_list_fusion")
+        return v.value
+
+    def batch_desc(self):
+        """What the private batch's last launch did (BatchScorer.describe's dict) plus "table_uploads": the member-table
+        uploads of the last mppi_run's launches."""
+        d, up = SfwBatchDesc(), C.c_int64()
+        self._check(lib().sfw_ensemble_batch_desc(self._e, C.byref(d), C.byref(up)), "sfw_ensemble_batch_desc")
+        out = {n: getattr(d, n) for n, _ in SfwBatchDesc._fields_}
+        out["table_uploads"] = up.value
+        return out
 
     def last_us(self):
         """Host wall-clock of the last calls: stage (the score calls only), enqueue, wait + copies out (microseconds)."""
