@@ -631,6 +631,24 @@ int sfw_grid_points_batch(sfw_handle h, int64_t first, int64_t count, double *po
  * costmap, the pedestrian integration).  Costs and selection are unaffected.  Larger grids ignore it.  Off by
  * default; takes effect at the next sfw_grid_launch / sfw_score_grid. */
 int sfw_set_points_capture(sfw_handle h, int32_t enabled);
+/* The footprint check's clearance map, on by default.  One byte per costmap cell on the device: 1 where every cell of
+ * the square window of half-width r_c = ceil(R / resolution) + 1 cells (R: the largest vertex distance of the
+ * footprint) around the cell is on the map and has cost 0.  A pose whose centre cell is clear has footprint cost 0
+ * whatever its heading, and the check returns it without converting a vertex or walking an edge; every other pose is
+ * checked as before.  Costs, sentinels, selection, captured terms and points are bit-identical on and off.
+ * The map is built by the first stage (sfw_grid_stage, sfw_samples_stage, sfw_sequences_*_stage and the blocking calls
+ * over them) of at least 368 640 poses (samples x steps: 96 x 96 samples at 40 steps) after the costmap's contents or size, or the window's
+ * half-width (footprint, resolution), have changed — two small kernels on the handle's stream behind the upload of the
+ * cells, about as long as the upload itself — and kept until they change again; smaller grids (a control cycle) never
+ * pay for it and walk every pose.  No map either when the window would be wider than 129 cells.  Off: no stage builds or
+ * reads a map; takes effect at the next launch (turned on again, at the next stage). */
+int sfw_set_footprint_clearance(sfw_handle h, int32_t on);
+/* Of the staged grid: *built = 1 when its footprint checks read a clearance map, *half_width = r_c in cells (-1: the
+ * footprint is too large for a map).  SFW_ERR_STATE when nothing is staged. */
+int sfw_footprint_clearance_info(sfw_handle h, int32_t *built, int32_t *half_width);
+/* The staged grid's clearance map, size_x * size_y bytes, row-major like the costmap (tests and inspection; blocking).
+ * SFW_ERR_STATE when the staged grid has none, SFW_ERR_INVALID_ARG when cells is not size_x * size_y. */
+int sfw_footprint_clearance_map(sfw_handle h, uint8_t *out, uint64_t cells);
 /* Raw HIP stream (hipStream_t) the handle launches on, for callers that want
  * to record their own events. */
 void *sfw_stream(sfw_handle h);

@@ -244,6 +244,9 @@ EXPORTED_SYMBOLS = (
     "sfw_ensemble_mppi_run",
     "sfw_ensemble_set_risk",
     "sfw_ensemble_get_risk",
+    "sfw_set_footprint_clearance",
+    "sfw_footprint_clearance_info",
+    "sfw_footprint_clearance_map",
 )
 # per-term costs (sfw_set_terms_capture / sfw_grid_rescore / sfw_grid_terms)
 SFW_TERM_VEL, SFW_TERM_DISTANCE, SFW_TERM_ANGLE, SFW_TERM_COSTMAP, SFW_TERM_SOCIAL = 0, 1, 2, 3, 4

@@ -49,6 +49,16 @@ template <typename T> struct dev_buf {
   }
 };
 
+// ---- the footprint clearance map (sfw_launch.clear, sfw_set_footprint_clearance) ----
+// A window of more than 2 * kClearMaxHalfWidth + 1 = 129 cells: no map, every pose walks (a footprint of 3 m at 0.05 m per
+// cell; the build's cost grows with the window and a window that wide is clear almost nowhere)
+constexpr int kClearMaxHalfWidth = 64;
+// Poses (samples x steps) of a stage from which it builds the map: 96 x 96 samples at 40 steps, the smallest grid measured at
+// which a build before EVERY step (a costmap that changes every cycle) still left the step shorter than walking every pose
+// (+5..+7 us at 9 216 samples; -6..-12 us at 4 096, where an unchanged map gained 1..4 us; control cycles never get here).
+// profiles/r23_footprint_clearance.txt has the sweep.
+constexpr int64_t kClearMinPoses = 368640;
+
 // Pinned host staging area for one logical upload.  The caller's buffer is copied
 // here synchronously (so it may be freed or reused on return) and the H2D copy is
 // enqueued on the handle's stream; `done` guards the area against being rewritten
@@ -176,6 +186,9 @@ struct sfw_planner_s {
     // a member of a sfw_batch: the batch's streams are borrowed (sfw_destroy refuses the handle; the batch destroys it)
     bool owns_streams = true;
     bool batch_member = false;
+    // poses (samples x steps) of a stage from which it builds the footprint clearance map when there is none for its costmap
+    // and footprint (kClearMinPoses has the measurement); SFW_CLEAR_MIN_POSES overrides it (0: every stage builds — tests)
+    int64_t clear_min_poses = kClearMinPoses;
   } cfg;
 
   struct switches {
@@ -188,6 +201,8 @@ struct sfw_planner_s {
     bool capture_points = false;
     // sfw_set_terms_capture: every grid launch also leaves the five cost terms of every sample in `terms` (SoA [5][T])
     bool capture_terms = false;
+    // sfw_set_footprint_clearance: K1b reads the clearance map of a stage that has one (off: every pose walks its edges)
+    bool fp_clear = true;
   } live;
 
   // Footprint, agents and laser points are small: sfw_set_* keep them on the host and every stage packs them into ONE
@@ -197,6 +212,7 @@ struct sfw_planner_s {
     map_geometry map_new{0, 0, 0, 0, 0};  // what sfw_set_costmap handed over last (pin_map holds its cells)
     bool have_costmap = false;
     bool cells_dirty = false;             // ... and the device has not seen yet
+    uint64_t cells_gen = 0;               // bumped whenever sfw_set_costmap takes a snapshot that differs from the last
     std::vector<double> footprint;        // 2K
     int K = 0;
     agent_set agents;
@@ -275,7 +291,20 @@ struct sfw_planner_s {
     bool early_poses_timed = false;  // ... and the stage recorded ev[0] in front of it (timing was on at stage time)
     bool early_poses_terms = false;  // ... and it wrote the pedestrian-free terms too
     bool clock_cleared = false;      // the stage cleared the clock probe in front of the pose rollout it started
+    // the footprint clearance map (stage_clearance): clear_map describes the staged costmap and footprint, for windows of
+    // half-width clear_r cells (-1: the footprint is too large for a map)
+    bool clear_on = false;
+    int clear_r = -1;
   } st;
+
+  // What `clear_map` on the device was built from (valid: it is enqueued or done): the snapshot's generation, the map's
+  // size and the window's half-width.  A stage builds again when any of them differs from its own.
+  struct clearance_record {
+    bool valid = false;
+    uint64_t cells_gen = 0;
+    uint32_t size_x = 0, size_y = 0;
+    int r = 0;
+  } clr;
 
   struct launch_record {
     bool launched = false;  // every kernel of the launch is enqueued; false: nothing to fetch
@@ -316,6 +345,7 @@ struct sfw_planner_s {
   dev_buf<double> base_cost, costs;  // costs: T doubles followed by the sfw_sel record (one D2H fetches both)
   dev_buf<sfw_unit> ptab, cs_tab;   // the K1 tables (sfw_device.h sfw_unit), sized for st.table_chunk samples per step row
   dev_buf<int16_t> fcode;
+  dev_buf<uint8_t> clear_map, clear_tmp;  // the footprint clearance map and the row pass's intermediate (one byte per cell each)
   dev_buf<sfw_sel> partials;
   dev_buf<double> points;
   dev_buf<int32_t> n_points;
@@ -494,6 +524,7 @@ void fill_launch(sfw_handle h, sfw_launch &L, int64_t begin, int64_t count, int6
   L.resolution = h->st.map.resolution;
   L.footprint = h->st.d_footprint;
   L.K = h->st.K;
+  L.clear = (h->live.fp_clear && h->st.clear_on) ? h->clear_map.p : nullptr;
   L.agent_pos = h->st.d_agent_pos;
   L.agent_vel = h->st.d_agent_vel;
   L.agent_c = h->st.d_agent_c;
@@ -1335,6 +1366,64 @@ const char *stage_finite_refusal(const sfw_robot_state *rs, const sfw_goal_args 
   return nullptr;
 }
 
+// The half-width r_c (cells) of the clearance window for a footprint at a resolution, or -1 when it exceeds
+// kClearMaxHalfWidth: r_c = ceil(R / res) + 1 with R the largest vertex distance.  Claim: for a pose whose centre is on the
+// map in cell (cx, cy), every vertex that sfw_kernels.hip footprint_cost_at converts lands in a cell within r_c of (cx, cy)
+// on each axis — and, when the window [cx - r_c, cx + r_c] x [cy - r_c, cy + r_c] is on the map, on the map.
+//   * A vertex's world x is x + d with d = fl(fl(qx c) - fl(qy s)), |d| <= hypot(qx, qy) hypot(c, s) (1 + 2^-51) by Cauchy-
+//     Schwarz and two roundings, and hypot(c, s) <= 1 + 2^-50 for a sincos good to a few ulp: |d| <= R (1 + 2^-49).
+//   * In real numbers the vertex's quotient differs from the centre's a = (x - origin) / res by d / res, and
+//     floor(a + t) - floor(a) lies in [-ceil(|t|), ceil(|t|)]: at most ceil(R / res) cells.
+//   * The roundings on the way (x + d, the subtraction of the origin, the division — or cell_index's product, which its 1e-9
+//     guard replaces by the division whenever the two could truncate differently — and the factor above) move a quotient by
+//     a few 2^-52 of its size, under 1e-8 cells for the 2^21 cells an axis may have (SFW_MAX_MAP_AXIS_CELLS): they can carry
+//     a quotient across ONE more cell edge, never two.  The host's own fl(R / res) may round down onto an integer that the
+//     exact quotient exceeds by the like amount.  The "+ 1" pays for all of these together (their sum is far below one cell).
+//   * With the window on the map, cx - r_c >= 0, so the vertex's exact quotient is at least cx - ceil(R / res) - 1e-8 > 0: it
+//     is not below the origin, and its cell is at most cx + r_c < size.  The same on y.
+// A walk between two vertex cells stays inside their bounding box (line_max: the minor axis advances `add` times over `den`
+// major steps), hence inside the window.  tests/test_footprint_clearance.py measures the largest offset the reference produces
+// against this bound, with centres on cell edges and the farthest vertex pointing along an axis.
+int clearance_half_width(const std::vector<double> &footprint, double resolution) {
+  double R = 0.0;
+  for (size_t i = 0; i + 1 < footprint.size(); i += 2) R = std::fmax(R, std::hypot(footprint[i], footprint[i + 1]));
+  const double q = std::ceil(R / resolution) + 1.0;
+  return q <= kClearMaxHalfWidth ? static_cast<int>(q) : -1;  // (written so that a NaN or an infinite quotient gives -1)
+}
+
+// The stage's last step before it commits: does K1b of this grid read a clearance map?  Yes when `clear_map` already describes
+// the staged costmap and window, or when the grid has enough poses to pay for building it — then the two passes are enqueued
+// on the handle's stream, behind the stage's copy of the cells (or the pose rollout that fetches them) and in front of every
+// launch.  A build that cannot be enqueued leaves the stage without a map (every pose walks), never with a stale one.
+void stage_clearance(sfw_handle h, int64_t T) {
+  h->st.clear_on = false;
+  h->st.clear_r = -1;
+  if (!h->live.fp_clear) return;
+  const map_geometry &m = h->st.map;
+  const int r = clearance_half_width(h->world.footprint, m.resolution);
+  h->st.clear_r = r;
+  if (r < 0) return;
+  auto &c = h->clr;
+  if (c.valid && c.cells_gen == h->world.cells_gen && c.size_x == m.size_x && c.size_y == m.size_y && c.r == r) {
+    h->st.clear_on = true;
+    return;
+  }
+  // (an arena still pending here — a small grid's, fetched by its launch — never carries cells: the device's copy of them is an
+  // earlier stage's, or the large map's own copy enqueued above)
+  if (T * num_steps_of(h->live.params) < h->cfg.clear_min_poses) return;
+  c.valid = false;
+  const size_t n = static_cast<size_t>(m.size_x) * m.size_y;
+  hipError_t e = h->clear_map.reserve(n);
+  if (e == hipSuccess) e = h->clear_tmp.reserve(n);
+  if (e == hipSuccess) e = sfw_launch_clearance(h->st.d_cells, m.size_x, m.size_y, r, h->clear_tmp.p, h->clear_map.p, h->stream);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    return;
+  }
+  c = {true, h->world.cells_gen, m.size_x, m.size_y, r};
+  h->st.clear_on = true;
+}
+
 int stage_common(sfw_handle h, const sfw_robot_state *rs, const sfw_goal_args *args, const stage_request &q) {
   if (!h) return SFW_ERR_INVALID_ARG;
   const std::string what = q.name();
@@ -1377,6 +1466,7 @@ int stage_common(sfw_handle h, const sfw_robot_state *rs, const sfw_goal_args *a
   if (knot_step) h->st.knot_step.assign(knot_step, knot_step + kn);
   else h->st.knot_step.clear();
   h->st.K = h->world.K;
+  h->st.clear_on = false;  // (until stage_clearance, at the end, says otherwise)
   h->st.A = ag.A;
   h->st.O = ag.O;
   h->st.NG = ag.NG;
@@ -1520,6 +1610,8 @@ int stage_common(sfw_handle h, const sfw_robot_state *rs, const sfw_goal_args *a
   if (T > 1024)
     if (int e = flush_arena(h)) return e;  // (no pose rollout was enqueued after all: the copy it would have stood in for)
   ph.mark("tables+K1a");
+  stage_clearance(h, T);
+  ph.mark("clearance");
   // commit: everything the arena carries is enqueued (a pending arena never carries cells: `small` keeps the head)
   if (merge) {
     h->world.cells_dirty = false;
@@ -2234,6 +2326,7 @@ int create_handle(const sfw_params *params, int device, hipStream_t stream, hipS
   if (const char *b = std::getenv("SFW_ARENA_DIRECT")) h->cfg.arena_direct_on = std::atoi(b) != 0;
   if (const char *b = std::getenv("SFW_MIRROR_MAX_MB")) h->cfg.mirror_max_bytes = static_cast<size_t>(std::max(0L, std::atol(b))) << 20;
   if (const char *b = std::getenv("SFW_OBS_TASKS")) h->cfg.obs_tasks_force = std::atoi(b) != 0 ? 1 : 0;
+  if (const char *b = std::getenv("SFW_CLEAR_MIN_POSES")) h->cfg.clear_min_poses = std::max(0LL, std::atoll(b));
   if (const char *b = std::getenv("SFW_TABLE_BUDGET_MB")) {
     long mb = std::atol(b);
     if (mb > 0) h->cfg.table_budget_bytes = static_cast<size_t>(mb) << 20;
@@ -2299,6 +2392,8 @@ int destroy_handle(sfw_handle h) {
   h->ptab.release();
   h->cs_tab.release();
   h->fcode.release();
+  h->clear_map.release();
+  h->clear_tmp.release();
   h->partials.release();
   h->clock.release();
   h->cycle_counter.release();
@@ -2396,6 +2491,7 @@ int sfw_set_costmap(sfw_handle h, const uint8_t *cells, uint32_t size_x, uint32_
   std::memcpy(h->pin_map.p, cells, n);
   h->world.map_new = {size_x, size_y, origin_x, origin_y, resolution};
   h->world.cells_dirty = true;
+  ++h->world.cells_gen;
   h->world.have_costmap = true;
   return SFW_OK;
 }
@@ -2830,6 +2926,32 @@ int sfw_last_launch_ms(sfw_handle h, int32_t which, float *ms_out) {
 int sfw_set_points_capture(sfw_handle h, int32_t enabled) {
   if (!h) return SFW_ERR_INVALID_ARG;
   h->live.capture_points = enabled != 0;
+  return SFW_OK;
+}
+
+int sfw_set_footprint_clearance(sfw_handle h, int32_t on) {
+  if (!h) return SFW_ERR_INVALID_ARG;
+  h->live.fp_clear = on != 0;
+  return SFW_OK;
+}
+
+int sfw_footprint_clearance_info(sfw_handle h, int32_t *built, int32_t *half_width) {
+  if (!h) return SFW_ERR_INVALID_ARG;
+  if (!built || !half_width) return fail(h, SFW_ERR_INVALID_ARG, "footprint_clearance_info: null pointer");
+  if (!h->st.valid) return fail(h, SFW_ERR_STATE, "footprint_clearance_info: nothing is staged");
+  *built = (h->live.fp_clear && h->st.clear_on) ? 1 : 0;
+  *half_width = h->st.clear_r;
+  return SFW_OK;
+}
+
+int sfw_footprint_clearance_map(sfw_handle h, uint8_t *out, uint64_t cells) {
+  if (!h) return SFW_ERR_INVALID_ARG;
+  if (!h->st.valid || !h->st.clear_on) return fail(h, SFW_ERR_STATE, "footprint_clearance_map: the staged grid has no clearance map");
+  if (!out || cells != static_cast<uint64_t>(h->st.map.size_x) * h->st.map.size_y)
+    return fail(h, SFW_ERR_INVALID_ARG, "footprint_clearance_map: null buffer, or not size_x * size_y cells");
+  SFW_HIP(h, hipSetDevice(h->device));
+  SFW_HIP(h, hipMemcpyAsync(out, h->clear_map.p, cells, hipMemcpyDeviceToHost, h->stream));
+  SFW_HIP(h, hipStreamSynchronize(h->stream));
   return SFW_OK;
 }
 

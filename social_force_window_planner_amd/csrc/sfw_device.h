@@ -233,6 +233,11 @@ struct sfw_launch {
   int32_t n_knots;
   const int32_t *knot_step;
   int64_t knot_stride;
+  // sfw_set_footprint_clearance, nullable: one byte per costmap cell, 1 where every cell of the square window of half-width
+  // r_c around the cell is on the map and has cost 0 — r_c so large that the window holds every cell a footprint check of a
+  // pose in that cell can read (sfw_capi.hip clearance_half_width).  Such a pose's footprint cost is 0 without walking an edge
+  // (sfw_kernels.hip footprint_cost_clear).  Null: every pose walks.  (Appended: no other field's offset moves.)
+  const uint8_t *clear;
 };
 
 // Writers of the captured cost terms (no-ops when terms is null): term k of sample t, the three pedestrian-free terms, or one
@@ -271,6 +276,10 @@ hipError_t sfw_launch_rollout(const sfw_launch &L, hipStream_t stream);  // = po
 // table), so the second can run beside it on another stream.
 hipError_t sfw_launch_rollout_poses(const sfw_launch &L, hipStream_t stream);
 hipError_t sfw_launch_rollout_costmap(const sfw_launch &L, hipStream_t stream);
+// The clearance map of a costmap (sfw_launch.clear): clear[c] = 1 iff the (2 r + 1)^2 window around cell c is on the map and
+// all 0.  Two separable passes, rows into tmp (size_x * size_y bytes), then columns into clear.
+hipError_t sfw_launch_clearance(const uint8_t *cells, uint32_t size_x, uint32_t size_y, int r, uint8_t *tmp, uint8_t *clear,
+                                hipStream_t stream);
 // sp (optional): a second stream and two events, with which a register-form launch whose waves do not divide evenly over
 // the SIMDs hands its last items to concurrent flat-form waves (bit-identical organisations; sfw_kernels.hip split_point)
 struct sfw_split_streams {

@@ -113,10 +113,9 @@ __device__ __forceinline__ int line_max(const sfw_launch &L, int x0, int y0, int
 }
 
 // reference world_model.hpp:45-75 + src/costmap_model.cpp:21-92; c,s = cos/sin(theta)
-__device__ double footprint_cost(const sfw_launch &L, double x, double y, double c, double s) {
-  const double inv_res = 1.0 / L.resolution;
-  unsigned cx, cy;
-  if (!world_to_map(L, inv_res, x, y, cx, cy)) return -3.0;
+// (the part behind the ref :545 check of the pose itself: (cx, cy) is the pose's cell)
+__device__ double footprint_cost_at(const sfw_launch &L, double inv_res, unsigned cx, unsigned cy, double x, double y, double c,
+                                    double s) {
   const int K = L.K;
   if (K < 3) {
     const int code = point_code(L, (int)cx, (int)cy);
@@ -148,6 +147,24 @@ __device__ double footprint_cost(const sfw_launch &L, double x, double y, double
     y0 = y1;
   }
   return static_cast<double>(fc);  // >= 254 (lethal / unknown on an edge): illegal, like the reference's -1 / -2
+}
+__device__ double footprint_cost(const sfw_launch &L, double x, double y, double c, double s) {
+  const double inv_res = 1.0 / L.resolution;
+  unsigned cx, cy;
+  if (!world_to_map(L, inv_res, x, y, cx, cy)) return -3.0;
+  return footprint_cost_at(L, inv_res, cx, cy, x, y, c, s);
+}
+// footprint_cost with the clearance map (L.clear, nullable): a pose whose cell is clear reads cells of cost 0 only, whatever
+// its heading and whatever K — every vertex's cell and every cell of a walk between two of them lie in the window the map
+// vouches for (sfw_capi.hip clearance_half_width has the bound; line_max stays inside the bounding box of its two ends, both
+// in the window) — so no vertex is off the map, no edge sees a cost, a K < 3 footprint reads 0 in the centre cell: 0.0, the
+// value the walk would return.  Any other pose runs footprint_cost_at as before.
+__device__ double footprint_cost_clear(const sfw_launch &L, double x, double y, double c, double s) {
+  const double inv_res = 1.0 / L.resolution;
+  unsigned cx, cy;
+  if (!world_to_map(L, inv_res, x, y, cx, cy)) return -3.0;
+  if (L.clear && L.clear[static_cast<size_t>(cy) * L.size_x + cx]) return 0.0;
+  return footprint_cost_at(L, inv_res, cx, cy, x, y, c, s);
 }
 
 // reference sfw_planner.hpp:457-463: if ((vg - vi) >= 0) return min(vg, vi + a_max dt); return max(vg, vi - a_max dt);
@@ -483,19 +500,43 @@ template <bool LIST, bool SEQ = false> __global__ void __launch_bounds__(64) sfw
 // K1b: footprint legality/cost of one pose, one thread per (step, sample).
 // Independent across steps once the poses are known, so the S*T checks run in
 // parallel instead of serially inside the rollout.
-template <bool LIST> __global__ void __launch_bounds__(256) sfw_footprint_kernel(const sfw_launch L) {
-  const int64_t idx = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-  const int64_t n = L.chunk_count;
-  if (idx >= n * L.S) return;
-  const int64_t step = idx / n, local = idx - step * n;
+// The grid's x dimension covers the chunk's samples, its y dimension the steps from step0 on (no per-thread 64-bit division).
+template <bool LIST> __global__ void __launch_bounds__(256) sfw_footprint_kernel(const sfw_launch L, const int step0) {
+  const int64_t local = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (local >= L.chunk_count) return;
+  const int64_t step = static_cast<int64_t>(step0) + blockIdx.y;
   if (L.status[L.chunk_begin + local] == SFW_ST_SKIPPED) return;
   // the pose before the step: where the step before it ended (the handed-over pose for step 0), heading by column
   const sfw_unit pos = step == 0 ? sfw_unit{L.rs.x, L.rs.y} : L.ptab[(step - 1) * L.row_units + local];
   // (a list: the sample's own unit, next to its neighbour lane's — one coalesced 16-byte load per lane, like `pos`)
   const sfw_unit cs = LIST ? L.cs_tab[step * L.rstep_stride + local] : L.cs_tab[step * L.nw + (L.chunk_begin + local) % L.nw];
-  const double fc = footprint_cost(L, pos.a, pos.b, cs.a, cs.b);  // includes the ref :545 map check
+  const double fc = footprint_cost_clear(L, pos.a, pos.b, cs.a, cs.b);  // includes the ref :545 map check
   L.fcode[step * L.rstep_stride + local] = static_cast<int16_t>(fc);
 }
+
+#ifndef SFW_STRICT_BUILD
+// The clearance map (sfw_launch.clear) as two separable passes of a (2 r + 1)-cell maximum, one thread per cell; a cell off
+// the map counts as 255.  Rows: tmp[y][x] = max cells[y][x - r .. x + r].  Columns: clear[y][x] = (max tmp[y - r .. y + r][x]
+// == 0).  2 r + 1 byte loads per cell and pass, neighbours in a wave reading neighbouring bytes: at a 500 x 500 map and a
+// window of 19 cells both passes together read under 10 MB through the cache — microseconds, paid when the map changes.
+__global__ void __launch_bounds__(256) sfw_clearance_rows_kernel(const uint8_t *cells, int size_x, int size_y, int y0, int r, uint8_t *tmp) {
+  const int x = blockIdx.x * blockDim.x + threadIdx.x, y = y0 + blockIdx.y;
+  if (x >= size_x || y >= size_y) return;
+  const uint8_t *row = cells + static_cast<size_t>(y) * size_x;
+  int m = (x - r < 0 || x + r >= size_x) ? 255 : 0;
+  const int lo = max(x - r, 0), hi = min(x + r, size_x - 1);
+  for (int i = lo; i <= hi; ++i) m = max(m, static_cast<int>(row[i]));
+  tmp[static_cast<size_t>(y) * size_x + x] = static_cast<uint8_t>(m);
+}
+__global__ void __launch_bounds__(256) sfw_clearance_cols_kernel(const uint8_t *tmp, int size_x, int size_y, int y0, int r, uint8_t *clear) {
+  const int x = blockIdx.x * blockDim.x + threadIdx.x, y = y0 + blockIdx.y;
+  if (x >= size_x || y >= size_y) return;
+  int m = (y - r < 0 || y + r >= size_y) ? 255 : 0;
+  const int lo = max(y - r, 0), hi = min(y + r, size_y - 1);
+  for (int j = lo; j <= hi; ++j) m = max(m, static_cast<int>(tmp[static_cast<size_t>(j) * size_x + x]));
+  clear[static_cast<size_t>(y) * size_x + x] = m == 0 ? 1 : 0;
+}
+#endif
 
 // K1c: in-order scan of the per-step footprint costs, one thread per sample.
 __global__ void __launch_bounds__(256) sfw_costmap_scan_kernel(const sfw_launch L) {
@@ -3720,9 +3761,11 @@ hipError_t sfw_launch_rollout_costmap(const sfw_launch &L, hipStream_t stream) {
   if (L.chunk_count <= 0 || sfw_rollout_is_fused(L)) return hipSuccess;
   {
     const int block = 256;
-    const int64_t n = L.chunk_count * L.S;
-    const unsigned grid = static_cast<unsigned>((n + block - 1) / block);
-    hipLaunchKernelGGL((L.list ? sfw_footprint_kernel<true> : sfw_footprint_kernel<false>), dim3(grid), dim3(block), 0, stream, L);
+    const unsigned grid = static_cast<unsigned>((L.chunk_count + block - 1) / block);
+    for (int step0 = 0; step0 < L.S; step0 += 65535) {  // (65 535: the limit of a grid's y dimension; one launch up to there)
+      const unsigned steps = static_cast<unsigned>(L.S - step0 < 65535 ? L.S - step0 : 65535);
+      hipLaunchKernelGGL((L.list ? sfw_footprint_kernel<true> : sfw_footprint_kernel<false>), dim3(grid, steps), dim3(block), 0, stream, L, step0);
+    }
   }
   {
     const int block = 256;
@@ -3731,6 +3774,26 @@ hipError_t sfw_launch_rollout_costmap(const sfw_launch &L, hipStream_t stream) {
   }
   return hipGetLastError();
 }
+
+#ifndef SFW_STRICT_BUILD
+hipError_t sfw_launch_clearance(const uint8_t *cells, uint32_t size_x, uint32_t size_y, int r, uint8_t *tmp, uint8_t *clear,
+                                hipStream_t stream) {
+  // (size_y rides in the grid's y dimension: 65 535 rows per launch, a map of up to 2^21 rows in slices)
+  const int block = 256;
+  const unsigned gx = (size_x + block - 1) / block;
+  for (int pass = 0; pass < 2; ++pass)
+    for (uint32_t y0 = 0; y0 < size_y; y0 += 65535u) {
+      const uint32_t ny = (size_y - y0 < 65535u) ? size_y - y0 : 65535u;
+      if (pass == 0)
+        hipLaunchKernelGGL(sfw_clearance_rows_kernel, dim3(gx, ny), dim3(block), 0, stream, cells, static_cast<int>(size_x),
+                           static_cast<int>(size_y), static_cast<int>(y0), r, tmp);
+      else
+        hipLaunchKernelGGL(sfw_clearance_cols_kernel, dim3(gx, ny), dim3(block), 0, stream, tmp, static_cast<int>(size_x),
+                           static_cast<int>(size_y), static_cast<int>(y0), r, clear);
+    }
+  return hipGetLastError();
+}
+#endif
 
 hipError_t sfw_launch_rollout(const sfw_launch &L, hipStream_t stream) {
   hipError_t e = sfw_launch_rollout_poses(L, stream);

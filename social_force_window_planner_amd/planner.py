@@ -201,6 +201,9 @@ def lib():
         L.sfw_ensemble_set_list_fusion.argtypes = [vp, C.c_int32]
         L.sfw_ensemble_get_list_fusion.argtypes = [vp, C.POINTER(C.c_int32)]
         L.sfw_ensemble_batch_desc.argtypes = [vp, C.POINTER(SfwBatchDesc), C.POINTER(C.c_int64)]
+        L.sfw_set_footprint_clearance.argtypes = [vp, C.c_int32]
+        L.sfw_footprint_clearance_info.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.sfw_footprint_clearance_map.argtypes = [vp, vp, C.c_uint64]
         _lib = L
     return _lib
 
@@ -567,6 +570,24 @@ class HipScorer(_Owner):
     def set_points_capture(self, enabled=True):
         """Small grids: the scoring launch also leaves the Trajectory points (one D2H per dump, no second rollout)."""
         self._check(lib().sfw_set_points_capture(self._h, 1 if enabled else 0), "sfw_set_points_capture")
+
+    def set_footprint_clearance(self, enabled=True):
+        """The footprint check's clearance map (on by default): poses whose whole footprint window is free space skip the
+        edge walks.  Off: every pose walks its edges.  Results are bit-identical either way (A/B and tests)."""
+        self._check(lib().sfw_set_footprint_clearance(self._h, 1 if enabled else 0), "sfw_set_footprint_clearance")
+
+    def footprint_clearance_info(self):
+        """(built, half_width) of the staged grid: whether its footprint checks read a clearance map, and the map's window
+        half-width r_c in cells (the window is 2 r_c + 1 cells wide; -1 when the footprint is too large for a map)."""
+        built, r = C.c_int32(), C.c_int32()
+        self._check(lib().sfw_footprint_clearance_info(self._h, C.byref(built), C.byref(r)), "sfw_footprint_clearance_info")
+        return bool(built.value), r.value
+
+    def footprint_clearance_map(self, size_y, size_x):
+        """The staged grid's clearance map as a (size_y, size_x) uint8 array: 1 where the whole window is on the map and free."""
+        out = np.zeros((size_y, size_x), dtype=np.uint8)
+        self._check(lib().sfw_footprint_clearance_map(self._h, out.ctypes.data, out.size), "sfw_footprint_clearance_map")
+        return out
 
     def grid_points_batch(self, first, count, n_steps):
         """Trajectory points of `count` consecutive samples: (points[count, n_steps, 3], n_points[count])."""
