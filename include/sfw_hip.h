@@ -1141,6 +1141,70 @@ int sfw_ensemble_batch_desc(sfw_ensemble e, sfw_batch_desc *out, int64_t *table_
  * the launch and the aggregation, 2 the wait and the copies out. */
 int sfw_ensemble_last_us(sfw_ensemble e, int32_t which, double *us_out);
 
+/* ---- the stop check: reject samples that cannot brake to a stop ---------------------------------------------------
+ * The dynamic window's admissibility test (reference SFWPlanner::mayIStop, sfw_planner.hpp:348, src/sfw_planner.cpp
+ * :717-765; its call at the end of scoreTrajectory, :636-640, is commented out there).  Off by default: with it off no
+ * kernel is added to a launch and every output is bit-identical to a build without it.
+ *
+ * With a check set, a sample whose rollout poses were all legal (VALID behind the costmap scan) is braked from the state
+ * the rollout left — (x_S, y_S, th_S) and the velocities of step S - 1 — with the rollout's own dt:
+ *     j = 0
+ *     while (vx != 0 || vy != 0):
+ *         if j == max_steps: hit = SFW_STOP_UNFINISHED; reject
+ *         vx  = new_velocity(0, vx,  dec_x, dt);  vy = new_velocity(0, vy, dec_y, dt);  vth = new_velocity(0, vth, dec_theta, dt)
+ *         x  += (vx cos(th) + vy cos(pi/2 + th)) dt;  y += (vx sin(th) + vy sin(pi/2 + th)) dt    (OLD heading, the rollout's
+ *         th += vth dt                                                        expressions; the lateral term only when vy != 0)
+ *         code = footprint cost of (x, y, th)                     (the post-step pose at its NEW heading; off the map: -3)
+ *         if code < 0 || code >= 254: hit = min(hit, j)
+ *         j++
+ *     steps = j
+ * steps is the length of the whole tail, hit the first illegal tail pose or SFW_STOP_NONE.  A sample with a hit (or
+ * UNFINISHED) is rejected exactly like a costmap rejection behind S legal poses: cost SFW_COST_INVALID, captured terms
+ * -1, not counted in n_valid, never selected, not integrated with the pedestrians (except for the point dumps, as
+ * before); its Trajectory keeps its S points.  Pedestrians play no part in the tail, as in the reference.  No
+ * contraction in this arithmetic, as in the rest of the robot's rollout: the result does not depend on which kernels ran.
+ *
+ * Where this departs from the reference's (dead) code, on purpose:
+ *   1. the reference hands `av`, the angular velocity, to computeNewXPosition / computeNewYPosition in the heading's place
+ *      (:734-735); here it is the heading, the evident intent;
+ *   2. the reference loops while the velocities are `> 0.0` and so never checks a reversing robot; here the condition is != 0;
+ *   3. the reference loops for ever at a zero limit; here max_steps ends the loop and the sample is rejected.
+ * A limit of exactly 0 is accepted: that axis never brakes, and a sample still moving on it ends UNFINISHED.
+ *
+ * The setting is sticky and per handle, and is read by the next stage; a launch of a grid staged earlier keeps what it was
+ * staged with (as with sfw_set_costmap).  It reaches sfw_score_one, the sample lists, sequences, perturbed rollouts,
+ * sfw_mppi_run and sfw_grid_rescore through the stage.  A stage with the check on never runs as the one-launch control
+ * cycle (sfw_plan_info.one_launch = 0; a batch member with the check on takes its own path): the tail is not part of that
+ * kernel yet.
+ * Refused with SFW_ERR_INVALID_ARG, the handle keeping what it had: a NULL handle; a limit that is not finite or below 0;
+ * max_steps outside 1 .. SFW_STOP_MAX_STEPS; reserved != 0. */
+#define SFW_STOP_MAX_STEPS 4096
+#define SFW_STOP_NONE (-1)       /* every tail pose legal */
+#define SFW_STOP_UNFINISHED (-2) /* still moving after max_steps tail steps: rejected */
+#define SFW_STOP_NOT_RUN (-3)    /* skipped, or rejected before the tail (costmap) */
+typedef struct sfw_stop_check {
+  double dec_x, dec_y, dec_theta; /* braking limits; the reference passes max_trans_acc_, max_trans_acc_, max_rot_acc_ */
+  int32_t max_steps;              /* 1 .. SFW_STOP_MAX_STEPS */
+  int32_t reserved;               /* 0 */
+} sfw_stop_check;
+typedef struct sfw_stop_rec {
+  int32_t steps; /* length of the tail (0 when it did not run) */
+  int32_t hit;   /* first illegal tail pose, or SFW_STOP_NONE / _UNFINISHED / _NOT_RUN */
+} sfw_stop_rec;
+int sfw_set_stop_check(sfw_handle h, const sfw_stop_check *c); /* NULL: off (the default) */
+/* *out: the setting (all zero while off); *active_out (nullable): 1 while a check is set, else 0. */
+int sfw_get_stop_check(sfw_handle h, sfw_stop_check *out, int32_t *active_out);
+/* The records of samples [first, first + count) of the last launch (blocking).  SFW_ERR_STATE before a stage, before its
+ * launch, and when the stage had the check off. */
+int sfw_grid_stop_info(sfw_handle h, int64_t first, int64_t count, sfw_stop_rec *out);
+/* The tail poses (x, y, theta) of samples [first, first + count) of the staged grid in check order — pose j is the one
+ * hit == j refers to — by a re-run into scratch outputs that leaves the launch's results intact (RViz markers of the
+ * braking path; blocking).  points_xyth: [count][steps_cap][3]; n_steps[i] is the full tail length even when it exceeds
+ * steps_cap (0 for a sample whose tail did not run).  SFW_ERR_STATE before a stage and when the stage had the check off. */
+int sfw_grid_stop_points(sfw_handle h, int64_t first, int64_t count, int32_t steps_cap, double *points_xyth, int32_t *n_steps);
+/* The check of every member, like sfw_ensemble_set_footprint. */
+int sfw_ensemble_set_stop_check(sfw_ensemble e, const sfw_stop_check *c);
+
 #ifdef __cplusplus
 }
 #endif

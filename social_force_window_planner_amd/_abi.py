@@ -247,6 +247,11 @@ EXPORTED_SYMBOLS = (
     "sfw_set_footprint_clearance",
     "sfw_footprint_clearance_info",
     "sfw_footprint_clearance_map",
+    "sfw_set_stop_check",
+    "sfw_get_stop_check",
+    "sfw_grid_stop_info",
+    "sfw_grid_stop_points",
+    "sfw_ensemble_set_stop_check",
 )
 # per-term costs (sfw_set_terms_capture / sfw_grid_rescore / sfw_grid_terms)
 SFW_TERM_VEL, SFW_TERM_DISTANCE, SFW_TERM_ANGLE, SFW_TERM_COSTMAP, SFW_TERM_SOCIAL = 0, 1, 2, 3, 4
@@ -309,6 +314,24 @@ class SfwRisk(C.Structure):
     """sfw_risk (include/sfw_hip.h): the tail mass of the social work's CVaR and the bound on the contact mass."""
 
     _fields_ = [("tail_mass", C.c_double), ("contact_mass", C.c_double), ("reserved", C.c_int64)]
+
+
+# the stop check (sfw_set_stop_check)
+SFW_STOP_MAX_STEPS = 4096
+SFW_STOP_NONE, SFW_STOP_UNFINISHED, SFW_STOP_NOT_RUN = -1, -2, -3
+
+
+class SfwStopCheck(C.Structure):
+    """sfw_stop_check (include/sfw_hip.h): the braking limits and the cap on the tail's length."""
+
+    _fields_ = [("dec_x", C.c_double), ("dec_y", C.c_double), ("dec_theta", C.c_double), ("max_steps", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class SfwStopRec(C.Structure):
+    """sfw_stop_rec (include/sfw_hip.h): a sample's tail length and its first illegal tail pose (or a SFW_STOP_* sentinel)."""
+
+    _fields_ = [("steps", C.c_int32), ("hit", C.c_int32)]
 
 
 SFW_MULTI_RCCL, SFW_MULTI_HOST_REDUCE = 0, 1

@@ -189,6 +189,9 @@ struct sfw_planner_s {
     // poses (samples x steps) of a stage from which it builds the footprint clearance map when there is none for its costmap
     // and footprint (kClearMinPoses has the measurement); SFW_CLEAR_MIN_POSES overrides it (0: every stage builds — tests)
     int64_t clear_min_poses = kClearMinPoses;
+    // SFW_STOP_TABLE_ROWS (tests): at most this many rows in the stop check's tail table, whatever stop_tail_bound says — the
+    // tail steps beyond them are checked by the thread that walks the tail (sfw_stop_tail_kernel), with the same result
+    int stop_rows_max = -1;
   } cfg;
 
   struct switches {
@@ -203,6 +206,9 @@ struct sfw_planner_s {
     bool capture_terms = false;
     // sfw_set_footprint_clearance: K1b reads the clearance map of a stage that has one (off: every pose walks its edges)
     bool fp_clear = true;
+    // sfw_set_stop_check: the braking tail behind the costmap scan (off: no kernel is added); read by the next stage
+    bool stop_on = false;
+    sfw_stop_check stop{};
   } live;
 
   // Footprint, agents and laser points are small: sfw_set_* keep them on the host and every stage packs them into ONE
@@ -295,6 +301,11 @@ struct sfw_planner_s {
     // half-width clear_r cells (-1: the footprint is too large for a map)
     bool clear_on = false;
     int clear_r = -1;
+    // the stop check as the stage found it (sfw_set_stop_check after a stage takes effect at the next stage), and the rows of
+    // the tail table: the host's bound on the tail length (stop_tail_bound), made with the plan for params epoch plan_epoch
+    bool stop_on = false;
+    sfw_stop_check stop{};
+    int stop_cap = 0;
   } st;
 
   // What `clear_map` on the device was built from (valid: it is enqueued or done): the snapshot's generation, the map's
@@ -356,6 +367,11 @@ struct sfw_planner_s {
   dev_buf<double> pts_base, pts_costs;
   dev_buf<sfw_unit> pts_ptab, pts_cs;
   dev_buf<int16_t> pts_fcode;
+  // the stop check's tail: per-sample records (T) and the per-chunk frame table (st.stop_cap rows of st.table_chunk frames);
+  // the scratch copies of the re-runs (fill_scratch_launch) and the poses sfw_grid_stop_points reads back
+  dev_buf<int32_t> stop_steps, stop_hit, pts_stop_steps, pts_stop_hit;
+  dev_buf<sfw_pose_frame> stop_tail, pts_stop_tail;
+  dev_buf<double> stop_pts;
   pinned_buf pin_map, pin_arena, pin_out, pin_cls;
   pinned_buf pin_one;     // sfw_score_one's outputs where the one-launch kernel writes them (cost | n_points | coll_step | points)
   pinned_buf pin_mirror;  // costs + selection record as the selection kernels of the last launch leave them (device writes)
@@ -567,6 +583,17 @@ void fill_launch(sfw_handle h, sfw_launch &L, int64_t begin, int64_t count, int6
   L.arena_host = nullptr;
   L.arena_dev = nullptr;
   L.arena_bytes = 0;
+  if (h->st.stop_on) {
+    L.stop_on = 1;
+    L.stop_max_steps = h->st.stop.max_steps;
+    L.stop_cap = h->st.stop_cap;
+    L.stop_dec_x = h->st.stop.dec_x;
+    L.stop_dec_y = h->st.stop.dec_y;
+    L.stop_dec_theta = h->st.stop.dec_theta;
+    L.stop_tail = h->stop_tail.p;
+    L.stop_steps = h->stop_steps.p;
+    L.stop_hit = h->stop_hit.p;
+  }
 }
 
 // ---- shared-prefix plan ---------------------------------------------------
@@ -1146,13 +1173,43 @@ bool rest_noise_unreproduced(sfw_handle h) {
   return false;
 }
 
+// Rows of the stop check's tail table: a bound on the tail length of every sample of the staged grid.  A velocity never
+// leaves the interval between its start and its targets, so an axis that starts the tail at |v| <= vmax is at 0 after at most
+// ceil(vmax / (dec dt)) + 1 steps (the + 1: the quotient's rounding, and the recurrence's own); the tail ends when vx and vy
+// both are.  vmax: over the robot's velocity and every knot's target — the clamp box for knots drawn on the device.  An axis
+// that cannot brake (dec dt == 0) or a box without a finite side: max_steps.  (The kernel checks a longer tail all the same.)
+int stop_axis_bound(double vmax, double dec, double dt, int max_steps) {
+  if (vmax == 0.0) return 0;
+  const double step = dec * dt;
+  if (!(step > 0.0) || !std::isfinite(vmax)) return max_steps;
+  const double q = std::ceil(vmax / step) + 1.0;
+  return q < max_steps ? static_cast<int>(q) : max_steps;
+}
+int stop_tail_bound(sfw_handle h, int S) {
+  const auto &st = h->st;
+  const double dt = h->live.params.sim_time / S;
+  double mx = std::fabs(st.rs.vx), my = std::fabs(st.rs.vy);
+  if (st.perturbed) {
+    mx = std::fmax(mx, std::fmax(std::fabs(st.pert.lo[0]), std::fabs(st.pert.hi[0])));
+    my = std::fmax(my, std::fmax(std::fabs(st.pert.lo[1]), std::fabs(st.pert.hi[1])));  // (also of a stage without a vy row: only rows)
+    if (std::isnan(mx) || std::isnan(my)) return st.stop.max_steps;
+  } else {
+    for (double v : st.lin) mx = std::fmax(mx, std::fabs(v));
+    for (double v : st.vy) my = std::fmax(my, std::fabs(v));
+    my = std::fmax(my, std::fabs(st.vy_samp));
+  }
+  return std::max(stop_axis_bound(mx, st.stop.dec_x, dt, st.stop.max_steps), stop_axis_bound(my, st.stop.dec_y, dt, st.stop.max_steps));
+}
+
 // Host half: chunk size under the table budget and the shared-prefix plan (class tables in h->st.cls_ints).  No device call.
 int64_t plan_tables_host(sfw_handle h, int *err) {
   const int64_t T = static_cast<int64_t>(h->st.nv) * h->st.nw;
   const int S = num_steps_of(h->live.params);
   h->st.early_poses = false;
+  h->st.stop_cap = h->st.stop_on ? stop_tail_bound(h, S) : 0;
+  if (h->cfg.stop_rows_max >= 0 && h->st.stop_cap > h->cfg.stop_rows_max) h->st.stop_cap = h->cfg.stop_rows_max;
   int64_t chunk = static_cast<int64_t>(
-      h->cfg.table_budget_bytes / (kTableBytesPerSampleStep * S));
+      h->cfg.table_budget_bytes / (kTableBytesPerSampleStep * S + sizeof(sfw_pose_frame) * static_cast<size_t>(h->st.stop_cap)));
   if (chunk < 1024) chunk = 1024;
   if (chunk > kRowLimit) chunk = kRowLimit;
   if (chunk > T) chunk = T;
@@ -1182,6 +1239,11 @@ int plan_tables_device(sfw_handle h, int64_t chunk, bool may_start_poses) {
   SFW_HIP(h, h->ptab.reserve(static_cast<size_t>(table_row_units(chunk, h->st.nw)) * S));
   SFW_HIP(h, h->cs_tab.reserve((h->st.list ? static_cast<size_t>(chunk) : static_cast<size_t>(h->st.nw)) * S));
   SFW_HIP(h, h->fcode.reserve(static_cast<size_t>(chunk) * S));
+  if (h->st.stop_on) {
+    SFW_HIP(h, h->stop_steps.reserve(static_cast<size_t>(T)));
+    SFW_HIP(h, h->stop_hit.reserve(static_cast<size_t>(T)));
+    SFW_HIP(h, h->stop_tail.reserve(static_cast<size_t>(chunk) * static_cast<size_t>(h->st.stop_cap)));
+  }
   h->st.table_chunk = chunk;
   if (!h->st.prefix_steps.empty())
     for (size_t b = 0; b < (h->st.cls_two ? 2u : 1u); ++b) {
@@ -1467,6 +1529,8 @@ int stage_common(sfw_handle h, const sfw_robot_state *rs, const sfw_goal_args *a
   else h->st.knot_step.clear();
   h->st.K = h->world.K;
   h->st.clear_on = false;  // (until stage_clearance, at the end, says otherwise)
+  h->st.stop_on = h->live.stop_on;
+  h->st.stop = h->live.stop;
   h->st.A = ag.A;
   h->st.O = ag.O;
   h->st.NG = ag.NG;
@@ -2215,6 +2279,19 @@ void fill_scratch_launch(sfw_handle h, sfw_launch &L, int64_t first, int64_t cou
   L.base_cost = h->pts_base.p - first;
   L.ptab = h->pts_ptab.p;
   L.cs_tab = h->pts_cs.p;
+  if (h->st.stop_on) {  // (reserve_scratch_stop)
+    L.stop_tail = h->pts_stop_tail.p;
+    L.stop_steps = h->pts_stop_steps.p - first;
+    L.stop_hit = h->pts_stop_hit.p - first;
+  }
+}
+// ... and the stop check's scratch records for such a re-run of `count` samples (nothing to do with the check off)
+hipError_t reserve_scratch_stop(sfw_handle h, int64_t count) {
+  if (!h->st.stop_on) return hipSuccess;
+  hipError_t e = h->pts_stop_steps.reserve(static_cast<size_t>(count));
+  if (e == hipSuccess) e = h->pts_stop_hit.reserve(static_cast<size_t>(count));
+  if (e == hipSuccess) e = h->pts_stop_tail.reserve(static_cast<size_t>(count) * static_cast<size_t>(h->st.stop_cap));
+  return e;
 }
 
 // The one-sample stage of sfw_score_one / sfw_score_one_crowd.  The agent set is checked before the stage (a refused call leaves
@@ -2327,6 +2404,7 @@ int create_handle(const sfw_params *params, int device, hipStream_t stream, hipS
   if (const char *b = std::getenv("SFW_MIRROR_MAX_MB")) h->cfg.mirror_max_bytes = static_cast<size_t>(std::max(0L, std::atol(b))) << 20;
   if (const char *b = std::getenv("SFW_OBS_TASKS")) h->cfg.obs_tasks_force = std::atoi(b) != 0 ? 1 : 0;
   if (const char *b = std::getenv("SFW_CLEAR_MIN_POSES")) h->cfg.clear_min_poses = std::max(0LL, std::atoll(b));
+  if (const char *b = std::getenv("SFW_STOP_TABLE_ROWS")) h->cfg.stop_rows_max = std::max(0, std::atoi(b));
   if (const char *b = std::getenv("SFW_TABLE_BUDGET_MB")) {
     long mb = std::atol(b);
     if (mb > 0) h->cfg.table_budget_bytes = static_cast<size_t>(mb) << 20;
@@ -2417,6 +2495,13 @@ int destroy_handle(sfw_handle h) {
   h->pts_ptab.release();
   h->pts_cs.release();
   h->pts_fcode.release();
+  h->stop_steps.release();
+  h->stop_hit.release();
+  h->pts_stop_steps.release();
+  h->pts_stop_hit.release();
+  h->stop_tail.release();
+  h->pts_stop_tail.release();
+  h->stop_pts.release();
   h->pin_map.release();
   h->pin_arena.release();
   h->pin_out.release();
@@ -2955,6 +3040,83 @@ int sfw_footprint_clearance_map(sfw_handle h, uint8_t *out, uint64_t cells) {
   return SFW_OK;
 }
 
+int sfw_set_stop_check(sfw_handle h, const sfw_stop_check *c) {
+  if (!h) return SFW_ERR_INVALID_ARG;
+  if (!c) {
+    h->live.stop_on = false;
+    h->live.stop = sfw_stop_check{};
+    return SFW_OK;
+  }
+  for (double d : {c->dec_x, c->dec_y, c->dec_theta})
+    if (!std::isfinite(d) || d < 0) return fail(h, SFW_ERR_INVALID_ARG, "set_stop_check: a braking limit is not finite or below 0");
+  if (c->max_steps < 1 || c->max_steps > SFW_STOP_MAX_STEPS)
+    return fail(h, SFW_ERR_INVALID_ARG, "set_stop_check: max_steps outside 1 .. SFW_STOP_MAX_STEPS");
+  if (c->reserved != 0) return fail(h, SFW_ERR_INVALID_ARG, "set_stop_check: reserved must be 0");
+  h->live.stop = *c;
+  h->live.stop_on = true;
+  return SFW_OK;
+}
+
+int sfw_get_stop_check(sfw_handle h, sfw_stop_check *out, int32_t *active_out) {
+  if (!h) return SFW_ERR_INVALID_ARG;
+  if (!out) return fail(h, SFW_ERR_INVALID_ARG, "get_stop_check: null pointer");
+  *out = h->live.stop;
+  if (active_out) *active_out = h->live.stop_on ? 1 : 0;
+  return SFW_OK;
+}
+
+int sfw_grid_stop_info(sfw_handle h, int64_t first, int64_t count, sfw_stop_rec *out) {
+  if (!h) return SFW_ERR_INVALID_ARG;
+  if (!h->st.valid) return fail(h, SFW_ERR_STATE, "grid_stop_info before grid_stage");
+  if (!h->st.stop_on) return fail(h, SFW_ERR_STATE, "grid_stop_info: the staged grid has no stop check (sfw_set_stop_check)");
+  if (!h->last.launched) return fail(h, SFW_ERR_STATE, "grid_stop_info before grid_launch");
+  const int64_t T = static_cast<int64_t>(h->st.nv) * h->st.nw;
+  if (!sample_range_ok(first, count, T) || !out) return fail(h, SFW_ERR_INVALID_ARG, "grid_stop_info: bad range or buffer");
+  SFW_HIP(h, hipSetDevice(h->device));
+  const size_t n = static_cast<size_t>(count);
+  std::vector<int32_t> steps(n), hit(n);
+  SFW_HIP(h, hipMemcpyAsync(steps.data(), h->stop_steps.p + first, sizeof(int32_t) * n, hipMemcpyDeviceToHost, h->stream));
+  SFW_HIP(h, hipMemcpyAsync(hit.data(), h->stop_hit.p + first, sizeof(int32_t) * n, hipMemcpyDeviceToHost, h->stream));
+  SFW_HIP(h, hipStreamSynchronize(h->stream));
+  for (size_t i = 0; i < n; ++i) out[i] = sfw_stop_rec{steps[i], hit[i]};
+  return SFW_OK;
+}
+
+int sfw_grid_stop_points(sfw_handle h, int64_t first, int64_t count, int32_t steps_cap, double *points_xyth, int32_t *n_steps) {
+  if (!h) return SFW_ERR_INVALID_ARG;
+  if (!h->st.valid) return fail(h, SFW_ERR_STATE, "grid_stop_points before grid_stage");
+  if (!h->st.stop_on) return fail(h, SFW_ERR_STATE, "grid_stop_points: the staged grid has no stop check (sfw_set_stop_check)");
+  const int64_t T = static_cast<int64_t>(h->st.nv) * h->st.nw;
+  if (!sample_range_ok(first, count, T) || steps_cap < 1 || !points_xyth || !n_steps)
+    return fail(h, SFW_ERR_INVALID_ARG, "grid_stop_points: bad range, steps_cap < 1 or null buffer");
+  SFW_HIP(h, hipSetDevice(h->device));
+  if (int e = flush_arena(h)) return e;  // (the re-run below reads the device copy of the arena)
+  const int S = num_steps_of(h->live.params);
+  const size_t n = static_cast<size_t>(count), pts = 3 * static_cast<size_t>(steps_cap) * n;
+  // K1 and the tail once more for those samples into scratch outputs, as sfw_grid_points_batch does
+  SFW_HIP(h, h->pts_status.reserve(n));
+  SFW_HIP(h, h->pts_base.reserve(n));
+  SFW_HIP(h, h->pts_costs.reserve(n));
+  SFW_HIP(h, h->pts_ptab.reserve(static_cast<size_t>(S) * static_cast<size_t>(table_row_units(count, h->st.nw))));
+  SFW_HIP(h, h->pts_cs.reserve(static_cast<size_t>(S) * (h->st.list ? n : static_cast<size_t>(h->st.nw))));
+  SFW_HIP(h, h->pts_fcode.reserve(static_cast<size_t>(S) * n));
+  SFW_HIP(h, reserve_scratch_stop(h, count));
+  SFW_HIP(h, h->stop_pts.reserve(pts));
+  sfw_launch L;
+  fill_scratch_launch(h, L, first, count);
+  L.costs = h->pts_costs.p - first;
+  L.coll_step = nullptr;
+  L.fcode = h->pts_fcode.p;
+  L.stop_points = h->stop_pts.p;
+  L.stop_points_cap = steps_cap;
+  SFW_HIP(h, hipMemsetAsync(h->stop_pts.p, 0, sizeof(double) * pts, h->stream));  // (poses behind a tail's end: zeros)
+  SFW_HIP(h, sfw_launch_rollout(L, h->stream));
+  SFW_HIP(h, hipMemcpyAsync(n_steps, h->pts_stop_steps.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, h->stream));
+  SFW_HIP(h, hipMemcpyAsync(points_xyth, h->stop_pts.p, sizeof(double) * pts, hipMemcpyDeviceToHost, h->stream));
+  SFW_HIP(h, hipStreamSynchronize(h->stream));
+  return SFW_OK;
+}
+
 int sfw_set_terms_capture(sfw_handle h, int32_t enabled) {
   if (!h) return SFW_ERR_INVALID_ARG;
   h->live.capture_terms = enabled != 0;
@@ -3137,6 +3299,7 @@ int sfw_grid_points_batch(sfw_handle h, int64_t first, int64_t count, double *po
   if (e == hipSuccess) e = h->pts_ptab.reserve(static_cast<size_t>(S) * static_cast<size_t>(table_row_units(count, h->st.nw)));
   if (e == hipSuccess) e = h->pts_cs.reserve(static_cast<size_t>(S) * (h->st.list ? n : static_cast<size_t>(h->st.nw)));
   if (e == hipSuccess) e = h->pts_fcode.reserve(static_cast<size_t>(S) * n);
+  if (e == hipSuccess) e = reserve_scratch_stop(h, count);
   if (e == hipSuccess) {
     sfw_launch L;
     fill_scratch_launch(h, L, first, count);
@@ -3227,6 +3390,7 @@ int crowd_run(sfw_handle h, int64_t t, double *cost_out, double *state_xyvv, dou
   SFW_HIP(h, h->pts_ptab.reserve(static_cast<size_t>(S) * static_cast<size_t>(table_row_units(1, h->st.nw))));
   SFW_HIP(h, h->pts_cs.reserve(static_cast<size_t>(S) * (h->st.list ? size_t(1) : static_cast<size_t>(h->st.nw))));
   SFW_HIP(h, h->pts_fcode.reserve(static_cast<size_t>(S)));
+  SFW_HIP(h, reserve_scratch_stop(h, 1));
   if (A > 0 && h->crowd_pair_tab_A != A) {
     h->crowd_pair_tab_A = -1;  // (until the table for this count is enqueued)
     SFW_HIP(h, h->crowd_pair_tab.reserve(static_cast<size_t>(sfw_pair_table_entries(A))));
@@ -4554,6 +4718,12 @@ int sfw_ensemble_set_costmap(sfw_ensemble e, const uint8_t *cells, uint32_t size
 int sfw_ensemble_set_footprint(sfw_ensemble e, const double *xy, int32_t K) {
   if (!e) return SFW_ERR_INVALID_ARG;
   return ensemble_each(e, "ensemble_set_footprint", [&](sfw_handle h) { return sfw_set_footprint(h, xy, K); });
+}
+
+int sfw_ensemble_set_stop_check(sfw_ensemble e, const sfw_stop_check *c) {
+  if (!e) return SFW_ERR_INVALID_ARG;
+  // (the checks are the same for every member: the first one refuses before any member has changed)
+  return ensemble_each(e, "ensemble_set_stop_check", [&](sfw_handle h) { return sfw_set_stop_check(h, c); });
 }
 
 int sfw_ensemble_set_hypothesis(sfw_ensemble e, int32_t m, const sfw_agent *agents, int32_t A, const double *obstacles_xy,

@@ -238,6 +238,18 @@ struct sfw_launch {
   // pose in that cell can read (sfw_capi.hip clearance_half_width).  Such a pose's footprint cost is 0 without walking an edge
   // (sfw_kernels.hip footprint_cost_clear).  Null: every pose walks.  (Appended: no other field's offset moves.)
   const uint8_t *clear;
+  // sfw_set_stop_check (stop_on: 0 off — nothing below is read and no kernel is added): the braking tail behind K1c
+  // (sfw_kernels.hip sfw_stop_*_kernel).  stop_tail: [stop_cap][rstep_stride] frames (x, y, cos, sin) of the tail poses of the
+  // chunk's samples, laid out like ptab / cs_tab (adjacent lanes store adjacent frames); stop_cap: the host's bound on the
+  // tail length (sfw_capi.hip stop_tail_bound; a longer tail is still checked, serially, by the thread that walks it).
+  // stop_steps / stop_hit: per sample, by GLOBAL sample index.  stop_points / stop_points_cap (nullable): the tail poses
+  // (x, y, theta) of the chunk's samples, [chunk_count][stop_points_cap][3] (sfw_grid_stop_points).
+  // (Appended: no other field's offset moves.)
+  int32_t stop_on, stop_max_steps, stop_cap, stop_points_cap;
+  double stop_dec_x, stop_dec_y, stop_dec_theta;
+  sfw_pose_frame *stop_tail;
+  int32_t *stop_steps, *stop_hit;
+  double *stop_points;
 };
 
 // Writers of the captured cost terms (no-ops when terms is null): term k of sample t, the three pedestrian-free terms, or one

@@ -564,6 +564,112 @@ __global__ void __launch_bounds__(256) sfw_costmap_scan_kernel(const sfw_launch 
   scan_finish(L, t, local, cm, n_ok);
 }
 
+// ---- the stop check (sfw_set_stop_check, sfw_launch.stop_on): the braking tail behind K1c, or behind the fused small K1 ----
+// Three kernels in the shape of K1a / K1b / K1c; every K1 organisation leaves the same ptab and status, so the tail is the
+// same whichever ran in front of it.
+// (1) Tail poses, one thread per sample that is VALID behind the costmap scan.  The end state of the rollout is formed here
+// again: (x_S, y_S) is the position unit of step S - 1; the three velocity recurrences and the heading sum are walked once
+// more — the operations of rollout_sample on the same values in the same order, no sincos, S cheap serial steps — so that
+// none of the K1a kernels changes.  Then the serial tail: one sincos per tail step, since the heading a pose is checked at is
+// the old heading of the next step.  Frames (x, y, cos, sin) go to stop_tail for (2); a tail beyond the host's bound stop_cap
+// (never, by sfw_capi.hip stop_tail_bound; SFW_STOP_TABLE_ROWS shortens the table for the tests) is checked here, by the thread
+// itself: the same poses, the same verdict.
+__global__ void __launch_bounds__(256) sfw_stop_tail_kernel(const sfw_launch L) {
+  const int64_t local = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (local >= L.chunk_count) return;
+  const int64_t t = L.chunk_begin + local;
+  if (L.status[t] != SFW_ST_VALID) {
+    L.stop_steps[t] = 0;
+    L.stop_hit[t] = SFW_STOP_NOT_RUN;
+    return;
+  }
+  const sample_cmd cmd = L.list ? sample_cmd_of<true>(L, t) : sample_cmd_of<false>(L, t);
+  double vx_samp = cmd.vx, vth_samp = cmd.vth, vy_samp = cmd.vy;
+  const bool seq = L.n_knots > 1;
+  knot_cursor kc{0, seq ? knot_next_step(L, 0) : INT_MAX};
+  double th = L.rs.theta, vx = L.rs.vx, vy = L.rs.vy, vth = L.rs.vtheta;
+  const int S = L.S;
+  const double dt = L.dt;
+  for (int i = 0; i < S; ++i) {
+    if (i == kc.next) {  // the next knot takes over at this step
+      ++kc.k;
+      vx_samp = knot_target(L, L.linvels, kc.k, t);
+      vy_samp = knot_target(L, L.vy_samps, kc.k, t);
+      vth_samp = knot_target(L, L.angvels, kc.k, t);
+      kc.next = knot_next_step(L, kc.k);
+    }
+    vx = new_velocity(vx_samp, vx, L.ga.acc_x, dt);  // ref :581-583
+    vy = new_velocity(vy_samp, vy, L.ga.acc_y, dt);
+    vth = new_velocity(vth_samp, vth, L.ga.acc_theta, dt);
+    th = th + vth * dt;
+  }
+  const sfw_unit end = L.ptab[static_cast<int64_t>(S - 1) * L.row_units + local];
+  double x = end.a, y = end.b;
+  double s, c;
+  sincos(th, &s, &c);
+  int j = 0, hit = INT_MAX;
+  bool unfinished = false;
+  while (vx != 0.0 || vy != 0.0) {
+    if (j == L.stop_max_steps) {
+      unfinished = true;
+      break;
+    }
+    vx = new_velocity(0.0, vx, L.stop_dec_x, dt);
+    vy = new_velocity(0.0, vy, L.stop_dec_y, dt);
+    vth = new_velocity(0.0, vth, L.stop_dec_theta, dt);
+    double c2 = 0.0, s2 = 0.0;
+    if (vy != 0.0) sincos(M_PI_2 + th, &s2, &c2);
+    const double xn = x + (vx * c + vy * c2) * dt;  // (old theta, as rollout_sample)
+    const double yn = y + (vx * s + vy * s2) * dt;
+    x = xn;
+    y = yn;
+    th = th + vth * dt;
+    sincos(th, &s, &c);  // the heading this pose is checked at, and the next step's old heading
+    if (j < L.stop_cap) {
+      L.stop_tail[static_cast<int64_t>(j) * L.rstep_stride + local] = sfw_pose_frame{x, y, c, s};
+    } else {
+      const double fc = footprint_cost_clear(L, x, y, c, s);
+      if (fc < 0 || fc >= 254.0) hit = min(hit, j);
+    }
+    if (L.stop_points && j < L.stop_points_cap) {
+      double *pt = L.stop_points + (local * L.stop_points_cap + j) * 3;
+      pt[0] = x;
+      pt[1] = y;
+      pt[2] = th;
+    }
+    ++j;
+  }
+  L.stop_steps[t] = j;
+  L.stop_hit[t] = unfinished ? SFW_STOP_UNFINISHED : hit;
+}
+// (2) Tail footprints, one thread per (tail step, sample) like K1b: the grid's y dimension covers the stop_cap rows of the
+// table.  The first illegal pose is an integer minimum: the same whatever order the threads run in.
+__global__ void __launch_bounds__(256) sfw_stop_footprint_kernel(const sfw_launch L) {
+  const int64_t local = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (local >= L.chunk_count) return;
+  const int64_t t = L.chunk_begin + local;
+  const int j = static_cast<int>(blockIdx.y);
+  if (j >= L.stop_steps[t]) return;  // (0 for a sample whose tail did not run)
+  const sfw_pose_frame f = L.stop_tail[static_cast<int64_t>(j) * L.rstep_stride + local];
+  const double fc = footprint_cost_clear(L, f.x, f.y, f.c, f.s);
+  if (fc < 0 || fc >= 254.0) atomicMin(&L.stop_hit[t], j);
+}
+// (3) Finish, one thread per sample: a sample with a hit (or still moving after max_steps steps) is rejected like a costmap
+// rejection behind S legal poses — for A == 0 the cost scan_finish wrote is overwritten.
+__global__ void __launch_bounds__(256) sfw_stop_finish_kernel(const sfw_launch L) {
+  const int64_t local = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (local >= L.chunk_count) return;
+  const int64_t t = L.chunk_begin + local;
+  if (L.status[t] != SFW_ST_VALID) return;  // (SFW_STOP_NOT_RUN is in place)
+  if (L.stop_hit[t] == INT_MAX) {
+    L.stop_hit[t] = SFW_STOP_NONE;
+    return;
+  }
+  L.status[t] = SFW_ST_INVALID;
+  L.costs[t] = SFW_COST_INVALID;
+  sfw_put_terms_sentinel(L.terms, L.terms_T, t, SFW_COST_INVALID);
+}
+
 // One footprint edge of a pose: the largest cell value on edge e (vertex e -> vertex e+1, the last edge closes the
 // polygon), or FOOT_OFFMAP when one of its vertices is off the map.  The same expressions as footprint_cost.
 constexpr int FOOT_OFFMAP = 300;
@@ -3756,9 +3862,22 @@ hipError_t sfw_launch_rollout_poses(const sfw_launch &L, hipStream_t stream) {
   return hipGetLastError();
 }
 
-// K1b + K1c (footprint checks, costmap scan); nothing to do after the fused K1.
+// The stop check's tail (sfw_launch.stop_on) behind whatever left the samples' status and ptab
+static hipError_t sfw_launch_stop_tail(const sfw_launch &L, hipStream_t stream) {
+  const int block = 256;
+  const unsigned grid = static_cast<unsigned>((L.chunk_count + block - 1) / block);
+  hipLaunchKernelGGL(sfw_stop_tail_kernel, dim3(grid), dim3(block), 0, stream, L);
+  if (L.stop_cap > 0)  // (at most SFW_STOP_MAX_STEPS rows: inside the limit of a grid's y dimension)
+    hipLaunchKernelGGL(sfw_stop_footprint_kernel, dim3(grid, static_cast<unsigned>(L.stop_cap)), dim3(block), 0, stream, L);
+  hipLaunchKernelGGL(sfw_stop_finish_kernel, dim3(grid), dim3(block), 0, stream, L);
+  return hipGetLastError();
+}
+
+// K1b + K1c (footprint checks, costmap scan); nothing to do after the fused K1 — but for the stop check's tail, which
+// follows either.
 hipError_t sfw_launch_rollout_costmap(const sfw_launch &L, hipStream_t stream) {
-  if (L.chunk_count <= 0 || sfw_rollout_is_fused(L)) return hipSuccess;
+  if (L.chunk_count <= 0) return hipSuccess;
+  if (sfw_rollout_is_fused(L)) return L.stop_on ? sfw_launch_stop_tail(L, stream) : hipSuccess;
   {
     const int block = 256;
     const unsigned grid = static_cast<unsigned>((L.chunk_count + block - 1) / block);
@@ -3772,6 +3891,7 @@ hipError_t sfw_launch_rollout_costmap(const sfw_launch &L, hipStream_t stream) {
     const unsigned grid = static_cast<unsigned>((L.chunk_count + block - 1) / block);
     hipLaunchKernelGGL(sfw_costmap_scan_kernel, dim3(grid), dim3(block), 0, stream, L);
   }
+  if (L.stop_on) return sfw_launch_stop_tail(L, stream);
   return hipGetLastError();
 }
 
@@ -4190,6 +4310,7 @@ static size_t cycle_k2_bytes(const sfw_launch &L, bool obs_lds) {
 bool sfw_cycle_applies(const sfw_launch &L) {
   if (const char *e = std::getenv("SFW_CYCLE_FUSED"))
     if (e[0] == '0') return false;
+  if (L.stop_on) return false;  // (sfw_set_stop_check: the tail is not part of cycle_block)
   if (L.phase != SFW_PHASE_WHOLE || L.resume || L.chunk_begin != 0 || L.chunk_count <= 0 || L.chunk_count > CYCLE_MAX_SAMPLES) return false;
   if (L.S > K1_SMALL_MAX_STEPS || (L.sel_out && !L.cycle_counter)) return false;
   const bool social = L.A > 0 && !(L.A == 1 && L.O == 0 && L.NG == 0);

@@ -58,6 +58,8 @@ def lib():
         L.sfwh_markers.restype = C.c_int64
         L.sfwh_set_marker_capture.argtypes = [vp, C.c_int32]
         L.sfwh_set_marker_capture.restype = None
+        L.sfwh_set_stop_check.argtypes = [vp, C.c_int32, C.c_int32]
+        L.sfwh_set_stop_check.restype = None
         L.sfwh_get_yaw.argtypes = [C.c_double] * 4
         L.sfwh_get_yaw.restype = C.c_double
         _lib = L
@@ -124,6 +126,10 @@ class HostPlanner:
     def set_marker_capture(self, on=True):
         """SFWPlanner::setMarkerCapture: the scoring launch also leaves the Trajectory points (one copy per marker dump)."""
         lib().sfwh_set_marker_capture(self._h, 1 if on else 0)
+
+    def set_stop_check(self, on=True, max_steps=4096):
+        """SFWPlanner::setStopCheck: reject samples that cannot brake to a stop under the controller's own acceleration limits."""
+        lib().sfwh_set_stop_check(self._h, 1 if on else 0, max_steps)
 
     def set_devices(self, devices, host_reduce=False):
         """SFWPlanner::setDevices: grid rows over several devices from this process (before the first scoring call)."""

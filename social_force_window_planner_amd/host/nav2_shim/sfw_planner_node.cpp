@@ -248,6 +248,17 @@ geometry_msgs::msg::TwistStamped SFWPlannerNode::computeVelocityCommands(const g
 
   sfw_planner_->setParams(readControllerParams());  // the reference re-reads its parameters every cycle (:125)
   sfw_planner_->setCostmap(costmapView());
+  // not in the reference's yaml: the admissibility test it leaves commented out (SFWPlanner::setStopCheck), off by default;
+  // read every cycle like the rest.  A step cap outside 1 .. SFW_STOP_MAX_STEPS is not handed down (sfw_set_stop_check would
+  // refuse it and the cycle would throw): it is clamped, with a warning
+  int stop_steps = param(node_.get(), name_ + ".stop_check_max_steps", static_cast<int>(SFW_STOP_MAX_STEPS));
+  if (stop_steps < 1 || stop_steps > SFW_STOP_MAX_STEPS) {
+    const int clamped = stop_steps < 1 ? 1 : SFW_STOP_MAX_STEPS;
+    RCLCPP_WARN(node_->get_logger(), "%s.stop_check_max_steps: %d is outside 1 .. %d: using %d", name_.c_str(), stop_steps,
+                SFW_STOP_MAX_STEPS, clamped);
+    stop_steps = clamped;
+  }
+  sfw_planner_->setStopCheck(param(node_.get(), name_ + ".stop_check", false), stop_steps);
   sfw_planner_->updatePlan(local);                   // ref :277
   Twist cmd;
   Twist in_speed;

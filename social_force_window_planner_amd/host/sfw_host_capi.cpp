@@ -215,6 +215,10 @@ int64_t sfwh_markers(void *hv, float *rgba, int32_t *counts, double *z0, int64_t
   }
   return static_cast<int64_t>(ms.size());
 }
+// SFWPlanner::setStopCheck (a function of its own: sfwh_params keeps its layout)
+void sfwh_set_stop_check(void *hv, int32_t on, int32_t max_steps) {
+  static_cast<HostHandle *>(hv)->planner->setStopCheck(on != 0, max_steps);
+}
 void sfwh_set_marker_capture(void *hv, int32_t on) { static_cast<HostHandle *>(hv)->planner->setMarkerCapture(on != 0); }
 double sfwh_get_yaw(double x, double y, double z, double w) { return getYaw(Quaternion{x, y, z, w}); }
 }

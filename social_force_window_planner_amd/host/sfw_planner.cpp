@@ -147,6 +147,11 @@ void SFWPlanner::setMarkerCapture(bool on) {
     sfw_set_points_capture(handle_, on ? 1 : 0);
   }
 }
+void SFWPlanner::setStopCheck(bool on, int max_steps) {
+  std::lock_guard<std::mutex> l(configuration_mutex_);
+  stop_check_ = on;
+  stop_max_steps_ = max_steps;
+}
 void SFWPlanner::setFootprint(std::vector<Point> footprint) { footprint_spec_ = std::move(footprint); }
 void SFWPlanner::setSampleSets(std::vector<double> lin, std::vector<double> ang) {
   linvels_ = std::move(lin);
@@ -166,6 +171,11 @@ void SFWPlanner::uploadWorld(const AgentSet &agents) {
   const double *obs = agents.obstacles_xy.empty() ? nullptr : agents.obstacles_xy.data();
   const int32_t O = static_cast<int32_t>(agents.obstacles_xy.size() / 2);
   int rc;
+  // the stop check's limits are the controller's own, re-read every cycle like the rest of the parameters (ref :125)
+  const sfw_stop_check stop{params_.max_trans_acc_, params_.max_trans_acc_, params_.max_rot_acc_, stop_max_steps_, 0};
+  const sfw_stop_check *const stop_p = stop_check_ ? &stop : nullptr;
+  for (int32_t r = 0; r < (multi_ ? sfw_multi_ranks(multi_) : 1); ++r)
+    if ((rc = sfw_set_stop_check(multi_ ? sfw_multi_rank_handle(multi_, r) : handle_, stop_p)) != SFW_OK) raise("sfw_set_stop_check", rc);
   if (multi_) {  // replicated to every rank
     if ((rc = sfw_multi_set_params(multi_, &abi)) != SFW_OK) raise("sfw_multi_set_params", rc);
     if ((rc = sfw_multi_set_costmap(multi_, costmap_.cells, costmap_.size_x, costmap_.size_y, costmap_.origin_x,

@@ -166,6 +166,13 @@ class SFWPlanner {
   // somebody listens to the markers — getMarkers is then one device-to-host copy per cycle —, off otherwise (the
   // reference fills its MarkerArray every cycle, :347-386; nothing needs the points when nobody subscribes).
   void setMarkerCapture(bool on);
+  // The admissibility test the reference declares and leaves switched off (mayIStop, sfw_planner.hpp:348; its call at
+  // src/sfw_planner.cpp:636-640 is commented out): a sample whose robot cannot brake to a stop in front of what lies beyond
+  // its rollout is rejected (include/sfw_hip.h: sfw_set_stop_check, with the three places where it departs from the
+  // reference's dead code).  Every cycle hands the limits {max_trans_acc_, max_trans_acc_, max_rot_acc_} down, as the
+  // reference's call would; the grid and both single-sample call sites (:204-206, :299-301) are checked.  Off by default.
+  void setStopCheck(bool on, int max_steps = SFW_STOP_MAX_STEPS);
+  bool stopCheck() const { return stop_check_; }
   int wpIndex() const { return wp_index_; }
   bool running() const { return running_; }
 
@@ -192,6 +199,8 @@ class SFWPlanner {
   int last_branch_ = kNotRunning;
   bool grid_staged_ = false;
   bool marker_capture_ = false;
+  bool stop_check_ = false;
+  int stop_max_steps_ = SFW_STOP_MAX_STEPS;
 
   int wp_index_ = -1;
   bool running_ = false, new_plan_ = false, goal_reached_ = false;

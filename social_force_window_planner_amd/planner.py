@@ -32,6 +32,8 @@ from ._abi import (
     SfwRisk,
     SfwRobotState,
     SfwPlanInfo,
+    SfwStopCheck,
+    SfwStopRec,
     SfwWeights,
     SFW_N_TERMS,
     default_params,
@@ -204,6 +206,11 @@ def lib():
         L.sfw_set_footprint_clearance.argtypes = [vp, C.c_int32]
         L.sfw_footprint_clearance_info.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.sfw_footprint_clearance_map.argtypes = [vp, vp, C.c_uint64]
+        L.sfw_set_stop_check.argtypes = [vp, C.POINTER(SfwStopCheck)]
+        L.sfw_get_stop_check.argtypes = [vp, C.POINTER(SfwStopCheck), C.POINTER(C.c_int32)]
+        L.sfw_grid_stop_info.argtypes = [vp, C.c_int64, C.c_int64, vp]
+        L.sfw_grid_stop_points.argtypes = [vp, C.c_int64, C.c_int64, C.c_int32, vp, vp]
+        L.sfw_ensemble_set_stop_check.argtypes = [vp, C.POINTER(SfwStopCheck)]
         _lib = L
     return _lib
 
@@ -588,6 +595,35 @@ class HipScorer(_Owner):
         out = np.zeros((size_y, size_x), dtype=np.uint8)
         self._check(lib().sfw_footprint_clearance_map(self._h, out.ctypes.data, out.size), "sfw_footprint_clearance_map")
         return out
+
+    def set_stop_check(self, check=None, *, dec_x=None, dec_y=None, dec_theta=None, max_steps=None):
+        """sfw_set_stop_check: reject samples that cannot brake to a stop in front of what lies beyond the rollout (read by the
+        next stage).  check: an SfwStopCheck, a (dec_x, dec_y, dec_theta, max_steps) tuple, or None with no keyword: off."""
+        if check is None and dec_x is None:
+            self._check(lib().sfw_set_stop_check(self._h, None), "sfw_set_stop_check")
+            return
+        if not isinstance(check, SfwStopCheck):
+            check = SfwStopCheck(*check) if check is not None else SfwStopCheck(dec_x, dec_y, dec_theta, max_steps)
+        self._check(lib().sfw_set_stop_check(self._h, C.byref(check)), "sfw_set_stop_check")
+
+    def stop_check(self):
+        """(dec_x, dec_y, dec_theta, max_steps) of the check in force for the next stage, or None while it is off."""
+        c, on = SfwStopCheck(), C.c_int32()
+        self._check(lib().sfw_get_stop_check(self._h, C.byref(c), C.byref(on)), "sfw_get_stop_check")
+        return (c.dec_x, c.dec_y, c.dec_theta, c.max_steps) if on.value else None
+
+    def stop_info(self, first, count):
+        """(steps[count], hit[count]) of the last launch: every sample's tail length and first illegal tail pose (SFW_STOP_*)."""
+        rec = np.zeros((count, 2), dtype=np.int32)
+        self._check(lib().sfw_grid_stop_info(self._h, first, count, rec.ctypes.data), "sfw_grid_stop_info")
+        return rec[:, 0].copy(), rec[:, 1].copy()
+
+    def stop_points(self, first, count, steps_cap):
+        """The tail poses of `count` consecutive samples of the staged grid: (points[count, steps_cap, 3], n_steps[count])."""
+        pts = np.zeros((count, steps_cap, 3), dtype=np.float64)
+        n = np.zeros(count, dtype=np.int32)
+        self._check(lib().sfw_grid_stop_points(self._h, first, count, steps_cap, pts.ctypes.data, n.ctypes.data), "sfw_grid_stop_points")
+        return pts, n
 
     def grid_points_batch(self, first, count, n_steps):
         """Trajectory points of `count` consecutive samples: (points[count, n_steps, 3], n_points[count])."""
@@ -1204,6 +1240,13 @@ class EnsembleScorer(_Owner):
         return res + (costs, rejected) if want_costs else res
 
     # -- risk ---------------------------------------------------------------
+    def set_stop_check(self, check=None):
+        """sfw_ensemble_set_stop_check: the stop check of every member (an SfwStopCheck or a (dec_x, dec_y, dec_theta,
+        max_steps) tuple; None: off)."""
+        if check is not None and not isinstance(check, SfwStopCheck):
+            check = SfwStopCheck(*check)
+        self._check(lib().sfw_ensemble_set_stop_check(self._e, None if check is None else C.byref(check)), "sfw_ensemble_set_stop_check")
+
     def set_risk(self, tail_mass=1.0, contact_mass=0.0):
         """sfw_ensemble_set_risk: from here on every aggregation (the score calls, aggregate, mppi_run) takes "mean" as the
         tail expectation of the social work over the worst `tail_mass` of the accepted probability mass, and rejects a sample
