@@ -1205,6 +1205,75 @@ int sfw_grid_stop_points(sfw_handle h, int64_t first, int64_t count, int32_t ste
 /* The check of every member, like sfw_ensemble_set_footprint. */
 int sfw_ensemble_set_stop_check(sfw_ensemble e, const sfw_stop_check *c);
 
+/* ---- the path term: how far a rollout strays from the global plan --------------------------------------------------
+ * A sixth cost term next to the reference's five: the mean squared distance of a sample's Trajectory points to the global
+ * plan (the `path_distance_bias_ * path_cost` of the classic DWA sum, which the reference leaves in a comment at
+ * src/sfw_planner.cpp:660-662 after reducing the plan to one way-point; DWB PathDist, the nav2 MPPI PathFollow critic).
+ * Off by default: with no path set no kernel is added to a launch and every output is bit-identical to a build without it.
+ *
+ * A path is a polyline of n_points world points (1 .. SFW_PATH_MAX_POINTS) with n_points - 1 segments; a one-point path is
+ * one zero-length segment.  Repeated points are legal (a zero-length segment).  The host turns each segment a -> b into a
+ * record {ax, ay, ex, ey, inv} in double, without contraction:
+ *     ex = bx - ax;  ey = by - ay;  len2 = ex*ex + ey*ey;  inv = len2 > 0 ? 1.0/len2 : 0.0
+ * For a pose (px, py) and one segment, every operation rounded once, no FMA (the rule of the robot's rollout):
+ *     rx = px - ax;  ry = py - ay
+ *     u  = (rx*ex + ry*ey) * inv
+ *     t  = u < 0 ? 0 : (u > 1 ? 1 : u)
+ *     qx = rx - t*ex;  qy = ry - t*ey
+ *     d  = qx*qx + qy*qy
+ * D(pose) = min over segments of d, the running minimum `d < m ? d : m` from m = +inf: a minimum of doubles, exact in any
+ * order.  The path term of a sample is the mean over the S points of its Trajectory — poses 0 .. S-1, the very doubles
+ * sfw_grid_points returns —, summed in step order:
+ *     p = (((D_0 + D_1) + D_2) + ... + D_{S-1}) / S
+ * Pose 0 is the robot's own pose and adds the same constant to every sample; that is documented, not special-cased.
+ * p is defined for every sample that is VALID behind the costmap scan (and behind the stop check when that is on); it does
+ * not depend on the pedestrians: a sample rejected by contact keeps its p and has a sentinel cost.
+ * The cost of a sample whose cost is not a sentinel becomes cost5 + path_weight * p — one multiply and one add, each rounded
+ * once, behind the reference's five-term sum (a cost that equals SFW_COST_INVALID counts as that sentinel).  Sentinels stay;
+ * n_valid, the cost == 10000.0 rule and the tie-breaks act on the new cost.  The captured terms stay the five (SFW_N_TERMS):
+ * p lives in a buffer of its own, 8 B per sample, that exists only while a path is staged; the distance table adds 8 B per
+ * step and sample to what SFW_TABLE_BUDGET_MB chunks.
+ *
+ * The setting is sticky and per handle and is read by the next stage (the points are copied); a launch of a grid staged
+ * earlier keeps what it was staged with.  It reaches sfw_score_grid, sfw_score_one (the cost includes the term), sample
+ * lists, sequences, perturbed rollouts, sfw_grid_blend* (they read the cost vector) and sfw_mppi_run through the stage.  A
+ * stage with a path never runs as the one-launch control cycle (sfw_plan_info.one_launch = 0; a batch member with a path takes
+ * its own path, sfw_batch_desc.own_path_members): the term is not part of that kernel.  sfw_multi_* has no wrapper: rank
+ * handles take sfw_set_path one by one.
+ * Refused with SFW_ERR_INVALID_ARG, the handle keeping what it had: a NULL handle or NULL xy; n_points outside
+ * 1 .. SFW_PATH_MAX_POINTS; a coordinate that is not finite or exceeds SFW_PATH_MAX_COORD in magnitude (so that no product
+ * overflows for an on-map pose); a weight that is not finite (a negative weight is accepted, as elsewhere); reserved != 0. */
+#define SFW_PATH_MAX_POINTS 1024
+#define SFW_PATH_MAX_COORD 1e7
+typedef struct sfw_path {
+  const double *xy; /* n_points x (x, y) */
+  int32_t n_points; /* 1 .. SFW_PATH_MAX_POINTS */
+  int32_t reserved; /* 0 */
+  double weight;    /* path_weight */
+} sfw_path;
+int sfw_set_path(sfw_handle h, const sfw_path *p); /* NULL: off (the default) */
+/* The setting in force for the next stage: up to cap points into xy_out (nullable when cap is 0), *n_points_out the number
+ * the path has (0 while off), *weight_out, *active_out (each nullable). */
+int sfw_get_path(sfw_handle h, double *xy_out, int32_t cap, int32_t *n_points_out, double *weight_out, int32_t *active_out);
+/* The unweighted p of samples [first, first + count) of the last launch (blocking).  A sample rejected before or at the path
+ * pass: SFW_COST_INVALID; the grid's (0,0) sample: SFW_COST_SKIPPED.  SFW_ERR_STATE before a stage, before its launch, and
+ * when the stage had no path. */
+int sfw_grid_path_term(sfw_handle h, int64_t first, int64_t count, double *out);
+/* sfw_grid_rescore keeps its contract — what sfw_score_grid would return with these weights —: with a path staged it adds the
+ * staged path_weight * p, and costs_out is bit-identical to that call's cost vector.  sfw_grid_rescore_path sweeps the sixth
+ * weight over one launch: K path weights (NULL: the staged weight, K times) under the one weight vector *w; best_out K
+ * records, costs_out (nullable) K x samples doubles, weight-major.  The rules of sfw_grid_rescore (K in
+ * 1 .. SFW_RESCORE_MAX_K, finite weights, a launch with terms captured), and SFW_ERR_STATE when the stage had no path. */
+int sfw_grid_rescore_path(sfw_handle h, const sfw_weights *w, const double *path_weight, int32_t K, sfw_best *best_out,
+                          double *costs_out);
+/* The path of every member, like sfw_ensemble_set_stop_check.  All members share robot state, map and path, so p is
+ * bit-identical across members; every aggregation (mean / worst / under a risk; grids and lists, hence
+ * sfw_ensemble_score_sequences, _score_perturbed, _aggregate, _blend* and _mppi_run) adds path_weight * p[t], taken from
+ * member 0, behind the aggregated five-term cost and in front of the selection — also for a sample that member 0 rejects by
+ * contact and a risk with contact_mass > 0 accepts.  Members whose path settings differ (one set through
+ * sfw_ensemble_member): the scoring call returns SFW_ERR_STATE. */
+int sfw_ensemble_set_path(sfw_ensemble e, const sfw_path *p);
+
 #ifdef __cplusplus
 }
 #endif

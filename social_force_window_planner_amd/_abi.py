@@ -252,6 +252,11 @@ EXPORTED_SYMBOLS = (
     "sfw_grid_stop_info",
     "sfw_grid_stop_points",
     "sfw_ensemble_set_stop_check",
+    "sfw_set_path",
+    "sfw_get_path",
+    "sfw_grid_path_term",
+    "sfw_grid_rescore_path",
+    "sfw_ensemble_set_path",
 )
 # per-term costs (sfw_set_terms_capture / sfw_grid_rescore / sfw_grid_terms)
 SFW_TERM_VEL, SFW_TERM_DISTANCE, SFW_TERM_ANGLE, SFW_TERM_COSTMAP, SFW_TERM_SOCIAL = 0, 1, 2, 3, 4
@@ -332,6 +337,17 @@ class SfwStopRec(C.Structure):
     """sfw_stop_rec (include/sfw_hip.h): a sample's tail length and its first illegal tail pose (or a SFW_STOP_* sentinel)."""
 
     _fields_ = [("steps", C.c_int32), ("hit", C.c_int32)]
+
+
+# the path term (sfw_set_path)
+SFW_PATH_MAX_POINTS = 1024
+SFW_PATH_MAX_COORD = 1e7
+
+
+class SfwPath(C.Structure):
+    """sfw_path (include/sfw_hip.h): the global plan's points and the path term's weight."""
+
+    _fields_ = [("xy", C.POINTER(C.c_double)), ("n_points", C.c_int32), ("reserved", C.c_int32), ("weight", C.c_double)]
 
 
 SFW_MULTI_RCCL, SFW_MULTI_HOST_REDUCE = 0, 1

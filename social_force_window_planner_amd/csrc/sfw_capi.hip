@@ -192,6 +192,8 @@ struct sfw_planner_s {
     // SFW_STOP_TABLE_ROWS (tests): at most this many rows in the stop check's tail table, whatever stop_tail_bound says — the
     // tail steps beyond them are checked by the thread that walks the tail (sfw_stop_tail_kernel), with the same result
     int stop_rows_max = -1;
+    // SFW_PATH_SLICES=0 (A/B and tests): the path term's distance kernel never splits the segments over the grid's z
+    bool path_slices_on = true;
   } cfg;
 
   struct switches {
@@ -209,6 +211,10 @@ struct sfw_planner_s {
     // sfw_set_stop_check: the braking tail behind the costmap scan (off: no kernel is added); read by the next stage
     bool stop_on = false;
     sfw_stop_check stop{};
+    // sfw_set_path: the path term (off: no kernel is added); read by the next stage.  path_xy: the points as handed over
+    bool path_on = false;
+    double path_weight = 0.0;
+    std::vector<double> path_xy;
   } live;
 
   // Footprint, agents and laser points are small: sfw_set_* keep them on the host and every stage packs them into ONE
@@ -306,6 +312,11 @@ struct sfw_planner_s {
     bool stop_on = false;
     sfw_stop_check stop{};
     int stop_cap = 0;
+    // the path term as the stage found it (sfw_set_path after a stage takes effect at the next stage): the segment records
+    // (path_segments) that `path_seg` on the device holds for this stage, and the weight
+    bool path_on = false;
+    double path_weight = 0.0;
+    std::vector<sfw_path_seg> path_segs;
   } st;
 
   // What `clear_map` on the device was built from (valid: it is enqueued or done): the snapshot's generation, the map's
@@ -372,6 +383,12 @@ struct sfw_planner_s {
   dev_buf<int32_t> stop_steps, stop_hit, pts_stop_steps, pts_stop_hit;
   dev_buf<sfw_pose_frame> stop_tail, pts_stop_tail;
   dev_buf<double> stop_pts;
+  // the path term: the stage's segment records (path_seg_sent: what the device copy holds, or is about to), the per-chunk
+  // distance table [S][st.table_chunk], the term per sample (T), and the scratch copies of the re-runs (fill_scratch_launch)
+  dev_buf<sfw_path_seg> path_seg;
+  pinned_buf pin_path;  // the records on their way to path_seg
+  std::vector<sfw_path_seg> path_seg_sent;
+  dev_buf<double> path_D, path_p, pts_path_D, pts_path_p, rescore_pw;
   pinned_buf pin_map, pin_arena, pin_out, pin_cls;
   pinned_buf pin_one;     // sfw_score_one's outputs where the one-launch kernel writes them (cost | n_points | coll_step | points)
   pinned_buf pin_mirror;  // costs + selection record as the selection kernels of the last launch leave them (device writes)
@@ -593,6 +610,18 @@ void fill_launch(sfw_handle h, sfw_launch &L, int64_t begin, int64_t count, int6
     L.stop_tail = h->stop_tail.p;
     L.stop_steps = h->stop_steps.p;
     L.stop_hit = h->stop_hit.p;
+  }
+  if (h->st.path_on) {
+    L.path_on = 1;
+    L.path_n_seg = static_cast<int32_t>(h->st.path_segs.size());
+    // Slices of 64 segments over the grid's z where the launch leaves the GPU idle (at most 65 536 poses: a control cycle's
+    // 45 x 40, a few thousand MPPI rollouts) and the path has more than two slices' worth: measured at 5 x 9 samples and
+    // 1024 points, one thread per pose took 82.3 us, more than the rest of the cycle (profiles/r25_path_term.txt).  SFW_PATH_SLICES=0 keeps one thread per pose.
+    const int64_t poses = count * static_cast<int64_t>(L.S);
+    if (h->cfg.path_slices_on && L.path_n_seg > 128 && poses <= 65536) L.path_slices = (L.path_n_seg + 63) / 64;
+    L.path_seg = h->path_seg.p;
+    L.path_D = h->path_D.p;
+    L.path_p = h->path_p.p;
   }
 }
 
@@ -1201,6 +1230,22 @@ int stop_tail_bound(sfw_handle h, int S) {
   return std::max(stop_axis_bound(mx, st.stop.dec_x, dt, st.stop.max_steps), stop_axis_bound(my, st.stop.dec_y, dt, st.stop.max_steps));
 }
 
+// The segment records of a path (sfw_hip.h "the path term"): n - 1 segments of n points, one zero-length segment of one point.
+// The pragma keeps the host compiler from contracting ex*ex + ey*ey into a fused multiply-add: every operation is rounded
+// once, as path.py and the header state it.
+void path_segments(const std::vector<double> &xy, std::vector<sfw_path_seg> &out) {
+#pragma clang fp contract(off)
+  const size_t n = xy.size() / 2;
+  out.clear();
+  for (size_t i = 0; i + 1 < n || (n == 1 && i == 0); ++i) {
+    const size_t j = n == 1 ? 0 : i + 1;
+    const double ax = xy[2 * i], ay = xy[2 * i + 1];
+    const double ex = xy[2 * j] - ax, ey = xy[2 * j + 1] - ay;
+    const double len2 = ex * ex + ey * ey;
+    out.push_back(sfw_path_seg{ax, ay, ex, ey, len2 > 0.0 ? 1.0 / len2 : 0.0});
+  }
+}
+
 // Host half: chunk size under the table budget and the shared-prefix plan (class tables in h->st.cls_ints).  No device call.
 int64_t plan_tables_host(sfw_handle h, int *err) {
   const int64_t T = static_cast<int64_t>(h->st.nv) * h->st.nw;
@@ -1209,7 +1254,8 @@ int64_t plan_tables_host(sfw_handle h, int *err) {
   h->st.stop_cap = h->st.stop_on ? stop_tail_bound(h, S) : 0;
   if (h->cfg.stop_rows_max >= 0 && h->st.stop_cap > h->cfg.stop_rows_max) h->st.stop_cap = h->cfg.stop_rows_max;
   int64_t chunk = static_cast<int64_t>(
-      h->cfg.table_budget_bytes / (kTableBytesPerSampleStep * S + sizeof(sfw_pose_frame) * static_cast<size_t>(h->st.stop_cap)));
+      h->cfg.table_budget_bytes / ((kTableBytesPerSampleStep + (h->st.path_on ? sizeof(double) : 0)) * S +
+                                   sizeof(sfw_pose_frame) * static_cast<size_t>(h->st.stop_cap)));
   if (chunk < 1024) chunk = 1024;
   if (chunk > kRowLimit) chunk = kRowLimit;
   if (chunk > T) chunk = T;
@@ -1243,6 +1289,10 @@ int plan_tables_device(sfw_handle h, int64_t chunk, bool may_start_poses) {
     SFW_HIP(h, h->stop_steps.reserve(static_cast<size_t>(T)));
     SFW_HIP(h, h->stop_hit.reserve(static_cast<size_t>(T)));
     SFW_HIP(h, h->stop_tail.reserve(static_cast<size_t>(chunk) * static_cast<size_t>(h->st.stop_cap)));
+  }
+  if (h->st.path_on) {
+    SFW_HIP(h, h->path_p.reserve(static_cast<size_t>(T)));
+    SFW_HIP(h, h->path_D.reserve(static_cast<size_t>(chunk) * S));
   }
   h->st.table_chunk = chunk;
   if (!h->st.prefix_steps.empty())
@@ -1531,6 +1581,27 @@ int stage_common(sfw_handle h, const sfw_robot_state *rs, const sfw_goal_args *a
   h->st.clear_on = false;  // (until stage_clearance, at the end, says otherwise)
   h->st.stop_on = h->live.stop_on;
   h->st.stop = h->live.stop;
+  h->st.path_on = h->live.path_on;
+  h->st.path_weight = h->live.path_weight;
+  if (h->st.path_on) {
+    path_segments(h->live.path_xy, h->st.path_segs);
+    // Unchanged records stay where they are.  Changed ones go through a pinned buffer of their own (pin_path: reserve waits
+    // for the last upload, mark guards this one), like the arena; the copy is on the stream, behind the launches of an earlier
+    // stage that read the old records
+    const size_t seg_bytes = sizeof(sfw_path_seg) * h->st.path_segs.size();
+    if (!h->path_seg.p || h->path_seg_sent.size() != h->st.path_segs.size() ||
+        std::memcmp(h->path_seg_sent.data(), h->st.path_segs.data(), seg_bytes) != 0) {
+      h->path_seg_sent.clear();
+      SFW_HIP(h, h->pin_path.reserve(seg_bytes));
+      std::memcpy(h->pin_path.p, h->st.path_segs.data(), seg_bytes);
+      SFW_HIP(h, h->path_seg.reserve(h->st.path_segs.size()));
+      SFW_HIP(h, hipMemcpyAsync(h->path_seg.p, h->pin_path.p, seg_bytes, hipMemcpyHostToDevice, h->stream));
+      SFW_HIP(h, h->pin_path.mark(h->stream));
+      h->path_seg_sent = h->st.path_segs;
+    }
+  } else {
+    h->st.path_segs.clear();
+  }
   h->st.A = ag.A;
   h->st.O = ag.O;
   h->st.NG = ag.NG;
@@ -1932,6 +2003,8 @@ int launch_kernels(sfw_handle h, const launch_prep &lp) {
       if (timing) SFW_HIP(h, hipEventRecord(single ? h->ev[1] : h->chunk_ev[3 * c + 1], h->stream));
       SFW_HIP(h, launch_social_of(L, h->stream, &h->split));
     }
+    // sfw_set_path: cost + w p behind whatever formed the chunk's costs, in front of the selection
+    if (L.path_on) SFW_HIP(h, sfw_launch_path_add(L.costs, L.path_p, h->st.path_weight, b, n, h->stream));
     if (!single && timing) SFW_HIP(h, hipEventRecord(h->chunk_ev[3 * c + 2], h->stream));
   }
   if (timing) SFW_HIP(h, hipEventRecord(h->ev[2], h->stream));
@@ -2273,7 +2346,9 @@ int score_staged(sfw_handle h, int staged, double *costs_out, sfw_best *best_out
 
 // The launch record of samples [first, first + count) run once more, alone, into the scratch outputs (the launch's own results
 // stay intact).  The kernels index per-sample outputs by the global sample index: the pointers are biased by -first.
-void fill_scratch_launch(sfw_handle h, sfw_launch &L, int64_t first, int64_t count) {
+// path: the re-run also forms the path term, into scratch of its own (reserve_scratch_path in front) — crowd_run, whose cost
+// carries the term; the re-runs that only want poses leave the term's kernels out
+void fill_scratch_launch(sfw_handle h, sfw_launch &L, int64_t first, int64_t count, bool path = false) {
   fill_launch(h, L, first, count, count);
   L.status = h->pts_status.p - first;
   L.base_cost = h->pts_base.p - first;
@@ -2284,6 +2359,13 @@ void fill_scratch_launch(sfw_handle h, sfw_launch &L, int64_t first, int64_t cou
     L.stop_steps = h->pts_stop_steps.p - first;
     L.stop_hit = h->pts_stop_hit.p - first;
   }
+  if (h->st.path_on && path) {  // (reserve_scratch_path)
+    L.path_D = h->pts_path_D.p;
+    L.path_p = h->pts_path_p.p - first;
+  } else {
+    L.path_on = 0;
+    L.path_D = L.path_p = nullptr;
+  }
 }
 // ... and the stop check's scratch records for such a re-run of `count` samples (nothing to do with the check off)
 hipError_t reserve_scratch_stop(sfw_handle h, int64_t count) {
@@ -2291,6 +2373,14 @@ hipError_t reserve_scratch_stop(sfw_handle h, int64_t count) {
   hipError_t e = h->pts_stop_steps.reserve(static_cast<size_t>(count));
   if (e == hipSuccess) e = h->pts_stop_hit.reserve(static_cast<size_t>(count));
   if (e == hipSuccess) e = h->pts_stop_tail.reserve(static_cast<size_t>(count) * static_cast<size_t>(h->st.stop_cap));
+  return e;
+}
+
+// ... and the path term's scratch (distance table and term) for a re-run with fill_scratch_launch(..., path = true)
+hipError_t reserve_scratch_path(sfw_handle h, int64_t count) {
+  if (!h->st.path_on) return hipSuccess;
+  hipError_t e = h->pts_path_p.reserve(static_cast<size_t>(count));
+  if (e == hipSuccess) e = h->pts_path_D.reserve(static_cast<size_t>(count) * static_cast<size_t>(num_steps_of(h->live.params)));
   return e;
 }
 
@@ -2405,6 +2495,7 @@ int create_handle(const sfw_params *params, int device, hipStream_t stream, hipS
   if (const char *b = std::getenv("SFW_OBS_TASKS")) h->cfg.obs_tasks_force = std::atoi(b) != 0 ? 1 : 0;
   if (const char *b = std::getenv("SFW_CLEAR_MIN_POSES")) h->cfg.clear_min_poses = std::max(0LL, std::atoll(b));
   if (const char *b = std::getenv("SFW_STOP_TABLE_ROWS")) h->cfg.stop_rows_max = std::max(0, std::atoi(b));
+  if (const char *b = std::getenv("SFW_PATH_SLICES")) h->cfg.path_slices_on = std::atoi(b) != 0;
   if (const char *b = std::getenv("SFW_TABLE_BUDGET_MB")) {
     long mb = std::atol(b);
     if (mb > 0) h->cfg.table_budget_bytes = static_cast<size_t>(mb) << 20;
@@ -2502,6 +2593,13 @@ int destroy_handle(sfw_handle h) {
   h->stop_tail.release();
   h->pts_stop_tail.release();
   h->stop_pts.release();
+  h->path_seg.release();
+  h->pin_path.release();
+  h->path_D.release();
+  h->path_p.release();
+  h->pts_path_D.release();
+  h->pts_path_p.release();
+  h->rescore_pw.release();
   h->pin_map.release();
   h->pin_arena.release();
   h->pin_out.release();
@@ -2879,6 +2977,7 @@ int sfw_score_one(sfw_handle h, const sfw_robot_state *rs, double vx_samp, doubl
   score_one_outputs_at(L, h->one_out.p);
   SFW_HIP(h, sfw_launch_rollout(L, h->stream));
   SFW_HIP(h, launch_social_of(L, h->stream));
+  if (L.path_on) SFW_HIP(h, sfw_launch_path_add(L.costs, L.path_p, h->st.path_weight, 0, 1, h->stream));
   const size_t fetch = head + ((points_xyth && points_cap > 0) ? pts_bytes : 0);
   SFW_HIP(h, h->pin_out.reserve(fetch));
   SFW_HIP(h, hipMemcpyAsync(h->pin_out.p, h->one_out.p, fetch, hipMemcpyDeviceToHost, h->stream));
@@ -3117,6 +3216,52 @@ int sfw_grid_stop_points(sfw_handle h, int64_t first, int64_t count, int32_t ste
   return SFW_OK;
 }
 
+int sfw_set_path(sfw_handle h, const sfw_path *p) {
+  if (!h) return SFW_ERR_INVALID_ARG;
+  if (!p) {
+    h->live.path_on = false;
+    h->live.path_weight = 0.0;
+    h->live.path_xy.clear();
+    return SFW_OK;
+  }
+  if (!p->xy) return fail(h, SFW_ERR_INVALID_ARG, "set_path: xy is NULL");
+  if (p->n_points < 1 || p->n_points > SFW_PATH_MAX_POINTS)
+    return fail(h, SFW_ERR_INVALID_ARG, "set_path: n_points outside 1 .. SFW_PATH_MAX_POINTS");
+  if (p->reserved != 0) return fail(h, SFW_ERR_INVALID_ARG, "set_path: reserved must be 0");
+  if (!std::isfinite(p->weight)) return fail(h, SFW_ERR_INVALID_ARG, "set_path: the weight is not finite");
+  for (int32_t i = 0; i < 2 * p->n_points; ++i)
+    if (!(std::fabs(p->xy[i]) <= SFW_PATH_MAX_COORD))  // (a NaN fails the comparison too)
+      return fail(h, SFW_ERR_INVALID_ARG, "set_path: a coordinate is not finite or beyond SFW_PATH_MAX_COORD");
+  h->live.path_xy.assign(p->xy, p->xy + 2 * static_cast<size_t>(p->n_points));
+  h->live.path_weight = p->weight;
+  h->live.path_on = true;
+  return SFW_OK;
+}
+
+int sfw_get_path(sfw_handle h, double *xy_out, int32_t cap, int32_t *n_points_out, double *weight_out, int32_t *active_out) {
+  if (!h) return SFW_ERR_INVALID_ARG;
+  if (cap < 0 || (cap > 0 && !xy_out)) return fail(h, SFW_ERR_INVALID_ARG, "get_path: cap < 0, or xy_out is NULL with cap > 0");
+  const size_t n = h->live.path_xy.size() / 2;
+  if (xy_out && n > 0) std::memcpy(xy_out, h->live.path_xy.data(), sizeof(double) * 2 * std::min(n, static_cast<size_t>(cap)));
+  if (n_points_out) *n_points_out = static_cast<int32_t>(n);
+  if (weight_out) *weight_out = h->live.path_weight;
+  if (active_out) *active_out = h->live.path_on ? 1 : 0;
+  return SFW_OK;
+}
+
+int sfw_grid_path_term(sfw_handle h, int64_t first, int64_t count, double *out) {
+  if (!h) return SFW_ERR_INVALID_ARG;
+  if (!h->st.valid) return fail(h, SFW_ERR_STATE, "grid_path_term before grid_stage");
+  if (!h->st.path_on) return fail(h, SFW_ERR_STATE, "grid_path_term: the staged grid has no path (sfw_set_path)");
+  if (!h->last.launched) return fail(h, SFW_ERR_STATE, "grid_path_term before grid_launch");
+  const int64_t T = static_cast<int64_t>(h->st.nv) * h->st.nw;
+  if (!sample_range_ok(first, count, T) || !out) return fail(h, SFW_ERR_INVALID_ARG, "grid_path_term: bad range or buffer");
+  SFW_HIP(h, hipSetDevice(h->device));
+  SFW_HIP(h, hipMemcpyAsync(out, h->path_p.p + first, sizeof(double) * static_cast<size_t>(count), hipMemcpyDeviceToHost, h->stream));
+  SFW_HIP(h, hipStreamSynchronize(h->stream));
+  return SFW_OK;
+}
+
 int sfw_set_terms_capture(sfw_handle h, int32_t enabled) {
   if (!h) return SFW_ERR_INVALID_ARG;
   h->live.capture_terms = enabled != 0;
@@ -3132,26 +3277,45 @@ int sfw_set_terms_capture(sfw_handle h, int32_t enabled) {
   return SFW_OK;
 }
 
-int sfw_grid_rescore(sfw_handle h, const sfw_weights *w, int32_t K, sfw_best *best_out, double *costs_out) {
+}  // extern "C"
+namespace {
+// sfw_grid_rescore (sweep false: K weight vectors w[0..K), the staged path weight where a path is staged) and
+// sfw_grid_rescore_path (sweep true: the one vector *w, K times, under path_weight[0..K) — null: the staged weight)
+int rescore_run(sfw_handle h, const char *what_c, const sfw_weights *w, bool sweep, const double *path_weight, int32_t K,
+                sfw_best *best_out, double *costs_out) {
   if (!h) return SFW_ERR_INVALID_ARG;
-  if (!w || !best_out) return fail(h, SFW_ERR_INVALID_ARG, "grid_rescore: weights or best_out is NULL");
-  if (K < 1 || K > SFW_RESCORE_MAX_K) return fail(h, SFW_ERR_INVALID_ARG, "grid_rescore: K out of [1, SFW_RESCORE_MAX_K]");
-  if (!all_finite(reinterpret_cast<const double *>(w), static_cast<size_t>(K) * SFW_N_TERMS))
-    return fail(h, SFW_ERR_INVALID_ARG, "grid_rescore: non-finite weight");
+  const std::string what = what_c;
+  if (!w || !best_out) return fail(h, SFW_ERR_INVALID_ARG, what + ": weights or best_out is NULL");
+  if (K < 1 || K > SFW_RESCORE_MAX_K) return fail(h, SFW_ERR_INVALID_ARG, what + ": K out of [1, SFW_RESCORE_MAX_K]");
+  if (!all_finite(reinterpret_cast<const double *>(w), (sweep ? size_t(1) : static_cast<size_t>(K)) * SFW_N_TERMS) ||
+      (path_weight && !all_finite(path_weight, static_cast<size_t>(K))))
+    return fail(h, SFW_ERR_INVALID_ARG, what + ": non-finite weight");
   if (!h->last.launched || !h->last.terms)
-    return fail(h, SFW_ERR_STATE, "grid_rescore: the last launch did not capture terms (sfw_set_terms_capture), or a stage or "
-                                  "sfw_score_one came in since");
+    return fail(h, SFW_ERR_STATE, what + ": the last launch did not capture terms (sfw_set_terms_capture), or a stage or "
+                                         "sfw_score_one came in since");
+  if (sweep && !h->st.path_on) return fail(h, SFW_ERR_STATE, what + ": the staged grid has no path (sfw_set_path)");
   SFW_HIP(h, hipSetDevice(h->device));
+  const bool path = h->st.path_on;
   const int64_t T = static_cast<int64_t>(h->st.nv) * h->st.nw;
   const size_t sel_bytes = (sizeof(sfw_sel) * static_cast<size_t>(K) + 15) & ~size_t(15);
   const size_t w_bytes = sizeof(sfw_weights) * static_cast<size_t>(K);
+  const size_t pw_bytes = path ? sizeof(double) * static_cast<size_t>(K) : 0;
   // (growing the pinned area frees the old one: nothing in the stream may still be writing there)
-  if (sel_bytes + w_bytes > h->pin_rescore.cap) SFW_HIP(h, hipStreamSynchronize(h->stream));
-  SFW_HIP(h, h->pin_rescore.reserve(sel_bytes + w_bytes));
+  if (sel_bytes + w_bytes + pw_bytes > h->pin_rescore.cap) SFW_HIP(h, hipStreamSynchronize(h->stream));
+  SFW_HIP(h, h->pin_rescore.reserve(sel_bytes + w_bytes + pw_bytes));
   sfw_sel *const sel_host = reinterpret_cast<sfw_sel *>(h->pin_rescore.p);
-  std::memcpy(h->pin_rescore.p + sel_bytes, w, w_bytes);
+  if (sweep)
+    for (int32_t k = 0; k < K; ++k) std::memcpy(h->pin_rescore.p + sel_bytes + sizeof(sfw_weights) * static_cast<size_t>(k), w, sizeof(sfw_weights));
+  else
+    std::memcpy(h->pin_rescore.p + sel_bytes, w, w_bytes);
   SFW_HIP(h, h->rescore_w.reserve(static_cast<size_t>(K)));
   SFW_HIP(h, hipMemcpyAsync(h->rescore_w.p, h->pin_rescore.p + sel_bytes, w_bytes, hipMemcpyHostToDevice, h->stream));
+  if (path) {  // one path weight per vector, behind the weight vectors
+    double *const pw = reinterpret_cast<double *>(h->pin_rescore.p + sel_bytes + w_bytes);
+    for (int32_t k = 0; k < K; ++k) pw[k] = path_weight ? path_weight[k] : h->st.path_weight;
+    SFW_HIP(h, h->rescore_pw.reserve(static_cast<size_t>(K)));
+    SFW_HIP(h, hipMemcpyAsync(h->rescore_pw.p, pw, pw_bytes, hipMemcpyHostToDevice, h->stream));
+  }
   // weight vectors per launch: all K, or — with costs_out — as many as 256 MB of device cost vectors hold (each launch's are
   // copied out behind it)
   int32_t k_step = K;
@@ -3166,7 +3330,7 @@ int sfw_grid_rescore(sfw_handle h, const sfw_weights *w, int32_t K, sfw_best *be
     SFW_HIP(h, h->rescore_partials.reserve(static_cast<size_t>(blocks) * static_cast<size_t>(n)));
     SFW_HIP(h, sfw_launch_rescore(h->terms.p, T, h->rescore_w.p + k0, n, h->st.d_linvels, h->st.d_angvels, h->st.nw, h->st.index_base,
                                   h->rescore_partials.p, costs_out ? h->rescore_costs.p : nullptr, sel_host + k0, h->stream,
-                                  h->st.list));
+                                  h->st.list, path ? h->path_p.p : nullptr, path ? h->rescore_pw.p + k0 : nullptr));
     if (costs_out)
       SFW_HIP(h, hipMemcpyAsync(costs_out + static_cast<int64_t>(k0) * T, h->rescore_costs.p,
                                 sizeof(double) * static_cast<size_t>(n) * static_cast<size_t>(T), hipMemcpyDeviceToHost, h->stream));
@@ -3177,6 +3341,17 @@ int sfw_grid_rescore(sfw_handle h, const sfw_weights *w, int32_t K, sfw_best *be
   for (int32_t k = 0; k < K; ++k)
     if (int e = sel_to_best(h, sel_host[k], best_out + k, nullptr)) return e;
   return SFW_OK;
+}
+}  // namespace
+extern "C" {
+
+int sfw_grid_rescore(sfw_handle h, const sfw_weights *w, int32_t K, sfw_best *best_out, double *costs_out) {
+  return rescore_run(h, "grid_rescore", w, false, nullptr, K, best_out, costs_out);
+}
+
+int sfw_grid_rescore_path(sfw_handle h, const sfw_weights *w, const double *path_weight, int32_t K, sfw_best *best_out,
+                          double *costs_out) {
+  return rescore_run(h, "grid_rescore_path", w, true, path_weight, K, best_out, costs_out);
 }
 
 int sfw_grid_blend(sfw_handle h, const double *lambda, int32_t L, const double *bias, sfw_blend_stat *stat_out, double *u_out,
@@ -3391,6 +3566,7 @@ int crowd_run(sfw_handle h, int64_t t, double *cost_out, double *state_xyvv, dou
   SFW_HIP(h, h->pts_cs.reserve(static_cast<size_t>(S) * (h->st.list ? size_t(1) : static_cast<size_t>(h->st.nw))));
   SFW_HIP(h, h->pts_fcode.reserve(static_cast<size_t>(S)));
   SFW_HIP(h, reserve_scratch_stop(h, 1));
+  SFW_HIP(h, reserve_scratch_path(h, 1));
   if (A > 0 && h->crowd_pair_tab_A != A) {
     h->crowd_pair_tab_A = -1;  // (until the table for this count is enqueued)
     SFW_HIP(h, h->crowd_pair_tab.reserve(static_cast<size_t>(sfw_pair_table_entries(A))));
@@ -3399,7 +3575,7 @@ int crowd_run(sfw_handle h, int64_t t, double *cost_out, double *state_xyvv, dou
   }
   char *const out = h->crowd_out.p;
   sfw_launch L;
-  fill_scratch_launch(h, L, t, 1);
+  fill_scratch_launch(h, L, t, 1, true);  // (with the path term: the sample's cost carries it)
   L.costs = reinterpret_cast<double *>(out) - t;
   L.coll_step = reinterpret_cast<int32_t *>(out + 12) - t;
   L.n_points = reinterpret_cast<int32_t *>(out + 8);
@@ -3413,6 +3589,7 @@ int crowd_run(sfw_handle h, int64_t t, double *cost_out, double *state_xyvv, dou
     SFW_HIP(h, h->live.params.precision == SFW_PRECISION_F64_STRICT ? sfw_launch_crowd_strict(L, cw, h->stream)
                                                                      : sfw_launch_crowd(L, cw, h->stream));
   }
+  if (L.path_on) SFW_HIP(h, sfw_launch_path_add(L.costs, L.path_p, h->st.path_weight, t, 1, h->stream));
   SFW_HIP(h, h->pin_crowd.reserve(total));
   SFW_HIP(h, hipMemcpyAsync(h->pin_crowd.p, out, total, hipMemcpyDeviceToHost, h->stream));
   SFW_HIP(h, hipStreamSynchronize(h->stream));
@@ -4448,18 +4625,21 @@ int ensemble_enqueue(sfw_ensemble e, int32_t mode, const double *probs, bool reu
   const double *const *const d_terms = reinterpret_cast<const double *const *>(e->tab.p);
   const double *const d_probs = reinterpret_cast<const double *>(e->tab.p + sizeof(double) * static_cast<size_t>(M));
   const double thr = e->risk_on ? e->risk.contact_mass * ensemble_mass(M, probs) : 0.0;  // (the risk's contact threshold: one product)
+  // sfw_set_path: member 0's term and weight as its stage found them (null: the five terms alone)
+  const double *const path_p = h0->st.path_on ? h0->path_p.p : nullptr;
+  const double path_w = h0->st.path_weight;
   const hipError_t he =
       e->risk_on
           ? sfw_launch_ensemble_risk(d_terms, d_probs, M, T, mode, w, e->risk.tail_mass, e->risk.contact_mass, thr, list,
                                      h0->st.d_linvels, h0->st.d_angvels, h0->st.nw, reinterpret_cast<double *>(out),
                                      list && e->mirrored ? e->d_cost.p : nullptr, reinterpret_cast<int32_t *>(out + cost_bytes),
-                                     e->partials.p, reinterpret_cast<sfw_sel *>(e->pin_out.p), e->b->stream)
+                                     e->partials.p, reinterpret_cast<sfw_sel *>(e->pin_out.p), e->b->stream, path_p, path_w)
       : list ? sfw_launch_ensemble_list(d_terms, d_probs, M, T, mode, w, h0->st.d_linvels, h0->st.d_angvels, reinterpret_cast<double *>(out),
                                       e->mirrored ? e->d_cost.p : nullptr, reinterpret_cast<int32_t *>(out + cost_bytes),
-                                      e->partials.p, reinterpret_cast<sfw_sel *>(e->pin_out.p), e->b->stream)
+                                      e->partials.p, reinterpret_cast<sfw_sel *>(e->pin_out.p), e->b->stream, path_p, path_w)
            : sfw_launch_ensemble(d_terms, d_probs, M, T, mode, w, h0->st.d_linvels, h0->st.d_angvels, h0->st.nw,
                                  reinterpret_cast<double *>(out), reinterpret_cast<int32_t *>(out + cost_bytes), e->partials.p,
-                                 reinterpret_cast<sfw_sel *>(e->pin_out.p), e->b->stream);
+                                 reinterpret_cast<sfw_sel *>(e->pin_out.p), e->b->stream, path_p, path_w);
   if (he != hipSuccess)
     return efail(e, SFW_ERR_HIP, std::string(e->risk_on ? (list ? "ensemble: sfw_ens_risk_list / sfw_ensemble_stage2: "
                                                                 : "ensemble: sfw_ens_risk_grid / sfw_ensemble_stage2: ")
@@ -4500,6 +4680,12 @@ int ensemble_check_members(sfw_ensemble e, const char *what) {
     if (!h->live.capture_terms)
       return efail(e, SFW_ERR_STATE, std::string(what) + ": member " + std::to_string(m) + "'s terms capture was turned off");
     if (!h->world.have_costmap) return efail(e, SFW_ERR_STATE, std::string(what) + ": no costmap set (sfw_ensemble_set_costmap)");
+    // the aggregation adds member 0's path term: every member must have the same path, bit for bit (sfw_ensemble_set_path)
+    const sfw_handle h0 = e->b->h[0];
+    if (h->live.path_on != h0->live.path_on || std::memcmp(&h->live.path_weight, &h0->live.path_weight, sizeof(double)) != 0 ||
+        h->live.path_xy.size() != h0->live.path_xy.size() ||
+        (!h->live.path_xy.empty() && std::memcmp(h->live.path_xy.data(), h0->live.path_xy.data(), sizeof(double) * h->live.path_xy.size()) != 0))
+      return efail(e, SFW_ERR_STATE, std::string(what) + ": member " + std::to_string(m) + "'s path differs from member 0's (sfw_ensemble_set_path)");
   }
   return SFW_OK;
 }
@@ -4724,6 +4910,12 @@ int sfw_ensemble_set_stop_check(sfw_ensemble e, const sfw_stop_check *c) {
   if (!e) return SFW_ERR_INVALID_ARG;
   // (the checks are the same for every member: the first one refuses before any member has changed)
   return ensemble_each(e, "ensemble_set_stop_check", [&](sfw_handle h) { return sfw_set_stop_check(h, c); });
+}
+
+int sfw_ensemble_set_path(sfw_ensemble e, const sfw_path *p) {
+  if (!e) return SFW_ERR_INVALID_ARG;
+  // (the checks are the same for every member: the first one refuses before any member has changed)
+  return ensemble_each(e, "ensemble_set_path", [&](sfw_handle h) { return sfw_set_path(h, p); });
 }
 
 int sfw_ensemble_set_hypothesis(sfw_ensemble e, int32_t m, const sfw_agent *agents, int32_t A, const double *obstacles_xy,

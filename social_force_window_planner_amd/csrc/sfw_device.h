@@ -113,6 +113,12 @@ struct sfw_sel {
   long long n_valid;
 };
 
+// One segment a -> b of the path (sfw_hip.h "the path term"): e = b - a, inv = 1 / |e|^2 or 0 for a zero-length segment,
+// formed on the host (sfw_capi.hip path_segments).
+struct sfw_path_seg {
+  double ax, ay, ex, ey, inv;
+};
+
 // Everything the kernels need that is uniform over a launch.
 struct sfw_launch {
   // scoring parameters
@@ -250,7 +256,24 @@ struct sfw_launch {
   sfw_pose_frame *stop_tail;
   int32_t *stop_steps, *stop_hit;
   double *stop_points;
+  // sfw_set_path (path_on: 0 off — nothing below is read and no kernel is added): the path term behind K1c / the stop check
+  // (sfw_kernels.hip sfw_path_*_kernel).  path_seg: path_n_seg segment records, read wave-uniformly; path_D: [step][rstep_stride]
+  // squared distances of the chunk's poses, laid out like fcode; path_p: per sample, by GLOBAL sample index, the term or the
+  // sample's sentinel.  (Appended: no other field's offset moves.)
+  // path_slices: > 1 — the distance kernel's grid z: slices of 64 segments that meet by an integer atomicMin (a long path
+  // under a launch that leaves the GPU idle); 0 or 1: one thread walks all segments of its pose
+  int32_t path_on, path_n_seg, path_slices, path_pad;
+  const sfw_path_seg *path_seg;
+  double *path_D;
+  double *path_p;
 };
+
+// cost + w * p behind the five-term sum: one product and one sum, each rounded once (the add kernel, the re-score kernel and
+// the ensemble's aggregations share the statement)
+__device__ __forceinline__ double sfw_cost_add_path(double cost, double w_path, double p) {
+#pragma clang fp contract(off)
+  return cost + w_path * p;
+}
 
 // Writers of the captured cost terms (no-ops when terms is null): term k of sample t, the three pedestrian-free terms, or one
 // sentinel in all five
@@ -288,6 +311,9 @@ hipError_t sfw_launch_rollout(const sfw_launch &L, hipStream_t stream);  // = po
 // table), so the second can run beside it on another stream.
 hipError_t sfw_launch_rollout_poses(const sfw_launch &L, hipStream_t stream);
 hipError_t sfw_launch_rollout_costmap(const sfw_launch &L, hipStream_t stream);
+// sfw_set_path: costs[t] = costs[t] + w * p[t] for t in [begin, begin + count) where neither is a sentinel, behind K2 and in
+// front of the selection (sfw_kernels.hip sfw_path_add_kernel; the distance and scan kernels ride with sfw_launch_rollout_costmap)
+hipError_t sfw_launch_path_add(double *costs, const double *p, double w, int64_t begin, int64_t count, hipStream_t stream);
 // The clearance map of a costmap (sfw_launch.clear): clear[c] = 1 iff the (2 r + 1)^2 window around cell c is on the map and
 // all 0.  Two separable passes, rows into tmp (size_x * size_y bytes), then columns into clear.
 hipError_t sfw_launch_clearance(const uint8_t *cells, uint32_t size_x, uint32_t size_y, int r, uint8_t *tmp, uint8_t *clear,
@@ -352,24 +378,32 @@ hipError_t sfw_launch_argmin(const double *costs, const double *linvels, const d
 int64_t sfw_rescore_blocks(int64_t T, int K);
 hipError_t sfw_launch_rescore(const double *terms, int64_t T, const sfw_weights *w, int K, const double *linvels,
                               const double *angvels, int32_t nw, int64_t index_base, sfw_sel *partials, double *costs,
-                              sfw_sel *sel_host, hipStream_t stream, bool list = false);
+                              sfw_sel *sel_host, hipStream_t stream, bool list = false, const double *path_p = nullptr,
+                              const double *path_w = nullptr);
+// (path_p, nullable: the path term of the launch, sfw_launch.path_p; path_w: K path weights in device memory, read
+// wave-uniformly — cost + path_w[k] * p behind the five-term sum where the cost is not a sentinel.  Null: the five terms alone.)
 // sfw_ensemble_*: M members' captured terms (terms: device table of M pointers to SoA [5][T]; probs: M doubles, MEAN only —
 // both read wave-uniformly) -> costs[T], rejected[T] (pinned or device) and the record at sel_host (pinned).  partials:
 // sfw_argmin_partials(T) records.
 hipError_t sfw_launch_ensemble(const double *const *terms, const double *probs, int M, int64_t T, int mode, const sfw_weights &w,
                                const double *linvels, const double *angvels, int32_t nw, double *costs, int32_t *rejected,
-                               sfw_sel *partials, sfw_sel *sel_host, hipStream_t stream);
+                               sfw_sel *partials, sfw_sel *sel_host, hipStream_t stream, const double *path_p = nullptr,
+                               double path_w = 0.0);
+// (path_p, nullable, here and in the two forms below: member 0's path term — path_w * p[t] is added behind the aggregated
+// five-term cost of a sample that is not rejected, in front of the selection.  Null: the five terms alone.)
 // ... over a LIST the members staged (sfw_launch.list): linvels / angvels hold one value per sample (the first knot row), the
 // selection is the list's, no sample is skipped.  costs_dev (nullable): a second, device-resident copy of the cost vector.
 hipError_t sfw_launch_ensemble_list(const double *const *terms, const double *probs, int M, int64_t T, int mode,
                                     const sfw_weights &w, const double *linvels, const double *angvels, double *costs,
-                                    double *costs_dev, int32_t *rejected, sfw_sel *partials, sfw_sel *sel_host, hipStream_t stream);
+                                    double *costs_dev, int32_t *rejected, sfw_sel *partials, sfw_sel *sel_host, hipStream_t stream,
+                                    const double *path_p = nullptr, double path_w = 0.0);
 // ... under a risk (sfw_ensemble_set_risk): the grid's first stage (list false: nw, no costs_dev) or the list's, then the same
 // second stage.  thr = contact_mass * P, the host's product.
 hipError_t sfw_launch_ensemble_risk(const double *const *terms, const double *probs, int M, int64_t T, int mode,
                                     const sfw_weights &w, double tail_mass, double contact_mass, double thr, bool list,
                                     const double *linvels, const double *angvels, int32_t nw, double *costs, double *costs_dev,
-                                    int32_t *rejected, sfw_sel *partials, sfw_sel *sel_host, hipStream_t stream);
+                                    int32_t *rejected, sfw_sel *partials, sfw_sel *sel_host, hipStream_t stream,
+                                    const double *path_p = nullptr, double path_w = 0.0);
 // sfw_grid_blend: the cost vector (+ bias, nullable) of a launch over T samples -> softmin weights for L temperatures, their
 // sums and the weighted mean of the K knot rows (list: linvels / vy (nullable) / angvels hold K rows of T values, knot-major;
 // else a grid of T / nw x nw samples, K == 1).  Three launches: `mins` (sfw_blend_min_blocks(T) records), `partials`

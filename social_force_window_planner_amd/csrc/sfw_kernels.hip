@@ -670,6 +670,101 @@ __global__ void __launch_bounds__(256) sfw_stop_finish_kernel(const sfw_launch L
   sfw_put_terms_sentinel(L.terms, L.terms_T, t, SFW_COST_INVALID);
 }
 
+// ---- the path term (sfw_set_path, sfw_launch.path_on): behind K1c, the fused small K1 or the stop check's tail ----
+// Three kernels in the shape of K1b / K1c; every K1 organisation leaves the same ptab and status, so the term is the same
+// whichever ran in front of it.  The definition, operation by operation, is the header's; no contraction here (this text
+// sits under K1's pragma), so every product and sum is rounded once, as in social_force_window_planner_amd/path.py.
+// (1) Distance, one thread per (step, sample) like K1b: the squared distance of the pose before the step — the Trajectory
+// point — to the nearest segment.  The segment index is wave-uniform, so a record is five scalar loads (address_space(4),
+// as the re-score kernel reads its weights) that every lane of the wave shares: per segment 2 subtractions, 6 products,
+// 4 sums / differences, a clamp and a minimum on the vector unit, no LDS, no divergence but for the samples that left.
+// the running minimum against one record: the header's five lines, then `d < m ? d : m`
+__device__ __forceinline__ double path_seg_min(double m, double px, double py, const sfw_path_seg r) {
+  const double rx = px - r.ax, ry = py - r.ay;
+  const double u = (rx * r.ex + ry * r.ey) * r.inv;
+  const double tc = u < 0.0 ? 0.0 : (u > 1.0 ? 1.0 : u);
+  const double qx = rx - tc * r.ex, qy = ry - tc * r.ey;
+  const double d = qx * qx + qy * qy;
+  return d < m ? d : m;
+}
+// record k through the constant address space: five scalar loads, member by member (a struct copy does not cross address spaces)
+typedef const __attribute__((address_space(4))) sfw_path_seg *path_seg_ptr;
+__device__ __forceinline__ sfw_path_seg path_seg_load(path_seg_ptr seg, int k) {
+  return sfw_path_seg{seg[k].ax, seg[k].ay, seg[k].ex, seg[k].ey, seg[k].inv};
+}
+// With more than one slice (sfw_launch.path_slices, gridDim.z: a long path under a launch that leaves the GPU idle — 45 samples
+// walked 1023 segments in 82.3 us, more than the rest of a control cycle: profiles/r25_path_term.txt) block z walks segments
+// [z, z + 1) * PATH_SLICE_SEGS and the slices meet in the table by an integer atomicMin on the bit pattern: non-negative doubles order as uint64, a NaN lies
+// above +inf and so never becomes the minimum — the same rule as `d < m ? d : m`, the same bits in any order.  The table
+// holds +inf then (sfw_path_fill_kernel, in front).
+constexpr int PATH_SLICE_SEGS = 64;
+__global__ void __launch_bounds__(256) sfw_path_fill_kernel(const sfw_launch L) {
+  const int64_t local = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (local >= L.chunk_count) return;
+  L.path_D[static_cast<int64_t>(blockIdx.y) * L.rstep_stride + local] = INFINITY;
+}
+__global__ void __launch_bounds__(256) sfw_path_dist_kernel(const sfw_launch L, const int step0) {
+  typedef path_seg_ptr seg_ptr;
+  const int64_t local = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (local >= L.chunk_count) return;
+  if (L.status[L.chunk_begin + local] != SFW_ST_VALID) return;  // (the scan writes such a sample's sentinel)
+  const int64_t step = static_cast<int64_t>(step0) + blockIdx.y;
+  const sfw_unit pos = step == 0 ? sfw_unit{L.rs.x, L.rs.y} : L.ptab[(step - 1) * L.row_units + local];
+  const seg_ptr seg = (seg_ptr)L.path_seg;
+  const bool sliced = gridDim.z > 1;
+  const int n = sliced ? min(L.path_n_seg, (static_cast<int>(blockIdx.z) + 1) * PATH_SLICE_SEGS) : L.path_n_seg;
+  double m = INFINITY;
+  // four records per round, so that their scalar loads are in flight together (a minimum: the order does not matter)
+  int k = sliced ? static_cast<int>(blockIdx.z) * PATH_SLICE_SEGS : 0;
+  for (; k + 4 <= n; k += 4) {
+    const sfw_path_seg r0 = path_seg_load(seg, k), r1 = path_seg_load(seg, k + 1), r2 = path_seg_load(seg, k + 2),
+                       r3 = path_seg_load(seg, k + 3);
+    m = path_seg_min(m, pos.a, pos.b, r0);
+    m = path_seg_min(m, pos.a, pos.b, r1);
+    m = path_seg_min(m, pos.a, pos.b, r2);
+    m = path_seg_min(m, pos.a, pos.b, r3);
+  }
+  for (; k < n; ++k) m = path_seg_min(m, pos.a, pos.b, path_seg_load(seg, k));
+  double *const out = L.path_D + step * L.rstep_stride + local;
+  if (sliced) atomicMin(reinterpret_cast<unsigned long long *>(out), static_cast<unsigned long long>(__double_as_longlong(m)));
+  else *out = m;
+}
+// (2) Scan, one thread per sample: the mean in step order, eight loads in flight as in K1c; a sample that is not VALID here
+// gets its sentinel.  (0.0 + D_0 is D_0 bit for bit: D is a sum of squares, never -0.)
+__global__ void __launch_bounds__(256) sfw_path_scan_kernel(const sfw_launch L) {
+  const int64_t local = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (local >= L.chunk_count) return;
+  const int64_t t = L.chunk_begin + local;
+  const int32_t st = L.status[t];
+  if (st != SFW_ST_VALID) {
+    L.path_p[t] = st == SFW_ST_SKIPPED ? SFW_COST_SKIPPED : SFW_COST_INVALID;
+    return;
+  }
+  const int S = L.S;
+  double sum = 0.0;
+  for (int base = 0; base < S; base += 8) {
+    double v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = (base + j < S) ? L.path_D[static_cast<int64_t>(base + j) * L.rstep_stride + local] : 0.0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      if (base + j < S) sum = sum + v[j];
+  }
+  L.path_p[t] = sum / S;
+}
+#ifndef SFW_STRICT_BUILD  // (costs are doubles in every precision mode: the kernel exists once)
+// (3) Add, behind K2 (or the no-social kernel, or scan_finish for A == 0) and in front of the selection's first stage, which
+// also mirrors the costs to the host: cost + w p where the cost is not a sentinel.  p < 0: the sample's sentinel (rejected in
+// front of the path pass); cost == SFW_COST_INVALID: rejected by contact behind it — that sample keeps its p.
+__global__ void __launch_bounds__(256) sfw_path_add_kernel(double *costs, const double *p, double w, int64_t begin, int64_t count) {
+  const int64_t local = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (local >= count) return;
+  const int64_t t = begin + local;
+  const double c = costs[t], pt = p[t];
+  if (pt >= 0.0 && c != SFW_COST_INVALID) costs[t] = sfw_cost_add_path(c, w, pt);
+}
+#endif
+
 // One footprint edge of a pose: the largest cell value on edge e (vertex e -> vertex e+1, the last edge closes the
 // polygon), or FOOT_OFFMAP when one of its vertices is off the map.  The same expressions as footprint_cost.
 constexpr int FOOT_OFFMAP = 300;
@@ -2837,9 +2932,12 @@ struct sfw_rescore_of_list {
 template <typename SAMPLES>
 __global__ void __launch_bounds__(ARGMIN_BLOCK)
 sfw_rescore_first(const double *terms, int64_t T, const sfw_weights *w, int K, const double *linvels, const double *angvels,
-                  int nw, int64_t index_base, sfw_sel *partials, double *costs, sfw_sel *sel_host) {
+                  int nw, int64_t index_base, sfw_sel *partials, double *costs, sfw_sel *sel_host, const double *path_p,
+                  const double *path_w) {
   typedef const __attribute__((address_space(4))) sfw_weights *weights_ptr;
+  typedef const __attribute__((address_space(4))) double *path_w_ptr;
   const weights_ptr ws = (weights_ptr)w;
+  const path_w_ptr pws = (path_w_ptr)path_w;  // (sfw_set_path: one path weight per vector; read only when path_p is there)
   const int k0 = static_cast<int>(blockIdx.y) * RESCORE_KT;
   sfw_sel best[RESCORE_KT];
 #pragma unroll
@@ -2850,12 +2948,14 @@ sfw_rescore_first(const double *terms, int64_t T, const sfw_weights *w, int K, c
     const double ang = terms[SFW_TERM_ANGLE * T + t], cm = terms[SFW_TERM_COSTMAP * T + t];
     const double sw = terms[SFW_TERM_SOCIAL * T + t];
     const bool sentinel = d < 0.0;
+    const double pt = path_p ? path_p[t] : 0.0;
     double c[RESCORE_KT];
 #pragma unroll
     for (int j = 0; j < RESCORE_KT; ++j) {
       const int k = min(k0 + j, K - 1);  // (a partial last tile repeats its last vector; nothing of it is stored)
       const double base = sfw_cost_add_costmap(sfw_cost_base(ws[k].vel, vel, ws[k].distance, d, ws[k].angle, ang), ws[k].costmap, cm);
       c[j] = sentinel ? d : sfw_cost_add_social(base, ws[k].social, sw);
+      if (path_p && !sentinel) c[j] = sfw_cost_add_path(c[j], pws[k], pt);  // (the add kernel's statement)
       sel_consider<SAMPLES::list>(best[j], c[j], linvels, angvels, nw, t, index_base);
     }
     if (costs) {  // (weight-major)
@@ -2897,7 +2997,7 @@ __device__ __forceinline__ double sfw_ensemble_mean_step(double acc, double p, d
 __global__ void __launch_bounds__(ARGMIN_BLOCK)
 sfw_ensemble_stage1(const double *const *terms, const double *probs, int M, int64_t T, int mode, sfw_weights w,
                     const double *linvels, const double *angvels, int nw, double *costs, int32_t *rejected,
-                    sfw_sel *partials, sfw_sel *sel_host) {
+                    sfw_sel *partials, sfw_sel *sel_host, const double *path_p, double path_w) {
   typedef const double *member_terms;
   typedef const __attribute__((address_space(4))) member_terms *terms_ptr;
   typedef const __attribute__((address_space(4))) double *probs_ptr;
@@ -2929,6 +3029,7 @@ sfw_ensemble_stage1(const double *const *terms, const double *probs, int M, int6
       const double vel = t0[SFW_TERM_VEL * T + t], ang = t0[SFW_TERM_ANGLE * T + t], cm = t0[SFW_TERM_COSTMAP * T + t];
       c = sfw_cost_add_social(sfw_cost_add_costmap(sfw_cost_base(w.vel, vel, w.distance, d0, w.angle, ang), w.costmap, cm),
                               w.social, acc);
+      if (path_p) c = sfw_cost_add_path(c, path_w, path_p[t]);  // (sfw_set_path: member 0's p, the same in every member)
     }
     costs[t] = c;
     rejected[t] = rej;
@@ -2955,7 +3056,7 @@ __global__ void __launch_bounds__(ARGMIN_BLOCK) sfw_ensemble_stage2(const sfw_se
 __global__ void __launch_bounds__(ARGMIN_BLOCK)
 sfw_ens_list_first(const double *const *terms, const double *probs, int M, int64_t T, int mode, sfw_weights w,
                    const double *linvels, const double *angvels, double *costs, double *costs_dev, int32_t *rejected,
-                   sfw_sel *partials, sfw_sel *sel_host) {
+                   sfw_sel *partials, sfw_sel *sel_host, const double *path_p, double path_w) {
   typedef const double *member_terms;
   typedef const __attribute__((address_space(4))) member_terms *terms_ptr;
   typedef const __attribute__((address_space(4))) double *probs_ptr;
@@ -2982,6 +3083,7 @@ sfw_ens_list_first(const double *const *terms, const double *probs, int M, int64
       const double vel = t0[SFW_TERM_VEL * T + t], ang = t0[SFW_TERM_ANGLE * T + t], cm = t0[SFW_TERM_COSTMAP * T + t];
       c = sfw_cost_add_social(sfw_cost_add_costmap(sfw_cost_base(w.vel, vel, w.distance, d0, w.angle, ang), w.costmap, cm),
                               w.social, acc);
+      if (path_p) c = sfw_cost_add_path(c, path_w, path_p[t]);  // (sfw_set_path: member 0's p, the same in every member)
     }
     costs[t] = c;
     if (costs_dev) costs_dev[t] = c;
@@ -3008,7 +3110,8 @@ template <bool LIST>
 __device__ __forceinline__ void sfw_ens_risk_first(const double *const *terms, const double *probs, int M, int64_t T, int mode,
                                                    const sfw_weights &w, double tail_mass, double contact_mass, double thr,
                                                    const double *linvels, const double *angvels, int nw, double *costs,
-                                                   double *costs_dev, int32_t *rejected, sfw_sel *partials, sfw_sel *sel_host) {
+                                                   double *costs_dev, int32_t *rejected, sfw_sel *partials, sfw_sel *sel_host,
+                                                   const double *path_p, double path_w) {
 #pragma clang fp contract(off)
   typedef const double *member_terms;
   typedef const __attribute__((address_space(4))) member_terms *terms_ptr;
@@ -3070,6 +3173,8 @@ __device__ __forceinline__ void sfw_ens_risk_first(const double *const *terms, c
       const double cm = t0[SFW_TERM_COSTMAP * T + t];
       c = sfw_cost_add_social(sfw_cost_add_costmap(sfw_cost_base(w.vel, vel, w.distance, d0, w.angle, ang), w.costmap, cm),
                               w.social, A);
+      // (sfw_set_path: member 0's p — a sample it rejects by contact has one all the same: p does not see the pedestrians)
+      if (path_p) c = sfw_cost_add_path(c, path_w, path_p[t]);
     }
     costs[t] = c;
     if (LIST && costs_dev) costs_dev[t] = c;
@@ -3085,16 +3190,16 @@ __device__ __forceinline__ void sfw_ens_risk_first(const double *const *terms, c
 __global__ void __launch_bounds__(ARGMIN_BLOCK)
 sfw_ens_risk_grid(const double *const *terms, const double *probs, int M, int64_t T, int mode, sfw_weights w, double tail_mass,
                   double contact_mass, double thr, const double *linvels, const double *angvels, int nw, double *costs,
-                  int32_t *rejected, sfw_sel *partials, sfw_sel *sel_host) {
+                  int32_t *rejected, sfw_sel *partials, sfw_sel *sel_host, const double *path_p, double path_w) {
   sfw_ens_risk_first<false>(terms, probs, M, T, mode, w, tail_mass, contact_mass, thr, linvels, angvels, nw, costs, nullptr, rejected,
-                            partials, sel_host);
+                            partials, sel_host, path_p, path_w);
 }
 __global__ void __launch_bounds__(ARGMIN_BLOCK)
 sfw_ens_risk_list(const double *const *terms, const double *probs, int M, int64_t T, int mode, sfw_weights w, double tail_mass,
                   double contact_mass, double thr, const double *linvels, const double *angvels, double *costs, double *costs_dev,
-                  int32_t *rejected, sfw_sel *partials, sfw_sel *sel_host) {
+                  int32_t *rejected, sfw_sel *partials, sfw_sel *sel_host, const double *path_p, double path_w) {
   sfw_ens_risk_first<true>(terms, probs, M, T, mode, w, tail_mass, contact_mass, thr, linvels, angvels, 1, costs, costs_dev, rejected,
-                           partials, sel_host);
+                           partials, sel_host, path_p, path_w);
 }
 #endif  // SFW_STRICT_BUILD
 
@@ -3873,11 +3978,33 @@ static hipError_t sfw_launch_stop_tail(const sfw_launch &L, hipStream_t stream) 
   return hipGetLastError();
 }
 
-// K1b + K1c (footprint checks, costmap scan); nothing to do after the fused K1 — but for the stop check's tail, which
-// follows either.
+// The path term's distance and scan kernels (sfw_launch.path_on) behind whatever left the samples' final status and ptab
+static hipError_t sfw_launch_path_term(const sfw_launch &L, hipStream_t stream) {
+  const int block = 256;
+  const unsigned grid = static_cast<unsigned>((L.chunk_count + block - 1) / block);
+  // slices (decided per launch by sfw_capi.hip fill_launch; here only where S fits one launch's y dimension): the table
+  // starts at +inf
+  const unsigned slices = (L.path_slices > 1 && L.S <= 65535) ? static_cast<unsigned>(L.path_slices) : 1u;
+  if (slices > 1) hipLaunchKernelGGL(sfw_path_fill_kernel, dim3(grid, static_cast<unsigned>(L.S)), dim3(block), 0, stream, L);
+  for (int step0 = 0; step0 < L.S; step0 += 65535) {  // (the limit of a grid's y dimension, as for K1b)
+    const unsigned steps = static_cast<unsigned>(L.S - step0 < 65535 ? L.S - step0 : 65535);
+    hipLaunchKernelGGL(sfw_path_dist_kernel, dim3(grid, steps, slices), dim3(block), 0, stream, L, step0);
+  }
+  hipLaunchKernelGGL(sfw_path_scan_kernel, dim3(grid), dim3(block), 0, stream, L);
+  return hipGetLastError();
+}
+// ... behind the stop check's tail when both are on
+static hipError_t sfw_launch_behind_costmap(const sfw_launch &L, hipStream_t stream) {
+  hipError_t e = L.stop_on ? sfw_launch_stop_tail(L, stream) : hipGetLastError();
+  if (e == hipSuccess && L.path_on) e = sfw_launch_path_term(L, stream);
+  return e;
+}
+
+// K1b + K1c (footprint checks, costmap scan); nothing to do after the fused K1 — but for the stop check's tail and the path
+// term, which follow either.
 hipError_t sfw_launch_rollout_costmap(const sfw_launch &L, hipStream_t stream) {
   if (L.chunk_count <= 0) return hipSuccess;
-  if (sfw_rollout_is_fused(L)) return L.stop_on ? sfw_launch_stop_tail(L, stream) : hipSuccess;
+  if (sfw_rollout_is_fused(L)) return (L.stop_on || L.path_on) ? sfw_launch_behind_costmap(L, stream) : hipSuccess;
   {
     const int block = 256;
     const unsigned grid = static_cast<unsigned>((L.chunk_count + block - 1) / block);
@@ -3891,11 +4018,18 @@ hipError_t sfw_launch_rollout_costmap(const sfw_launch &L, hipStream_t stream) {
     const unsigned grid = static_cast<unsigned>((L.chunk_count + block - 1) / block);
     hipLaunchKernelGGL(sfw_costmap_scan_kernel, dim3(grid), dim3(block), 0, stream, L);
   }
-  if (L.stop_on) return sfw_launch_stop_tail(L, stream);
+  if (L.stop_on || L.path_on) return sfw_launch_behind_costmap(L, stream);
   return hipGetLastError();
 }
 
 #ifndef SFW_STRICT_BUILD
+hipError_t sfw_launch_path_add(double *costs, const double *p, double w, int64_t begin, int64_t count, hipStream_t stream) {
+  if (count <= 0) return hipSuccess;
+  const int block = 256;
+  hipLaunchKernelGGL(sfw_path_add_kernel, dim3(static_cast<unsigned>((count + block - 1) / block)), dim3(block), 0, stream, costs, p, w,
+                     begin, count);
+  return hipGetLastError();
+}
 hipError_t sfw_launch_clearance(const uint8_t *cells, uint32_t size_x, uint32_t size_y, int r, uint8_t *tmp, uint8_t *clear,
                                 hipStream_t stream) {
   // (size_y rides in the grid's y dimension: 65 535 rows per launch, a map of up to 2^21 rows in slices)
@@ -4147,13 +4281,13 @@ int64_t sfw_rescore_blocks(int64_t T, int K) {
 }
 hipError_t sfw_launch_rescore(const double *terms, int64_t T, const sfw_weights *w, int K, const double *linvels,
                               const double *angvels, int32_t nw, int64_t index_base, sfw_sel *partials, double *costs,
-                              sfw_sel *sel_host, hipStream_t stream, bool list) {
+                              sfw_sel *sel_host, hipStream_t stream, bool list, const double *path_p, const double *path_w) {
   if (K < 1 || T < 1) return hipErrorInvalidValue;
   const int64_t blocks = sfw_rescore_blocks(T, K);
   const dim3 grid(static_cast<unsigned>(blocks), static_cast<unsigned>((K + RESCORE_KT - 1) / RESCORE_KT));
   const auto stage1 = list ? sfw_rescore_first<sfw_rescore_of_list> : sfw_rescore_first<sfw_rescore_stage1>;
   hipLaunchKernelGGL(stage1, grid, dim3(ARGMIN_BLOCK), 0, stream, terms, T, w, K, linvels, angvels, nw, index_base,
-                     partials, costs, blocks == 1 ? sel_host : static_cast<sfw_sel *>(nullptr));
+                     partials, costs, blocks == 1 ? sel_host : static_cast<sfw_sel *>(nullptr), path_p, path_w);
   if (blocks > 1)
     hipLaunchKernelGGL(sfw_rescore_stage2, dim3(static_cast<unsigned>(K)), dim3(ARGMIN_BLOCK), 0, stream, partials,
                        static_cast<int>(blocks), sel_host);
@@ -4162,11 +4296,12 @@ hipError_t sfw_launch_rescore(const double *terms, int64_t T, const sfw_weights 
 
 hipError_t sfw_launch_ensemble(const double *const *terms, const double *probs, int M, int64_t T, int mode, const sfw_weights &w,
                                const double *linvels, const double *angvels, int32_t nw, double *costs, int32_t *rejected,
-                               sfw_sel *partials, sfw_sel *sel_host, hipStream_t stream) {
+                               sfw_sel *partials, sfw_sel *sel_host, hipStream_t stream, const double *path_p, double path_w) {
   if (M < 1 || T < 1) return hipErrorInvalidValue;
   const int blocks = static_cast<int>(sfw_argmin_partials(T));
   hipLaunchKernelGGL(sfw_ensemble_stage1, dim3(static_cast<unsigned>(blocks)), dim3(ARGMIN_BLOCK), 0, stream, terms, probs, M, T,
-                     mode, w, linvels, angvels, nw, costs, rejected, partials, blocks == 1 ? sel_host : static_cast<sfw_sel *>(nullptr));
+                     mode, w, linvels, angvels, nw, costs, rejected, partials, blocks == 1 ? sel_host : static_cast<sfw_sel *>(nullptr),
+                     path_p, path_w);
   if (blocks > 1)
     hipLaunchKernelGGL(sfw_ensemble_stage2, dim3(1), dim3(ARGMIN_BLOCK), 0, stream, static_cast<const sfw_sel *>(partials), blocks,
                        sel_host);
@@ -4176,12 +4311,13 @@ hipError_t sfw_launch_ensemble(const double *const *terms, const double *probs, 
 #ifndef SFW_STRICT_BUILD
 hipError_t sfw_launch_ensemble_list(const double *const *terms, const double *probs, int M, int64_t T, int mode,
                                     const sfw_weights &w, const double *linvels, const double *angvels, double *costs,
-                                    double *costs_dev, int32_t *rejected, sfw_sel *partials, sfw_sel *sel_host, hipStream_t stream) {
+                                    double *costs_dev, int32_t *rejected, sfw_sel *partials, sfw_sel *sel_host, hipStream_t stream,
+                                    const double *path_p, double path_w) {
   if (M < 1 || T < 1) return hipErrorInvalidValue;
   const int blocks = static_cast<int>(sfw_argmin_partials(T));
   hipLaunchKernelGGL(sfw_ens_list_first, dim3(static_cast<unsigned>(blocks)), dim3(ARGMIN_BLOCK), 0, stream, terms, probs, M, T,
                      mode, w, linvels, angvels, costs, costs_dev, rejected, partials,
-                     blocks == 1 ? sel_host : static_cast<sfw_sel *>(nullptr));
+                     blocks == 1 ? sel_host : static_cast<sfw_sel *>(nullptr), path_p, path_w);
   if (blocks > 1)
     hipLaunchKernelGGL(sfw_ensemble_stage2, dim3(1), dim3(ARGMIN_BLOCK), 0, stream, static_cast<const sfw_sel *>(partials), blocks,
                        sel_host);
@@ -4190,16 +4326,17 @@ hipError_t sfw_launch_ensemble_list(const double *const *terms, const double *pr
 hipError_t sfw_launch_ensemble_risk(const double *const *terms, const double *probs, int M, int64_t T, int mode,
                                     const sfw_weights &w, double tail_mass, double contact_mass, double thr, bool list,
                                     const double *linvels, const double *angvels, int32_t nw, double *costs, double *costs_dev,
-                                    int32_t *rejected, sfw_sel *partials, sfw_sel *sel_host, hipStream_t stream) {
+                                    int32_t *rejected, sfw_sel *partials, sfw_sel *sel_host, hipStream_t stream,
+                                    const double *path_p, double path_w) {
   if (M < 1 || M > SFW_ENSEMBLE_MAX_M || T < 1) return hipErrorInvalidValue;  // (the accepting members are a 64-bit mask)
   const int blocks = static_cast<int>(sfw_argmin_partials(T));
   sfw_sel *const rec = blocks == 1 ? sel_host : static_cast<sfw_sel *>(nullptr);
   if (list)
     hipLaunchKernelGGL(sfw_ens_risk_list, dim3(static_cast<unsigned>(blocks)), dim3(ARGMIN_BLOCK), 0, stream, terms, probs, M, T, mode,
-                       w, tail_mass, contact_mass, thr, linvels, angvels, costs, costs_dev, rejected, partials, rec);
+                       w, tail_mass, contact_mass, thr, linvels, angvels, costs, costs_dev, rejected, partials, rec, path_p, path_w);
   else
     hipLaunchKernelGGL(sfw_ens_risk_grid, dim3(static_cast<unsigned>(blocks)), dim3(ARGMIN_BLOCK), 0, stream, terms, probs, M, T, mode,
-                       w, tail_mass, contact_mass, thr, linvels, angvels, nw, costs, rejected, partials, rec);
+                       w, tail_mass, contact_mass, thr, linvels, angvels, nw, costs, rejected, partials, rec, path_p, path_w);
   if (blocks > 1)
     hipLaunchKernelGGL(sfw_ensemble_stage2, dim3(1), dim3(ARGMIN_BLOCK), 0, stream, static_cast<const sfw_sel *>(partials), blocks,
                        sel_host);
@@ -4311,6 +4448,7 @@ bool sfw_cycle_applies(const sfw_launch &L) {
   if (const char *e = std::getenv("SFW_CYCLE_FUSED"))
     if (e[0] == '0') return false;
   if (L.stop_on) return false;  // (sfw_set_stop_check: the tail is not part of cycle_block)
+  if (L.path_on) return false;  // (sfw_set_path: neither is the path term)
   if (L.phase != SFW_PHASE_WHOLE || L.resume || L.chunk_begin != 0 || L.chunk_count <= 0 || L.chunk_count > CYCLE_MAX_SAMPLES) return false;
   if (L.S > K1_SMALL_MAX_STEPS || (L.sel_out && !L.cycle_counter)) return false;
   const bool social = L.A > 0 && !(L.A == 1 && L.O == 0 && L.NG == 0);

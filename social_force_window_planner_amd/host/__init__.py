@@ -60,6 +60,10 @@ def lib():
         L.sfwh_set_marker_capture.restype = None
         L.sfwh_set_stop_check.argtypes = [vp, C.c_int32, C.c_int32]
         L.sfwh_set_stop_check.restype = None
+        L.sfwh_set_path_term.argtypes = [vp, C.c_double, C.c_int32]
+        L.sfwh_set_path_term.restype = None
+        L.sfwh_path_term.argtypes = [vp, vp, C.c_int32, C.POINTER(C.c_double)]
+        L.sfwh_path_term.restype = C.c_int32
         L.sfwh_get_yaw.argtypes = [C.c_double] * 4
         L.sfwh_get_yaw.restype = C.c_double
         _lib = L
@@ -130,6 +134,21 @@ class HostPlanner:
     def set_stop_check(self, on=True, max_steps=4096):
         """SFWPlanner::setStopCheck: reject samples that cannot brake to a stop under the controller's own acceleration limits."""
         lib().sfwh_set_stop_check(self._h, 1 if on else 0, max_steps)
+
+    def set_path_term(self, weight, max_points=1024):
+        """SFWPlanner::setPathTerm: the path term over the global plan from the way-point behind the current one on; a weight of
+        exactly 0 means off."""
+        lib().sfwh_set_path_term(self._h, float(weight), max_points)
+
+    def path_term(self):
+        """(xy[n, 2], weight) the device handle holds after the last scoring cycle, or None while it has no path."""
+        w = C.c_double()
+        n = lib().sfwh_path_term(self._h, None, 0, C.byref(w))
+        if n == 0:
+            return None
+        xy = np.zeros((n, 2), dtype=np.float64)
+        lib().sfwh_path_term(self._h, xy.ctypes.data, n, C.byref(w))
+        return xy, w.value
 
     def set_devices(self, devices, host_reduce=False):
         """SFWPlanner::setDevices: grid rows over several devices from this process (before the first scoring call)."""

@@ -4,6 +4,8 @@
 
 #include <tf2/utils.h>
 
+#include <cmath>
+
 #include "nav2_core/exceptions.hpp"
 #include "nav2_util/node_utils.hpp"
 #include "pluginlib/class_list_macros.hpp"
@@ -259,6 +261,15 @@ geometry_msgs::msg::TwistStamped SFWPlannerNode::computeVelocityCommands(const g
     stop_steps = clamped;
   }
   sfw_planner_->setStopCheck(param(node_.get(), name_ + ".stop_check", false), stop_steps);
+  // not in the reference's yaml either: the path term it leaves in a comment (SFWPlanner::setPathTerm), weight 0.0 = off.  A
+  // weight that is not finite is not handed down (sfw_set_path would refuse it and the cycle would throw): off, with a
+  // warning; setPathTerm clamps the point count itself
+  double path_weight = param(node_.get(), name_ + ".path_weight", 0.0);
+  if (!std::isfinite(path_weight)) {
+    RCLCPP_WARN(node_->get_logger(), "%s.path_weight is not finite: the path term stays off", name_.c_str());
+    path_weight = 0.0;
+  }
+  sfw_planner_->setPathTerm(path_weight, param(node_.get(), name_ + ".path_max_points", static_cast<int>(SFW_PATH_MAX_POINTS)));
   sfw_planner_->updatePlan(local);                   // ref :277
   Twist cmd;
   Twist in_speed;

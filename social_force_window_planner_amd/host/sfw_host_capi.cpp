@@ -219,6 +219,20 @@ int64_t sfwh_markers(void *hv, float *rgba, int32_t *counts, double *z0, int64_t
 void sfwh_set_stop_check(void *hv, int32_t on, int32_t max_steps) {
   static_cast<HostHandle *>(hv)->planner->setStopCheck(on != 0, max_steps);
 }
+// SFWPlanner::setPathTerm / pathTerm
+void sfwh_set_path_term(void *hv, double weight, int32_t max_points) {
+  static_cast<HostHandle *>(hv)->planner->setPathTerm(weight, max_points);
+}
+// the points the device handle holds (up to cap of them into xy) and the weight; returns their number, 0 while it has no path
+int32_t sfwh_path_term(void *hv, double *xy, int32_t cap, double *weight) {
+  std::vector<double> pts;
+  double w = 0.0;
+  if (!static_cast<HostHandle *>(hv)->planner->pathTerm(pts, w)) return 0;
+  const int32_t n = static_cast<int32_t>(pts.size() / 2);
+  if (xy && cap > 0) std::memcpy(xy, pts.data(), sizeof(double) * 2 * static_cast<size_t>(n < cap ? n : cap));
+  if (weight) *weight = w;
+  return n;
+}
 void sfwh_set_marker_capture(void *hv, int32_t on) { static_cast<HostHandle *>(hv)->planner->setMarkerCapture(on != 0); }
 double sfwh_get_yaw(double x, double y, double z, double w) { return getYaw(Quaternion{x, y, z, w}); }
 }

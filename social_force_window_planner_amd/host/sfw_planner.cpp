@@ -5,6 +5,7 @@
 // executed by the HIP kernels behind include/sfw_hip.h.
 #include "sfw_planner.hpp"
 
+#include <algorithm>
 #include <cmath>
 #include <stdexcept>
 
@@ -152,6 +153,20 @@ void SFWPlanner::setStopCheck(bool on, int max_steps) {
   stop_check_ = on;
   stop_max_steps_ = max_steps;
 }
+void SFWPlanner::setPathTerm(double weight, int max_points) {
+  std::lock_guard<std::mutex> l(configuration_mutex_);
+  path_weight_ = weight;
+  path_max_points_ = max_points < 1 ? 1 : (max_points > SFW_PATH_MAX_POINTS ? SFW_PATH_MAX_POINTS : max_points);
+}
+bool SFWPlanner::pathTerm(std::vector<double> &xy, double &weight) const {
+  xy.clear();
+  weight = 0.0;
+  if (!handle_) return false;
+  int32_t n = 0, on = 0;
+  if (sfw_get_path(handle_, nullptr, 0, &n, &weight, &on) != SFW_OK || !on) return false;
+  xy.resize(2 * static_cast<size_t>(n));
+  return sfw_get_path(handle_, xy.data(), n, nullptr, nullptr, nullptr) == SFW_OK;
+}
 void SFWPlanner::setFootprint(std::vector<Point> footprint) { footprint_spec_ = std::move(footprint); }
 void SFWPlanner::setSampleSets(std::vector<double> lin, std::vector<double> ang) {
   linvels_ = std::move(lin);
@@ -176,6 +191,20 @@ void SFWPlanner::uploadWorld(const AgentSet &agents) {
   const sfw_stop_check *const stop_p = stop_check_ ? &stop : nullptr;
   for (int32_t r = 0; r < (multi_ ? sfw_multi_ranks(multi_) : 1); ++r)
     if ((rc = sfw_set_stop_check(multi_ ? sfw_multi_rank_handle(multi_, r) : handle_, stop_p)) != SFW_OK) raise("sfw_set_stop_check", rc);
+  // the path term: the global plan from the way-point behind the current one on, handed down every cycle like the rest
+  std::vector<double> path_xy;
+  if (path_weight_ != 0.0 && !global_plan_.empty()) {
+    const size_t first = wp_index_ > 0 ? static_cast<size_t>(wp_index_) - 1 : 0;
+    const size_t n = std::min(global_plan_.size() - first, static_cast<size_t>(path_max_points_));
+    for (size_t i = first; i < first + n; ++i) {
+      path_xy.push_back(global_plan_[i].pose.position.x);
+      path_xy.push_back(global_plan_[i].pose.position.y);
+    }
+  }
+  const sfw_path path{path_xy.data(), static_cast<int32_t>(path_xy.size() / 2), 0, path_weight_};
+  const sfw_path *const path_p = path_xy.empty() ? nullptr : &path;
+  for (int32_t r = 0; r < (multi_ ? sfw_multi_ranks(multi_) : 1); ++r)
+    if ((rc = sfw_set_path(multi_ ? sfw_multi_rank_handle(multi_, r) : handle_, path_p)) != SFW_OK) raise("sfw_set_path", rc);
   if (multi_) {  // replicated to every rank
     if ((rc = sfw_multi_set_params(multi_, &abi)) != SFW_OK) raise("sfw_multi_set_params", rc);
     if ((rc = sfw_multi_set_costmap(multi_, costmap_.cells, costmap_.size_x, costmap_.size_y, costmap_.origin_x,

@@ -173,6 +173,15 @@ class SFWPlanner {
   // reference's call would; the grid and both single-sample call sites (:204-206, :299-301) are checked.  Off by default.
   void setStopCheck(bool on, int max_steps = SFW_STOP_MAX_STEPS);
   bool stopCheck() const { return stop_check_; }
+  // The path term the reference leaves in a comment (`path_distance_bias_ * path_cost`, src/sfw_planner.cpp:660-662): the mean
+  // squared distance of a sample's Trajectory points to the global plan joins the cost with this weight (include/sfw_hip.h:
+  // sfw_set_path).  A weight of exactly 0 means off, the default.  Every cycle hands the plan's points from the way-point
+  // BEHIND the current one on — [max(0, wp_index_ - 1), ...), at most max_points (clamped to 1 .. SFW_PATH_MAX_POINTS) — down,
+  // so that the segment the robot is on is part of the path; the grid and both single-sample call sites are scored with it.
+  void setPathTerm(double weight, int max_points = SFW_PATH_MAX_POINTS);
+  double pathWeight() const { return path_weight_; }
+  // what the device handle holds after the last scoring cycle: its points (x, y pairs) and weight; false while it has no path
+  bool pathTerm(std::vector<double> &xy, double &weight) const;
   int wpIndex() const { return wp_index_; }
   bool running() const { return running_; }
 
@@ -201,6 +210,8 @@ class SFWPlanner {
   bool marker_capture_ = false;
   bool stop_check_ = false;
   int stop_max_steps_ = SFW_STOP_MAX_STEPS;
+  double path_weight_ = 0.0;
+  int path_max_points_ = SFW_PATH_MAX_POINTS;
 
   int wp_index_ = -1;
   bool running_ = false, new_plan_ = false, goal_reached_ = false;

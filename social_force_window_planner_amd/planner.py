@@ -31,6 +31,7 @@ from ._abi import (
     SfwPerturb,
     SfwRisk,
     SfwRobotState,
+    SfwPath,
     SfwPlanInfo,
     SfwStopCheck,
     SfwStopRec,
@@ -211,6 +212,11 @@ def lib():
         L.sfw_grid_stop_info.argtypes = [vp, C.c_int64, C.c_int64, vp]
         L.sfw_grid_stop_points.argtypes = [vp, C.c_int64, C.c_int64, C.c_int32, vp, vp]
         L.sfw_ensemble_set_stop_check.argtypes = [vp, C.POINTER(SfwStopCheck)]
+        L.sfw_set_path.argtypes = [vp, C.POINTER(SfwPath)]
+        L.sfw_get_path.argtypes = [vp, vp, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int32)]
+        L.sfw_grid_path_term.argtypes = [vp, C.c_int64, C.c_int64, vp]
+        L.sfw_grid_rescore_path.argtypes = [vp, C.POINTER(SfwWeights), vp, C.c_int32, C.POINTER(SfwBest), vp]
+        L.sfw_ensemble_set_path.argtypes = [vp, C.POINTER(SfwPath)]
         _lib = L
     return _lib
 
@@ -284,6 +290,18 @@ def _mppi_args(robot_state, n, seed, nominal, sigma, lo, hi, knot_steps, goal_ar
     plans = np.zeros((room, K, 3), dtype=np.float64)
     head = (C.byref(rs), C.byref(p), n, K, ks.ctypes.data if len(ks) else None, C.byref(ga))
     return head, (C.byref(m), stats, plans.ctypes.data), K, I, stats, plans, (p, nom, ks, rs, ga, m)
+
+
+def _path_arg(xy, weight):
+    """(pointer to an sfw_path or None, the array it points into) for sfw_set_path / sfw_ensemble_set_path"""
+    if xy is None:
+        return None, None
+    if isinstance(xy, SfwPath):
+        return C.byref(xy), xy
+    xy = np.ascontiguousarray(np.asarray(xy, dtype=np.float64).reshape(-1, 2))
+    p = SfwPath(xy.ctypes.data_as(C.POINTER(C.c_double)), len(xy), 0, weight)
+    p._keep = xy
+    return C.byref(p), p
 
 
 class HipScorer(_Owner):
@@ -624,6 +642,45 @@ class HipScorer(_Owner):
         n = np.zeros(count, dtype=np.int32)
         self._check(lib().sfw_grid_stop_points(self._h, first, count, steps_cap, pts.ctypes.data, n.ctypes.data), "sfw_grid_stop_points")
         return pts, n
+
+    def set_path(self, xy=None, weight=0.0):
+        """sfw_set_path: the path term over the global plan xy ((n, 2) points) with its weight, read by the next stage; None: off."""
+        self._check(lib().sfw_set_path(self._h, _path_arg(xy, weight)[0]), "sfw_set_path")
+
+    def path(self):
+        """(xy[n, 2], weight) of the path in force for the next stage, or None while it is off."""
+        n, w, on = C.c_int32(), C.c_double(), C.c_int32()
+        self._check(lib().sfw_get_path(self._h, None, 0, C.byref(n), C.byref(w), C.byref(on)), "sfw_get_path")
+        if not on.value:
+            return None
+        xy = np.zeros((n.value, 2), dtype=np.float64)
+        self._check(lib().sfw_get_path(self._h, xy.ctypes.data, n.value, None, None, None), "sfw_get_path")
+        return xy, w.value
+
+    def path_term(self, first=0, count=None):
+        """The unweighted path term p of `count` samples of the last launch (sentinels where a sample was rejected or skipped)."""
+        if count is None:
+            nv, nw = self._grid if self._grid is not None else (0, 0)
+            count = max(nv * nw - first, 0)
+        out = np.zeros(max(count, 1), dtype=np.float64)
+        self._check(lib().sfw_grid_path_term(self._h, first, count, out.ctypes.data), "sfw_grid_path_term")
+        return out[:count]
+
+    def rescore_path(self, weights, path_weights=None, K=None, want_costs=False):
+        """sfw_grid_rescore_path: the last launch under ONE weight vector (5 values) and K path weights (None: the staged
+        weight, K times): (K best dicts, (K, samples) costs or None)."""
+        w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).reshape(SFW_N_TERMS))
+        pw = None if path_weights is None else np.ascontiguousarray(np.asarray(path_weights, dtype=np.float64).reshape(-1))
+        K = len(pw) if pw is not None else (1 if K is None else K)
+        best = (SfwBest * max(K, 1))()
+        costs = None
+        if want_costs and self._grid is not None:
+            nv, nw = self._grid
+            costs = np.empty((K, nv * nw), dtype=np.float64)
+        self._check(lib().sfw_grid_rescore_path(self._h, C.cast(w.ctypes.data, C.POINTER(SfwWeights)),
+                                                pw.ctypes.data if pw is not None else None, K, best,
+                                                costs.ctypes.data if costs is not None else None), "sfw_grid_rescore_path")
+        return [best[k].as_dict() for k in range(K)], costs
 
     def grid_points_batch(self, first, count, n_steps):
         """Trajectory points of `count` consecutive samples: (points[count, n_steps, 3], n_points[count])."""
@@ -1246,6 +1303,10 @@ class EnsembleScorer(_Owner):
         if check is not None and not isinstance(check, SfwStopCheck):
             check = SfwStopCheck(*check)
         self._check(lib().sfw_ensemble_set_stop_check(self._e, None if check is None else C.byref(check)), "sfw_ensemble_set_stop_check")
+
+    def set_path(self, xy=None, weight=0.0):
+        """sfw_ensemble_set_path: the path term of every member ((n, 2) points and the weight; None: off)."""
+        self._check(lib().sfw_ensemble_set_path(self._e, _path_arg(xy, weight)[0]), "sfw_ensemble_set_path")
 
     def set_risk(self, tail_mass=1.0, contact_mass=0.0):
         """sfw_ensemble_set_risk: from here on every aggregation (the score calls, aggregate, mppi_run) takes "mean" as the
