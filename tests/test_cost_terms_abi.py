@@ -13,10 +13,10 @@ from social_force_window_planner_amd import planner
 from social_force_window_planner_amd._abi import (EXPORTED_SYMBOLS, SFW_ERR_INVALID_ARG, SFW_N_TERMS, SFW_RESCORE_MAX_K,
                                                    SFW_TERM_ANGLE, SFW_TERM_COSTMAP, SFW_TERM_DISTANCE, SFW_TERM_SOCIAL,
                                                    SFW_TERM_VEL, SfwBest, SfwWeights)
+from kernel_listing import TUS, listing
 from sfw_test_util import _header
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "social_force_window_planner_amd", "csrc")
 TERM_SYMBOLS = ("sfw_set_terms_capture", "sfw_grid_rescore", "sfw_grid_terms")
 
 
@@ -69,27 +69,9 @@ def test_null_handle_and_bad_arguments_without_gpu():
     assert L.sfw_grid_terms(None, 0, 1, terms) == SFW_ERR_INVALID_ARG
 
 
-@pytest.fixture(scope="module", params=["sfw_kernels.hip", "sfw_kernels_strict.hip"])
+@pytest.fixture(scope="module", params=TUS)
 def resources(request):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc")
-    r = subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-Wno-unused-function", "--cuda-device-only",
-                        "-Rpass-analysis=kernel-resource-usage", "-c", request.param, "-o", os.devnull],
-                       cwd=CSRC, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    out, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = out.setdefault(m.group(1), {})
-            continue
-        for key, pat in (("vgpr", r"remark:\s+VGPRs: (\d+)"), ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"),
-                         ("occupancy", r"Occupancy \[waves/SIMD\]: (\d+)")):
-            m = re.search(pat, line)
-            if m and cur is not None:
-                cur[key] = int(m.group(1))
-    return request.param, out
+    return request.param, listing(request.param).resources
 
 
 @pytest.mark.parametrize("kernel", ["sfw_rescore_stage1", "sfw_rescore_stage2"])

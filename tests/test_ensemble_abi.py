@@ -16,10 +16,10 @@ from social_force_window_planner_amd import synthetic as syn
 from social_force_window_planner_amd._abi import (EXPORTED_SYMBOLS, SFW_ENSEMBLE_MAX, SFW_ENSEMBLE_MAX_M, SFW_ENSEMBLE_MEAN,
                                                    SFW_ERR_INVALID_ARG, SFW_ERR_NO_DEVICE, SFW_OK, SfwBest, default_params)
 from social_force_window_planner_amd.hypotheses import naive_goal_hypotheses
+from kernel_listing import TUS, listing
 from sfw_test_util import _gpu, _header
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "social_force_window_planner_amd", "csrc")
 ENSEMBLE_SYMBOLS = ("sfw_ensemble_create", "sfw_ensemble_destroy", "sfw_ensemble_last_error", "sfw_ensemble_size",
                     "sfw_ensemble_member", "sfw_ensemble_set_params", "sfw_ensemble_set_costmap", "sfw_ensemble_set_footprint",
                     "sfw_ensemble_set_hypothesis", "sfw_ensemble_score_grid", "sfw_ensemble_aggregate", "sfw_ensemble_last_us")
@@ -112,27 +112,9 @@ def test_ensemble_without_gpu_is_no_device():
     assert ex.value.status == SFW_ERR_NO_DEVICE
 
 
-@pytest.fixture(scope="module", params=["sfw_kernels.hip", "sfw_kernels_strict.hip"])
+@pytest.fixture(scope="module", params=TUS)
 def resources(request):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc")
-    r = subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-Wno-unused-function", "--cuda-device-only",
-                        "-Rpass-analysis=kernel-resource-usage", "-c", request.param, "-o", os.devnull],
-                       cwd=CSRC, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    out, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = out.setdefault(m.group(1), {})
-            continue
-        for key, pat in (("vgpr", r"remark:\s+VGPRs: (\d+)"), ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"),
-                         ("occupancy", r"Occupancy \[waves/SIMD\]: (\d+)")):
-            m = re.search(pat, line)
-            if m and cur is not None:
-                cur[key] = int(m.group(1))
-    return request.param, out
+    return request.param, listing(request.param).resources
 
 
 @pytest.mark.parametrize("kernel", ["sfw_ensemble_stage1", "sfw_ensemble_stage2"])

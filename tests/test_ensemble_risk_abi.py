@@ -13,13 +13,13 @@ import pytest
 from social_force_window_planner_amd import planner, risk
 from social_force_window_planner_amd._abi import (EXPORTED_SYMBOLS, SFW_COST_INVALID, SFW_COST_SKIPPED, SFW_ERR_INVALID_ARG,
                                                    SfwRisk)
+from kernel_listing import KERNELS_TU, listing, source
 from sfw_test_util import _bits, _header, _same
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "social_force_window_planner_amd", "csrc")
 RISK_SYMBOLS = ("sfw_ensemble_set_risk", "sfw_ensemble_get_risk")
 # the one translation unit that holds the new kernels (both sit under #ifndef SFW_STRICT_BUILD, as sfw_ens_list_first does)
-RISK_TU, RISK_KERNELS = "sfw_kernels.hip", ("sfw_ens_risk_grid", "sfw_ens_risk_list")
+RISK_TU, RISK_KERNELS = KERNELS_TU, ("sfw_ens_risk_grid", "sfw_ens_risk_list")
 
 
 def test_risk_symbols_declared_and_exported():
@@ -61,25 +61,7 @@ def test_null_ensemble_is_refused():
 
 @pytest.fixture(scope="module")
 def resources():
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc")
-    r = subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-Wno-unused-function", "--cuda-device-only",
-                        "-Rpass-analysis=kernel-resource-usage", "-c", RISK_TU, "-o", os.devnull],
-                       cwd=CSRC, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    out, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = out.setdefault(m.group(1), {})
-            continue
-        for key, pat in (("vgpr", r"remark:\s+VGPRs: (\d+)"), ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"),
-                         ("occupancy", r"Occupancy \[waves/SIMD\]: (\d+)")):
-            m = re.search(pat, line)
-            if m and cur is not None:
-                cur[key] = int(m.group(1))
-    return out
+    return listing(RISK_TU).resources
 
 
 def test_risk_kernels_within_the_ensemble_budgets(resources):
@@ -91,13 +73,13 @@ def test_risk_kernels_within_the_ensemble_budgets(resources):
         assert r["scratch"] == 0 and r["occupancy"] >= 4 and r["vgpr"] <= 128, (kernel, r)
     # the existing resource tests find kernels by substring: no existing ensemble kernel's name occurs in a new one's
     assert not [n for n in res if "sfw_ens_risk" in n and ("sfw_ensemble_stage" in n or "sfw_ens_list_first" in n)]
-    src = open(os.path.join(CSRC, "sfw_kernels.hip")).read()
+    src = source(RISK_TU)
     assert src.index("#ifndef SFW_STRICT_BUILD  // (terms and costs") < src.index("sfw_ens_risk_first(") < \
         src.index("sfw_ens_risk_list(") < src.index("#endif  // SFW_STRICT_BUILD", src.index("sfw_ens_risk_list("))
 
 
 def test_risk_kernels_use_no_floating_point_atomics():
-    src = open(os.path.join(CSRC, "sfw_kernels.hip")).read()
+    src = source(RISK_TU)
     body = src[src.index("sfw_ens_risk_first("):src.index("sfw_ens_risk_list(")]
     assert "atomic" not in body and "#pragma clang fp contract(off)" in body
 

@@ -11,10 +11,10 @@ import pytest
 
 from social_force_window_planner_amd import planner
 from social_force_window_planner_amd._abi import EXPORTED_SYMBOLS, SFW_ERR_INVALID_ARG, SfwBest, SfwBlendStat
+from kernel_listing import KERNELS_TU, listing
 from sfw_test_util import _header
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "social_force_window_planner_amd", "csrc")
 NEW_SYMBOLS = ("sfw_ensemble_score_sequences", "sfw_ensemble_score_perturbed", "sfw_ensemble_blend")
 LIST_KERNEL = "sfw_ens_list_first"
 
@@ -68,32 +68,9 @@ def test_null_ensemble_calls():
     assert L.sfw_ensemble_blend(None, None, 0, None, None, None, None) == SFW_ERR_INVALID_ARG
 
 
-def _resources(tu):
-    """The -Rpass-analysis=kernel-resource-usage recipe of tests/test_ensemble_abi.py: {kernel symbol: {vgpr, scratch, occupancy}}"""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc")
-    r = subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-Wno-unused-function", "--cuda-device-only",
-                        "-Rpass-analysis=kernel-resource-usage", "-c", tu, "-o", os.devnull],
-                       cwd=CSRC, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    out, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = out.setdefault(m.group(1), {})
-            continue
-        for key, pat in (("vgpr", r"remark:\s+VGPRs: (\d+)"), ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"),
-                         ("occupancy", r"Occupancy \[waves/SIMD\]: (\d+)")):
-            m = re.search(pat, line)
-            if m and cur is not None:
-                cur[key] = int(m.group(1))
-    return out
-
-
 def test_list_kernel_without_scratch():
     """Costs and terms are doubles in every precision mode: the kernel exists in the default translation unit only."""
-    res = _resources("sfw_kernels.hip")
+    res = listing(KERNELS_TU).resources
     names = [n for n in res if LIST_KERNEL in n]
     assert len(names) == 1, names
     assert "sfw_ensemble_stage1" not in names[0]  # (the grid form stays the one symbol of that name)

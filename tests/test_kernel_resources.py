@@ -11,47 +11,23 @@ cross-compiles gfx950).  The occupancy the launch plan counts on is a property o
 """
 import os
 import re
-import shutil
 import subprocess
 
 import pytest
 
+from kernel_listing import KERNELS_TU, TUS, listing, one
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "social_force_window_planner_amd", "csrc")
 
 
-@pytest.fixture(scope="module", params=["sfw_kernels.hip", "sfw_kernels_strict.hip"])
+@pytest.fixture(scope="module", params=TUS)
 def resources(request):
     """... of both builds of the K2 kernels: the default one and the one with the longer polynomials (SFW_PRECISION_F64_STRICT)"""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc")
-    r = subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-Wno-unused-function", "--cuda-device-only",
-                        "-Rpass-analysis=kernel-resource-usage", "-c", request.param, "-o", os.devnull],
-                       cwd=CSRC, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    out, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = out.setdefault(m.group(1), {})
-            continue
-        for key, pat in (("vgpr", r"remark:\s+VGPRs: (\d+)"), ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"),
-                         ("occupancy", r"Occupancy \[waves/SIMD\]: (\d+)")):
-            m = re.search(pat, line)
-            if m and cur is not None:
-                cur[key] = int(m.group(1))
-    return out
-
-
-def _kernel(resources, fragment):
-    names = [n for n in resources if fragment in n]
-    assert len(names) == 1, (fragment, names)
-    return resources[names[0]]
+    return listing(request.param).resources
 
 
 def test_register_form_six_waves_without_scratch(resources):
-    k = _kernel(resources, "sfw_social_kernelIdLi1ELb0E")
+    k = one(resources, "sfw_social_kernelIdLi1ELb0E")
     assert k["vgpr"] <= 80 and k["scratch"] == 0 and k["occupancy"] >= 6, k
 
 
@@ -59,7 +35,7 @@ def test_flat_form_five_waves_without_scratch(resources):
     """... both kernels of every plane capacity: without the laser-point pass (the headline's) and with it"""
     for cap in (64, 104, 128, 208, 256):
         for obs in (0, 1):
-            k = _kernel(resources, f"sfw_social_kernel_flatIdLb0ELi{cap}ELb{obs}E")
+            k = one(resources, f"sfw_social_kernel_flatIdLb0ELi{cap}ELb{obs}E")
             scratch = 0 if obs == 0 else 24 if cap == 64 else 12  # (module docstring)
             assert k["vgpr"] <= 96 and k["scratch"] <= scratch and k["occupancy"] >= 5, (cap, obs, k)
 
@@ -69,7 +45,7 @@ def test_mixed_launch_kernel_holds_six_waves_per_simd(resources):
     streams) is launched where five register-form waves and one flat-form wave share a SIMD: its allocation is the larger of the
     two bodies' and must stay within the six-wave budget; a few bytes of scratch (one spilled pair in the flat body's per-step
     part, measured harmless: profiles/r06_ab_mixed.txt) are tolerated, a stack is not."""
-    k = _kernel(resources, "sfw_social_kernel_mixedId")
+    k = one(resources, "sfw_social_kernel_mixedId")
     assert k["vgpr"] <= 80 and k["scratch"] <= 16 and k["occupancy"] >= 6, k
 
 
@@ -77,30 +53,22 @@ def test_mixed_launch_kernel_holds_six_waves_per_simd(resources):
 # issues, so a compiler or source change that adds one shows here before it shows on a GPU) ----
 @pytest.fixture(scope="module")
 def isa_loops():
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc")
-    import tempfile
-    with tempfile.TemporaryDirectory() as d:
-        asm = os.path.join(d, "k2.s")
-        r = subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-Wno-unused-function", "--cuda-device-only", "-S",
-                            "sfw_kernels.hip", "-o", asm], cwd=CSRC, capture_output=True, text=True, timeout=600)
-        assert r.returncode == 0, r.stderr[-2000:]
+    asm = listing(KERNELS_TU).asm
 
-        def loops(symbol):
-            out = subprocess.run(["python3", os.path.join(ROOT, "tools", "isa_loops.py"), asm, symbol], capture_output=True, text=True,
-                                 timeout=120)
-            assert out.returncode == 0, out.stderr[-1000:]
-            res = []
-            for line in out.stdout.splitlines():
-                m = re.search(r"valu\s+(\d+) \(f64 (\d+), trans (\d+)\)\s+salu\s+(\d+)\s+ds\s+(\d+)\s+vmem\s+(\d+)", line)
-                if m:
-                    res.append(dict(zip(("valu", "f64", "trans", "salu", "ds", "vmem"), map(int, m.groups()))))
-            return res
+    def loops(symbol):
+        out = subprocess.run(["python3", os.path.join(ROOT, "tools", "isa_loops.py"), asm, symbol], capture_output=True, text=True,
+                             timeout=120)
+        assert out.returncode == 0, out.stderr[-1000:]
+        res = []
+        for line in out.stdout.splitlines():
+            m = re.search(r"valu\s+(\d+) \(f64 (\d+), trans (\d+)\)\s+salu\s+(\d+)\s+ds\s+(\d+)\s+vmem\s+(\d+)", line)
+            if m:
+                res.append(dict(zip(("valu", "f64", "trans", "salu", "ds", "vmem"), map(int, m.groups()))))
+        return res
 
-        hz = subprocess.run(["python3", os.path.join(ROOT, "tools", "isa_asm_hazards.py"), asm], capture_output=True, text=True, timeout=300)
-        yield {"hazards": (hz.returncode, hz.stdout), "flat": loops("sfw_social_kernel_flatIdLb0ELi64ELb0E"), "flat_obs": loops("sfw_social_kernel_flatIdLb0ELi64ELb1E"),
-               "reg": loops("sfw_social_kernelIdLi1ELb0E")}
+    hz = subprocess.run(["python3", os.path.join(ROOT, "tools", "isa_asm_hazards.py"), asm], capture_output=True, text=True, timeout=300)
+    return {"hazards": (hz.returncode, hz.stdout), "flat": loops("sfw_social_kernel_flatIdLb0ELi64ELb0E"), "flat_obs": loops("sfw_social_kernel_flatIdLb0ELi64ELb1E"),
+           "reg": loops("sfw_social_kernelIdLi1ELb0E")}
 
 
 def test_pair_loop_instruction_counts(isa_loops):

@@ -14,6 +14,7 @@ import pytest
 from social_force_window_planner_amd import planner
 from social_force_window_planner_amd._abi import (EXPORTED_SYMBOLS, SFW_ERR_INVALID_ARG, SFW_PATH_MAX_COORD, SFW_PATH_MAX_POINTS, SFW_N_TERMS,
                                                   SfwBest, SfwPath, SfwWeights)
+from kernel_listing import KERNELS_TU, listing, one, source
 from sfw_test_util import _header
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -86,31 +87,7 @@ def test_null_handle_is_refused_and_outputs_stay():
 
 @pytest.fixture(scope="module")
 def resources():
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc")
-    r = subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-Wno-unused-function", "--cuda-device-only",
-                        "-Rpass-analysis=kernel-resource-usage", "-c", "sfw_kernels.hip", "-o", os.devnull],
-                       cwd=CSRC, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    out, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = out.setdefault(m.group(1), {})
-            continue
-        for key, pat in (("vgpr", r"remark:\s+VGPRs: (\d+)"), ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"),
-                         ("lds", r"LDS Size \[bytes/block\]: (\d+)"), ("occupancy", r"Occupancy \[waves/SIMD\]: (\d+)")):
-            m = re.search(pat, line)
-            if m and cur is not None:
-                cur[key] = int(m.group(1))
-    return out
-
-
-def _one(res, fragment):
-    names = [n for n in res if fragment in n]
-    assert len(names) == 1, (fragment, names)
-    return res[names[0]]
+    return listing(KERNELS_TU).resources
 
 
 def test_path_kernels_without_scratch_and_within_budget(resources):
@@ -118,7 +95,7 @@ def test_path_kernels_without_scratch_and_within_budget(resources):
     SIMD — the kernels wait on memory, the distance kernel on its scalar loads), no scratch, no LDS.  The re-score and ensemble
     kernels that took the nullable term pointer keep the budgets their own tests state."""
     for name in ("sfw_path_fill_kernel", "sfw_path_dist_kernel", "sfw_path_scan_kernel", "sfw_path_add_kernel"):
-        k = _one(resources, name)
+        k = one(resources, name)
         assert k["scratch"] == 0 and k["lds"] == 0 and k["vgpr"] <= 64 and k["occupancy"] >= 8, (name, k)
     # the existing resource tests find kernels by substring: no existing kernel's name occurs in a new one's
     for old in ("sfw_footprint_kernel", "sfw_costmap_scan", "sfw_stop_", "sfw_rescore_stage", "sfw_ensemble_stage", "sfw_ens_"):
@@ -126,7 +103,7 @@ def test_path_kernels_without_scratch_and_within_budget(resources):
 
 
 def test_path_kernels_sit_under_the_no_contraction_pragma():
-    src = open(os.path.join(CSRC, "sfw_kernels.hip")).read()
+    src = source()
     off, fast = src.index("#pragma clang fp contract(off)"), src.index("#pragma clang fp contract(fast)")
     for name in ("sfw_path_fill_kernel(", "sfw_path_dist_kernel(", "sfw_path_scan_kernel(", "sfw_path_add_kernel("):
         assert off < src.index(name) < fast, name

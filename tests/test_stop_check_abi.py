@@ -14,10 +14,10 @@ import pytest
 from social_force_window_planner_amd import planner
 from social_force_window_planner_amd._abi import (EXPORTED_SYMBOLS, SFW_ERR_INVALID_ARG, SFW_STOP_MAX_STEPS, SFW_STOP_NONE, SFW_STOP_NOT_RUN,
                                                   SFW_STOP_UNFINISHED, SfwStopCheck, SfwStopRec)
+from kernel_listing import KERNELS_TU, listing, one, source
 from sfw_test_util import _header
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "social_force_window_planner_amd", "csrc")
 STOP_SYMBOLS = ("sfw_set_stop_check", "sfw_get_stop_check", "sfw_grid_stop_info", "sfw_grid_stop_points", "sfw_ensemble_set_stop_check")
 
 
@@ -79,31 +79,7 @@ def test_null_handle_is_refused_and_outputs_stay():
 
 @pytest.fixture(scope="module")
 def resources():
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc")
-    r = subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-Wno-unused-function", "--cuda-device-only",
-                        "-Rpass-analysis=kernel-resource-usage", "-c", "sfw_kernels.hip", "-o", os.devnull],
-                       cwd=CSRC, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    out, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = out.setdefault(m.group(1), {})
-            continue
-        for key, pat in (("vgpr", r"remark:\s+VGPRs: (\d+)"), ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"),
-                         ("lds", r"LDS Size \[bytes/block\]: (\d+)")):
-            m = re.search(pat, line)
-            if m and cur is not None:
-                cur[key] = int(m.group(1))
-    return out
-
-
-def _one(res, fragment):
-    names = [n for n in res if fragment in n]
-    assert len(names) == 1, (fragment, names)
-    return res[names[0]]
+    return listing(KERNELS_TU).resources
 
 
 def test_tail_kernels_without_scratch_and_within_budget(resources):
@@ -111,11 +87,11 @@ def test_tail_kernels_without_scratch_and_within_budget(resources):
     footprint kernel is sfw_footprint_kernel's body behind another load: no more registers than that kernel of the same build.
     The pose kernel and the finish kernel run 256-thread blocks, one thread per sample: at most 96 VGPRs (five waves per SIMD,
     the K1a kernels' own class), no scratch, no LDS."""
-    fp = max(_one(resources, f"sfw_footprint_kernelILb{b}E")["vgpr"] for b in (0, 1))
-    k = _one(resources, "sfw_stop_footprint_kernel")
+    fp = max(one(resources, f"sfw_footprint_kernelILb{b}E")["vgpr"] for b in (0, 1))
+    k = one(resources, "sfw_stop_footprint_kernel")
     assert k["scratch"] == 0 and k["lds"] == 0 and k["vgpr"] <= fp, (k, fp)
     for name in ("sfw_stop_tail_kernel", "sfw_stop_finish_kernel"):
-        k = _one(resources, name)
+        k = one(resources, name)
         assert k["scratch"] == 0 and k["lds"] == 0 and k["vgpr"] <= 96, (name, k)
 
 
@@ -131,12 +107,12 @@ K1A_BEFORE = {
 
 def test_k1a_kernels_keep_their_resources(resources):
     for name, want in K1A_BEFORE.items():
-        k = _one(resources, name)
+        k = one(resources, name)
         assert (k["vgpr"], k["scratch"], k["lds"]) == want, (name, k, want)
 
 
 def test_tail_sits_above_the_contraction_pragma():
-    src = open(os.path.join(CSRC, "sfw_kernels.hip")).read()
+    src = source()
     off, fast = src.index("#pragma clang fp contract(off)"), src.index("#pragma clang fp contract(fast)")
     for name in ("sfw_stop_tail_kernel(", "sfw_stop_footprint_kernel(", "sfw_stop_finish_kernel("):
         assert off < src.index(name) < fast, name
