@@ -519,7 +519,8 @@ int sfw_sequences_normals(sfw_handle h, int64_t first, int64_t count, double *z_
 /* How the staged grid will be launched.  levels > 0: the shared-prefix
  * rollout is in use — under the acceleration limits (sfw_planner.hpp:457-463)
  * the robot's first steps are bit-identical for all samples of a class (same
- * clipped linear x angular velocity sequences), and classes refine step by
+ * clipped linear x angular velocity sequences; the angular one a step shorter,
+ * see sfw_plan_shared_prefix_items), and classes refine step by
  * step, so the first split_step steps are simulated along a tree of `levels`
  * levels of classes (class_steps class-steps in all instead of
  * samples * split_step sample-steps) and every sample resumes from its class
@@ -537,8 +538,8 @@ typedef struct sfw_plan_info {
   int32_t organisation; /* SFW_ORG_*: how a wave of the launch over the SAMPLES is organised (the suffix
                            launch of the shared-prefix rollout, or the whole rollout); the prefix levels
                            pick theirs by their class counts.  Costs do not depend on it.  */
-  int64_t classes;     /* classes of the last level, summed over chunks      */
-  int64_t class_steps; /* sum over levels of classes x steps of the level    */
+  int64_t classes;     /* work items of the last level (sfw_plan_shared_prefix_items), summed over chunks */
+  int64_t class_steps; /* sum over levels of items x steps of the level      */
   int64_t samples;     /* nv * nw                                            */
   int64_t flat_samples; /* organisation = SFW_ORG_REGISTER_1 only: samples (of the first chunk's launch) that the launch
                            hands to flat-form waves running beside the register-form ones, so that every SIMD holds
@@ -572,6 +573,15 @@ int sfw_plan_shared_prefix(const double *linvels, int32_t nv,
                            int32_t n_agents, int32_t *level_ends,
                            int64_t *level_classes, int32_t cap,
                            int32_t *n_levels);
+/* The WORK ITEMS of the same plan (same arguments, same level_ends): what a level's launch integrates once each.  A level
+ * ending at step p reads the robot's records of steps 0..p-1 only, and a record holds the position after its step, which takes
+ * the heading BEFORE the step (sfw_planner.cpp:586-588): records 0..p-1 depend on the linear velocities of steps 0..p-1 but on
+ * the angular velocities of steps 0..p-2.  So the items of the level are row classes(p) x column classes(p - 1) — one column
+ * class for p = 1 —, fewer than the velocity classes sfw_plan_shared_prefix reports (row classes(p) x column classes(p): the
+ * samples whose first p commanded velocities coincide).  sfw_plan_info.classes / class_steps count items. */
+int sfw_plan_shared_prefix_items(const double *linvels, int32_t nv, const double *angvels, int32_t nw, double vx0,
+                                 double vtheta0, double acc_x, double acc_theta, double sim_time, int32_t num_steps,
+                                 int32_t n_agents, int32_t *level_ends, int64_t *level_items, int32_t cap, int32_t *n_levels);
 /* One axis of that plan (host only; diagnostics and tests): the classes of `n` target velocities whose first p clipped
  * velocities (computeNewVelocity, sfw_planner.hpp:457-463, from the current velocity v0 under a_max, dt) are bit-equal,
  * for p = 1 .. *n_levels <= max_p (the walk stops once every target is its own class).  counts[p-1] = classes of level

@@ -166,6 +166,7 @@ EXPORTED_SYMBOLS = (
     "sfw_grid_costs_view",
     "sfw_grid_plan_info",
     "sfw_plan_shared_prefix",
+    "sfw_plan_shared_prefix_items",
     "sfw_plan_row_blocks",
     "sfw_plan_axis_classes",
     "sfw_set_k2_form",

@@ -843,6 +843,14 @@ struct prefix_classes {
   // a level past the last computed one has every value in its own class
   int32_t n_rows_at(int p) const { return rows.n[std::min<size_t>(static_cast<size_t>(p), rows.n.size()) - 1]; }
   int32_t n_cols_at(int p) const { return cols->n[std::min<size_t>(static_cast<size_t>(p), cols->n.size()) - 1]; }
+  // The WORK ITEMS of a level ending at step p are row classes(p) x column classes(p - 1): the robot records of steps
+  // 0..p-1 hold positions, and the position after step i takes the heading BEFORE the step (ref :586-588) — the angular
+  // velocities of steps 0..i-1 only —, so the column axis lags the row axis by one step.  p = 1: no angular velocity has
+  // acted yet, one column class.
+  int32_t n_item_cols_at(int p) const { return p >= 2 ? n_cols_at(p - 1) : 1; }
+  const std::vector<int32_t> &item_cols(int p) const { return p >= 2 ? cols->level(p - 1) : one_col; }
+  int64_t n_items_at(int p) const { return static_cast<int64_t>(n_rows_at(p)) * n_item_cols_at(p); }
+  std::vector<int32_t> one_col;  // every column in class 0
 };
 
 void classes_of_grid(prefix_classes &pc, const std::vector<double> &lin, const std::vector<double> &ang, double vx0,
@@ -855,21 +863,23 @@ void classes_of_grid(prefix_classes &pc, const std::vector<double> &lin, const s
     pc.own_cols = classes_of_axis(ang, vth0, acc_theta, dt, pc.max_p);
     pc.cols = &pc.own_cols;
   }
+  pc.one_col.assign(ang.size(), 0);
 }
 
-// The levels' end steps.  A level ending at step p costs (p - q) steps over classes(p) items plus a
+// The levels' end steps.  A level ending at step p costs (p - q) steps over items(p) = rows(p) x columns(p - 1) plus a
 // launch and the class records (0.4 to 1.0 of a round); the suffix costs (S - p) steps over all
 // samples.  Dynamic programme over the end step of the last level; empty when sharing does not pay.
 std::vector<int> choose_levels(const prefix_classes &pc, int64_t T, int S, double samples_per_wave, int cus) {
   std::vector<int> steps;
   const double full = step_cost(static_cast<double>(T), samples_per_wave, cus);
-  const int last_p = std::min<int>(pc.max_p, static_cast<int>(std::max(pc.rows.n.size(), pc.cols->n.size())));
+  // (the column axis lags by one step: its last computed level is the items' axis one step later)
+  const int last_p = std::min<int>(pc.max_p, static_cast<int>(std::max(pc.rows.n.size(), pc.cols->n.size() + 1)));
   std::vector<double> best(static_cast<size_t>(last_p) + 1, 0.0);
   std::vector<int> from(static_cast<size_t>(last_p) + 1, 0);
   double best_total = S * full;
   int best_end = 0;
   for (int p = 1; p <= last_p; ++p) {
-    const double c = step_cost(static_cast<double>(pc.n_rows_at(p)) * pc.n_cols_at(p), samples_per_wave, cus);
+    const double c = step_cost(static_cast<double>(pc.n_items_at(p)), samples_per_wave, cus);
     // per extra launch: dispatch + class records for an under-filled level; a level that fills the GPU
     // also pays its ramp-up and tail (measured: 0.4 / 1.0 pick the fastest plans at cfg2 / target)
     const double launch_cost = c < 1.0 ? 0.4 : 1.0;
@@ -890,7 +900,7 @@ std::vector<int> choose_levels(const prefix_classes &pc, int64_t T, int S, doubl
 // Row blocks of (about) equal PLANNED work for R ranks.  A block's work is its class-steps through the shared-prefix
 // levels plus its samples' remaining steps, and the share of steps the tree saves differs along the row axis (rows are
 // ordered by target velocity: cfg5 cut into 8 equal blocks integrates 64 %..76 % of its steps per block).  With the
-// levels of the whole grid's plan every row gets a weight — for each level, (steps of the level) x (column classes) if
+// levels of the whole grid's plan every row gets a weight — for each level, (steps of the level) x (the items' column classes) if
 // the row opens a new row class at that level, plus nw x (S - split) for its samples' own steps — and the cuts go where
 // the running sum passes r/R of the total.  Equal row counts when nothing is shared.  Each rank still makes its own plan
 // for its block; costs do not depend on the cut.
@@ -910,7 +920,7 @@ void plan_row_blocks(const std::vector<double> &lin, const std::vector<double> &
   int prev = 0;
   for (int p : steps) {
     const std::vector<int32_t> &rc = pc.rows.level(p);
-    const double per_class = static_cast<double>(pc.n_cols_at(p)) * (p - prev);
+    const double per_class = static_cast<double>(pc.n_item_cols_at(p)) * (p - prev);
     for (int64_t i = 0; i < nv; ++i)
       if (i == 0 || rc[static_cast<size_t>(i)] != rc[static_cast<size_t>(i - 1)]) w[static_cast<size_t>(i)] += per_class;
     prev = p;
@@ -944,8 +954,8 @@ int plan_prefix(sfw_handle h, int64_t chunk, int S) {
   prefix_classes pc;
   classes_of_grid(pc, h->st.lin, h->st.ang, h->st.rs.vx, h->st.rs.vtheta, h->st.ga.acc_x, h->st.ga.acc_theta, h->live.params.sim_time / S, S,
                   static_cast<const axis_classes *>(h->shared_cols));
-  const axis_classes &rc = pc.rows, &cc = *pc.cols;
-  const std::vector<int32_t> &nr = pc.rows.n, &nc = pc.cols->n;
+  const axis_classes &rc = pc.rows;
+  const std::vector<int32_t> &nr = pc.rows.n;
   auto level = [](const axis_classes &c, int p) -> const std::vector<int32_t> & { return c.level(p); };
   auto count_at = [](const std::vector<int32_t> &n, int p) { return n[std::min<size_t>(static_cast<size_t>(p), n.size()) - 1]; };
   std::vector<int> steps;
@@ -989,10 +999,11 @@ int plan_prefix(sfw_handle h, int64_t chunk, int S) {
   };
   struct axis_level { std::vector<int32_t> local, rep, src; };
   // levels of one axis over [i0, i1): local classes, representatives, parent classes
-  auto axis_levels = [&](const axis_classes &cls, int64_t i0, int64_t i1) {
+  // (cls null: the items' column axis, which lags the rows by one step — prefix_classes::item_cols)
+  auto axis_levels = [&](const axis_classes *cls, int64_t i0, int64_t i1) {
     std::vector<axis_level> out(n_lv);
     for (size_t l = 0; l < n_lv; ++l) {
-      relabel(level(cls, steps[l]), i0, i1, out[l].local, out[l].rep);
+      relabel(cls ? level(*cls, steps[l]) : pc.item_cols(steps[l]), i0, i1, out[l].local, out[l].rep);
       if (l > 0) {  // classes refine: the parent of a class is the previous level's class of its representative
         out[l].src.reserve(out[l].rep.size());
         for (int32_t r : out[l].rep) out[l].src.push_back(out[l - 1].local[static_cast<size_t>(r)]);
@@ -1000,7 +1011,7 @@ int plan_prefix(sfw_handle h, int64_t chunk, int S) {
     }
     return out;
   };
-  const std::vector<axis_level> cols = axis_levels(cc, 0, h->st.nw);
+  const std::vector<axis_level> cols = axis_levels(nullptr, 0, h->st.nw);
   std::vector<size_t> o_col_rep(n_lv), o_col_src(n_lv);
   for (size_t l = 0; l < n_lv; ++l) {
     o_col_rep[l] = append(cols[l].rep);
@@ -1010,7 +1021,7 @@ int plan_prefix(sfw_handle h, int64_t chunk, int S) {
   int64_t max_cls = 0;
   for (int64_t r0 = 0; r0 < h->st.nv; r0 += rows_per_chunk) {
     const int64_t r1 = std::min<int64_t>(h->st.nv, r0 + rows_per_chunk);
-    const std::vector<axis_level> rows = axis_levels(rc, r0, r1);
+    const std::vector<axis_level> rows = axis_levels(&rc, r0, r1);
     chunk_plan cp;
     for (size_t l = 0; l < n_lv; ++l) {
       level_tables t;
@@ -1037,7 +1048,7 @@ int plan_prefix(sfw_handle h, int64_t chunk, int S) {
   if (std::getenv("SFW_DEBUG_PLAN")) {
     std::fprintf(stderr, "[sfw] shared prefix, %d x %d samples, S=%d, %zu chunk(s):", h->st.nv, h->st.nw, S, h->st.prefix_chunks.size());
     for (size_t l = 0; l < n_lv; ++l)
-      std::fprintf(stderr, " [%d,%d) %d x %d;", l ? steps[l - 1] : 0, steps[l], count_at(nr, steps[l]), count_at(nc, steps[l]));
+      std::fprintf(stderr, " [%d,%d) %d x %d;", l ? steps[l - 1] : 0, steps[l], count_at(nr, steps[l]), pc.n_item_cols_at(steps[l]));
     std::fprintf(stderr, " [%d,%d) samples\n", steps.back(), S);
   }
   h->st.prefix_steps = steps;
@@ -2986,9 +2997,11 @@ int sfw_score_one(sfw_handle h, const sfw_robot_state *rs, double vx_samp, doubl
   return SFW_OK;
 }
 
-int sfw_plan_shared_prefix(const double *linvels, int32_t nv, const double *angvels, int32_t nw, double vx0, double vtheta0,
-                           double acc_x, double acc_theta, double sim_time, int32_t num_steps, int32_t n_agents,
-                           int32_t *level_ends, int64_t *level_classes, int32_t cap, int32_t *n_levels) {
+// sfw_plan_shared_prefix (items false: the velocity classes of each level) and sfw_plan_shared_prefix_items (items true: its
+// work items, whose column axis lags by one step) of ONE plan
+static int plan_shared_prefix(const double *linvels, int32_t nv, const double *angvels, int32_t nw, double vx0, double vtheta0,
+                              double acc_x, double acc_theta, double sim_time, int32_t num_steps, int32_t n_agents,
+                              int32_t *level_ends, int64_t *level_classes, int32_t cap, int32_t *n_levels, bool items) {
   if (!linvels || !angvels || nv <= 0 || nw <= 0 || num_steps < 1 || !n_levels || cap < 0 ||
       (cap > 0 && (!level_ends || !level_classes)))
     return SFW_ERR_INVALID_ARG;
@@ -3003,9 +3016,21 @@ int sfw_plan_shared_prefix(const double *linvels, int32_t nv, const double *angv
   *n_levels = static_cast<int32_t>(steps.size());
   for (size_t l = 0; l < steps.size() && l < static_cast<size_t>(cap); ++l) {
     level_ends[l] = steps[l];
-    level_classes[l] = static_cast<int64_t>(pc.n_rows_at(steps[l])) * pc.n_cols_at(steps[l]);
+    level_classes[l] = items ? pc.n_items_at(steps[l]) : static_cast<int64_t>(pc.n_rows_at(steps[l])) * pc.n_cols_at(steps[l]);
   }
   return SFW_OK;
+}
+int sfw_plan_shared_prefix(const double *linvels, int32_t nv, const double *angvels, int32_t nw, double vx0, double vtheta0,
+                           double acc_x, double acc_theta, double sim_time, int32_t num_steps, int32_t n_agents,
+                           int32_t *level_ends, int64_t *level_classes, int32_t cap, int32_t *n_levels) {
+  return plan_shared_prefix(linvels, nv, angvels, nw, vx0, vtheta0, acc_x, acc_theta, sim_time, num_steps, n_agents, level_ends,
+                            level_classes, cap, n_levels, false);
+}
+int sfw_plan_shared_prefix_items(const double *linvels, int32_t nv, const double *angvels, int32_t nw, double vx0, double vtheta0,
+                                 double acc_x, double acc_theta, double sim_time, int32_t num_steps, int32_t n_agents,
+                                 int32_t *level_ends, int64_t *level_items, int32_t cap, int32_t *n_levels) {
+  return plan_shared_prefix(linvels, nv, angvels, nw, vx0, vtheta0, acc_x, acc_theta, sim_time, num_steps, n_agents, level_ends,
+                            level_items, cap, n_levels, true);
 }
 
 int sfw_plan_axis_classes(const double *targets, int32_t n, double v0, double a_max, double dt, int32_t max_p, int32_t form,

@@ -73,7 +73,8 @@ struct sfw_derived {
 
 // Shared-prefix rollout (K2).  Under the acceleration limits the robot's first P steps are
 // bit-identical for every sample of a CLASS (same clipped linear-velocity sequence x same clipped
-// angular-velocity sequence), hence so is the whole pedestrian simulation of those steps.  Classes
+// angular-velocity sequence up to the step before: the angular velocity of a step turns the heading
+// the NEXT step moves along), hence so is the whole pedestrian simulation of those steps.  Classes
 // refine as P grows, so the shared steps form a tree: level l simulates steps [P(l-1), P(l)) once per
 // class of level l, each class resuming from the record its parent class (level l-1) left and leaving
 // its own 64-byte record per agent; the suffix phase resumes every sample from its class of the last
@@ -164,7 +165,9 @@ struct sfw_launch {
   int32_t NG;
   int32_t n_grp_mem;
   // shared-prefix rollout (see sfw_cls_agent); chunks are whole grid rows when phase != WHOLE.
-  // Items of a PREFIX launch are the classes of one level (row class x column class), items of a
+  // Items of a PREFIX launch are the classes of one level (row class x column class; for a level ending at step p the row
+  // classes of the first p linear velocities and the column classes of the first p - 1 angular ones — a robot record holds
+  // the position, which takes the heading before its step: sfw_capi.hip prefix_classes::item_cols), items of a
   // SUFFIX / WHOLE launch are the chunk's samples.
   int32_t phase;                 // SFW_PHASE_*
   int32_t step_begin, step_end;  // steps this launch integrates

@@ -129,6 +129,7 @@ def lib():
         L.sfw_grid_costs_view.restype = C.c_void_p
         L.sfw_plan_shared_prefix.argtypes = [vp, C.c_int32, vp, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double,
                                              C.c_double, C.c_int32, C.c_int32, vp, vp, C.c_int32, C.POINTER(C.c_int32)]
+        L.sfw_plan_shared_prefix_items.argtypes = L.sfw_plan_shared_prefix.argtypes
         L.sfw_multi_grid_points.argtypes = [vp, C.c_int64, vp, C.c_int32, C.POINTER(C.c_int32)]
         L.sfw_batch_create.argtypes = [C.POINTER(SfwParams), C.c_int, C.c_int32, C.POINTER(vp)]
         L.sfw_batch_destroy.argtypes = [vp]
@@ -814,14 +815,15 @@ def plan_row_blocks(linvels, angvels, robot_state, goal_args, sim_time, num_step
 
 
 def planned_share(linvels, angvels, robot_state, goal_args, sim_time, num_steps, n_agents):
-    """Share of the algorithmic sample-steps the plan of this grid would integrate (sfw_plan_shared_prefix, host only)."""
+    """Share of the algorithmic sample-steps the plan of this grid would integrate (sfw_plan_shared_prefix_items: the work
+    items of each level, host only)."""
     lin, ang = _f64(linvels), _f64(angvels)
     ends, cls, n = np.zeros(64, dtype=np.int32), np.zeros(64, dtype=np.int64), C.c_int32()
-    rc = lib().sfw_plan_shared_prefix(lin.ctypes.data, len(lin), ang.ctypes.data, len(ang), robot_state[3], robot_state[5],
-                                      goal_args[0], goal_args[2], sim_time, num_steps, n_agents, ends.ctypes.data,
-                                      cls.ctypes.data, 64, C.byref(n))
+    rc = lib().sfw_plan_shared_prefix_items(lin.ctypes.data, len(lin), ang.ctypes.data, len(ang), robot_state[3], robot_state[5],
+                                            goal_args[0], goal_args[2], sim_time, num_steps, n_agents, ends.ctypes.data,
+                                            cls.ctypes.data, 64, C.byref(n))
     if rc != SFW_OK:
-        raise SfwError(rc, "sfw_plan_shared_prefix")
+        raise SfwError(rc, "sfw_plan_shared_prefix_items")
     k = min(n.value, 64)
     if k == 0:
         return 1.0
