@@ -158,6 +158,32 @@ struct mppi_buffers {
   }
 };
 
+// The scratch outputs of a re-run of some samples of the staged grid (sfw_grid_points_batch, sfw_grid_stop_points, crowd_run:
+// reserve_scratch, fill_scratch_launch), so that the launch's own results stay intact: one set per handle, kept across calls
+// (hipMalloc/hipFree synchronise the device) — per-sample records, the K1 tables, the stop check's records and tail table, the
+// path term's distance table and term
+struct rerun_buffers {
+  dev_buf<int32_t> status, coll, stop_steps, stop_hit;
+  dev_buf<double> base, costs, path_D, path_p;
+  dev_buf<sfw_unit> ptab, cs;
+  dev_buf<int16_t> fcode;
+  dev_buf<sfw_pose_frame> stop_tail;
+  void release() {
+    status.release();
+    coll.release();
+    stop_steps.release();
+    stop_hit.release();
+    base.release();
+    costs.release();
+    path_D.release();
+    path_p.release();
+    ptab.release();
+    cs.release();
+    fcode.release();
+    stop_tail.release();
+  }
+};
+
 }  // namespace
 
 // The handle's state, grouped by who owns it:
@@ -373,22 +399,18 @@ struct sfw_planner_s {
   dev_buf<int32_t> n_points;
   dev_buf<unsigned long long> clock;  // sfw_launch.clock_probe (timing only)
   dev_buf<char> one_out;  // sfw_score_one: cost | n_points | coll_step | points, contiguous -> one D2H
-  // scratch outputs of sfw_grid_points_batch's K1 re-run (kept across calls: hipMalloc/hipFree synchronise the device)
-  dev_buf<int32_t> pts_status, pts_coll;
-  dev_buf<double> pts_base, pts_costs;
-  dev_buf<sfw_unit> pts_ptab, pts_cs;
-  dev_buf<int16_t> pts_fcode;
+  rerun_buffers pts;  // the scratch outputs of the re-runs
   // the stop check's tail: per-sample records (T) and the per-chunk frame table (st.stop_cap rows of st.table_chunk frames);
-  // the scratch copies of the re-runs (fill_scratch_launch) and the poses sfw_grid_stop_points reads back
-  dev_buf<int32_t> stop_steps, stop_hit, pts_stop_steps, pts_stop_hit;
-  dev_buf<sfw_pose_frame> stop_tail, pts_stop_tail;
+  // the poses sfw_grid_stop_points reads back
+  dev_buf<int32_t> stop_steps, stop_hit;
+  dev_buf<sfw_pose_frame> stop_tail;
   dev_buf<double> stop_pts;
   // the path term: the stage's segment records (path_seg_sent: what the device copy holds, or is about to), the per-chunk
-  // distance table [S][st.table_chunk], the term per sample (T), and the scratch copies of the re-runs (fill_scratch_launch)
+  // distance table [S][st.table_chunk] and the term per sample (T)
   dev_buf<sfw_path_seg> path_seg;
   pinned_buf pin_path;  // the records on their way to path_seg
   std::vector<sfw_path_seg> path_seg_sent;
-  dev_buf<double> path_D, path_p, pts_path_D, pts_path_p, rescore_pw;
+  dev_buf<double> path_D, path_p, rescore_pw;
   pinned_buf pin_map, pin_arena, pin_out, pin_cls;
   pinned_buf pin_one;     // sfw_score_one's outputs where the one-launch kernel writes them (cost | n_points | coll_step | points)
   pinned_buf pin_mirror;  // costs + selection record as the selection kernels of the last launch leave them (device writes)
@@ -1311,36 +1333,35 @@ int plan_tables_device(sfw_handle h, int64_t chunk, bool may_start_poses) {
       SFW_HIP(h, h->cls_dead[b].reserve(static_cast<size_t>(h->st.cls_max)));
       SFW_HIP(h, h->cls_state[b].reserve(static_cast<size_t>(h->st.cls_max) * h->st.A));
     }
-  if (may_start_poses && chunk >= T) {
+  // (the fused small-grid K1 is one launch with the costmap part, and may capture points)
+  if (may_start_poses && chunk >= T && !sfw_rollout_is_fused(T, S)) {
     sfw_launch L;
     fill_launch(h, L, 0, T, T);
-    if (!sfw_rollout_is_fused(L)) {  // (the fused small-grid K1 is one launch with the costmap part, and may capture points)
-      h->st.clock_cleared = false;
-      if (h->live.timing) {  // the clock probe of a timed launch is cleared by the pose rollout itself (clear_clock_probe)
-        SFW_HIP(h, h->clock.reserve(4));
-        L.clock_probe = h->clock.p;
-        h->st.clock_cleared = true;
-      }
-      if (h->live.timing) SFW_HIP(h, hipEventRecord(h->ev[0], h->stream));
-      h->st.early_poses_timed = h->live.timing;
-      h->st.early_poses_terms = h->live.capture_terms;
-      if (h->live.capture_terms) {
-        SFW_HIP(h, h->terms.reserve(static_cast<size_t>(SFW_N_TERMS) * static_cast<size_t>(T)));
-        L.terms = h->terms.p;
-        L.terms_T = T;
-      }
-      arena_by_kernel(h, L);
-      if (h->st.arena_pending) {  // no copy was enqueued: this kernel reads its sample vectors at their host addresses
-        L.linvels = reinterpret_cast<const double *>(h->pin_arena.p + (reinterpret_cast<const char *>(h->st.d_linvels) - h->arena.p));
-        L.angvels = reinterpret_cast<const double *>(h->pin_arena.p + (reinterpret_cast<const char *>(h->st.d_angvels) - h->arena.p));
-        if (h->st.d_vy) L.vy_samps = reinterpret_cast<const double *>(h->pin_arena.p + (reinterpret_cast<const char *>(h->st.d_vy) - h->arena.p));
-        if (h->st.d_knot_step)
-          L.knot_step = reinterpret_cast<const int32_t *>(h->pin_arena.p + (reinterpret_cast<const char *>(h->st.d_knot_step) - h->arena.p));
-      }
-      SFW_HIP(h, sfw_launch_rollout_poses(L, h->stream));
-      SFW_HIP(h, arena_fetched(h));
-      h->st.early_poses = true;
+    h->st.clock_cleared = false;
+    if (h->live.timing) {  // the clock probe of a timed launch is cleared by the pose rollout itself (clear_clock_probe)
+      SFW_HIP(h, h->clock.reserve(4));
+      L.clock_probe = h->clock.p;
+      h->st.clock_cleared = true;
     }
+    if (h->live.timing) SFW_HIP(h, hipEventRecord(h->ev[0], h->stream));
+    h->st.early_poses_timed = h->live.timing;
+    h->st.early_poses_terms = h->live.capture_terms;
+    if (h->live.capture_terms) {
+      SFW_HIP(h, h->terms.reserve(static_cast<size_t>(SFW_N_TERMS) * static_cast<size_t>(T)));
+      L.terms = h->terms.p;
+      L.terms_T = T;
+    }
+    arena_by_kernel(h, L);
+    if (h->st.arena_pending) {  // no copy was enqueued: this kernel reads its sample vectors at their host addresses
+      L.linvels = reinterpret_cast<const double *>(h->pin_arena.p + (reinterpret_cast<const char *>(h->st.d_linvels) - h->arena.p));
+      L.angvels = reinterpret_cast<const double *>(h->pin_arena.p + (reinterpret_cast<const char *>(h->st.d_angvels) - h->arena.p));
+      if (h->st.d_vy) L.vy_samps = reinterpret_cast<const double *>(h->pin_arena.p + (reinterpret_cast<const char *>(h->st.d_vy) - h->arena.p));
+      if (h->st.d_knot_step)
+        L.knot_step = reinterpret_cast<const int32_t *>(h->pin_arena.p + (reinterpret_cast<const char *>(h->st.d_knot_step) - h->arena.p));
+    }
+    SFW_HIP(h, sfw_launch_rollout_poses(L, h->stream));
+    SFW_HIP(h, arena_fetched(h));
+    h->st.early_poses = true;
   }
   return SFW_OK;
 }
@@ -1830,9 +1851,7 @@ int launch_prepare(sfw_handle h, bool timing, launch_prep &lp) {
     // planning anyway, instead of between the rollout and the first K2 dispatch)
     // ... or will be by the pose rollout this launch enqueues; only the small-grid kernels (a block per sample, no kernel in
     // front of their K2 part) need the memset
-    sfw_launch probe0;
-    fill_launch(h, probe0, 0, std::min<int64_t>(T, chunk), chunk);
-    if (!(poses_done && h->st.clock_cleared) && sfw_rollout_is_fused(probe0))
+    if (!(poses_done && h->st.clock_cleared) && sfw_rollout_is_fused(std::min<int64_t>(T, chunk), S))
       SFW_HIP(h, hipMemsetAsync(h->clock.p, 0, 4 * sizeof(unsigned long long), h->stream));
     if (!poses_done) SFW_HIP(h, hipEventRecord(h->ev[0], h->stream));
   }
@@ -1849,9 +1868,7 @@ int launch_prepare(sfw_handle h, bool timing, launch_prep &lp) {
   // Trajectory points on request (sfw_set_points_capture), when the whole grid goes through the fused K1
   char *cap_pts = nullptr, *cap_n = nullptr, *cap_coll = nullptr;
   if (h->live.capture_points && single) {
-    sfw_launch probe;
-    fill_launch(h, probe, 0, T, chunk);
-    if (sfw_rollout_is_fused(probe)) {
+    if (sfw_rollout_is_fused(T, S)) {
       const size_t pts_bytes = sizeof(double) * 3 * static_cast<size_t>(S) * static_cast<size_t>(T);
       // (in pinned HOST memory: the kernels write points, counts and contact steps over PCIe as they go — 43 KB for 45 samples
       // of 40 steps — and the dump is a memcpy; until round 5 a device buffer and a D2H copy per dump, 12 us)
@@ -1897,22 +1914,30 @@ int launch_prepare(sfw_handle h, bool timing, launch_prep &lp) {
   return SFW_OK;
 }
 
+// What a launch record of the staged grid writes beside the handle's own per-sample buffers: the captured points, the clock
+// probe of a timed launch, the captured terms
+void bind_launch_outputs(sfw_handle h, const launch_prep &lp, sfw_launch &L) {
+  if (h->last.captured) {
+    L.points = reinterpret_cast<double *>(lp.cap_pts);
+    L.n_points = reinterpret_cast<int32_t *>(lp.cap_n);
+    L.coll_step = reinterpret_cast<int32_t *>(lp.cap_coll);
+    // a sample the costmap rejects at pose a may touch a pedestrian at an earlier step b < a, where the reference's
+    // Trajectory ends (ref :613-627): integrated all the same, its cost stays -1 (finish_wave)
+    L.force_alive = 1;
+  }
+  L.clock_probe = lp.timing ? h->clock.p : nullptr;  // every K2 dispatch writes it; the last one (the launch over the samples) stays
+  L.terms = lp.terms;
+  L.terms_T = lp.T;
+}
+
 // A control cycle's grid: K1 + K2 + K3 in ONE launch (sfw_cycle_kernel) when the launch qualifies.  Step 1: the launch record
 // (false: it does not qualify; nothing has changed).
 bool cycle_launch_of(sfw_handle h, const launch_prep &lp, sfw_launch &L) {
   if (!(lp.single && !lp.prefix && !lp.poses_done)) return false;
   fill_launch(h, L, 0, lp.T, lp.chunk);
-  if (h->last.captured) {
-    L.points = reinterpret_cast<double *>(lp.cap_pts);
-    L.n_points = reinterpret_cast<int32_t *>(lp.cap_n);
-    L.coll_step = reinterpret_cast<int32_t *>(lp.cap_coll);
-    L.force_alive = 1;  // (as in launch_kernels)
-  }
-  L.clock_probe = lp.timing ? h->clock.p : nullptr;
+  bind_launch_outputs(h, lp, L);
   L.costs_host = lp.costs_host;
   L.sel_host = lp.sel_host;
-  L.terms = lp.terms;
-  L.terms_T = lp.T;
   if (!sfw_cycle_applies(L)) return false;
   arena_by_kernel(h, L);  // no copy at all this cycle
   return true;
@@ -1936,7 +1961,6 @@ int launch_kernels(sfw_handle h, const launch_prep &lp) {
   const int64_t T = lp.T, chunk = lp.chunk;
   const int S = lp.S;
   const bool prefix = lp.prefix, poses_done = lp.poses_done, single = lp.single, timing = lp.timing;
-  char *const cap_pts = lp.cap_pts, *const cap_n = lp.cap_n, *const cap_coll = lp.cap_coll;
   double *const costs_host = lp.costs_host;
   sfw_sel *const sel_host = lp.sel_host;
   if (int e = flush_arena(h)) return e;
@@ -1945,17 +1969,7 @@ int launch_kernels(sfw_handle h, const launch_prep &lp) {
     const int64_t n = (T - b < chunk) ? (T - b) : chunk;
     sfw_launch L;
     fill_launch(h, L, b, n, chunk);
-    if (h->last.captured) {
-      L.points = reinterpret_cast<double *>(cap_pts);
-      L.n_points = reinterpret_cast<int32_t *>(cap_n);
-      L.coll_step = reinterpret_cast<int32_t *>(cap_coll);
-      // a sample the costmap rejects at pose a may touch a pedestrian at an earlier step b < a, where the reference's
-      // Trajectory ends (ref :613-627): integrated all the same, its cost stays -1 (finish_wave)
-      L.force_alive = 1;
-    }
-    L.clock_probe = timing ? h->clock.p : nullptr;  // every K2 dispatch writes it; the last one (the launch over the samples) stays
-    L.terms = lp.terms;
-    L.terms_T = T;
+    bind_launch_outputs(h, lp, L);
     if (!single && timing) SFW_HIP(h, hipEventRecord(h->chunk_ev[3 * c], h->stream));
     if (prefix) {
       // K1a -> { K2 prefix phase on the main stream  ||  K1b + K1c on the side stream } -> K2 suffix phase.
@@ -2355,44 +2369,54 @@ int score_staged(sfw_handle h, int staged, double *costs_out, sfw_best *best_out
   return sfw_grid_fetch(h, costs_out, best_out, nullptr);
 }
 
-// The launch record of samples [first, first + count) run once more, alone, into the scratch outputs (the launch's own results
-// stay intact).  The kernels index per-sample outputs by the global sample index: the pointers are biased by -first.
-// path: the re-run also forms the path term, into scratch of its own (reserve_scratch_path in front) — crowd_run, whose cost
-// carries the term; the re-runs that only want poses leave the term's kernels out
-void fill_scratch_launch(sfw_handle h, sfw_launch &L, int64_t first, int64_t count, bool path = false) {
-  fill_launch(h, L, first, count, count);
-  L.status = h->pts_status.p - first;
-  L.base_cost = h->pts_base.p - first;
-  L.ptab = h->pts_ptab.p;
-  L.cs_tab = h->pts_cs.p;
-  if (h->st.stop_on) {  // (reserve_scratch_stop)
-    L.stop_tail = h->pts_stop_tail.p;
-    L.stop_steps = h->pts_stop_steps.p - first;
-    L.stop_hit = h->pts_stop_hit.p - first;
+// The scratch set (rerun_buffers) for a re-run of `count` samples of the staged grid.  path: the re-run also forms the path
+// term — crowd_run, whose cost carries the term; the re-runs that only want poses leave the term's kernels out.
+hipError_t reserve_scratch(sfw_handle h, int64_t count, bool path) {
+  rerun_buffers &b = h->pts;
+  const size_t n = static_cast<size_t>(count), S = static_cast<size_t>(num_steps_of(h->live.params));
+  hipError_t e = b.status.reserve(n);
+  if (e == hipSuccess) e = b.coll.reserve(n);
+  if (e == hipSuccess) e = b.base.reserve(n);
+  if (e == hipSuccess) e = b.costs.reserve(n);
+  if (e == hipSuccess) e = b.ptab.reserve(S * static_cast<size_t>(table_row_units(count, h->st.nw)));
+  if (e == hipSuccess) e = b.cs.reserve(S * (h->st.list ? n : static_cast<size_t>(h->st.nw)));
+  if (e == hipSuccess) e = b.fcode.reserve(S * n);
+  if (h->st.stop_on) {
+    if (e == hipSuccess) e = b.stop_steps.reserve(n);
+    if (e == hipSuccess) e = b.stop_hit.reserve(n);
+    if (e == hipSuccess) e = b.stop_tail.reserve(n * static_cast<size_t>(h->st.stop_cap));
   }
-  if (h->st.path_on && path) {  // (reserve_scratch_path)
-    L.path_D = h->pts_path_D.p;
-    L.path_p = h->pts_path_p.p - first;
+  if (h->st.path_on && path) {
+    if (e == hipSuccess) e = b.path_p.reserve(n);
+    if (e == hipSuccess) e = b.path_D.reserve(n * S);
+  }
+  return e;
+}
+// The launch record of samples [first, first + count) run once more, alone, into that set (reserve_scratch with the same count
+// and path in front).  The kernels index per-sample outputs by the global sample index: the pointers are biased by -first.
+// coll: the re-run's contact steps go to the set too (else nowhere: the launch's own are kept).
+void fill_scratch_launch(sfw_handle h, sfw_launch &L, int64_t first, int64_t count, bool path, bool coll) {
+  const rerun_buffers &b = h->pts;
+  fill_launch(h, L, first, count, count);
+  L.status = b.status.p - first;
+  L.base_cost = b.base.p - first;
+  L.costs = b.costs.p - first;
+  L.coll_step = coll ? b.coll.p - first : nullptr;
+  L.ptab = b.ptab.p;
+  L.cs_tab = b.cs.p;
+  L.fcode = b.fcode.p;
+  if (h->st.stop_on) {
+    L.stop_tail = b.stop_tail.p;
+    L.stop_steps = b.stop_steps.p - first;
+    L.stop_hit = b.stop_hit.p - first;
+  }
+  if (h->st.path_on && path) {
+    L.path_D = b.path_D.p;
+    L.path_p = b.path_p.p - first;
   } else {
     L.path_on = 0;
     L.path_D = L.path_p = nullptr;
   }
-}
-// ... and the stop check's scratch records for such a re-run of `count` samples (nothing to do with the check off)
-hipError_t reserve_scratch_stop(sfw_handle h, int64_t count) {
-  if (!h->st.stop_on) return hipSuccess;
-  hipError_t e = h->pts_stop_steps.reserve(static_cast<size_t>(count));
-  if (e == hipSuccess) e = h->pts_stop_hit.reserve(static_cast<size_t>(count));
-  if (e == hipSuccess) e = h->pts_stop_tail.reserve(static_cast<size_t>(count) * static_cast<size_t>(h->st.stop_cap));
-  return e;
-}
-
-// ... and the path term's scratch (distance table and term) for a re-run with fill_scratch_launch(..., path = true)
-hipError_t reserve_scratch_path(sfw_handle h, int64_t count) {
-  if (!h->st.path_on) return hipSuccess;
-  hipError_t e = h->pts_path_p.reserve(static_cast<size_t>(count));
-  if (e == hipSuccess) e = h->pts_path_D.reserve(static_cast<size_t>(count) * static_cast<size_t>(num_steps_of(h->live.params)));
-  return e;
 }
 
 // The one-sample stage of sfw_score_one / sfw_score_one_crowd.  The agent set is checked before the stage (a refused call leaves
@@ -2415,14 +2439,16 @@ void score_one_outputs_at(sfw_launch &L, char *base) {
   L.coll_step = reinterpret_cast<int32_t *>(base + 12);
   L.points = reinterpret_cast<double *>(base + kOneHead);
 }
+// The points of a Trajectory of n poses whose pedestrian contact step is coll (-1: none): rejected by contact at step c, the
+// poses (steps) 0..c were added — addPoint precedes the test (ref :578, :613-627)
+int32_t contact_trim(int32_t n, int32_t coll) { return (coll >= 0 && coll + 1 < n) ? coll + 1 : n; }
 // ... and from a host copy of them to the caller
 int32_t one_head_unpack(const char *src, double *cost_out) {  // -> the point (step) count
   int32_t n = 0, coll = -1;
   if (cost_out) std::memcpy(cost_out, src, sizeof(double));
   std::memcpy(&n, src + 8, sizeof(n));
   std::memcpy(&coll, src + 12, sizeof(coll));
-  if (coll >= 0 && coll + 1 < n) n = coll + 1;  // rejected by contact at step `coll`: poses (steps) 0..coll were added (integrated)
-  return n;
+  return contact_trim(n, coll);
 }
 void score_one_unpack(const char *src, double *cost_out, double *points_xyth, int32_t points_cap, int32_t *n_points) {
   const int32_t n = one_head_unpack(src, cost_out);
@@ -2590,26 +2616,15 @@ int destroy_handle(sfw_handle h) {
   h->points.release();
   h->n_points.release();
   h->one_out.release();
-  h->pts_status.release();
-  h->pts_coll.release();
-  h->pts_base.release();
-  h->pts_costs.release();
-  h->pts_ptab.release();
-  h->pts_cs.release();
-  h->pts_fcode.release();
+  h->pts.release();
   h->stop_steps.release();
   h->stop_hit.release();
-  h->pts_stop_steps.release();
-  h->pts_stop_hit.release();
   h->stop_tail.release();
-  h->pts_stop_tail.release();
   h->stop_pts.release();
   h->path_seg.release();
   h->pin_path.release();
   h->path_D.release();
   h->path_p.release();
-  h->pts_path_D.release();
-  h->pts_path_p.release();
   h->rescore_pw.release();
   h->pin_map.release();
   h->pin_arena.release();
@@ -3215,27 +3230,17 @@ int sfw_grid_stop_points(sfw_handle h, int64_t first, int64_t count, int32_t ste
     return fail(h, SFW_ERR_INVALID_ARG, "grid_stop_points: bad range, steps_cap < 1 or null buffer");
   SFW_HIP(h, hipSetDevice(h->device));
   if (int e = flush_arena(h)) return e;  // (the re-run below reads the device copy of the arena)
-  const int S = num_steps_of(h->live.params);
   const size_t n = static_cast<size_t>(count), pts = 3 * static_cast<size_t>(steps_cap) * n;
   // K1 and the tail once more for those samples into scratch outputs, as sfw_grid_points_batch does
-  SFW_HIP(h, h->pts_status.reserve(n));
-  SFW_HIP(h, h->pts_base.reserve(n));
-  SFW_HIP(h, h->pts_costs.reserve(n));
-  SFW_HIP(h, h->pts_ptab.reserve(static_cast<size_t>(S) * static_cast<size_t>(table_row_units(count, h->st.nw))));
-  SFW_HIP(h, h->pts_cs.reserve(static_cast<size_t>(S) * (h->st.list ? n : static_cast<size_t>(h->st.nw))));
-  SFW_HIP(h, h->pts_fcode.reserve(static_cast<size_t>(S) * n));
-  SFW_HIP(h, reserve_scratch_stop(h, count));
+  SFW_HIP(h, reserve_scratch(h, count, false));
   SFW_HIP(h, h->stop_pts.reserve(pts));
   sfw_launch L;
-  fill_scratch_launch(h, L, first, count);
-  L.costs = h->pts_costs.p - first;
-  L.coll_step = nullptr;
-  L.fcode = h->pts_fcode.p;
+  fill_scratch_launch(h, L, first, count, false, false);
   L.stop_points = h->stop_pts.p;
   L.stop_points_cap = steps_cap;
   SFW_HIP(h, hipMemsetAsync(h->stop_pts.p, 0, sizeof(double) * pts, h->stream));  // (poses behind a tail's end: zeros)
   SFW_HIP(h, sfw_launch_rollout(L, h->stream));
-  SFW_HIP(h, hipMemcpyAsync(n_steps, h->pts_stop_steps.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, h->stream));
+  SFW_HIP(h, hipMemcpyAsync(n_steps, h->pts.stop_steps.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, h->stream));
   SFW_HIP(h, hipMemcpyAsync(points_xyth, h->stop_pts.p, sizeof(double) * pts, hipMemcpyDeviceToHost, h->stream));
   SFW_HIP(h, hipStreamSynchronize(h->stream));
   return SFW_OK;
@@ -3480,32 +3485,16 @@ int sfw_grid_points_batch(sfw_handle h, int64_t first, int64_t count, double *po
     }
     const int32_t *np = reinterpret_cast<const int32_t *>(h->pin_cap.p + pts_bytes), *coll = np + T;
     std::memcpy(points_xyth, h->pin_cap.p + sizeof(double) * 3 * static_cast<size_t>(S) * static_cast<size_t>(first), sizeof(double) * 3 * S * n);
-    for (size_t i = 0; i < n; ++i) {
-      const int32_t c = coll[first + static_cast<int64_t>(i)];
-      int32_t k = np[first + static_cast<int64_t>(i)];
-      if (c >= 0 && c + 1 < k) k = c + 1;  // rejected by contact at step c: poses 0..c were added (ref :578, :613-627)
-      n_points[i] = k;
-    }
+    for (size_t i = 0; i < n; ++i) n_points[i] = contact_trim(np[first + static_cast<int64_t>(i)], coll[first + static_cast<int64_t>(i)]);
     return SFW_OK;
   }
   SFW_HIP(h, h->points.reserve(3 * static_cast<size_t>(S) * n));
   SFW_HIP(h, h->n_points.reserve(n));
-  // Re-run K1 for those samples into scratch outputs so the grid results stay intact.  The scratch is
-  // `count` records long and lives in the handle; the kernels index per-sample outputs by the global
-  // sample index, so the pointers are biased by -first.
-  hipError_t e = h->pts_status.reserve(n);
-  if (e == hipSuccess) e = h->pts_base.reserve(n);
-  if (e == hipSuccess) e = h->pts_costs.reserve(n);
-  if (e == hipSuccess) e = h->pts_ptab.reserve(static_cast<size_t>(S) * static_cast<size_t>(table_row_units(count, h->st.nw)));
-  if (e == hipSuccess) e = h->pts_cs.reserve(static_cast<size_t>(S) * (h->st.list ? n : static_cast<size_t>(h->st.nw)));
-  if (e == hipSuccess) e = h->pts_fcode.reserve(static_cast<size_t>(S) * n);
-  if (e == hipSuccess) e = reserve_scratch_stop(h, count);
+  // Re-run K1 for those samples into scratch outputs so the grid results stay intact.
+  hipError_t e = reserve_scratch(h, count, false);
   if (e == hipSuccess) {
     sfw_launch L;
-    fill_scratch_launch(h, L, first, count);
-    L.costs = h->pts_costs.p - first;
-    L.coll_step = nullptr;  // keep the launch's contact steps
-    L.fcode = h->pts_fcode.p;
+    fill_scratch_launch(h, L, first, count, false, false);  // (keep the launch's contact steps)
     L.points = h->points.p;
     L.n_points = h->n_points.p;
     e = sfw_launch_rollout(L, h->stream);
@@ -3530,20 +3519,15 @@ int sfw_grid_points_batch(sfw_handle h, int64_t first, int64_t count, double *po
   for (size_t i = 0; i < n && !rejected; ++i) rejected = n_points[i] < S;
   if ((rejected || coll_elsewhere) && h->st.A > 1) {
     if (int rc = check_lds(h, h->st.A, h->st.O, h->st.NG, h->st.n_grp_mem, count)) return rc;
-    SFW_HIP(h, h->pts_coll.reserve(n));
     sfw_launch L;
-    fill_scratch_launch(h, L, first, count);
-    L.costs = h->pts_costs.p - first;
-    L.coll_step = h->pts_coll.p - first;
+    fill_scratch_launch(h, L, first, count, false, true);
     L.force_alive = 1;
-    SFW_HIP(h, hipMemsetAsync(h->pts_coll.p, 0xff, sizeof(int32_t) * n, h->stream));  // -1: no contact
+    SFW_HIP(h, hipMemsetAsync(h->pts.coll.p, 0xff, sizeof(int32_t) * n, h->stream));  // -1: no contact
     SFW_HIP(h, launch_social_of(L, h->stream));
-    SFW_HIP(h, hipMemcpyAsync(coll.data(), h->pts_coll.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, h->stream));
+    SFW_HIP(h, hipMemcpyAsync(coll.data(), h->pts.coll.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, h->stream));
     SFW_HIP(h, hipStreamSynchronize(h->stream));
   }
-  // a trajectory rejected by contact at step i holds the poses 0..i (addPoint precedes the test, ref :578, :613-627)
-  for (size_t i = 0; i < n; ++i)
-    if (coll[i] >= 0 && coll[i] + 1 < n_points[i]) n_points[i] = coll[i] + 1;
+  for (size_t i = 0; i < n; ++i) n_points[i] = contact_trim(n_points[i], coll[i]);
   return SFW_OK;
 }
 
@@ -3585,13 +3569,7 @@ int crowd_run(sfw_handle h, int64_t t, double *cost_out, double *state_xyvv, dou
   const size_t head = 16, o_work = head + sizeof(double) * 4 * SA, o_hg = o_work + sizeof(double) * SA,
                total = o_hg + sizeof(int32_t) * SA;
   SFW_HIP(h, h->crowd_out.reserve(total));
-  SFW_HIP(h, h->pts_status.reserve(1));
-  SFW_HIP(h, h->pts_base.reserve(1));
-  SFW_HIP(h, h->pts_ptab.reserve(static_cast<size_t>(S) * static_cast<size_t>(table_row_units(1, h->st.nw))));
-  SFW_HIP(h, h->pts_cs.reserve(static_cast<size_t>(S) * (h->st.list ? size_t(1) : static_cast<size_t>(h->st.nw))));
-  SFW_HIP(h, h->pts_fcode.reserve(static_cast<size_t>(S)));
-  SFW_HIP(h, reserve_scratch_stop(h, 1));
-  SFW_HIP(h, reserve_scratch_path(h, 1));
+  SFW_HIP(h, reserve_scratch(h, 1, true));
   if (A > 0 && h->crowd_pair_tab_A != A) {
     h->crowd_pair_tab_A = -1;  // (until the table for this count is enqueued)
     SFW_HIP(h, h->crowd_pair_tab.reserve(static_cast<size_t>(sfw_pair_table_entries(A))));
@@ -3600,11 +3578,10 @@ int crowd_run(sfw_handle h, int64_t t, double *cost_out, double *state_xyvv, dou
   }
   char *const out = h->crowd_out.p;
   sfw_launch L;
-  fill_scratch_launch(h, L, t, 1, true);  // (with the path term: the sample's cost carries it)
+  fill_scratch_launch(h, L, t, 1, true, false);  // (with the path term: the sample's cost carries it)
   L.costs = reinterpret_cast<double *>(out) - t;
   L.coll_step = reinterpret_cast<int32_t *>(out + 12) - t;
   L.n_points = reinterpret_cast<int32_t *>(out + 8);
-  L.fcode = h->pts_fcode.p;
   L.pair_tab = h->crowd_pair_tab.p;
   L.force_alive = 1;
   SFW_HIP(h, sfw_launch_rollout(L, h->stream));
@@ -4653,18 +4630,29 @@ int ensemble_enqueue(sfw_ensemble e, int32_t mode, const double *probs, bool reu
   // sfw_set_path: member 0's term and weight as its stage found them (null: the five terms alone)
   const double *const path_p = h0->st.path_on ? h0->path_p.p : nullptr;
   const double path_w = h0->st.path_weight;
-  const hipError_t he =
-      e->risk_on
-          ? sfw_launch_ensemble_risk(d_terms, d_probs, M, T, mode, w, e->risk.tail_mass, e->risk.contact_mass, thr, list,
-                                     h0->st.d_linvels, h0->st.d_angvels, h0->st.nw, reinterpret_cast<double *>(out),
-                                     list && e->mirrored ? e->d_cost.p : nullptr, reinterpret_cast<int32_t *>(out + cost_bytes),
-                                     e->partials.p, reinterpret_cast<sfw_sel *>(e->pin_out.p), e->b->stream, path_p, path_w)
-      : list ? sfw_launch_ensemble_list(d_terms, d_probs, M, T, mode, w, h0->st.d_linvels, h0->st.d_angvels, reinterpret_cast<double *>(out),
-                                      e->mirrored ? e->d_cost.p : nullptr, reinterpret_cast<int32_t *>(out + cost_bytes),
-                                      e->partials.p, reinterpret_cast<sfw_sel *>(e->pin_out.p), e->b->stream, path_p, path_w)
-           : sfw_launch_ensemble(d_terms, d_probs, M, T, mode, w, h0->st.d_linvels, h0->st.d_angvels, h0->st.nw,
-                                 reinterpret_cast<double *>(out), reinterpret_cast<int32_t *>(out + cost_bytes), e->partials.p,
-                                 reinterpret_cast<sfw_sel *>(e->pin_out.p), e->b->stream, path_p, path_w);
+  sfw_ensemble_launch a{};
+  a.terms = d_terms;
+  a.probs = d_probs;
+  a.M = M;
+  a.T = T;
+  a.mode = mode;
+  a.w = w;
+  a.list = list;
+  a.linvels = h0->st.d_linvels;
+  a.angvels = h0->st.d_angvels;
+  a.nw = h0->st.nw;
+  a.costs = reinterpret_cast<double *>(out);
+  a.costs_dev = list && e->mirrored ? e->d_cost.p : nullptr;
+  a.rejected = reinterpret_cast<int32_t *>(out + cost_bytes);
+  a.partials = e->partials.p;
+  a.sel_host = reinterpret_cast<sfw_sel *>(e->pin_out.p);
+  a.risk = e->risk_on;
+  a.tail_mass = e->risk.tail_mass;
+  a.contact_mass = e->risk.contact_mass;
+  a.thr = thr;
+  a.path_p = path_p;
+  a.path_w = path_w;
+  const hipError_t he = sfw_launch_ensemble(a, e->b->stream);
   if (he != hipSuccess)
     return efail(e, SFW_ERR_HIP, std::string(e->risk_on ? (list ? "ensemble: sfw_ens_risk_list / sfw_ensemble_stage2: "
                                                                 : "ensemble: sfw_ens_risk_grid / sfw_ensemble_stage2: ")

@@ -366,7 +366,8 @@ hipError_t sfw_launch_crowd_strict(const sfw_launch &L, const sfw_crowd_out &cw,
 // (sfw_kernels.hip sfw_crowd_kernel).  L.pair_tab must be a table built with runtime_cap (below); L.A >= 1.
 hipError_t sfw_launch_crowd(const sfw_launch &L, const sfw_crowd_out &cw, hipStream_t stream);
 // true when sfw_launch_rollout_poses runs all of K1 in one launch (small grids): the only form that writes L.points
-bool sfw_rollout_is_fused(const sfw_launch &L);
+// (of a launch over `count` samples of S steps)
+bool sfw_rollout_is_fused(int64_t count, int S);
 // Reduces costs[0..T) to one sfw_sel at *out (device memory).  partials must
 // hold >= sfw_argmin_partials(T) records.
 int64_t sfw_argmin_partials(int64_t T);
@@ -387,26 +388,32 @@ hipError_t sfw_launch_rescore(const double *terms, int64_t T, const sfw_weights 
 // wave-uniformly — cost + path_w[k] * p behind the five-term sum where the cost is not a sentinel.  Null: the five terms alone.)
 // sfw_ensemble_*: M members' captured terms (terms: device table of M pointers to SoA [5][T]; probs: M doubles, MEAN only —
 // both read wave-uniformly) -> costs[T], rejected[T] (pinned or device) and the record at sel_host (pinned).  partials:
-// sfw_argmin_partials(T) records.
-hipError_t sfw_launch_ensemble(const double *const *terms, const double *probs, int M, int64_t T, int mode, const sfw_weights &w,
-                               const double *linvels, const double *angvels, int32_t nw, double *costs, int32_t *rejected,
-                               sfw_sel *partials, sfw_sel *sel_host, hipStream_t stream, const double *path_p = nullptr,
-                               double path_w = 0.0);
-// (path_p, nullable, here and in the two forms below: member 0's path term — path_w * p[t] is added behind the aggregated
-// five-term cost of a sample that is not rejected, in front of the selection.  Null: the five terms alone.)
-// ... over a LIST the members staged (sfw_launch.list): linvels / angvels hold one value per sample (the first knot row), the
-// selection is the list's, no sample is skipped.  costs_dev (nullable): a second, device-resident copy of the cost vector.
-hipError_t sfw_launch_ensemble_list(const double *const *terms, const double *probs, int M, int64_t T, int mode,
-                                    const sfw_weights &w, const double *linvels, const double *angvels, double *costs,
-                                    double *costs_dev, int32_t *rejected, sfw_sel *partials, sfw_sel *sel_host, hipStream_t stream,
-                                    const double *path_p = nullptr, double path_w = 0.0);
-// ... under a risk (sfw_ensemble_set_risk): the grid's first stage (list false: nw, no costs_dev) or the list's, then the same
-// second stage.  thr = contact_mass * P, the host's product.
-hipError_t sfw_launch_ensemble_risk(const double *const *terms, const double *probs, int M, int64_t T, int mode,
-                                    const sfw_weights &w, double tail_mass, double contact_mass, double thr, bool list,
-                                    const double *linvels, const double *angvels, int32_t nw, double *costs, double *costs_dev,
-                                    int32_t *rejected, sfw_sel *partials, sfw_sel *sel_host, hipStream_t stream,
-                                    const double *path_p = nullptr, double path_w = 0.0);
+// sfw_argmin_partials(T) records.  One first stage of four, then the same second stage.
+struct sfw_ensemble_launch {
+  const double *const *terms;
+  const double *probs;
+  int M;
+  int64_t T;
+  int mode;
+  sfw_weights w;
+  // over a LIST the members staged (sfw_launch.list): linvels / angvels hold one value per sample (the first knot row), the
+  // selection is the list's, no sample is skipped, nw is not read.  costs_dev (nullable, a list's only): a second,
+  // device-resident copy of the cost vector.
+  bool list;
+  const double *linvels, *angvels;
+  int32_t nw;
+  double *costs, *costs_dev;
+  int32_t *rejected;
+  sfw_sel *partials, *sel_host;
+  // under a risk (sfw_ensemble_set_risk; M <= SFW_ENSEMBLE_MAX_M): thr = contact_mass * P, the host's product
+  bool risk;
+  double tail_mass, contact_mass, thr;
+  // path_p (nullable): member 0's path term — path_w * p[t] is added behind the aggregated five-term cost of a sample that is not
+  // rejected, in front of the selection.  Null: the five terms alone.
+  const double *path_p;
+  double path_w;
+};
+hipError_t sfw_launch_ensemble(const sfw_ensemble_launch &a, hipStream_t stream);
 // sfw_grid_blend: the cost vector (+ bias, nullable) of a launch over T samples -> softmin weights for L temperatures, their
 // sums and the weighted mean of the K knot rows (list: linvels / vy (nullable) / angvels hold K rows of T values, knot-major;
 // else a grid of T / nw x nw samples, K == 1).  Three launches: `mins` (sfw_blend_min_blocks(T) records), `partials`

@@ -3943,27 +3943,34 @@ static bool sfw_k1a_threads() {
   return e && e[0] == '1';
 }
 
-bool sfw_rollout_is_fused(const sfw_launch &L) { return L.chunk_count <= 2048 && L.S <= K1_SMALL_MAX_STEPS; }
+bool sfw_rollout_is_fused(int64_t count, int S) { return count <= 2048 && S <= K1_SMALL_MAX_STEPS; }
+
+// What picks a kernel of a family for a launch.  Its stage kind: sequences of more than one knot (2) / a sample list (1) / a
+// grid (0) — a sequence stage of one knot is a list.  Its K2 variant: the kernels with the group pass (2: at least one agent
+// carries a group id) / with the laser-point pass (1) / with neither (0).
+static int stage_kind(const sfw_launch &L) { return L.n_knots > 1 ? 2 : L.list ? 1 : 0; }
+static int k2_variant(const sfw_launch &L) { return L.NG > 0 ? 2 : L.O > 0 ? 1 : 0; }
+// A robot alone without a laser point has no social work to integrate (sfw_no_social_kernel, cycle_block)
+static bool has_social_work(const sfw_launch &L) { return L.A > 0 && !(L.A == 1 && L.O == 0 && L.NG == 0); }
+
+// K1's pose rollout <LIST, SEQ> for a stage kind: the fused small-grid K1 (a block per sample), K1a as one thread per sample,
+// or K1a in teams
+enum k1_form { K1_SMALL, K1_THREADS, K1_TEAM };
+static auto k1_kernel_for(k1_form f, int kind) -> void (*)(const sfw_launch) {
+  if (f == K1_SMALL) return kind == 2 ? sfw_rollout_small_kernel<true, true> : kind == 1 ? sfw_rollout_small_kernel<true> : sfw_rollout_small_kernel<false>;
+  if (f == K1_THREADS) return kind == 2 ? sfw_rollout_kernel<true, true> : kind == 1 ? sfw_rollout_kernel<true> : sfw_rollout_kernel<false>;
+  return kind == 2 ? sfw_rollout_team_kernel<true, true> : kind == 1 ? sfw_rollout_team_kernel<true> : sfw_rollout_team_kernel<false>;
+}
 
 // K1a alone (pose integration + robot-step table), or the fused small-grid K1.
 hipError_t sfw_launch_rollout_poses(const sfw_launch &L, hipStream_t stream) {
   if (L.chunk_count <= 0) return hipSuccess;
-  if (sfw_rollout_is_fused(L)) {  // latency path: one launch does all of K1
-    hipLaunchKernelGGL((L.n_knots > 1 ? sfw_rollout_small_kernel<true, true> : L.list ? sfw_rollout_small_kernel<true> : sfw_rollout_small_kernel<false>),
-                       dim3(static_cast<unsigned>(L.chunk_count)), dim3(K1_SMALL_BLOCK), 0, stream, L);
-    return hipGetLastError();
-  }
-  const int block = 64;  // latency-bound serial rollout: spread the waves over all CUs
-  if (sfw_k1a_threads()) {  // SFW_K1A_THREADS=1: round 1-5's one thread per sample (A/B and the equality test)
-    const unsigned grid = static_cast<unsigned>((L.chunk_count + block - 1) / block);
-    hipLaunchKernelGGL((L.n_knots > 1 ? sfw_rollout_kernel<true, true> : L.list ? sfw_rollout_kernel<true> : sfw_rollout_kernel<false>),
-                       dim3(grid), dim3(block), 0, stream, L);
-    return hipGetLastError();
-  }
-  constexpr int per_wave = WAVE / K1A_TEAM;
-  const unsigned grid = static_cast<unsigned>((L.chunk_count + per_wave - 1) / per_wave);
-  hipLaunchKernelGGL((L.n_knots > 1 ? sfw_rollout_team_kernel<true, true> : L.list ? sfw_rollout_team_kernel<true> : sfw_rollout_team_kernel<false>),
-                     dim3(grid), dim3(block), 0, stream, L);
+  // latency path: one launch does all of K1.  Else the latency-bound serial rollout in blocks of 64 (spread the waves over all
+  // CUs), or with SFW_K1A_THREADS=1 round 1-5's one thread per sample (A/B and the equality test)
+  const k1_form f = sfw_rollout_is_fused(L.chunk_count, L.S) ? K1_SMALL : sfw_k1a_threads() ? K1_THREADS : K1_TEAM;
+  const int block = f == K1_SMALL ? K1_SMALL_BLOCK : 64, per_block = f == K1_SMALL ? 1 : f == K1_THREADS ? block : WAVE / K1A_TEAM;
+  const unsigned grid = static_cast<unsigned>((L.chunk_count + per_block - 1) / per_block);
+  hipLaunchKernelGGL(k1_kernel_for(f, stage_kind(L)), dim3(grid), dim3(block), 0, stream, L);
   return hipGetLastError();
 }
 
@@ -4004,7 +4011,7 @@ static hipError_t sfw_launch_behind_costmap(const sfw_launch &L, hipStream_t str
 // term, which follow either.
 hipError_t sfw_launch_rollout_costmap(const sfw_launch &L, hipStream_t stream) {
   if (L.chunk_count <= 0) return hipSuccess;
-  if (sfw_rollout_is_fused(L)) return (L.stop_on || L.path_on) ? sfw_launch_behind_costmap(L, stream) : hipSuccess;
+  if (sfw_rollout_is_fused(L.chunk_count, L.S)) return (L.stop_on || L.path_on) ? sfw_launch_behind_costmap(L, stream) : hipSuccess;
   {
     const int block = 256;
     const unsigned grid = static_cast<unsigned>((L.chunk_count + block - 1) / block);
@@ -4099,6 +4106,10 @@ int64_t sfw_social_flat_items(int A, int O, int NG, int64_t T, int form, int cus
   return T - split_point(plan_for(A, T, O, form, cus), A, O, NG, form, T, cus);
 }
 
+// the flat form's kernel for a plane capacity and a K2 variant (the laser-point pass rides with the group pass)
+template <typename R, int CAP> static auto flat_kernel_for(int v) -> void (*)(const sfw_launch, const int) {
+  return v == 2 ? sfw_social_kernel_flat<R, true, CAP, true> : v == 1 ? sfw_social_kernel_flat<R, false, CAP, true> : sfw_social_kernel_flat<R, false, CAP, false>;
+}
 template <typename R> static hipError_t launch_social_typed(const sfw_launch &L_in, hipStream_t stream, const sfw_split_streams *sp = nullptr) {
   // The organisations are bit-identical and the class records of the shared-prefix rollout are
   // organisation-neutral, so every launch picks its own by its item count (measured: forcing the
@@ -4153,40 +4164,19 @@ template <typename R> static hipError_t launch_social_typed(const sfw_launch &L_
   if (!pl.flat && pl.G > lds_layout::REG_DEAD_CAP) return hipErrorInvalidValue;
   if (pl.flat) {
     if (8 * (static_cast<int64_t>(L.A) + 1) > 65535 || !L.pair_tab) return hipErrorInvalidValue;  // 16-bit plane offsets
-    const bool obs = L.O > 0;  // the kernels with the laser-point pass (sfw_social_kernel_flat<.., OBS>)
+    const int v = k2_variant(L);
     switch (flat_cap(L.A)) {
-      case 64:
-        return groups ? launch_social_as(sfw_social_kernel_flat<R, true, 64, true>, L, 1, grid, lds, stream)
-               : obs  ? launch_social_as(sfw_social_kernel_flat<R, false, 64, true>, L, 1, grid, lds, stream)
-                      : launch_social_as(sfw_social_kernel_flat<R, false, 64, false>, L, 1, grid, lds, stream);
-      case 104:
-        return groups ? launch_social_as(sfw_social_kernel_flat<R, true, 104, true>, L, 1, grid, lds, stream)
-               : obs  ? launch_social_as(sfw_social_kernel_flat<R, false, 104, true>, L, 1, grid, lds, stream)
-                      : launch_social_as(sfw_social_kernel_flat<R, false, 104, false>, L, 1, grid, lds, stream);
-      case 128:
-        return groups ? launch_social_as(sfw_social_kernel_flat<R, true, 128, true>, L, 1, grid, lds, stream)
-               : obs  ? launch_social_as(sfw_social_kernel_flat<R, false, 128, true>, L, 1, grid, lds, stream)
-                      : launch_social_as(sfw_social_kernel_flat<R, false, 128, false>, L, 1, grid, lds, stream);
-      case 208:
-        return groups ? launch_social_as(sfw_social_kernel_flat<R, true, 208, true>, L, 1, grid, lds, stream)
-               : obs  ? launch_social_as(sfw_social_kernel_flat<R, false, 208, true>, L, 1, grid, lds, stream)
-                      : launch_social_as(sfw_social_kernel_flat<R, false, 208, false>, L, 1, grid, lds, stream);
-      case 256:
-        return groups ? launch_social_as(sfw_social_kernel_flat<R, true, 256, true>, L, 1, grid, lds, stream)
-               : obs  ? launch_social_as(sfw_social_kernel_flat<R, false, 256, true>, L, 1, grid, lds, stream)
-                      : launch_social_as(sfw_social_kernel_flat<R, false, 256, false>, L, 1, grid, lds, stream);
-      default:
-        return groups ? launch_social_as(sfw_social_kernel_flat<R, true, 0, true>, L, 1, grid, lds, stream)
-               : obs  ? launch_social_as(sfw_social_kernel_flat<R, false, 0, true>, L, 1, grid, lds, stream)
-                      : launch_social_as(sfw_social_kernel_flat<R, false, 0, false>, L, 1, grid, lds, stream);
+      case 64: return launch_social_as(flat_kernel_for<R, 64>(v), L, 1, grid, lds, stream);
+      case 104: return launch_social_as(flat_kernel_for<R, 104>(v), L, 1, grid, lds, stream);
+      case 128: return launch_social_as(flat_kernel_for<R, 128>(v), L, 1, grid, lds, stream);
+      case 208: return launch_social_as(flat_kernel_for<R, 208>(v), L, 1, grid, lds, stream);
+      case 256: return launch_social_as(flat_kernel_for<R, 256>(v), L, 1, grid, lds, stream);
+      default: return launch_social_as(flat_kernel_for<R, 0>(v), L, 1, grid, lds, stream);
     }
   }
-  if (groups) {
-    if (pl.ns == 1) return launch_social_as(sfw_social_kernel<R, 1, true>, L, pl.G, grid, lds, stream);
-    return launch_social_as(sfw_social_kernel<R, 2, true>, L, pl.G, grid, lds, stream);
-  }
-  if (pl.ns == 1) return launch_social_as(sfw_social_kernel<R, 1, false>, L, pl.G, grid, lds, stream);
-  return launch_social_as(sfw_social_kernel<R, 2, false>, L, pl.G, grid, lds, stream);
+  const auto kernel = groups ? (pl.ns == 1 ? sfw_social_kernel<R, 1, true> : sfw_social_kernel<R, 2, true>)
+                             : (pl.ns == 1 ? sfw_social_kernel<R, 1, false> : sfw_social_kernel<R, 2, false>);
+  return launch_social_as(kernel, L, pl.G, grid, lds, stream);
 }
 
 // A robot alone without a laser point has no social work to integrate: no pair, no obstacle force, so Wr = |0| and Wp = 0
@@ -4206,7 +4196,7 @@ __global__ void __launch_bounds__(256) sfw_no_social_kernel(const sfw_launch L) 
 
 hipError_t sfw_launch_social(const sfw_launch &L, hipStream_t stream, const sfw_split_streams *sp) {
   if (L.chunk_count <= 0 || L.A <= 0) return hipSuccess;
-  if (L.A == 1 && L.O == 0 && L.NG == 0 && L.phase != SFW_PHASE_PREFIX && !L.out_state) {
+  if (!has_social_work(L) && L.phase != SFW_PHASE_PREFIX && !L.out_state) {
     hipLaunchKernelGGL(sfw_no_social_kernel, dim3(static_cast<unsigned>((L.chunk_count + 255) / 256)), dim3(256), 0, stream, L);
     return hipGetLastError();
   }
@@ -4294,52 +4284,27 @@ hipError_t sfw_launch_rescore(const double *terms, int64_t T, const sfw_weights 
   return hipGetLastError();
 }
 
-hipError_t sfw_launch_ensemble(const double *const *terms, const double *probs, int M, int64_t T, int mode, const sfw_weights &w,
-                               const double *linvels, const double *angvels, int32_t nw, double *costs, int32_t *rejected,
-                               sfw_sel *partials, sfw_sel *sel_host, hipStream_t stream, const double *path_p, double path_w) {
-  if (M < 1 || T < 1) return hipErrorInvalidValue;
-  const int blocks = static_cast<int>(sfw_argmin_partials(T));
-  hipLaunchKernelGGL(sfw_ensemble_stage1, dim3(static_cast<unsigned>(blocks)), dim3(ARGMIN_BLOCK), 0, stream, terms, probs, M, T,
-                     mode, w, linvels, angvels, nw, costs, rejected, partials, blocks == 1 ? sel_host : static_cast<sfw_sel *>(nullptr),
-                     path_p, path_w);
-  if (blocks > 1)
-    hipLaunchKernelGGL(sfw_ensemble_stage2, dim3(1), dim3(ARGMIN_BLOCK), 0, stream, static_cast<const sfw_sel *>(partials), blocks,
-                       sel_host);
-  return hipGetLastError();
-}
-
 #ifndef SFW_STRICT_BUILD
-hipError_t sfw_launch_ensemble_list(const double *const *terms, const double *probs, int M, int64_t T, int mode,
-                                    const sfw_weights &w, const double *linvels, const double *angvels, double *costs,
-                                    double *costs_dev, int32_t *rejected, sfw_sel *partials, sfw_sel *sel_host, hipStream_t stream,
-                                    const double *path_p, double path_w) {
-  if (M < 1 || T < 1) return hipErrorInvalidValue;
-  const int blocks = static_cast<int>(sfw_argmin_partials(T));
-  hipLaunchKernelGGL(sfw_ens_list_first, dim3(static_cast<unsigned>(blocks)), dim3(ARGMIN_BLOCK), 0, stream, terms, probs, M, T,
-                     mode, w, linvels, angvels, costs, costs_dev, rejected, partials,
-                     blocks == 1 ? sel_host : static_cast<sfw_sel *>(nullptr), path_p, path_w);
-  if (blocks > 1)
-    hipLaunchKernelGGL(sfw_ensemble_stage2, dim3(1), dim3(ARGMIN_BLOCK), 0, stream, static_cast<const sfw_sel *>(partials), blocks,
-                       sel_host);
-  return hipGetLastError();
-}
-hipError_t sfw_launch_ensemble_risk(const double *const *terms, const double *probs, int M, int64_t T, int mode,
-                                    const sfw_weights &w, double tail_mass, double contact_mass, double thr, bool list,
-                                    const double *linvels, const double *angvels, int32_t nw, double *costs, double *costs_dev,
-                                    int32_t *rejected, sfw_sel *partials, sfw_sel *sel_host, hipStream_t stream,
-                                    const double *path_p, double path_w) {
-  if (M < 1 || M > SFW_ENSEMBLE_MAX_M || T < 1) return hipErrorInvalidValue;  // (the accepting members are a 64-bit mask)
-  const int blocks = static_cast<int>(sfw_argmin_partials(T));
-  sfw_sel *const rec = blocks == 1 ? sel_host : static_cast<sfw_sel *>(nullptr);
-  if (list)
-    hipLaunchKernelGGL(sfw_ens_risk_list, dim3(static_cast<unsigned>(blocks)), dim3(ARGMIN_BLOCK), 0, stream, terms, probs, M, T, mode,
-                       w, tail_mass, contact_mass, thr, linvels, angvels, costs, costs_dev, rejected, partials, rec, path_p, path_w);
+hipError_t sfw_launch_ensemble(const sfw_ensemble_launch &a, hipStream_t stream) {
+  // (under a risk the accepting members are a 64-bit mask)
+  if (a.M < 1 || a.T < 1 || (a.risk && a.M > SFW_ENSEMBLE_MAX_M)) return hipErrorInvalidValue;
+  const int blocks = static_cast<int>(sfw_argmin_partials(a.T));
+  const dim3 grid(static_cast<unsigned>(blocks)), block(ARGMIN_BLOCK);
+  sfw_sel *const rec = blocks == 1 ? a.sel_host : static_cast<sfw_sel *>(nullptr);
+  if (a.risk && a.list)
+    hipLaunchKernelGGL(sfw_ens_risk_list, grid, block, 0, stream, a.terms, a.probs, a.M, a.T, a.mode, a.w, a.tail_mass, a.contact_mass,
+                       a.thr, a.linvels, a.angvels, a.costs, a.costs_dev, a.rejected, a.partials, rec, a.path_p, a.path_w);
+  else if (a.risk)
+    hipLaunchKernelGGL(sfw_ens_risk_grid, grid, block, 0, stream, a.terms, a.probs, a.M, a.T, a.mode, a.w, a.tail_mass, a.contact_mass,
+                       a.thr, a.linvels, a.angvels, a.nw, a.costs, a.rejected, a.partials, rec, a.path_p, a.path_w);
+  else if (a.list)
+    hipLaunchKernelGGL(sfw_ens_list_first, grid, block, 0, stream, a.terms, a.probs, a.M, a.T, a.mode, a.w, a.linvels, a.angvels,
+                       a.costs, a.costs_dev, a.rejected, a.partials, rec, a.path_p, a.path_w);
   else
-    hipLaunchKernelGGL(sfw_ens_risk_grid, dim3(static_cast<unsigned>(blocks)), dim3(ARGMIN_BLOCK), 0, stream, terms, probs, M, T, mode,
-                       w, tail_mass, contact_mass, thr, linvels, angvels, nw, costs, rejected, partials, rec, path_p, path_w);
+    hipLaunchKernelGGL(sfw_ensemble_stage1, grid, block, 0, stream, a.terms, a.probs, a.M, a.T, a.mode, a.w, a.linvels, a.angvels, a.nw,
+                       a.costs, a.rejected, a.partials, rec, a.path_p, a.path_w);
   if (blocks > 1)
-    hipLaunchKernelGGL(sfw_ensemble_stage2, dim3(1), dim3(ARGMIN_BLOCK), 0, stream, static_cast<const sfw_sel *>(partials), blocks,
-                       sel_host);
+    hipLaunchKernelGGL(sfw_ensemble_stage2, dim3(1), block, 0, stream, static_cast<const sfw_sel *>(a.partials), blocks, a.sel_host);
   return hipGetLastError();
 }
 int64_t sfw_blend_blocks(int64_t T) { return (T + BLEND_C - 1) / BLEND_C; }
@@ -4396,32 +4361,30 @@ hipError_t sfw_launch_perturb(const sfw_perturb_dev &a, int64_t n, int K, int64_
                      index_base, vx, vy, vtheta, z_out);
   return hipGetLastError();
 }
-hipError_t sfw_launch_perturb_plan(const sfw_perturb_dev &a, const double *plan, int64_t n, int K, int64_t index_base, double *vx,
-                                   double *vy, double *vtheta, double *z_out, hipStream_t stream) {
-  const int64_t blocks = (n + PERTURB_C - 1) / PERTURB_C;
-  if (n < 1 || K < 1 || K > SFW_SEQ_MAX_KNOTS || index_base < 0 || blocks > INT_MAX || !vx || !vtheta || !plan) return hipErrorInvalidValue;
+// what the kernels that read the plan from device memory take: a up to its nominal rows
+static sfw_perturb_head perturb_head_of(const sfw_perturb_dev &a) {
   sfw_perturb_head head{a.key0, a.key1, a.keep_nominal, 0, {}, {}, {}};
   for (int c = 0; c < 3; ++c) {
     head.sigma[c] = a.sigma[c];
     head.lo[c] = a.lo[c];
     head.hi[c] = a.hi[c];
   }
+  return head;
+}
+hipError_t sfw_launch_perturb_plan(const sfw_perturb_dev &a, const double *plan, int64_t n, int K, int64_t index_base, double *vx,
+                                   double *vy, double *vtheta, double *z_out, hipStream_t stream) {
+  const int64_t blocks = (n + PERTURB_C - 1) / PERTURB_C;
+  if (n < 1 || K < 1 || K > SFW_SEQ_MAX_KNOTS || index_base < 0 || blocks > INT_MAX || !vx || !vtheta || !plan) return hipErrorInvalidValue;
   hipLaunchKernelGGL(sfw_perturb_plan_kernel, dim3(static_cast<unsigned>(blocks), static_cast<unsigned>(K)), dim3(PERTURB_C), 0, stream,
-                     head, plan, n, index_base, vx, vy, vtheta, z_out);
+                     perturb_head_of(a), plan, n, index_base, vx, vy, vtheta, z_out);
   return hipGetLastError();
 }
 hipError_t sfw_launch_perturb_members(const sfw_perturb_dev &a, const double *plan, int64_t n, int K, int64_t index_base,
                                       const sfw_perturb_dst *dst, int M, hipStream_t stream) {
   const int64_t blocks = (n + PERTURB_C - 1) / PERTURB_C;
   if (n < 1 || K < 1 || K > SFW_SEQ_MAX_KNOTS || index_base < 0 || blocks > INT_MAX || !plan || !dst || M < 1) return hipErrorInvalidValue;
-  sfw_perturb_head head{a.key0, a.key1, a.keep_nominal, 0, {}, {}, {}};
-  for (int c = 0; c < 3; ++c) {
-    head.sigma[c] = a.sigma[c];
-    head.lo[c] = a.lo[c];
-    head.hi[c] = a.hi[c];
-  }
   hipLaunchKernelGGL(sfw_perturb_members_kernel, dim3(static_cast<unsigned>(blocks), static_cast<unsigned>(K)), dim3(PERTURB_C), 0, stream,
-                     head, plan, n, index_base, dst, M);
+                     perturb_head_of(a), plan, n, index_base, dst, M);
   return hipGetLastError();
 }
 hipError_t sfw_launch_control_cost(const sfw_perturb_dev &a, const double *plan, int K, int64_t n, int64_t index_base,
@@ -4435,11 +4398,25 @@ hipError_t sfw_launch_control_cost(const sfw_perturb_dev &a, const double *plan,
 #endif  // SFW_STRICT_BUILD
 
 // ---- one launch per control cycle ------------------------------------------------------------------------------------
-static size_t cycle_k2_bytes(const sfw_launch &L, bool obs_lds) {
-  const bool social = L.A > 0 && !(L.A == 1 && L.O == 0 && L.NG == 0);
-  if (!social) return 0;
-  // the flat form's layout on 64-double planes, with the agents' constants staged (social_flat_wave<.., CYCLE>)
-  return (lds_layout(nullptr, L.A, 64, L.A, 1, L.O, L.NG, L.n_grp_mem, true, true, obs_lds).bytes + 15) & ~size_t(15);
+// The block of the one-launch control cycle over L: is there social work, do the laser points ride in LDS (decided as the
+// flat form of K2 decides it), and its dynamic LDS — the K2 wave's area | k1s_lds | cycle_result.  sfw_cycle_applies,
+// sfw_launch_cycle and a batch member's record all read this one value.
+struct cycle_shape {
+  bool social, obs_lds;
+  size_t k2_bytes, lds_bytes;
+};
+static cycle_shape cycle_shape_of(const sfw_launch &L) {
+  cycle_shape s{has_social_work(L), false, 0, 0};
+  if (s.social) {
+    const wave_plan fl{1, 0, true};
+    s.obs_lds = obs_in_lds(fl, L.A, L.O, L.NG, L.n_grp_mem, L.chunk_count, L.n_cu > 0 ? L.n_cu : SFW_DEFAULT_CUS);
+    // the flat form's layout on 64-double planes, with the agents' constants staged (social_flat_wave<.., CYCLE>)
+    s.k2_bytes = (lds_layout(nullptr, L.A, 64, L.A, 1, L.O, L.NG, L.n_grp_mem, true, true, s.obs_lds).bytes + 15) & ~size_t(15);
+  }
+  size_t k1_bytes = 0;
+  (void)k1s_lds(nullptr, L.S, &k1_bytes);
+  s.lds_bytes = s.k2_bytes + k1_bytes + ((sizeof(cycle_result) + 15) & ~size_t(15));
+  return s;
 }
 // Does sfw_launch_cycle take this launch?  A whole (unshared, single-chunk) rollout of a small grid whose K2 would run the
 // flat form on 64-double planes, or has no pedestrians to integrate.  SFW_CYCLE_FUSED=0 in the environment (read at every
@@ -4451,43 +4428,25 @@ bool sfw_cycle_applies(const sfw_launch &L) {
   if (L.path_on) return false;  // (sfw_set_path: neither is the path term)
   if (L.phase != SFW_PHASE_WHOLE || L.resume || L.chunk_begin != 0 || L.chunk_count <= 0 || L.chunk_count > CYCLE_MAX_SAMPLES) return false;
   if (L.S > K1_SMALL_MAX_STEPS || (L.sel_out && !L.cycle_counter)) return false;
-  const bool social = L.A > 0 && !(L.A == 1 && L.O == 0 && L.NG == 0);
-  if (social) {
+  if (has_social_work(L)) {
     const int cus = L.n_cu > 0 ? L.n_cu : SFW_DEFAULT_CUS;
     if (flat_cap(L.A) != 64 || !L.pair_tab || !plan_for(L.A, L.chunk_count, L.O, L.k2_form, cus).flat) return false;
   }
-  const wave_plan fl{1, 0, true};
-  const bool obs_lds = social && obs_in_lds(fl, L.A, L.O, L.NG, L.n_grp_mem, L.chunk_count, L.n_cu > 0 ? L.n_cu : SFW_DEFAULT_CUS);
-  size_t k1_bytes = 0;
-  (void)k1s_lds(nullptr, L.S, &k1_bytes);
-  return cycle_k2_bytes(L, obs_lds) + k1_bytes + ((sizeof(cycle_result) + 15) & ~size_t(15)) <= 64 * 1024;
+  return cycle_shape_of(L).lds_bytes <= 64 * 1024;
+}
+// The cycle kernel <R, GROUPS, OBS> for a stage kind and a K2 variant.  Sequences (sfw_sequences_stage): the list's block with
+// the knot cursor in the robot's wave; a list (sfw_samples_stage): the same block over the list's sample lookup and selection.
+template <typename R> static auto cycle_kernel_for(int kind, int v) -> void (*)(const sfw_launch, const int) {
+  if (kind == 2) return v == 2 ? sfw_cycle_seq_kernel<R, true, true> : v == 1 ? sfw_cycle_seq_kernel<R, false, true> : sfw_cycle_seq_kernel<R, false, false>;
+  if (kind == 1) return v == 2 ? sfw_cycle_list_kernel<R, true, true> : v == 1 ? sfw_cycle_list_kernel<R, false, true> : sfw_cycle_list_kernel<R, false, false>;
+  return v == 2 ? sfw_cycle_kernel<R, true, true> : v == 1 ? sfw_cycle_kernel<R, false, true> : sfw_cycle_kernel<R, false, false>;
 }
 template <typename R> static hipError_t launch_cycle_typed(const sfw_launch &L_in, hipStream_t stream) {
   sfw_launch L = L_in;
-  const bool social = L.A > 0 && !(L.A == 1 && L.O == 0 && L.NG == 0);
-  const wave_plan fl{1, 0, true};
-  L.k.obs_lds = (social && obs_in_lds(fl, L.A, L.O, L.NG, L.n_grp_mem, L.chunk_count, L.n_cu > 0 ? L.n_cu : SFW_DEFAULT_CUS)) ? 1 : 0;
-  const size_t k2 = cycle_k2_bytes(L, L.k.obs_lds != 0);
-  size_t k1_bytes = 0;
-  (void)k1s_lds(nullptr, L.S, &k1_bytes);
-  const size_t lds = k2 + k1_bytes + ((sizeof(cycle_result) + 15) & ~size_t(15));
-  const dim3 grid(static_cast<unsigned>(L.chunk_count)), block(CYCLE_BLOCK);
-  const int k2i = static_cast<int>(k2);
-  if (L.n_knots > 1) {  // (sfw_sequences_stage: the list's block with the knot cursor in the robot's wave)
-    if (L.NG > 0) hipLaunchKernelGGL((sfw_cycle_seq_kernel<R, true, true>), grid, block, lds, stream, L, k2i);
-    else if (L.O > 0) hipLaunchKernelGGL((sfw_cycle_seq_kernel<R, false, true>), grid, block, lds, stream, L, k2i);
-    else hipLaunchKernelGGL((sfw_cycle_seq_kernel<R, false, false>), grid, block, lds, stream, L, k2i);
-    return hipGetLastError();
-  }
-  if (L.list) {  // (sfw_samples_stage: the same block over the list's sample lookup and selection)
-    if (L.NG > 0) hipLaunchKernelGGL((sfw_cycle_list_kernel<R, true, true>), grid, block, lds, stream, L, k2i);
-    else if (L.O > 0) hipLaunchKernelGGL((sfw_cycle_list_kernel<R, false, true>), grid, block, lds, stream, L, k2i);
-    else hipLaunchKernelGGL((sfw_cycle_list_kernel<R, false, false>), grid, block, lds, stream, L, k2i);
-    return hipGetLastError();
-  }
-  if (L.NG > 0) hipLaunchKernelGGL((sfw_cycle_kernel<R, true, true>), grid, block, lds, stream, L, k2i);
-  else if (L.O > 0) hipLaunchKernelGGL((sfw_cycle_kernel<R, false, true>), grid, block, lds, stream, L, k2i);
-  else hipLaunchKernelGGL((sfw_cycle_kernel<R, false, false>), grid, block, lds, stream, L, k2i);
+  const cycle_shape sh = cycle_shape_of(L);
+  L.k.obs_lds = sh.obs_lds ? 1 : 0;
+  hipLaunchKernelGGL(cycle_kernel_for<R>(stage_kind(L), k2_variant(L)), dim3(static_cast<unsigned>(L.chunk_count)), dim3(CYCLE_BLOCK),
+                     sh.lds_bytes, stream, L, static_cast<int>(sh.k2_bytes));
   return hipGetLastError();
 }
 hipError_t sfw_launch_cycle(const sfw_launch &L, hipStream_t stream) {
@@ -4501,43 +4460,29 @@ hipError_t sfw_launch_cycle(const sfw_launch &L, hipStream_t stream) {
 // (the build and the force type) x the kernel variant the single launcher picks (groups / laser points / neither).  Kind 0 keeps
 // the numbering grids have always had (0..8); a sequence stage of one knot is a list, as in launch_cycle_typed.
 int sfw_cycle_batch_variant(const sfw_launch &L) {
-  const int v = L.NG > 0 ? 2 : L.O > 0 ? 1 : 0;
   const int prec = L.p.precision == SFW_PRECISION_F64_STRICT ? 2 : L.p.precision == SFW_PRECISION_F32 ? 1 : 0;
-  const int kind = L.n_knots > 1 ? 2 : L.list ? 1 : 0;
-  return 9 * kind + 3 * prec + v;
+  return 9 * stage_kind(L) + 3 * prec + k2_variant(L);
 }
 void sfw_cycle_batch_record(const sfw_launch &L, sfw_batch_rec *rec) {
-  // what launch_cycle_typed would launch: the same obs_lds decision, the same layout
+  const cycle_shape sh = cycle_shape_of(L);  // (what launch_cycle_typed launches)
   rec->L = L;
-  const bool social = L.A > 0 && !(L.A == 1 && L.O == 0 && L.NG == 0);
-  const wave_plan fl{1, 0, true};
-  rec->L.k.obs_lds = (social && obs_in_lds(fl, L.A, L.O, L.NG, L.n_grp_mem, L.chunk_count, L.n_cu > 0 ? L.n_cu : SFW_DEFAULT_CUS)) ? 1 : 0;
+  rec->L.k.obs_lds = sh.obs_lds ? 1 : 0;
   rec->L.clock_probe = nullptr;  // (no clock probe in a batch)
-  const size_t k2 = cycle_k2_bytes(rec->L, rec->L.k.obs_lds != 0);
-  size_t k1_bytes = 0;
-  (void)k1s_lds(nullptr, L.S, &k1_bytes);
-  rec->k2_bytes = static_cast<int32_t>(k2);
-  rec->lds_bytes = static_cast<int32_t>(k2 + k1_bytes + ((sizeof(cycle_result) + 15) & ~size_t(15)));
+  rec->k2_bytes = static_cast<int32_t>(sh.k2_bytes);
+  rec->lds_bytes = static_cast<int32_t>(sh.lds_bytes);
+}
+template <typename R>
+static auto cycle_batch_kernel_for(int kind, int v) -> void (*)(const uint32_t *const, const sfw_batch_rec *const, const int) {
+  if (kind == 2)
+    return v == 2 ? sfw_batch_cycle_seq_kernel<R, true, true> : v == 1 ? sfw_batch_cycle_seq_kernel<R, false, true> : sfw_batch_cycle_seq_kernel<R, false, false>;
+  if (kind == 1)
+    return v == 2 ? sfw_batch_cycle_list_kernel<R, true, true> : v == 1 ? sfw_batch_cycle_list_kernel<R, false, true> : sfw_batch_cycle_list_kernel<R, false, false>;
+  return v == 2 ? sfw_batch_cycle_kernel<R, true, true> : v == 1 ? sfw_batch_cycle_kernel<R, false, true> : sfw_batch_cycle_kernel<R, false, false>;
 }
 template <typename R>
 static hipError_t launch_cycle_batch_typed(int kind, int v, const uint32_t *d_first, const sfw_batch_rec *d_recs, int B, unsigned blocks,
                                            size_t lds, hipStream_t stream) {
-  const dim3 grid(blocks), block(CYCLE_BLOCK);
-  if (kind == 2) {
-    if (v == 2) hipLaunchKernelGGL((sfw_batch_cycle_seq_kernel<R, true, true>), grid, block, lds, stream, d_first, d_recs, B);
-    else if (v == 1) hipLaunchKernelGGL((sfw_batch_cycle_seq_kernel<R, false, true>), grid, block, lds, stream, d_first, d_recs, B);
-    else hipLaunchKernelGGL((sfw_batch_cycle_seq_kernel<R, false, false>), grid, block, lds, stream, d_first, d_recs, B);
-    return hipGetLastError();
-  }
-  if (kind == 1) {
-    if (v == 2) hipLaunchKernelGGL((sfw_batch_cycle_list_kernel<R, true, true>), grid, block, lds, stream, d_first, d_recs, B);
-    else if (v == 1) hipLaunchKernelGGL((sfw_batch_cycle_list_kernel<R, false, true>), grid, block, lds, stream, d_first, d_recs, B);
-    else hipLaunchKernelGGL((sfw_batch_cycle_list_kernel<R, false, false>), grid, block, lds, stream, d_first, d_recs, B);
-    return hipGetLastError();
-  }
-  if (v == 2) hipLaunchKernelGGL((sfw_batch_cycle_kernel<R, true, true>), grid, block, lds, stream, d_first, d_recs, B);
-  else if (v == 1) hipLaunchKernelGGL((sfw_batch_cycle_kernel<R, false, true>), grid, block, lds, stream, d_first, d_recs, B);
-  else hipLaunchKernelGGL((sfw_batch_cycle_kernel<R, false, false>), grid, block, lds, stream, d_first, d_recs, B);
+  hipLaunchKernelGGL(cycle_batch_kernel_for<R>(kind, v), dim3(blocks), dim3(CYCLE_BLOCK), lds, stream, d_first, d_recs, B);
   return hipGetLastError();
 }
 hipError_t sfw_launch_cycle_batch(int variant, const uint32_t *d_first, const sfw_batch_rec *d_recs, int B, unsigned blocks,

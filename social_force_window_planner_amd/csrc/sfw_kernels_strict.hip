@@ -32,5 +32,4 @@
 #define sfw_launch_argmin sfw_strict_unused_launch_argmin
 #define sfw_rescore_blocks sfw_strict_unused_rescore_blocks
 #define sfw_launch_rescore sfw_strict_unused_launch_rescore
-#define sfw_launch_ensemble sfw_strict_unused_launch_ensemble
 #include "sfw_kernels.hip"

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 from social_force_window_planner_amd import synthetic as syn
-from social_force_window_planner_amd._abi import default_params
+from social_force_window_planner_amd._abi import SfwAgent, default_params
 from sfw_test_util import _same, _workload_params as _params
 
 pytestmark = pytest.mark.gpu
@@ -160,3 +160,56 @@ def test_a_points_dump_between_stage_and_launch(hip_mod):
     assert _same(costs, ref_costs) and best == ref_best
     pts, n = g2.grid_points_batch(0, 45, w.n_steps)
     assert np.array_equal(n, ref_n) and _same(pts, ref_pts)
+
+
+@pytest.mark.parametrize("people", [3, 0])
+def test_the_reruns_share_one_scratch_set(hip_mod, people):
+    """sfw_grid_points_batch, sfw_grid_crowd and sfw_grid_stop_points run samples of the staged grid once more into ONE set of
+    scratch outputs in the handle.  Interleaved on one handle with counts that grow and shrink, the stop check and the path term
+    on: every result is bit for bit the same call made as the only re-run on a fresh handle, and the launch's own results (cost
+    vector, record, stop records, path term) are afterwards what they were.  Without people the crowd calls return 0 steps."""
+    S, cap = 12, 16
+    w = dataclasses.replace(syn.WORKLOADS["ref5x9"], n_people=3, sim_time=S * syn.WORKLOADS["ref5x9"].sim_granularity)
+    assert w.n_steps == S
+    scene = syn.make_scene(w)
+    x0, y0, th = scene.robot_state[0], scene.robot_state[1], scene.robot_state[2]
+    s = np.linspace(0.0, 1.5, 16)
+    path = np.stack([x0 + s * np.cos(th) - 0.2 * s * s * np.sin(th), y0 + s * np.sin(th) + 0.2 * s * s * np.cos(th)], axis=1)
+
+    def scored():
+        g = hip_mod.HipScorer(_params(w))
+        g.load_scene(scene)
+        if people == 0:
+            g.set_agents((SfwAgent * 0)(), None)
+        g.set_stop_check((0.3, 0.3, 1.0, 256))
+        g.set_path(path, 1.0)
+        g.score_grid(scene.robot_state, scene.linvels, scene.angvels, scene.goal_args)
+        return g
+
+    def launch_results(g):
+        costs, best, key = g.fetch()
+        return costs, best, key, g.stop_info(0, 45), g.path_term()
+
+    def crowd(g, t):
+        d = g.grid_crowd(t)
+        assert people > 0 or d["n_steps"] == 0
+        return d["cost"], d["n_steps"], d["state"], d["work"], d["has_goal"]
+
+    calls = [lambda g: g.grid_points_batch(0, 45, S), lambda g: crowd(g, 7), lambda g: g.stop_points(3, 5, cap),
+             lambda g: g.grid_points_batch(40, 2, S), lambda g: crowd(g, 44), lambda g: g.stop_points(0, 45, cap),
+             lambda g: (g.grid_points(0),)]
+
+    def same(a, b):
+        return len(a) == len(b) and all(_same(x, y) for x, y in zip(a, b))
+
+    g = scored()
+    before = launch_results(g)
+    got = [call(g) for call in calls]
+    after = launch_results(g)
+    assert same(before[0:1] + before[3] + before[4:], after[0:1] + after[3] + after[4:]) and before[1:3] == after[1:3]
+    assert (before[0] >= 0).any() and (before[4] >= 0).any() and (before[3][0] > 0).any()  # (a scene with something to disturb)
+    g.close()
+    for i, call in enumerate(calls):
+        alone = scored()
+        assert same(got[i], call(alone)), i
+        alone.close()
